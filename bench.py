@@ -1,14 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- batched DoNothing env.step throughput of the MI355X power-flow engine.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--env NAME] [--batch B] [--cascade]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--env NAME] [--batch B] [--cascade] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch: for every lane (independent environment copy)
 chronics row -> injections -> AC Newton-Raphson power flow (init="dc", <=10 iterations, 1e-8 MVA) ->
 result extraction -> overflow bookkeeping, i.e. what ``Environment.step`` asks of the Backend for a
 DoNothing agent.  The headline uses ``NO_OVERFLOW_DISCONNECTION=True`` (the setting of the reference's own
 DoNothing profiler, _profiling/profiler_do_nothing.py:42-65); the same workload with the reference's DEFAULT
-parameters (overflow disconnections / cascade on) is reported beside it (``cascade_on``).  Inputs (chronics
+parameters (overflow disconnections / cascade on) is reported beside it with ``--full`` (``cascade_on``).  Inputs (chronics
 tables, lane state) are resident in HBM before the timed region; outputs stay in HBM.
 
 Workload (BASELINE.json configs[1], SURVEY.md 8(d) cfg 2): ``l2rpn_case14_sandbox``, batch = 4096 lanes
@@ -26,24 +26,27 @@ Observations: the reference returns one observation per ``env.step``.  The headl
 every one of the 16 steps of a launch writes its complete backend observation (results row, topo_vect, shunt buses, line
 status, rho, status) to its own rows in HBM.  The cheaper contracts are labelled secondaries: ``rollout_last_observation_only``
 (16 steps per launch, each step overwrites the lane's single row: only the last observation of a launch exists) and
-``one_launch_per_step``.  After each timed workload a sample of lanes is re-solved by the C oracle (checker only, outside
-every timed region): ``max_abs_err_vs_oracle``.
+``one_launch_per_step``; they, the BASELINE configs and the CPU baselines are measured with ``--full`` only.  With ``--full``, after
+each timed workload a sample of lanes is re-solved by the C oracle (checker only, outside every timed region): ``max_abs_err_vs_oracle``.
 
-Timing: W warm-up steps, then ``--windows`` (default 5) timed windows of EXACTLY K steps each, every window
+Plain run (no ``--full``): set up, W warm-up steps, ONE timed window of exactly K steps, ``--dump-outputs DIR`` if given (the result
+arrays of the last timed step, DIR/<name>.npy), the result line.  Nothing else is launched or measured.
+
+Timing: W warm-up steps, then ``--windows`` (default 1; 5 with ``--full``) timed windows of EXACTLY K steps each, every window
 bracketed by barrier + synchronize on both sides.  ``value`` / ``ms_per_step`` are the WALL CLOCK between those brackets,
 MAX-reduced over the ranks, of the MEDIAN window (min / median / max in ``windows``).  The HIP-event window on the engine's
 stream around the same K steps (closed right behind the last launch) is reported beside it (``value_hip_event_window``) and
 is the clock of ``roofline`` (average launch duration of the dominant kernel).  The BASELINE-config secondaries are kernel
 measurements: >= 5 HIP-event windows of >= 2 launches each, min / median / max reported.
 
-Output: ONE stdout line (rank 0) -- a compact JSON record (< 4 KB: the contract's keys, ``roofline``, ``cpu_baseline``, one number +
-roofline fraction per BASELINE config, the oracle verdict).  Everything else the run measured goes to ``bench_full.json`` next to
-this file (and to ``gpurun_out/`` when that directory exists).
+Output: ONE stdout line (rank 0) -- a compact JSON record (< 4 KB: the contract's keys, ``roofline``, and with ``--full`` also
+``cpu_baseline``, one number + roofline fraction per BASELINE config, the oracle verdict).  Everything else the run measured goes to
+``bench_full.json`` next to this file (or to $GRIDPF_BENCH_FULL).
 
 Kernels: by default every engine switches its solver launches to kernels compiled at run time for the workload's grid
 (``PowerFlowEngine.specialize`` = gpf_jit_enable: the grid's sizes / table offsets as literals, results bit-identical to the
 shipped kernels, self-tested against them on a twin engine first; compilation happens in the untimed warm-up and is cached on
-disk; ``specialization`` in the JSON says what was loaded).  The same headline on the shipped kernels is reported as
+disk; ``specialization`` in the JSON says what was loaded).  With ``--full`` the same headline on the shipped kernels is reported as
 ``shipped_kernels``; ``--no-jit`` runs everything on the shipped kernels (also what happens when no hipcc is available).
 
 """
@@ -435,15 +438,16 @@ def timed_windows(ctx, eng, steps, warmup, step_kw, n_windows, t0=0, preroll_ste
     spl = ctx.args.steps_per_launch if spl is None else spl
     t = t0
     preroll(eng, step_kw, max(0, preroll_steps - warmup), spl)
-    t = run_steps(eng, t, warmup, step_kw, spl)
     out = []
-    for _ in range(n_windows):
+    # window -1 = the W warm-up steps, bracketed exactly like the timed windows and not reported: whatever the first pass through the
+    # brackets costs (event creation, first calls) is paid there, so that a single timed window is as representative as the later ones
+    for i in range(-1 if warmup > 0 else 0, n_windows):
         eng.sync()
         eng.kernel_time()
         ctx.sync_all(eng)
         eng.set_profiling(1)     # ONE HIP event pair on the engine's stream around the K timed launches (no per-launch events)
         w0 = time.perf_counter()
-        t = run_steps(eng, t, steps, step_kw, spl)
+        t = run_steps(eng, t, warmup if i < 0 else steps, step_kw, spl)
         eng.set_profiling(3)     # the event window ends right behind the last launch (not when it is read, after the barrier)
         ctx.sync_all(eng)
         el = time.perf_counter() - w0
@@ -454,7 +458,8 @@ def timed_windows(ctx, eng, steps, warmup, step_kw, n_windows, t0=0, preroll_ste
         # is outside it.  The wall clock between the two barrier + synchronize brackets is kept beside it (`wall`).
         wall = ctx.max(el)
         dev = ctx.max(k_ms * 1e-3) if k_ms > 0 else wall
-        out.append((dev, k_ms, n_l, wall))
+        if i >= 0:
+            out.append((dev, k_ms, n_l, wall))
     return out, t
 
 
@@ -730,6 +735,50 @@ def write_full_record(res, path=None):
         return None
 
 
+DUMP_LIMIT = 64 << 20     # bytes of --dump-outputs
+
+
+def dump_outputs(r, d, step_outputs=None, seed=0):
+    """--dump-outputs DIR: what the headline's last timed step returned to its caller, i.e. the `LaneResults` of `PowerFlowEngine.results()`
+    and the (rho, overflow_count, disc_round) of `step_outputs()`, one DIR/<name>.npy per field: every named row of the observation block
+    and rho (float32, as returned), the bus voltages (float64) and topo_vect / shunt_bus / line_status / status / the counters (integers,
+    exact in float32).  Beyond DUMP_LIMIT bytes the same fixed sample of lanes (default_rng(seed), sorted) is written for every field, with
+    its lane ids as `lanes.npy`.
+    Values that do not exist are written as 0 and flagged, so that every file is finite: the engine returns NaN voltages for the buses a
+    lane does not use (`bus_active.npy`: 1 where bus_vm is a number) and NaN rows for lanes whose step failed (`status.npy`, column 0
+    non-zero).  A non-finite value anywhere else is left as it is.  A field the grid has no element for (storage on a grid without
+    storage units: zero columns) holds nothing and is not written."""
+    arrs = {name: r.out[:, sl] for name, sl in (r.__dict__.get("_slices") or {"out": slice(None)}).items()}
+    for name in ("bus_vm", "bus_va", "topo_vect", "shunt_bus", "line_status", "status"):
+        if r.__dict__.get(name) is not None:
+            arrs[name] = r.__dict__[name]
+    if step_outputs is not None:
+        arrs.update(zip(("rho", "overflow_count", "disc_round"), step_outputs))
+    arrs = {k: np.array(v, dtype=np.float64 if v.dtype == np.float64 else np.float32, order="C") for k, v in arrs.items() if v.size > 0}
+    if "bus_vm" in arrs:
+        active = np.isfinite(arrs["bus_vm"])
+        arrs["bus_active"] = active.astype(np.float32)
+        for k in ("bus_vm", "bus_va"):
+            if k in arrs:
+                arrs[k][~active] = 0.0
+    failed = r.status[:, 0] != 0
+    if failed.any():
+        for k, v in arrs.items():
+            if v.ndim == 2 and v.dtype.kind == "f":
+                rows = v[failed]
+                rows[~np.isfinite(rows)] = 0.0
+                v[failed] = rows
+    n = r.out.shape[0]
+    per_lane = sum(v.nbytes for v in arrs.values()) / max(n, 1)
+    if per_lane * n > DUMP_LIMIT:
+        lanes = np.sort(np.random.default_rng(seed).choice(n, int(DUMP_LIMIT // (per_lane + 8)), replace=False))
+        arrs = {k: v[lanes] for k, v in arrs.items()}
+        arrs["lanes"] = lanes.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, f"{k}.npy"), v)
+
+
 def emit(res):
     """full record -> file, compact record -> the single stdout line"""
     line = json.dumps(compact_record(res, write_full_record(res)))
@@ -743,7 +792,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each (the median one is reported)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each (the median one is reported); default 1, so that a plain run times exactly "
+                         "--steps steps, and 5 with --full")
     ap.add_argument("--steps-per-launch", type=int, default=DEFAULT_STEPS_PER_LAUNCH,
                     help="env steps per kernel launch (gpf_step_n): every step does the full work and writes its results; between "
                          "the steps of a launch the lane state stays on chip (1 = one launch per step, also reported)")
@@ -774,12 +825,21 @@ def main():
     ap.add_argument("--no-jit", action="store_true",
                     help="run on the shipped (ahead-of-time) kernels only.  Default: the engines switch their step launches to kernels compiled at run "
                          "time for the workload's grid (gpf_jit_enable: sizes / offsets as literals, bit-identical results, self-tested against the "
-                         "shipped kernels); the shipped-kernel headline is then reported beside it as `shipped_kernels`")
+                         "shipped kernels); with --full the shipped-kernel headline is then reported beside it as `shipped_kernels`")
     ap.add_argument("--dump-aot", default=None, help="developer: write the generated headers + launched kernel variants of every engine to this directory")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: 5 timed windows, the oracle spot checks, the headline on the shipped kernels, the "
+                         "secondary workloads and BASELINE configs, the batch sweep and the CPU baselines.  Without it a run sets up, warms "
+                         "up, times --steps steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last step returned to its caller (rank 0's lanes) to "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed sample of lanes beyond that)")
     ap.add_argument("--stub-engine", action="store_true", help=argparse.SUPPRESS)   # CPU launcher test: no arithmetic
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -834,7 +894,9 @@ def main():
     elapsed, kern_ms, n_launch, _ = median_window(wins)
     wall_el = median_window(wins, key=3)[3]
     r = eng.results()
-    check = oracle_spot_check(ctx, eng, 32, t_last=None if (args.cascade or args.n1) else t_next - 1) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, args.dump_outputs, eng.step_outputs())
+    check = oracle_spot_check(ctx, eng, 32, t_last=None if (args.cascade or args.n1) else t_next - 1) if rank == 0 and args.full else None
     if args.dump_results:
         np.savez(f"{args.dump_results}.rank{rank}.npz", out=r.out, status=r.status, topo_vect=r.topo_vect, lane0=lane0, t_last=t_next - 1)
     frac_conv = float(r.converged.mean())
@@ -911,7 +973,7 @@ def main():
             "cpu_baseline": None,
         }
 
-    secondary = not args.no_secondary and args.env == "l2rpn_case14_sandbox" and not args.n1 and not args.stub_engine
+    secondary = args.full and not args.no_secondary and args.env == "l2rpn_case14_sandbox" and not args.n1 and not args.stub_engine
     k_sec = max(20, args.steps // 4)
     w_sec = max(2, args.warmup // 4)
 
@@ -920,7 +982,7 @@ def main():
 
     # ---- the same workload, same engine, same state on the SHIPPED (ahead-of-time) kernels ------------------------------------------
     jit_on = (not args.stub_engine) and hasattr(eng, "specialization") and eng.specialization()["enabled"]
-    if jit_on and not args.profile:
+    if jit_on and args.full and not args.profile:
         eng.specialize(False)
         w, _ = timed_windows(ctx, eng, k_sec, w_sec, step_kw, 3, preroll_steps=0)
         eng.specialize(True, verify=False)
@@ -1086,7 +1148,7 @@ def main():
     if rank == 0:
         # the CPU baseline is timed LAST (rank 0 of the 1-GPU run only): host-only work in the middle of the run would
         # let the GPU clocks drop before the secondary workloads
-        if not args.no_cpu_baseline and world == 1 and not args.stub_engine:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.stub_engine:
             res["cpu_baseline"] = cpu_baseline(args.env, m, ch, T)
             res["cpu_baseline"]["reference_environment_step_loop"] = reference_step_loop()
             # an honest CPU row for every BASELINE config (the same sparse port on that config's grid)

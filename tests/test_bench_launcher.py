@@ -87,3 +87,78 @@ def test_sharded_engine_routes_global_lanes(load_model):
     with pytest.raises(ValueError):
         se.results(30, 10)
     se.close()
+
+
+def test_plain_run_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run times ONE window of exactly --steps steps and measures nothing else; --dump-outputs writes the result arrays of the
+    last timed step (the stub engine's first result column is the lane's chronics offset), identical from run to run."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        p = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "64", "--stub-engine", "--dump-outputs", str(d)],
+                 env_extra={"GRIDPF_BENCH_FULL": str(tmp_path / "full.json")})
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == 7 and res["windows"]["n"] == 1 and res["ms_per_step"] > 0
+        assert res["cpu_baseline"] is None and res["configs"] == {} and "parity" not in res
+        with open(tmp_path / "full.json") as f:
+            full = json.load(f)
+        assert len(full["windows"]["elapsed_ms"]) == 1 and "shipped_kernels" not in full
+        files = sorted(os.listdir(d))
+        assert {"p_or", "rho", "bus_vm", "topo_vect", "status"} <= {f[:-4] for f in files} and "lanes.npy" not in files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and a.shape[0] == 64 and a.size > 0 and np.isfinite(a).all() for a in arrs.values())
+        assert "storage_p" not in arrs                                          # l2rpn_case14_sandbox has no storage unit: no empty file
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_dump_outputs_samples_lanes_beyond_64_mb(tmp_path):
+    import bench
+    from grid2op_amd.engine import LaneResults
+    n = 70000
+    out = np.arange(n, dtype=np.float32)[:, None] * np.ones((1, 300), np.float32)          # 84 MB of float32 rows
+    r = LaneResults(out=out, topo_vect=np.ones((n, 4), np.int32), shunt_bus=np.zeros((n, 1), np.int32), line_status=np.ones((n, 2), bool),
+                    status=np.zeros((n, 4), np.int32), bus_vm=None, bus_va=None, _slices={"a": slice(0, 100), "b": slice(100, 300)})
+    for k in range(2):
+        bench.dump_outputs(r, str(tmp_path / f"d{k}"))
+    a = {f[:-4]: np.load(tmp_path / "d0" / f) for f in os.listdir(tmp_path / "d0")}
+    assert sorted(a) == ["a", "b", "lanes", "line_status", "shunt_bus", "status", "topo_vect"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    lanes = a["lanes"].astype(np.int64)
+    assert 0 < lanes.size < n and np.all(np.diff(lanes) > 0)
+    assert np.array_equal(a["a"][:, 0], lanes.astype(np.float32)) and a["b"].shape == (lanes.size, 200)
+    for f in os.listdir(tmp_path / "d0"):
+        assert np.array_equal(np.load(tmp_path / "d0" / f), np.load(tmp_path / "d1" / f)), f
+
+
+def test_dump_outputs_writes_missing_values_as_flagged_zeros(tmp_path):
+    """Unused buses (NaN voltages) and failed lanes (NaN rows) are written as 0 and flagged by bus_active / status: every file is finite,
+    nothing else is touched."""
+    import bench
+    from grid2op_amd.engine import LaneResults
+    n, nb = 4, 6
+    out = np.arange(n * 5, dtype=np.float32).reshape(n, 5)
+    out[2] = np.nan                                                              # lane 2 failed: no results
+    vm = np.linspace(0.9, 1.1, n * nb).reshape(n, nb)
+    vm[:, 3:] = np.nan                                                           # buses 3.. unused
+    vm[2] = np.nan
+    va = np.where(np.isnan(vm), np.nan, -vm)
+    st = np.zeros((n, 4), np.int32)
+    st[2, 0] = 3
+    r = LaneResults(out=out, topo_vect=np.ones((n, 4), np.int32), shunt_bus=np.zeros((n, 1), np.int32), line_status=np.ones((n, 2), bool),
+                    status=st, bus_vm=vm, bus_va=va, _slices={"a": slice(0, 2), "b": slice(2, 5), "c": slice(5, 5)})
+    rho = np.ones((n, 2), np.float32)
+    rho[2] = np.nan
+    bench.dump_outputs(r, str(tmp_path), (rho, np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32)))
+    a = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(np.isfinite(v).all() and v.size > 0 for v in a.values()) and "c" not in a          # a field without elements: no file
+    assert np.array_equal(a["bus_active"], np.isfinite(vm).astype(np.float32))
+    assert np.array_equal(a["bus_vm"], np.nan_to_num(vm)) and np.array_equal(a["bus_va"], np.nan_to_num(va))
+    assert np.array_equal(a["a"][[0, 1, 3]], out[[0, 1, 3], :2]) and not a["a"][2].any() and not a["rho"][2].any()
+    assert a["status"][2, 0] == 3

@@ -30,7 +30,7 @@ def _run(argv, timeout=900, full=None):
 @pytest.mark.parametrize("env_name,batch", [("l2rpn_case14_sandbox", 256), ("l2rpn_neurips_2020_track1", 96),
                                             ("l2rpn_wcci_2022_dev", 64)])       # 118 substations: the 2-wavefront kernel (BASELINE configs[3])
 def test_two_ranks_with_real_engines_equal_the_halves_of_one_rank(env_name, batch, tmp_path):
-    common = ["--env", env_name, "--steps", "12", "--warmup", "4", "--windows", "2", "--no-secondary", "--no-cpu-baseline"]
+    common = ["--env", env_name, "--steps", "12", "--warmup", "4", "--windows", "2", "--full", "--no-secondary", "--no-cpu-baseline"]
     two = str(tmp_path / "two")
     full2 = str(tmp_path / "full2.json")
     p2 = _run(["--gpus", "2", "--share-device", "--dist-backend", "gloo", "--batch", str(batch), "--dump-results", two] + common, full=full2)

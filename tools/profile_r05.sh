@@ -36,7 +36,7 @@ for w in "$@"; do
     idf) prof r05_kernels_idf118 20 $((14014*1024*20)) "step_sparse_kernel<1, 0, 1, 2, 2" "$LITE" "--steps 200 --warmup 40" --only dc_ptdf --steps 60 --warmup 20 --steps-per-launch 20 ;;
     ptdf_build) prof r05_ptdf_build_batch 1 956301312 "ptdf_build" "$MEM" "" --only ptdf_build_batch --steps 20 --warmup 5 ;;
     all) O=$R/gpurun_out/prof/r05_all; mkdir -p $O
-         rocprofv3 --kernel-trace --stats -d $O/stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/stats.log 2>&1
+         rocprofv3 --kernel-trace --stats -d $O/stats -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/stats.log 2>&1
          python profiles/summarize_rocprof.py "r05_all_kernels_bench: python bench.py --steps 20 --warmup 5 --no-cpu-baseline (1x MI355X; every kernel of the driver's run)" $(find $O/stats -name "*_results.db" | head -1) > $R/gpurun_out/prof/r05_all_kernels_bench.txt
          tail -1 $O/stats.log | cut -c1-300 ;;
   esac
