@@ -16,7 +16,7 @@ __all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
-ABI_VERSION = 323          # include/gridpf.h GPF_ABI_VERSION
+ABI_VERSION = 324          # include/gridpf.h GPF_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "gpf_last_error", "gpf_version", "gpf_set_deterministic", "gpf_device_count", "gpf_create", "gpf_destroy", "gpf_get_layout", "gpf_n_lanes",
@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = [
     "gpf_get_results_pinned", "gpf_set_profiling", "gpf_get_kernel_time", "gpf_get_plan", "gpf_device_pointers", "gpf_device_pointers_n",
     "gpf_get_counters", "gpf_upload_outage_durations", "gpf_get_cooldown", "gpf_set_cooldown", "gpf_get_trajectory_cooldown", "gpf_ptdf_build", "gpf_ptdf_build_batch", "gpf_ptdf_batch_info", "gpf_ptdf_batch_get", "gpf_ptdf_get", "gpf_ptdf_flows", "gpf_get_ptdf_flows", "gpf_ptdf_flows_rows", "gpf_get_ptdf_flows_rows", "gpf_lodf_screen",
     "gpf_jit_enable", "gpf_jit_disable", "gpf_jit_info", "gpf_jit_source",
+    "gpf_set_topo_rules", "gpf_upload_topo_actions", "gpf_set_lane_topo_actions", "gpf_topo_actions_on_device", "gpf_get_sub_cooldown",
+    "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags",
 ]
 
 
@@ -170,6 +172,15 @@ def lib() -> C.CDLL:
     L.gpf_ptdf_get.argtypes = [h, _dp]
     L.gpf_get_counters.argtypes = [h, C.POINTER(C.c_int64)]
     L.gpf_get_cooldown.argtypes = [h, i32, i32, _ip]
+    L.gpf_set_topo_rules.argtypes = [h, i32, i32, i32, i32, i32]
+    L.gpf_upload_topo_actions.argtypes = [h, i32, _ip, _ip, _bp]
+    L.gpf_set_lane_topo_actions.argtypes = [h, _ip]
+    L.gpf_topo_actions_on_device.argtypes = [h, i32]
+    L.gpf_get_sub_cooldown.argtypes = [h, i32, i32, _ip]
+    L.gpf_set_sub_cooldown.argtypes = [h, i32, i32, _ip]
+    L.gpf_get_last_bus.argtypes = [h, i32, i32, _ip]
+    L.gpf_set_last_bus.argtypes = [h, i32, i32, _ip]
+    L.gpf_get_topo_flags.argtypes = [h, i32, i32, _bp]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

@@ -24,6 +24,7 @@
 #include "gridpf_ptdf_batch.hpp"
 #include "gridpf_ptdf_group.hpp"
 #include "gridpf_redispatch.hpp"
+#include "gridpf_topo.hpp"
 #include <string>
 #include <thread>
 #include <condition_variable>
@@ -224,6 +225,19 @@ struct gpf_engine {
   DevArr<double> inj, bus_vm, bus_va, work;
   DevArr<int> topo, shunt_bus, topo_out, shunt_bus_out, status, overflow_count, disc_round, lane_table, lane_offset, tmp_lines;
   DevArr<int> cooldown;                 // [B][n_line] line cooldowns of the environment (gpf::Bufs::cooldown)
+  // topology actions of the batched acting path (gridpf_topo.hpp): allocated by the first gpf_set_topo_rules / gpf_upload_topo_actions
+  bool ta_on = false;
+  gpf::TopoRules ta_rules{};
+  DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_list, ta_list_rows, ta_off, ta_items, ta_pos_sub, ta_pos_other;
+  DevArr<unsigned char> ta_flags, ta_aff, ta_amb;
+  int ta_n_act = 0;
+  bool ta_bus_items = false;            // an entry of the table sets / changes a bus: the read-back of class changes is needed
+  bool ta_may_split = false;            // some row or last-bus entry was on a busbar >= 2 (then line-status actions can change a class key too)
+  bool ta_host = false, ta_dev = false; // the next launch carries indices set by the host / written on the device
+  std::vector<char> ta_moved;           // per lane: an action moved it to another topology class than its reset topology's (auto-reset re-keys it)
+  int ta_n_moved = 0;
+  int* ta_pin = nullptr;                // pinned read-back block: count | lane ids | rows
+  size_t ta_pin_n = 0;
   // topology-derived state of the reference topology shared by the lanes of one-step launches (gpf::KeepArgs): two blobs (Ybus in LDS /
   // in registers), allocated and keyed by the first gpf_step_n with n_steps = 1; GRIDPF_KEEP=0 at gpf_create turns it off
   DevArr<unsigned char> keep;
@@ -399,6 +413,28 @@ struct gpf_engine {
 };
 
 namespace {
+
+// the lanes' rows were sent by the host (their reset topology is their topology again)
+void topo_unmoved(gpf_engine* e, int lane0, int n) {
+  if (e->ta_n_moved == 0) return;
+  for (int k = lane0; k < lane0 + n; ++k) if (e->ta_moved[k]) { e->ta_moved[k] = 0; --e->ta_n_moved; }
+}
+
+gpf::TopoDev topo_dev(const gpf_engine* e) {
+  const gpf::GridDev& g = e->g;
+  gpf::TopoDev d{};
+  d.dim_topo = g.dim_topo; d.n_line = g.n_line; d.n_sub = g.n_sub; d.n_shunt = g.n_shunt; d.n_busbar = g.n_busbar;
+  d.line_or_pos = g.line_or_pos; d.line_ex_pos = g.line_ex_pos; d.shunt_sub = g.shunt_sub;
+  d.topo = e->topo.p; d.shunt_bus = e->shunt_bus.p; d.cooldown = e->cooldown.p; d.topo0 = e->topo0.p; d.episode = e->episode.p; d.done = e->done.p;
+  return d;
+}
+
+gpf::TopoLanes topo_lanes(const gpf_engine* e) {
+  gpf::TopoLanes t{};
+  t.act = e->ta_act.p; t.sub_cd = e->ta_sub_cd.p; t.last_bus = e->ta_last_bus.p; t.flags = e->ta_flags.p; t.aff = e->ta_aff.p;
+  t.ep_snap = e->ta_ep_snap.p; t.list = e->ta_list.p; t.list_rows = e->ta_list_rows.p; t.pos_sub = e->ta_pos_sub.p; t.pos_other = e->ta_pos_other.p;
+  return t;
+}
 
 // number of active buses and Newton unknowns of one lane (host mirror of K1's counting)
 void count_lane(const gpf_engine* e, const int* topo, const int* shunt_bus, int& nb, int& nj, int& mb) {
@@ -856,6 +892,21 @@ int reset_env_state(gpf_engine* e, int lane0, int n) {
   return GPF_OK;
 }
 
+// acting-path state of lanes [lane0, lane0 + n) back to env.reset(): no cooldown, no pending action, last known busbar = the lanes'
+// reset topology (busbar 1 where it has an open end)
+int reset_topo_state(gpf_engine* e, int lane0, int n) {
+  const gpf::GridDev& g = e->g;
+  std::vector<int> lb((size_t)n * g.dim_topo), act((size_t)n, -1);
+  for (int k = 0; k < n; ++k)
+    for (int i = 0; i < g.dim_topo; ++i) lb[(size_t)k * g.dim_topo + i] = std::max(e->h_init_topo[i], 1);
+  HIP_TRY(hipMemcpyAsync(e->ta_last_bus.p + (size_t)lane0 * g.dim_topo, lb.data(), lb.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->ta_act.p + lane0, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemsetAsync(e->ta_sub_cd.p + (size_t)lane0 * g.n_sub, 0, (size_t)n * g.n_sub * sizeof(int), e->stream));
+  HIP_TRY(hipMemsetAsync(e->ta_flags.p + (size_t)lane0 * 2, 0, (size_t)n * 2, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));                 // (the host vectors go out of scope)
+  return GPF_OK;
+}
+
 int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   HIP_TRY(hipSetDevice(e->device));
   const gpf::GridDev& g = e->g;
@@ -878,6 +929,8 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   HIP_TRY(hipMemsetAsync(e->episode.p + (size_t)lane0 * 2, 0, (size_t)n * 2 * sizeof(int), e->stream));
   HIP_TRY(hipMemsetAsync(e->status.p + (size_t)lane0 * 4, 0xFF, (size_t)n * 4 * sizeof(int), e->stream));
   if (e->env_on) { int rc_e = reset_env_state(e, lane0, n); if (rc_e != GPF_OK) return rc_e; }
+  if (e->ta_on) { int rc_t = reset_topo_state(e, lane0, n); if (rc_t != GPF_OK) return rc_t; }
+  topo_unmoved(e, lane0, n);
   HIP_TRY(hipStreamSynchronize(e->stream));
   const int init_class = topo_class_of(e, e->h_init_topo.data(), g.n_shunt ? e->h_init_shunt_bus.data() : nullptr);
   for (int k = lane0; k < lane0 + n; ++k) {
@@ -1292,6 +1345,9 @@ int gpf_destroy(gpf_handle e) {
   e->sto_sub.release(); e->sto_pos.release(); e->shunt_sub.release(); e->gen_slack.release();
   e->inj.release(); e->bus_vm.release(); e->bus_va.release(); e->work.release(); e->topo.release(); e->shunt_bus.release();
   e->topo_out.release(); e->shunt_bus_out.release(); e->status.release(); e->overflow_count.release(); e->disc_round.release(); e->cooldown.release(); e->keep.release(); e->maint_dur.release(); e->traj_cool.release();
+  e->ta_act.release(); e->ta_sub_cd.release(); e->ta_last_bus.release(); e->ta_ep_snap.release(); e->ta_list.release(); e->ta_list_rows.release();
+  e->ta_off.release(); e->ta_items.release(); e->ta_pos_sub.release(); e->ta_pos_other.release(); e->ta_flags.release(); e->ta_aff.release(); e->ta_amb.release();
+  if (e->ta_pin) (void)hipHostFree(e->ta_pin);
   e->lane_table.release(); e->lane_offset.release(); e->tmp_lines.release(); e->out.release(); e->chron.release();
   e->lane_scale.release(); e->thermal_limit.release(); e->rho.release(); e->line_status.release();
   e->d_init_inj.release(); e->d_init_topo.release(); e->d_init_shunt_bus.release();
@@ -1361,6 +1417,23 @@ namespace {
 // gpf_set_topology.  `engine_rows`: the rows were built by the library itself in its own PINNED block (gpf_simulate_batch: validated
 // action items applied to rows that came from the device) -- no validation pass, the uploads are true asynchronous DMA and nothing is
 // waited for (the block stays untouched until the stream has drained: the next user of it synchronises first).
+// the host's bookkeeping of one lane whose topology row is now `t` / `sb` (busbar / unknown counts, topology class, mirror of the
+// sent rows); true: it changed.  gpf_set_topology and the read-back of the device-side topology actions (gpf_step_n) both use it.
+bool note_lane_row(gpf_engine* e, int lane, const int* t, const int* sb) {
+  const gpf::GridDev& g = e->g;
+  if (!e->ta_may_split)                                    // (a row on a busbar >= 2: line-status actions may move lanes between classes)
+    for (int i = 0; i < g.dim_topo && !e->ta_may_split; ++i) e->ta_may_split = t[i] >= 2;
+  int* mt = e->h_lane_topo.data() + (size_t)lane * g.dim_topo;
+  int* ms = e->h_lane_sb.data() + (size_t)lane * std::max(g.n_shunt, 1);
+  if (std::memcmp(mt, t, (size_t)g.dim_topo * sizeof(int)) == 0 && (!g.n_shunt || std::memcmp(ms, sb, (size_t)g.n_shunt * sizeof(int)) == 0))
+    return false;                                          // re-sent unchanged: counts and topology class stay
+  std::memcpy(mt, t, (size_t)g.dim_topo * sizeof(int));
+  if (g.n_shunt) std::memcpy(ms, sb, (size_t)g.n_shunt * sizeof(int));
+  count_lane(e, t, sb, e->lane_nb[lane], e->lane_nj[lane], e->lane_mb[lane]);
+  e->lane_class[lane] = topo_class_of(e, t, sb);
+  return true;
+}
+
 int set_topology_rows(gpf_engine* e, int32_t lane0, int32_t n, const int32_t* topo, const int32_t* shunt_bus, bool engine_rows) {
   const gpf::GridDev& g = e->g;
   if (!engine_rows) {
@@ -1387,20 +1460,12 @@ int set_topology_rows(gpf_engine* e, int32_t lane0, int32_t n, const int32_t* to
                            hipMemcpyDeviceToHost, e->stream));
   }
   if (!engine_rows || !sb_host.empty()) HIP_TRY(hipStreamSynchronize(e->stream));
+  topo_unmoved(e, lane0, n);                               // (the rows sent are the lanes' reset topology too: topo0 above)
   bool changed = false;
   for (int k = 0; k < n; ++k) {
-    const int* t = topo + (size_t)k * g.dim_topo;
     const int* sb = nullptr;
     if (g.n_shunt) sb = shunt_bus ? shunt_bus + (size_t)k * g.n_shunt : sb_host.data() + (size_t)k * g.n_shunt;
-    int* mt = e->h_lane_topo.data() + (size_t)(lane0 + k) * g.dim_topo;
-    int* ms = e->h_lane_sb.data() + (size_t)(lane0 + k) * std::max(g.n_shunt, 1);
-    if (std::memcmp(mt, t, (size_t)g.dim_topo * sizeof(int)) == 0 && (!g.n_shunt || std::memcmp(ms, sb, (size_t)g.n_shunt * sizeof(int)) == 0))
-      continue;                                              // re-sent unchanged: counts and topology class stay
-    std::memcpy(mt, t, (size_t)g.dim_topo * sizeof(int));
-    if (g.n_shunt) std::memcpy(ms, sb, (size_t)g.n_shunt * sizeof(int));
-    count_lane(e, t, sb, e->lane_nb[lane0 + k], e->lane_nj[lane0 + k], e->lane_mb[lane0 + k]);
-    e->lane_class[lane0 + k] = topo_class_of(e, t, sb);
-    changed = true;
+    changed |= note_lane_row(e, lane0 + k, topo + (size_t)k * g.dim_topo, sb);
   }
   if (changed) e->plan_valid = false;
   return GPF_OK;
@@ -1473,6 +1538,10 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
     CP(env_target, g.n_gen); CP(env_actual, g.n_gen); CP(env_prev, g.n_gen); CP(env_already, g.n_gen); CP(env_limit, g.n_gen);
     CP(env_charge, g.n_sto); CP(env_amount_prev, 1); CP(env_curt_prev, 1); CP(env_fresh, 1); CP(env_illegal, 1);
   }
+  if (e->ta_on) {                           // the acting path's state
+    CP(ta_sub_cd, g.n_sub); CP(ta_last_bus, g.dim_topo); CP(ta_flags, 2); CP(ta_act, 1);
+    for (int k = 0; k < n; ++k) { e->ta_n_moved += e->ta_moved[src + k] - e->ta_moved[dst + k]; e->ta_moved[dst + k] = e->ta_moved[src + k]; }
+  }
 #undef CP
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
@@ -1499,9 +1568,14 @@ int gpf_fanout_n1(gpf_handle e, int32_t src, int32_t dst0, int32_t n_out, const 
     hipLaunchKernelGGL(gpf::simulate_env_copy_kernel, dim3((unsigned)n_out), dim3(64), 0, e->stream, E, e->g.n_gen, e->g.n_sto, e->sim_src.p, n_out, n_out, dst0);
     HIP_TRY(hipGetLastError());
   }
+  if (e->ta_on) {                           // ... and its acting-path state (cooldowns, last known busbars)
+    hipLaunchKernelGGL(gpf::topo_fanout_kernel, dim3((unsigned)n_out), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), src, dst0, n_out);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(e->stream));   // out_lines may be reused by the caller
   for (int k = 0; k < n_out; ++k) { e->lane_nb[dst0 + k] = e->lane_nb[src]; e->lane_nj[dst0 + k] = e->lane_nj[src]; e->lane_mb[dst0 + k] = e->lane_mb[src]; e->lane_class[dst0 + k] = e->lane_class[src];
     e->h_lane_topo[(size_t)(dst0 + k) * e->g.dim_topo] = INT_MIN; }     // a line was forced off on the device: mirror unknown
+  topo_unmoved(e, dst0, n_out);                 // (fanout_kernel writes the contingency row as the lanes' reset topology too)
   e->plan_valid = false;
   return GPF_OK;
 }
@@ -1590,7 +1664,9 @@ int gpf_solve_lane(gpf_handle e, int32_t lane, const double* inj, const int32_t*
     const bool same = std::memcmp(mt, topo, (size_t)g.dim_topo * sizeof(int)) == 0 &&
                       (!g.n_shunt || std::memcmp(ms, shunt_bus, (size_t)g.n_shunt * sizeof(int)) == 0);
     const int o_nb = e->lane_nb[lane], o_nj = e->lane_nj[lane], o_mb = e->lane_mb[lane], o_cls = e->lane_class[lane];
+    topo_unmoved(e, lane, 1);                                // (lane_scatter_kernel writes the row as the lane's reset topology too)
     if (!same) {
+      for (int i = 0; i < g.dim_topo && !e->ta_may_split; ++i) e->ta_may_split = topo[i] >= 2;
       count_lane(e, topo, g.n_shunt ? shunt_bus : nullptr, e->lane_nb[lane], e->lane_nj[lane], e->lane_mb[lane]);
       e->lane_class[lane] = topo_class_of(e, topo, g.n_shunt ? shunt_bus : nullptr);
       e->plan_valid = false;
@@ -1891,42 +1967,69 @@ int step_range(gpf_engine* e, const gpf::Bufs& b_in, int lane0, int n, int t0, i
   return GPF_OK;
 }
 
-// _BackendAction.__iadd__ restricted to topology (Action/_backendAction.py:836-919; ValueStore.set_status / change_status / set_val /
-// change_val :140-234, _aux_iadd_reconcile_disco_reco :738-765) on one topology row; items = {kind, id, value} triples
+// _BackendAction.__iadd__ restricted to topology on one topology row (gridpf_topo.hpp: the implementation the device path shares)
 void apply_topo_action(const gpf_engine* e, int* row, int* sb, const int* last, const int32_t* items, int n_items) {
-  const gpf::GridDev& g = e->g;
-  auto old = [&](int pos) { return (last && last[pos] >= 1) ? last[pos] : 1; };
-  auto reco = [&](int l) { const int po = e->h_line_or_pos[l], pe = e->h_line_ex_pos[l]; if (row[po] < 0) row[po] = old(po); if (row[pe] < 0) row[pe] = old(pe); };
-  auto disco = [&](int l) { row[e->h_line_or_pos[l]] = -1; row[e->h_line_ex_pos[l]] = -1; };
-  // III line status: change_status, then set_status (a reconnected end goes back to its last known busbar)
-  for (int k = 0; k < n_items; ++k) if (items[3 * k] == GPF_ACT_CHANGE_LINE_STATUS) {
-    const int l = items[3 * k + 1];
-    if (row[e->h_line_or_pos[l]] > 0 || row[e->h_line_ex_pos[l]] > 0) disco(l); else reco(l);
-  }
-  for (int k = 0; k < n_items; ++k) if (items[3 * k] == GPF_ACT_SET_LINE_STATUS) {
-    const int l = items[3 * k + 1], v = items[3 * k + 2];
-    if (v < 0) disco(l); else if (v > 0) reco(l);
-  }
-  bool any_bus = false;                                         // (the line ends "before" are only needed by rule V)
-  for (int k = 0; k < n_items && !any_bus; ++k) any_bus = items[3 * k] == GPF_ACT_CHANGE_BUS || (items[3 * k] == GPF_ACT_SET_BUS && items[3 * k + 2] != 0);
   static thread_local std::vector<int> or_before, ex_before;
-  if (any_bus) {
-    or_before.resize(g.n_line); ex_before.resize(g.n_line);
-    for (int l = 0; l < g.n_line; ++l) { or_before[l] = row[e->h_line_or_pos[l]]; ex_before[l] = row[e->h_line_ex_pos[l]]; }
+  or_before.resize(std::max(e->g.n_line, 1)); ex_before.resize(std::max(e->g.n_line, 1));
+  const gpf::TopoMaps m{e->h_line_or_pos.data(), e->h_line_ex_pos.data(), e->g.n_line};
+  gpf::apply_topo_action(m, row, sb, last, items, n_items, or_before.data(), ex_before.data(), 0, 1, gpf::NoSync{});
+}
+
+int topo_readback(gpf_engine* e, bool moved);
+
+// Steps 1-4 of the acting path on the device (topo_prestep_kernel), then the host's planning bookkeeping of the lanes it moved to another
+// topology class or busbar count: ONE compact read-back (count, lane ids, rows), skipped when the table cannot move a lane.
+int topo_prestep(gpf_engine* e, bool acts) {
+  const gpf::GridDev& g = e->g;
+  const bool readback = acts && g.n_busbar >= 2 && (e->ta_bus_items || e->ta_may_split);
+  if (acts) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
+  const gpf::TopoTab tab{e->ta_off.p, e->ta_items.p, e->ta_amb.p, e->ta_n_act};
+  const size_t lds = acts ? gpf::topo_prestep_lds_ints(g.dim_topo, g.n_line, g.n_sub, g.n_shunt, g.n_busbar) * sizeof(int) : 0;
+  hipLaunchKernelGGL(gpf::topo_prestep_kernel, dim3((unsigned)e->n_lanes), dim3(64), lds, e->stream, topo_dev(e), tab, topo_lanes(e),
+                     e->ta_rules, e->n_lanes, acts ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  if (!readback) return GPF_OK;
+  return topo_readback(e, true);
+}
+
+// The compact list the topology kernels left in ta_list / ta_list_rows (count, lane ids, rows) -> the host's per-lane planning bookkeeping
+// (note_lane_row: what gpf_set_topology does).  moved: the rows are action results (the lane's class may differ from its reset
+// topology's); else they are reset topologies (the lane is back on the class of the rows last sent).
+int topo_readback(gpf_engine* e, bool moved) {
+  const gpf::GridDev& g = e->g;
+  const size_t w = (size_t)g.dim_topo + g.n_shunt;
+  const size_t need = 1 + (size_t)e->n_lanes + (size_t)e->n_lanes * w;
+  if (e->ta_pin_n < need) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->ta_pin) (void)hipHostFree(e->ta_pin);
+    e->ta_pin = nullptr; e->ta_pin_n = 0;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->ta_pin), need * sizeof(int), hipHostMallocDefault));
+    e->ta_pin_n = need;
   }
-  // IV change_bus, then set_bus
-  bool bus_modif = false;
-  for (int k = 0; k < n_items; ++k) if (items[3 * k] == GPF_ACT_CHANGE_BUS) { int& v = row[items[3 * k + 1]]; if (v > 0) v = (1 - v) + 2; bus_modif = true; }
-  for (int k = 0; k < n_items; ++k) if (items[3 * k] == GPF_ACT_SET_BUS && items[3 * k + 2] != 0) { row[items[3 * k + 1]] = items[3 * k + 2]; bus_modif = true; }
-  // V a line with an open end is open; a line that was open and got a bus on one end is reconnected (other end: last known busbar)
-  if (bus_modif)
-    for (int l = 0; l < g.n_line; ++l) {
-      const int o_ = row[e->h_line_or_pos[l]], x_ = row[e->h_line_ex_pos[l]];
-      const bool d_now = or_before[l] == -1 || o_ == -1 || ex_before[l] == -1 || x_ == -1;
-      const bool r_now = or_before[l] == -1 && (o_ >= 1 || x_ >= 1);
-      if (r_now) reco(l); else if (d_now) disco(l);
-    }
-  for (int k = 0; k < n_items; ++k) if (items[3 * k] == GPF_ACT_SET_SHUNT_BUS && sb && items[3 * k + 2] != 0) sb[items[3 * k + 1]] = items[3 * k + 2];
+  HIP_TRY(hipMemcpyAsync(e->ta_pin, e->ta_list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const int cnt = e->ta_pin[0];
+  if (cnt <= 0) return GPF_OK;
+  if (cnt > e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back count)");
+  int* ids = e->ta_pin + 1;
+  int* rows = ids + e->n_lanes;
+  HIP_TRY(hipMemcpyAsync(ids, e->ta_list.p + 1, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(rows, e->ta_list_rows.p, (size_t)cnt * w * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  std::vector<int> order(cnt);                           // lane order: classes are created in the order gpf_set_topology would create them
+  for (int i = 0; i < cnt; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [ids](int a, int b) { return ids[a] < ids[b]; });
+  bool changed = false;
+  for (int i : order) {
+    const int lane = ids[i];
+    if (lane < 0 || lane >= e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back lane)");
+    const int* t = rows + (size_t)i * w;
+    changed |= note_lane_row(e, lane, t, g.n_shunt ? t + g.dim_topo : nullptr);
+    if (moved && !e->ta_moved[lane]) { e->ta_moved[lane] = 1; ++e->ta_n_moved; }
+    if (!moved && e->ta_moved[lane]) { e->ta_moved[lane] = 0; --e->ta_n_moved; }
+  }
+  if (changed) e->plan_valid = false;
+  return GPF_OK;
 }
 }  // namespace
 extern "C" {
@@ -1937,9 +2040,38 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_step_n: no chronics uploaded");
   if (e->traj_cap && n_steps > e->traj_cap)
     return fail(GPF_E_INVALID, "gpf_step_n: n_steps exceeds the trajectory buffer (gpf_set_trajectory sizes it; 0 releases it)");
+  const bool acts = e->ta_on && (e->ta_host || e->ta_dev);
+  if (acts && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: a launch that carries topology actions must be a one-step launch (the line-cooldown rule needs the "
+                               "action step's trips and outages): use n_steps = 1");
+  if (acts && e->ta_rules.cd_line > 0 && !o->track_cooldown)
+    return fail(GPF_E_INVALID, "gpf_step_n: topology actions with cooldown_line > 0 need gpf_step_opts::track_cooldown (the agents' line "
+                               "cooldowns are only counted down by a launch that maintains the line cooldowns)");
+  if (e->ta_on && e->ta_n_moved > 0 && o->auto_reset && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: auto-reset in a multi-step launch while topology actions keep lanes on another topology class than "
+                               "their reset topology (the launch plan cannot follow a reset inside the launch): use n_steps = 1, or send the "
+                               "lanes' rows with gpf_set_topology / gpf_reset_lanes");
+  if (acts && e->env_on && (e->env_act_r || e->env_act_s || e->env_act_c))
+    return fail(GPF_E_INVALID, "gpf_step_n: topology actions and injection actions (redispatch / storage / curtailment) are pending for the same "
+                               "launch: combined actions are not supported (in the reference the illegality of either part cancels both)");
   HIP_TRY(hipSetDevice(e->device));
-  int rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
+  int rc = GPF_OK;
+  if (e->ta_on) {
+    if (acts) { e->ta_host = e->ta_dev = false; e->dev_topo_dirty = true; }   // consumed by this launch, whatever happens below
+    rc = topo_prestep(e, acts);
+    if (rc != GPF_OK) return rc;
+  }
+  rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
   if (rc != GPF_OK) return rc;
+  if (e->ta_on) {
+    // lanes an action moved to another class than their reset topology's: an auto-reset puts them back, the host re-keys them
+    const bool list_resets = o->auto_reset && e->ta_n_moved > 0;
+    if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
+    hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), e->ta_rules,
+                       e->n_lanes, acts ? 1 : 0, n_steps, list_resets ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    if (list_resets) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
+  }
   e->traj_valid = e->traj_cap ? n_steps : 0;
   if (e->env_on) {                          // the actions were consumed by this launch (a held storage action stays)
     // (the kernels only read an action buffer whose flag is set -- EnvDyn::act_* is NULL otherwise --, so "consumed" is the flag: no
@@ -1949,6 +2081,170 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     e->env_act_c = false;                   // (the curtailment limits live on in the lanes' state)
   }
   return GPF_OK;
+}
+
+}  // extern "C"
+namespace {
+// the acting path's buffers + static maps, once per engine (lanes start as after gpf_reset_lanes)
+int topo_enable(gpf_engine* e) {
+  if (e->ta_on) return GPF_OK;
+  const gpf::GridDev& g = e->g;
+  const size_t lds = gpf::topo_prestep_lds_ints(g.dim_topo, g.n_line, g.n_sub, g.n_shunt, g.n_busbar) * sizeof(int);
+  if (lds > 64 * 1024) return fail(GPF_E_CAPACITY, "topology actions: the grid's rows do not fit the 64 KiB of LDS of the pre-step kernel");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t cap = (size_t)e->cap_lanes;
+  std::vector<int> pos_sub(g.dim_topo, 0), pos_other(g.dim_topo, -1);
+  for (int l = 0; l < g.n_line; ++l) {
+    pos_sub[e->h_line_or_pos[l]] = e->h_line_or_sub[l]; pos_sub[e->h_line_ex_pos[l]] = e->h_line_ex_sub[l];
+    pos_other[e->h_line_or_pos[l]] = e->h_line_ex_pos[l]; pos_other[e->h_line_ex_pos[l]] = e->h_line_or_pos[l];
+  }
+  for (int i = 0; i < g.n_gen; ++i) pos_sub[e->h_gen_pos[i]] = e->h_gen_sub[i];
+  for (int i = 0; i < g.n_load; ++i) pos_sub[e->h_load_pos[i]] = e->h_load_sub[i];
+  for (int i = 0; i < g.n_sto; ++i) pos_sub[e->h_sto_pos[i]] = e->h_sto_sub[i];
+  HIP_TRY(e->ta_pos_sub.upload(pos_sub.data(), pos_sub.size()));
+  HIP_TRY(e->ta_pos_other.upload(pos_other.data(), pos_other.size()));
+  HIP_TRY(e->ta_act.alloc(cap)); HIP_TRY(e->ta_sub_cd.alloc(cap * g.n_sub)); HIP_TRY(e->ta_last_bus.alloc(cap * g.dim_topo));
+  HIP_TRY(e->ta_ep_snap.alloc(cap)); HIP_TRY(e->ta_list.alloc(cap + 1)); HIP_TRY(e->ta_list_rows.alloc(cap * ((size_t)g.dim_topo + g.n_shunt)));
+  HIP_TRY(e->ta_flags.alloc(cap * 2)); HIP_TRY(e->ta_aff.alloc(cap * ((size_t)g.n_line + g.n_sub)));
+  HIP_TRY(hipMemsetAsync(e->ta_aff.p, 0, cap * ((size_t)g.n_line + g.n_sub), e->stream));
+  e->ta_moved.assign(cap, 0);
+  e->ta_n_moved = 0;
+  e->ta_on = true;
+  for (int v : e->h_init_topo) e->ta_may_split |= v >= 2;
+  return reset_topo_state(e, 0, (int)cap);
+}
+}  // namespace
+extern "C" {
+
+int gpf_set_topo_rules(gpf_handle e, int32_t on, int32_t max_sub_changed, int32_t max_line_status_changed, int32_t cooldown_sub,
+                       int32_t cooldown_line) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_set_topo_rules: null");
+  if (max_sub_changed < 0 || max_line_status_changed < 0 || cooldown_sub < 0 || cooldown_line < 0)
+    return fail(GPF_E_INVALID, "gpf_set_topo_rules: negative parameter");
+  int rc = topo_enable(e);
+  if (rc != GPF_OK) return rc;
+  e->ta_rules = gpf::TopoRules{on ? 1 : 0, max_sub_changed, max_line_status_changed, cooldown_sub, cooldown_line};
+  return GPF_OK;
+}
+
+int gpf_upload_topo_actions(gpf_handle e, int32_t n_act, const int32_t* act_off, const int32_t* act_items, uint8_t* ambiguous) {
+  if (!e || n_act < 0 || (n_act > 0 && !act_off)) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad arguments");
+  const gpf::GridDev& g = e->g;
+  const int n_items_total = n_act ? act_off[n_act] : 0;
+  if (n_act && (act_off[0] != 0 || (n_items_total > 0 && !act_items))) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action offsets");
+  for (int k = 0; k < n_act; ++k) if (act_off[k + 1] < act_off[k]) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action offsets");
+  bool bus_items = false;
+  for (int q = 0; q < n_items_total; ++q) {                  // (the validation of gpf_simulate_batch)
+    const int kind = act_items[3 * q], id = act_items[3 * q + 1], v = act_items[3 * q + 2];
+    const bool pos_kind = kind == GPF_ACT_SET_BUS || kind == GPF_ACT_CHANGE_BUS, line_kind = kind == GPF_ACT_SET_LINE_STATUS || kind == GPF_ACT_CHANGE_LINE_STATUS;
+    if (!(pos_kind || line_kind || kind == GPF_ACT_SET_SHUNT_BUS) || id < 0 || (pos_kind && id >= g.dim_topo) || (line_kind && id >= g.n_line) ||
+        (kind == GPF_ACT_SET_SHUNT_BUS && id >= g.n_shunt) || ((kind == GPF_ACT_SET_BUS || kind == GPF_ACT_SET_SHUNT_BUS) && (v < -1 || v > g.n_busbar)) ||
+        (kind == GPF_ACT_CHANGE_BUS && g.n_busbar != 2))
+      return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action item (kind, id or bus; change_bus needs exactly 2 busbars per substation)");
+    bus_items |= kind == GPF_ACT_CHANGE_BUS || kind == GPF_ACT_SET_SHUNT_BUS || (kind == GPF_ACT_SET_BUS && v != 0);
+  }
+  // static ambiguity of every entry (BaseAction._check_for_ambiguity, Action/baseAction.py:3668-3760 -- the topology kinds)
+  std::vector<unsigned char> amb((size_t)n_act, 0);
+  std::vector<int> setv(g.dim_topo), chg(g.dim_topo), setl(g.n_line), swl(g.n_line);
+  for (int k = 0; k < n_act; ++k) {
+    std::fill(setv.begin(), setv.end(), 0); std::fill(chg.begin(), chg.end(), 0); std::fill(setl.begin(), setl.end(), 0); std::fill(swl.begin(), swl.end(), 0);
+    for (int q = act_off[k]; q < act_off[k + 1]; ++q) {
+      const int kind = act_items[3 * q], id = act_items[3 * q + 1], v = act_items[3 * q + 2];
+      if (kind == GPF_ACT_SET_BUS) setv[id] = v;
+      else if (kind == GPF_ACT_CHANGE_BUS) chg[id] = 1;
+      else if (kind == GPF_ACT_SET_LINE_STATUS) setl[id] = v;
+      else if (kind == GPF_ACT_CHANGE_LINE_STATUS) swl[id] = 1;
+    }
+    bool a = false;
+    for (int p = 0; p < g.dim_topo && !a; ++p) a = chg[p] && setv[p] != 0;              // set_bus and change_bus of one element
+    for (int l = 0; l < g.n_line && !a; ++l) {
+      const int po = e->h_line_or_pos[l], pe = e->h_line_ex_pos[l];
+      a = (swl[l] && setl[l] != 0)                                                       // set and change of one line status
+          || (setv[po] == -1 && setv[pe] > 0) || (setv[pe] == -1 && setv[po] > 0)         // one end set to -1, the other to a bus
+          || (setl[l] == -1 && (setv[po] > 0 || setv[pe] > 0 || chg[po] || chg[pe]))       // disconnected and (re)assigned / changed
+          || (setl[l] == 1 && (setv[po] == -1 || setv[pe] == -1 || chg[po] || chg[pe]));   // reconnected and disconnected / changed
+    }
+    amb[k] = a ? 1 : 0;
+  }
+  int rc = topo_enable(e);
+  if (rc != GPF_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));                 // (a launch in flight may read the old table)
+  e->ta_off.release(); e->ta_items.release(); e->ta_amb.release();
+  e->ta_n_act = 0;
+  if (n_act) {
+    HIP_TRY(e->ta_off.upload(act_off, (size_t)n_act + 1));
+    if (n_items_total) HIP_TRY(e->ta_items.upload(act_items, 3 * (size_t)n_items_total));
+    HIP_TRY(e->ta_amb.upload(amb.data(), amb.size()));
+    e->ta_n_act = n_act;
+  }
+  e->ta_bus_items = bus_items;
+  for (int q = 0; q < n_items_total; ++q)
+    e->ta_may_split |= (act_items[3 * q] == GPF_ACT_SET_BUS && act_items[3 * q + 2] >= 2) || act_items[3 * q] == GPF_ACT_CHANGE_BUS;
+  if (ambiguous) std::memcpy(ambiguous, amb.data(), amb.size());
+  return GPF_OK;
+}
+
+int gpf_set_lane_topo_actions(gpf_handle e, const int32_t* index) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_set_lane_topo_actions: null");
+  if (!index) { e->ta_host = false; return GPF_OK; }
+  int rc = topo_enable(e);
+  if (rc != GPF_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(e->ta_act.p, index, (size_t)e->n_lanes * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));                 // (the caller may reuse `index`)
+  e->ta_host = true;
+  return GPF_OK;
+}
+
+int gpf_topo_actions_on_device(gpf_handle e, int32_t on) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_topo_actions_on_device: null");
+  int rc = topo_enable(e);
+  if (rc != GPF_OK) return rc;
+  e->ta_dev = on != 0;
+  return GPF_OK;
+}
+}  // extern "C"
+namespace {
+template <typename T>
+int topo_rows_io(gpf_engine* e, DevArr<T>& arr, size_t stride, int lane0, int n, T* host, bool to_device, const char* who) {
+  if (!check_range(e, lane0, n) || (!host && n)) return fail(GPF_E_INVALID, std::string(who) + ": bad range");
+  int rc = topo_enable(e);
+  if (rc != GPF_OK) return rc;
+  if (n == 0 || stride == 0) return GPF_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  T* d = arr.p + (size_t)lane0 * stride;
+  if (to_device) HIP_TRY(hipMemcpyAsync(d, host, (size_t)n * stride * sizeof(T), hipMemcpyHostToDevice, e->stream));
+  else HIP_TRY(hipMemcpyAsync(host, d, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return GPF_OK;
+}
+}  // namespace
+extern "C" {
+
+int gpf_get_sub_cooldown(gpf_handle e, int32_t lane0, int32_t n, int32_t* sub_cooldown) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_get_sub_cooldown: null");
+  return topo_rows_io<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, sub_cooldown, false, "gpf_get_sub_cooldown");
+}
+int gpf_set_sub_cooldown(gpf_handle e, int32_t lane0, int32_t n, const int32_t* sub_cooldown) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_set_sub_cooldown: null");
+  if (sub_cooldown) for (size_t i = 0; i < (size_t)std::max(n, 0) * e->g.n_sub; ++i)
+    if (sub_cooldown[i] < 0) return fail(GPF_E_INVALID, "gpf_set_sub_cooldown: negative cooldown");
+  return topo_rows_io<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, const_cast<int32_t*>(sub_cooldown), true, "gpf_set_sub_cooldown");
+}
+int gpf_get_last_bus(gpf_handle e, int32_t lane0, int32_t n, int32_t* last_bus) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_get_last_bus: null");
+  return topo_rows_io<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, last_bus, false, "gpf_get_last_bus");
+}
+int gpf_set_last_bus(gpf_handle e, int32_t lane0, int32_t n, const int32_t* last_bus) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_set_last_bus: null");
+  if (last_bus) for (size_t i = 0; i < (size_t)std::max(n, 0) * e->g.dim_topo; ++i) {
+    if (last_bus[i] < 1 || last_bus[i] > e->g.n_busbar) return fail(GPF_E_INVALID, "gpf_set_last_bus: busbars must be 1..n_busbar");
+    e->ta_may_split |= last_bus[i] >= 2;
+  }
+  return topo_rows_io<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, const_cast<int32_t*>(last_bus), true, "gpf_set_last_bus");
+}
+int gpf_get_topo_flags(gpf_handle e, int32_t lane0, int32_t n, uint8_t* flags) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_get_topo_flags: null");
+  return topo_rows_io<unsigned char>(e, e->ta_flags, 2, lane0, n, flags, false, "gpf_get_topo_flags");
 }
 
 int gpf_set_storage_params(gpf_handle e, const double* emax, const double* emin, const double* loss, const double* eff_charge,
@@ -3427,6 +3723,8 @@ int gpf_device_pointers_n(gpf_handle e, void** out, int32_t n_ptrs, void** strea
   ptrs[22] = e->env_on ? e->env_act_redisp.p : nullptr; ptrs[23] = e->env_on ? e->env_act_storage.p : nullptr;
   ptrs[24] = e->env_on ? e->env_act_curtail.p : nullptr; ptrs[25] = e->env_on ? e->env_target.p : nullptr;
   ptrs[26] = e->env_on ? e->env_actual.p : nullptr; ptrs[27] = e->env_on ? e->env_charge.p : nullptr;
+  ptrs[28] = e->ta_on ? e->ta_act.p : nullptr; ptrs[29] = e->ta_on ? e->ta_sub_cd.p : nullptr;
+  ptrs[30] = e->ta_on ? e->ta_flags.p : nullptr; ptrs[31] = e->ta_on ? e->ta_last_bus.p : nullptr;
   for (int i = 0; i < n_ptrs; ++i) out[i] = i < GPF_N_DEVICE_POINTERS ? ptrs[i] : nullptr;     // never writes beyond the caller's array
   if (stream) *stream = e->stream;
   return GPF_OK;

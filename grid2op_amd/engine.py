@@ -550,6 +550,62 @@ class PowerFlowEngine:
         check(self._lib.gpf_lane_actions_on_device(self._h, int(bool(redispatch)), int(bool(storage_power)), int(bool(curtailment)),
                                                    int(bool(hold_storage))), "gpf_lane_actions_on_device")
 
+    # ---- topology actions in the batched step (include/gridpf.h: gpf_upload_topo_actions) ------------------------------------
+    def set_topo_rules(self, max_sub_changed: int = 1, max_line_status_changed: int = 1, cooldown_sub: int = 0, cooldown_line: int = 0,
+                       legal_rules: bool = True):
+        """Parameters.MAX_SUB_CHANGED / MAX_LINE_STATUS_CHANGED (DefaultRules; ``legal_rules=False``: AlwaysLegal) and
+        NB_TIMESTEP_COOLDOWN_SUB / NB_TIMESTEP_COOLDOWN_LINE of the topology actions of the batched step."""
+        check(self._lib.gpf_set_topo_rules(self._h, int(bool(legal_rules)), int(max_sub_changed), int(max_line_status_changed),
+                                           int(cooldown_sub), int(cooldown_line)), "gpf_set_topo_rules")
+
+    def upload_topo_actions(self, actions) -> np.ndarray:
+        """The action table of the topology actions (dicts as `pack_actions` takes them); returns the static ambiguity flags (bool ``[n]``).
+        Lanes then pick an entry per launch: `set_lane_topo_actions` (host) or ``device_views()["act_topo"]`` + `topo_actions_on_device`."""
+        off, items = self.pack_actions(actions)
+        n = len(off) - 1
+        amb = np.zeros(max(n, 1), dtype=np.uint8)
+        items = np.ascontiguousarray(items, dtype=np.int32)
+        check(self._lib.gpf_upload_topo_actions(self._h, n, ptr(off, C.c_int32), ptr(items if items.size else None, C.c_int32),
+                                                ptr(amb, C.c_uint8)), "gpf_upload_topo_actions")
+        return amb[:n].astype(bool)
+
+    def set_lane_topo_actions(self, index):
+        """Entry of the action table every lane plays at the NEXT launch (int ``[n_lanes]``, -1 = do nothing; None: none) -- that launch
+        must be a one-step launch."""
+        a = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(self.n_lanes)
+        check(self._lib.gpf_set_lane_topo_actions(self._h, ptr(a, C.c_int32)), "gpf_set_lane_topo_actions")
+
+    def topo_actions_on_device(self, on: bool = True):
+        """The NEXT launch takes the indices written into ``device_views()["act_topo"]`` (on ``views["stream"]`` or ordered before it)."""
+        check(self._lib.gpf_topo_actions_on_device(self._h, int(bool(on))), "gpf_topo_actions_on_device")
+
+    def _topo_rows(self, fn, cols, dtype, ctype, lane0, n):
+        lane0, n = self._range(lane0, n)
+        out = np.empty((n, cols), dtype=dtype)
+        check(getattr(self._lib, fn)(self._h, lane0, n, ptr(out, ctype)), fn)
+        return out
+
+    def sub_cooldown(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """obs.time_before_cooldown_sub of the lanes, int32 ``[n, n_sub]``."""
+        return self._topo_rows("gpf_get_sub_cooldown", self.model.n_sub, np.int32, C.c_int32, lane0, n)
+
+    def set_sub_cooldown(self, sub_cooldown, lane0: int = 0):
+        c = np.ascontiguousarray(sub_cooldown, dtype=np.int32).reshape(-1, self.model.n_sub)
+        check(self._lib.gpf_set_sub_cooldown(self._h, int(lane0), c.shape[0], ptr(c, C.c_int32)), "gpf_set_sub_cooldown")
+
+    def last_bus(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Last known busbar of every element (where a reconnected line end goes back to), int32 ``[n, dim_topo]``."""
+        return self._topo_rows("gpf_get_last_bus", self.model.dim_topo, np.int32, C.c_int32, lane0, n)
+
+    def set_last_bus(self, last_bus, lane0: int = 0):
+        c = np.ascontiguousarray(last_bus, dtype=np.int32).reshape(-1, self.model.dim_topo)
+        check(self._lib.gpf_set_last_bus(self._h, int(lane0), c.shape[0], ptr(c, C.c_int32)), "gpf_set_last_bus")
+
+    def topo_action_flags(self, lane0: int = 0, n: Optional[int] = None):
+        """(is_illegal, is_ambiguous) bool ``[n]`` of the last launch that carried topology actions."""
+        f = self._topo_rows("gpf_get_topo_flags", 2, np.uint8, C.c_uint8, lane0, n)
+        return f[:, 0].astype(bool), f[:, 1].astype(bool)
+
     def set_gen_renewable(self, renewable):
         """``gen_renewable`` mask (curtailment only acts on these generators); None switches curtailment off."""
         r = None if renewable is None else np.ascontiguousarray(renewable, dtype=np.uint8).reshape(self.model.n_gen)
@@ -651,12 +707,14 @@ class PowerFlowEngine:
         ``topo_vect``, ``line_status`` uint8, ``overflow_count``, ``done`` uint8, ``episode`` int32 ``[n_lanes, 2]``, ``inj``
         float64, ``bus_vm`` / ``bus_va`` float64; with the environment dynamics on also the action buffers ``act_redispatch`` /
         ``act_curtail`` ``[n_lanes, n_gen]``, ``act_storage`` ``[n_lanes, n_storage]`` (`lane_actions_on_device`) and
-        ``target_dispatch`` / ``actual_dispatch`` / ``storage_charge`` float32 (obs.target_dispatch, ...).  The engine works on its own HIP stream: call `sync` (or make the consumer's
+        ``target_dispatch`` / ``actual_dispatch`` / ``storage_charge`` float32 (obs.target_dispatch, ...); once topology actions are enabled
+        (`set_topo_rules` / `upload_topo_actions`) also ``act_topo`` int32 ``[n_lanes, 1]`` (`topo_actions_on_device`), ``sub_cooldown``
+        ``[n_lanes, n_sub]``, ``topo_flags`` uint8 ``[n_lanes, 2]`` and ``last_bus`` ``[n_lanes, dim_topo]``.  The engine works on its own HIP stream: call `sync` (or make the consumer's
         stream wait on ``views["stream"]``, a ``torch.cuda.ExternalStream``) before reading."""
         import torch
-        ptrs = (C.c_void_p * 28)()
+        ptrs = (C.c_void_p * 32)()
         stream = C.c_void_p()
-        check(self._lib.gpf_device_pointers_n(self._h, ptrs, 28, C.byref(stream)), "gpf_device_pointers_n")
+        check(self._lib.gpf_device_pointers_n(self._h, ptrs, 32, C.byref(stream)), "gpf_device_pointers_n")
         cap = self._lib.gpf_lane_capacity(self._h)
         m = self.model
         dev = torch.device("cuda", self.device)
@@ -678,7 +736,9 @@ class PowerFlowEngine:
              "disc_round": view(15, m.n_line, "<i4"),
              "act_redispatch": view(22, m.n_gen, "<f4"), "act_storage": view(23, m.n_storage, "<f4"), "act_curtail": view(24, m.n_gen, "<f4"),
              "target_dispatch": view(25, m.n_gen, "<f4"), "actual_dispatch": view(26, m.n_gen, "<f4"),
-             "storage_charge": view(27, m.n_storage, "<f4")}
+             "storage_charge": view(27, m.n_storage, "<f4"),
+             "act_topo": view(28, 1, "<i4"), "sub_cooldown": view(29, m.n_sub, "<i4"), "topo_flags": view(30, 2, "|u1"),
+             "last_bus": view(31, m.dim_topo, "<i4")}
 
         def tview(idx, cols, typestr):       # trajectory buffers: [cap_steps][cap][cols]
             if cols == 0 or not ptrs[idx] or not getattr(self, "_traj_cap", 0):

@@ -350,6 +350,43 @@ class ShardedEngine:
         for eng in self.engines:
             eng.lane_actions_on_device(*a, **kw)
 
+    # topology actions: the table and the rules go to every device, indices / per-lane state are cut by block
+    def set_topo_rules(self, *a, **kw):
+        for eng in self.engines:
+            eng.set_topo_rules(*a, **kw)
+
+    def upload_topo_actions(self, actions):
+        return [eng.upload_topo_actions(actions) for eng in self.engines][0]
+
+    def set_lane_topo_actions(self, index):
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.set_lane_topo_actions(None if index is None else np.asarray(index)[b0:b0 + bn])
+
+    def topo_actions_on_device(self, on: bool = True):
+        """every device's ``act_topo`` buffer holds the next launch's indices of its own lanes"""
+        for eng in self.engines:
+            eng.topo_actions_on_device(on)
+
+    def sub_cooldown(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.sub_cooldown(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
+    def set_sub_cooldown(self, sub_cooldown, lane0: int = 0):
+        c = np.asarray(sub_cooldown).reshape(-1, self.model.n_sub)
+        for eng, l0, k, off in self._parts(lane0, c.shape[0]):
+            eng.set_sub_cooldown(c[off:off + k], lane0=l0)
+
+    def last_bus(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.last_bus(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
+    def set_last_bus(self, last_bus, lane0: int = 0):
+        c = np.asarray(last_bus).reshape(-1, self.model.dim_topo)
+        for eng, l0, k, off in self._parts(lane0, c.shape[0]):
+            eng.set_last_bus(c[off:off + k], lane0=l0)
+
+    def topo_action_flags(self, lane0: int = 0, n=None):
+        parts = [eng.topo_action_flags(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(2))
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

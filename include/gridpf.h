@@ -105,8 +105,8 @@ const char* gpf_last_error(void);
  * call (grid2op_amd/_capi.py does): 300 = round 4 (gpf_set_trajectory(h, cap, what), 22 device pointers, GPF_ST_REDISPATCH,
  * gpf_device_pointers_n); 310 = + gpf_jit_*, GPF_E_UNSUPPORTED, gpf_set_profiling mode 3; 321 = 28 device pointers (action buffers and
  * dispatch / charge state of the environment dynamics), gpf_lane_actions_on_device; 322 = + gpf_get_results_pinned; 323 = gpf_step_opts::track_cooldown,
- * GPF_DEVICE_NONE (header-only handles). */
-#define GPF_ABI_VERSION 323
+ * GPF_DEVICE_NONE (header-only handles); 324 = 32 device pointers, topology actions in the batched step (gpf_upload_topo_actions ...). */
+#define GPF_ABI_VERSION 324
 int gpf_version(void);
 /* Bitwise run-to-run reproducibility is the DEFAULT on every grid: the same lane inputs give bit-identical results from run to
  * run and whatever the lane's position in the batch (grid2op's determinism contract: same seeds -> same episode,
@@ -247,7 +247,8 @@ typedef struct gpf_step_opts {
                             gpf_get_trajectory_cooldown; cleared by gpf_reset_lanes and by an auto-reset, copied by gpf_copy_lanes,
                             gpf_fanout_n1 and gpf_simulate_batch -- whose scratch step never maintains them (one look-ahead step on the
                             forecast tables: the source's counters are what obs.simulate starts from, _obsEnv.py:321-428).
-                            (Cooldowns caused by the agents' own line / substation actions belong to the caller: a DoNothing step has none.) */
+                            (Cooldowns caused by the agents' own line / substation actions: the acting path of gpf_upload_topo_actions
+                            books them on the device when it is enabled; otherwise they belong to the caller -- a DoNothing step has none.) */
   int32_t nb_ts_reco;    /* Parameters.NB_TIMESTEP_RECONNECTION (default 10; >= 0): the cooldown of a line the protections trip;
                             only read when track_cooldown != 0 */
 } gpf_step_opts;
@@ -372,6 +373,59 @@ int gpf_simulate_batch(gpf_handle h, int32_t t_obs, int32_t time_step, int32_t n
                        const int32_t* act_off, const int32_t* act_items, const int32_t* last_bus, int32_t dst_lane0,
                        const gpf_step_opts* opts);
 
+/* ---- topology actions in the batched step (what BaseEnv.step does between the agent and the backend for the topology part of an
+ * action, Environment/baseEnv.py:3562-3931, on the device for every lane; grid2op_amd/csrc/gridpf_topo.hpp) ------------------------------
+ * A launch of gpf_step_n that carries topology actions takes, for every lane, the entry act_topo[lane] of an uploaded action table
+ * (-1: do nothing) and, before the step: rejects an ambiguous entry (BaseAction._check_for_ambiguity, Action/baseAction.py:3668-3760:
+ * static per entry, computed here at upload; an index outside the table written on the device counts as ambiguous), computes its
+ * impact with the lane's line status before the step (get_topological_impact, Action/baseAction.py:1782-2020), checks the rules
+ * (Rules/DefaultRules.py = LookParam.py:28-53 + PreventReconnection.py:23-60 against the lane's line and substation cooldowns), turns an
+ * ambiguous or illegal action into do-nothing with its flag set (baseEnv.py:3700-3770) and applies a legal one to the lane's topology
+ * row as gpf_simulate_batch does (a reconnected end goes back to the lane's last known busbar).  After the step (baseEnv.py:3346-3395):
+ * lines the action affected whose cooldown is below cooldown_line get cooldown_line (after the step's own cooldown update --
+ * gpf_step_opts::track_cooldown), substation cooldowns are decremented and the affected substations set to cooldown_sub, and the last
+ * known busbar of every connected element is updated (_BackendAction.update_state, Action/_backendAction.py:1533-1555).  A
+ * multi-step launch without actions decrements the substation cooldowns by its step count.  A lane that auto-resets is cleared (no
+ * substation cooldown, last known busbar = its reset topology); a lane whose step failed without auto-reset books nothing.
+ * Rules:
+ *   - a launch that carries topology actions must be a one-step launch (GPF_E_INVALID otherwise: the line-cooldown rule needs the
+ *     action step's trips and outages);
+ *   - topology actions and injection actions (gpf_set_lane_actions / gpf_lane_actions_on_device / gpf_set_lane_curtailment, a held
+ *     storage action included) pending for the same launch: GPF_E_INVALID.  Combined actions are out of scope: in the reference the
+ *     illegality of either part cancels both, a coupling that reaches into the dynamics of the step kernel;
+ *   - cooldown_line > 0 needs gpf_step_opts::track_cooldown on the action launch (GPF_E_INVALID otherwise): the agents' line cooldowns
+ *     are counted down by the launches that maintain the line cooldowns, never by the acting path itself;
+ *   - an auto-reset puts a lane an action moved to another topology class back on its reset topology: after such a one-step launch the
+ *     host reads those lanes back and re-keys them (one more synchronisation, only while moved lanes exist); a MULTI-step launch with
+ *     auto_reset while any lane is on a moved class is refused (GPF_E_INVALID: the plan of a launch cannot follow a reset inside it);
+ *   - the pending indices are consumed by the launch that takes them, also when it fails after the pre-step (the rows may already be
+ *     rewritten: reset or re-send the lanes after a failed launch);
+ *   - also out of scope: RulesByArea (l2rpn_idf_2023), the opponent, PreventDiscoStorageModif.
+ * The launch planner needs every lane's topology class: the pre-step kernel lists the lanes whose class key or busbar count changed
+ * and the host reads that one compact list back (skipped when no entry of the table can change a class).  The auto-reset target
+ * (the rows last sent with gpf_set_topology) is not changed by an action.
+ *   gpf_set_topo_rules        : on != 0: DefaultRules with Parameters.MAX_SUB_CHANGED / MAX_LINE_STATUS_CHANGED; on = 0: AlwaysLegal.
+ *                               cooldown_sub / cooldown_line: NB_TIMESTEP_COOLDOWN_SUB / NB_TIMESTEP_COOLDOWN_LINE (0: not booked).
+ *   gpf_upload_topo_actions   : the table in the encoding of gpf_simulate_batch (act_off[n_act + 1], act_items[][3], validated the same
+ *                               way); ambiguous[n_act] (may be NULL) receives the static ambiguity flags.  n_act = 0 empties it.
+ *   gpf_set_lane_topo_actions : index[n_lanes] of the NEXT launch from the host (NULL: none); consumed by that launch.
+ *   gpf_topo_actions_on_device: on != 0: the next launch takes the indices written into the device buffer act_topo (gpf_device_pointers
+ *                               entry 28) on the engine's stream or ordered before the launch; consumed by that launch.
+ *   gpf_get/set_sub_cooldown  : [n][n_sub] obs.time_before_cooldown_sub.      gpf_get/set_last_bus: [n][dim_topo] busbars 1..n_busbar.
+ *   gpf_get_topo_flags        : [n][2] {is_illegal, is_ambiguous} of the last launch that carried actions.
+ * The first of these calls enables the acting path (buffers for every lane); gpf_reset_lanes / auto-reset clear its state,
+ * gpf_copy_lanes / gpf_fanout_n1 copy it. */
+int gpf_set_topo_rules(gpf_handle h, int32_t on, int32_t max_sub_changed, int32_t max_line_status_changed, int32_t cooldown_sub,
+                       int32_t cooldown_line);
+int gpf_upload_topo_actions(gpf_handle h, int32_t n_act, const int32_t* act_off, const int32_t* act_items, uint8_t* ambiguous);
+int gpf_set_lane_topo_actions(gpf_handle h, const int32_t* index);
+int gpf_topo_actions_on_device(gpf_handle h, int32_t on);
+int gpf_get_sub_cooldown(gpf_handle h, int32_t lane0, int32_t n, int32_t* sub_cooldown);
+int gpf_set_sub_cooldown(gpf_handle h, int32_t lane0, int32_t n, const int32_t* sub_cooldown);
+int gpf_get_last_bus(gpf_handle h, int32_t lane0, int32_t n, int32_t* last_bus);
+int gpf_set_last_bus(gpf_handle h, int32_t lane0, int32_t n, const int32_t* last_bus);
+int gpf_get_topo_flags(gpf_handle h, int32_t lane0, int32_t n, uint8_t* flags);
+
 /* Trajectory buffers of multi-step launches (n_steps_cap = 0 or what = 0 releases them).
  *   GPF_TRAJ_RHO: rho [cap][n_lanes][n_line] and status [cap][n_lanes] of every step of the last gpf_step_n.
  *   GPF_TRAJ_OBS: in addition the complete backend observation of every step -- results row out [cap][n_lanes][n_out]
@@ -480,8 +534,10 @@ int gpf_get_plan(gpf_handle h, int32_t out[8]);
  * [cap][gpf_lane_capacity][row]); 22..27 = the environment dynamics (NULL while they are off): the action buffers redispatch
  * [lanes][n_gen], storage power [lanes][n_storage], curtailment [lanes][n_gen] (gpf_lane_actions_on_device), then target dispatch,
  * actual dispatch [lanes][n_gen] and state of charge [lanes][n_storage] (obs.target_dispatch / actual_dispatch / storage_charge);
+ * 28..31 = the acting path of the topology actions (NULL until it is enabled): act_topo int32 [lanes], sub_cooldown int32 [lanes][n_sub],
+ * topo_flags uint8 [lanes][2], last_bus int32 [lanes][dim_topo] (gpf_upload_topo_actions);
  * stream = hipStream_t */
-#define GPF_N_DEVICE_POINTERS 28
+#define GPF_N_DEVICE_POINTERS 32
 int gpf_device_pointers(gpf_handle h, void** ptrs /* [GPF_N_DEVICE_POINTERS] */, void** stream);
 /* The same with the length of the caller's array: entries beyond n_ptrs are not written, entries beyond the library's count are
  * NULL -- a caller built against an older / newer header cannot be overrun. */
