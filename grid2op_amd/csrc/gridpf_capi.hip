@@ -1,7 +1,6 @@
-// gridpf_capi.hip -- host side of libgridpf.so: the C ABI declared in include/gridpf.h.
-// Owns the device buffers of one engine (static grid tables + lane-major per-lane state), one HIP
-// stream, and launches the kernels of gridpf_sparse.hpp / gridpf_ptdf.hpp.  gfx950 only; no fallback path: if HIP is
-// unavailable every entry point fails with GPF_E_DEVICE.
+// gridpf_capi.hip -- host side of libgridpf.so: the C ABI declared in include/gridpf.h (its DC sensitivity part: gridpf_capi_ptdf.hip) on
+// the engine of gridpf_engine.hpp; launches the kernels of gridpf_sparse.hpp, gridpf_topo.hpp and gridpf_redispatch.hpp.  gfx950 only; no
+// fallback path: if HIP is unavailable every entry point fails with GPF_E_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,21 +15,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/gridpf.h"
-#include "gridpf_common.hpp"
-#include "gridpf_sparse.hpp"
-#include "gridpf_host.hpp"
-#include "gridpf_ptdf.hpp"
-#include "gridpf_ptdf_batch.hpp"
-#include "gridpf_ptdf_group.hpp"
+#include "gridpf_engine.hpp"
 #include "gridpf_redispatch.hpp"
 #include "gridpf_topo.hpp"
-#include <string>
-#include <thread>
-#include <condition_variable>
-#include <functional>
-#include <unordered_map>
-#include "gridpf_symbolic.hpp"
 
 namespace gpf {
 // device-side lane utilities ------------------------------------------------------------------------------------------
@@ -144,275 +131,24 @@ __global__ void simulate_env_copy_kernel(EnvDyn E, int n_gen, int n_sto, const i
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess)                                                                   \
-      return fail(GPF_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));         \
-  } while (0)
-
-// gpf_create(device = GPF_DEVICE_NONE): a HEADER-ONLY handle is being built -- every host-side step of gpf_create runs (symbolic analysis, static
-// tables, launch planning), nothing is allocated on or copied to a device (there may be none).  Thread-local: set for the duration of that call.
-static thread_local bool g_dry_create = false;
-
+// Rows [lane0, lane0 + n) of a lane-major device array with `stride` elements per lane, copied on the engine's stream (asynchronous:
+// the caller synchronises).  No-op when the host pointer is null or the stride is 0.
 template <typename T>
-struct DevArr {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    n = count;
-    if (count == 0 || g_dry_create) { p = nullptr; return hipSuccess; }
-    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-  }
-  hipError_t upload(const T* src, size_t count) {
-    hipError_t e = alloc(count);
-    if (e != hipSuccess || count == 0 || g_dry_create) return e;
-    return hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    cap = 0;
-  }
-  size_t cap = 0;                          // elements allocated (ensure / put: grow-only buffers reused across calls)
-  hipError_t ensure(size_t count) {        // room for `count` elements; contents undefined afterwards when it had to grow
-    if (count <= cap && p) { n = count; return hipSuccess; }
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    const size_t want = count + count / 4;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(want, 1) * sizeof(T));
-    cap = e == hipSuccess ? std::max<size_t>(want, 1) : 0;
-    n = e == hipSuccess ? count : 0;
-    return e;
-  }
-  hipError_t put(const T* src, size_t count, hipStream_t stream) {   // ensure + asynchronous upload on `stream` (src must stay alive until it ran)
-    hipError_t e = ensure(count);
-    if (e != hipSuccess || count == 0) return e;
-    return hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
-  }
-};
-
-}  // namespace
-
-struct gpf_engine {
-  int device = 0;
-  bool dry = false;                     // header-only handle (gpf_create with GPF_DEVICE_NONE): no device resources, no launches
-  int n_lanes = 0;
-  hipStream_t stream = nullptr;
-  gpf::GridDev g{};
-  gpf::OutOff oo{};
-  gpf_layout layout{};
-  // static tables (device)
-  DevArr<double> sub_vn_kv, br_y, br_bdc, gen_min_q, gen_max_q, shunt_fact;
-  DevArr<int> line_or_sub, line_ex_sub, line_or_pos, line_ex_pos, gen_sub, gen_pos, load_sub, load_pos, sto_sub, sto_pos,
-      shunt_sub;
-  DevArr<unsigned char> gen_slack;
-  // host copies needed to size launches
-  std::vector<int> h_line_or_sub, h_line_ex_sub, h_line_or_pos, h_line_ex_pos, h_gen_sub, h_gen_pos, h_load_sub, h_load_pos,
-      h_sto_sub, h_sto_pos, h_shunt_sub;
-  std::vector<unsigned char> h_gen_slack;
-  std::vector<double> h_init_inj;
-  std::vector<int> h_init_topo, h_init_shunt_bus;
-  // per-lane state (device)
-  DevArr<double> inj, bus_vm, bus_va, work;
-  DevArr<int> topo, shunt_bus, topo_out, shunt_bus_out, status, overflow_count, disc_round, lane_table, lane_offset, tmp_lines;
-  DevArr<int> cooldown;                 // [B][n_line] line cooldowns of the environment (gpf::Bufs::cooldown)
-  // topology actions of the batched acting path (gridpf_topo.hpp): allocated by the first gpf_set_topo_rules / gpf_upload_topo_actions
-  bool ta_on = false;
-  gpf::TopoRules ta_rules{};
-  DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_list, ta_list_rows, ta_off, ta_items, ta_pos_sub, ta_pos_other;
-  DevArr<unsigned char> ta_flags, ta_aff, ta_amb;
-  int ta_n_act = 0;
-  bool ta_bus_items = false;            // an entry of the table sets / changes a bus: the read-back of class changes is needed
-  bool ta_may_split = false;            // some row or last-bus entry was on a busbar >= 2 (then line-status actions can change a class key too)
-  bool ta_host = false, ta_dev = false; // the next launch carries indices set by the host / written on the device
-  std::vector<char> ta_moved;           // per lane: an action moved it to another topology class than its reset topology's (auto-reset re-keys it)
-  int ta_n_moved = 0;
-  int* ta_pin = nullptr;                // pinned read-back block: count | lane ids | rows
-  size_t ta_pin_n = 0;
-  // topology-derived state of the reference topology shared by the lanes of one-step launches (gpf::KeepArgs): two blobs (Ybus in LDS /
-  // in registers), allocated and keyed by the first gpf_step_n with n_steps = 1; GRIDPF_KEEP=0 at gpf_create turns it off
-  DevArr<unsigned char> keep;
-  gpf::KeepArgs keep_args{};
-  int keep_launch = 0;
-  bool keep_enabled = true;
-  DevArr<unsigned short> maint_dur;     // [chron_tables][chron_T][n_line] remaining duration of the maintenance / hazard under way, or empty
-  DevArr<short> traj_cool;              // [traj_cap][cap_lanes][n_line]
-  DevArr<float> out, chron, lane_scale, thermal_limit, rho;
-  DevArr<unsigned char> line_status, done;
-  DevArr<int> topo0, episode;           // topology last sent by the host (auto-reset target); {steps survived, resets} per lane
-  DevArr<float> lane_gen_delta, traj_rho;
-  DevArr<unsigned char> maint;          // [chron_tables][chron_T][n_line] scheduled maintenance OR hazards (forced outages), or empty
-  std::vector<unsigned char> h_maint, h_hazard;   // host copies of the two tables (the device holds their union)
-  std::vector<unsigned short> h_outage_dur;       // gpf_upload_outage_durations: remaining durations given by the caller (else derived from the tables)
-  std::vector<int> h_lane_table, h_lane_offset;   // host mirror of lane_table / lane_offset (gpf_simulate_batch: maintenance ahead of a source lane)
-  std::vector<char> h_lane_forecast;              // 1: the lane is a scratch lane of gpf_simulate_batch (its offset is an absolute row, of the forecast tables for time_step > 0)
-  // injection dynamics of the environment (gpf::EnvDyn)
-  bool env_on = false, env_hold = false, env_act_r = false, env_act_s = false, sto_ready = false;
-  int env_loss_on = 1;
-  double env_coeff = 300.0 / 3600.0, env_tol = 1e-2;
-  DevArr<float> env_target, env_actual, env_prev, env_charge, env_amount_prev, env_act_redisp, env_act_storage, sto_charge0;
-  DevArr<float> env_limit, env_curt_prev, env_act_curtail;
-  DevArr<int> env_illegal;              // [B] cancelled (illegal) actions since the reset
-  DevArr<unsigned char> env_already, env_fresh, env_renewable;
-  bool env_act_c = false, env_has_ren = false;
-  DevArr<double> sto_emax, sto_emin, sto_loss, sto_effc, sto_effd;
-  std::vector<float> h_charge0;
-  DevArr<float> forecast;               // [chron_tables][chron_T][fc_h][n_chron] *_forecasted tables (gpf_upload_forecasts), or empty
-  int fc_h = 0;
-  DevArr<int> sim_src, sim_rows;        // gpf_simulate_batch staging: source lane list, gathered topology rows
-  struct PtdfbCached { std::vector<int> row, desc, c2b; };      // gpf_ptdf_build_batch: descriptor of a topology row seen before
-  std::unordered_map<uint64_t, std::vector<PtdfbCached>> ptdfb_cache;
-  size_t ptdfb_cache_n = 0;
-  int ptdfb_cache_stride = 0;
-  unsigned char* res_pin = nullptr;     // pinned block of gpf_get_results_pinned
-  size_t res_pin_bytes = 0;
-  float* act_pin = nullptr;             // pinned staging of gpf_set_lane_actions / gpf_set_lane_curtailment (redispatch | storage | curtailment)
-  size_t act_pin_n = 0;
-  hipEvent_t act_up = nullptr;          // recorded behind the uploads that read it: the next call waits for it before rewriting the block
-  int* sim_pin = nullptr;               // its pinned host block (grow-only): gathered source rows | candidate topology rows | candidate shunt rows
-  size_t sim_pin_n = 0;
-  DevArr<signed char> traj_status;
-  DevArr<float> traj_out;               // per-step observation trajectory (GPF_TRAJ_OBS): [traj_cap][cap_lanes][n_out] ...
-  DevArr<int> traj_topo, traj_shb;
-  DevArr<unsigned char> traj_lstat;
-  int traj_cap = 0;
-  int traj_what = 0;                    // GPF_TRAJ_* bits of the current buffers
-  int traj_valid = 0;                   // steps of the trajectory written by the last gpf_step_n
-  bool has_delta = false;
-  DevArr<double> rd_pmin, rd_pmax, rd_ru, rd_rd, rd_in;      // generator limits + staging of gpf_redispatch
-  DevArr<unsigned char> rd_redisp, rd_u8;
-  DevArr<float> rd_after;
-  double rd_eps = 1e-4;
-  bool rd_ready = false;
-  unsigned char* pin = nullptr;         // pinned host block of gpf_solve_lane (one lane in, one lane out), mapped into the device
-  unsigned char* pin_dev = nullptr;     // its device-side address (hipHostGetDevicePointer)
-  size_t pin_bytes = 0;
-  GpfJit jit;                           // grid-specialised step kernels (gpf_jit_enable; gridpf_jit.hip)
-  gpf::GridDev jit_g;                   // the grid-level part of the parameter block the specialisation was generated from
-  gpf::OutOff jit_oo;
-  gpf::SymDev jit_sym;
-  int dcf = 0;                          // the NB == 1 LDS layout has room for the factored DC matrix (decided once at gpf_create)
-  DevArr<double> d_init_inj;
-  DevArr<int> d_init_topo, d_init_shunt_bus;
-  int chron_T = 0, chron_tables = 0;
-  bool has_scale = false;
-  // per-lane capacity bookkeeping (host): number of active buses / NR unknowns of each lane
-  std::vector<int> lane_nb, lane_nj;
-  int init_nb = 0, init_nj = 0;
-  // block-sparse path (kernel S)
-  gpf::Symbolic sym;
-  // DC sensitivity path (gridpf_ptdf.hpp)
-  DevArr<int> ptdf_inj_bus;
-  DevArr<double> ptdf_inj_w, ptdf_t;
-  DevArr<float> ptdf_flow, lodf_worst, lodf_inv_cap;
-  DevArr<float> ptdf_flow_rows;    // [rows][cap_lanes][line_pad] flows of the last gpf_ptdf_flows_rows
-  int ptdf_rows_valid = 0;
-  DevArr<float> lodf;              // [n_line][line_pad] line outage distribution factors of the PTDF topology, float32 (NaN column: islanding outage)
-  std::vector<double> h_ptdf;      // [n_line][nb_tot]
-  std::vector<double> h_br_bdc, h_shunt_fact;
-  std::vector<int> h_gen_cnt;
-  int ptdf_nb_pad = 0, ptdf_line_pad = 0;
-  bool ptdf_ready = false;
-  // per-lane topologies (gpf_ptdf_build_batch, gridpf_ptdf_batch.hpp): one PTDF^T / LODF block per distinct topology class of a lane range
-  long long n_step_calls = 0, n_step_dispatches = 0;   // gpf_step_n calls / kernel dispatches they issued (gpf_get_counters)
-  bool ptdf_batch = false;                 // the flows / screening calls run on the class tables of the last gpf_ptdf_build_batch
-  int ptdfb_lane0 = 0, ptdfb_n = 0, ptdfb_classes = 0, ptdfb_slots = 0, ptdfb_kpad = 0, ptdfb_npad_max = 0, ptdfb_desc_stride = 0;
-  DevArr<int> ptdfb_desc, ptdfb_order, ptdfb_blk_class, ptdfb_status;
-  DevArr<double> ptdfb_work, ptdfb_t, ptdfb_inj_w;
-  DevArr<float> ptdfb_lodf;
-  std::vector<int> h_ptdfb_lane_class, h_ptdfb_status, h_ptdfb_desc;
-  std::vector<std::vector<int>> h_ptdfb_bus;   // per class: compact bus index -> bus id (sub + (local - 1) * n_sub)
-  double ptdfb_kernel_ms = 0.0;            // duration of the last build kernel (HIP events)
-  // the build call returns once its kernel is QUEUED: class status + kernel time are fetched when somebody asks (gpf_ptdf_batch_info)
-  hipEvent_t ptdfb_ev_a = nullptr, ptdfb_ev_b = nullptr;
-  int* ptdfb_status_pin = nullptr; size_t ptdfb_status_pin_n = 0;
-  bool ptdfb_pending = false;
-  // device-side grouping + descriptors (gridpf_ptdf_group.hpp): their outputs, and the host mirrors fetched on demand
-  DevArr<unsigned long long> ptdfg_hash;
-  DevArr<int> ptdfg_lane_class, ptdfg_first, ptdfg_c2b, ptdfg_info;
-  int* ptdfg_info_pin = nullptr;
-  int* ptdfg_back_pin = nullptr; size_t ptdfg_back_pin_n = 0;     // lane -> class map + descriptor headers, queued behind the factorisation (pinned)
-  bool ptdfb_prefetched = false;
-  bool ptdfb_host_stale = false;           // h_ptdfb_lane_class / h_ptdfb_hdr are not what the device holds: ptdfb_fetch_host
-  bool ptdfb_bus_stale = false;            // ... nor h_ptdfb_bus (only gpf_ptdf_batch_get reads it)
-  std::vector<int> h_ptdfb_hdr;            // device path: the 4-int headers of the class descriptors (nr, n_act, n_pad, status); empty: h_ptdfb_desc has them
-  DevArr<double> dc_inv_g;     // static DC inverse of the larger grids (gpf::SymDev::dc_inv_g)
-  DevArr<double> stat_dbl;     // static blob of kernel S (gpf::StatOff)
-  DevArr<int> stat_int;
-  DevArr<int> flat_prog;       // flat programs of the substation graph (4 group widths)
-  gpf::SymDev sym_dev{};
-  gpf::DevParamsS h_params_s{};
-  gpf::DevParamsS* d_params_s = nullptr;
-  bool params_s_valid = false;
-  // mixed batches: lanes without / with split substations are launched separately (single-busbar kernel / NB = n_busbar)
-  DevArr<int> list_a, list_b, list_c;   // list_c: topology class of every lane of list_b
-  // topology classes (gpf::TopoClassDev): bus-level graphs of the split topologies seen so far, each with its own symbolic program
-  struct TopoClassHost { DevArr<int> tables, flat; gpf::TopoClassDev dev; int n_nodes, nslot, nslot_y; };
-  std::vector<TopoClassHost*> classes;
-  std::unordered_map<std::string, int> class_of_key;
-  // host mirror of the topology last SENT for every lane (gpf_set_topology skips the per-lane bookkeeping when a lane is
-  // re-sent unchanged: agents resend whole batches with few changes); first entry INT_MIN = unknown
-  std::vector<int> h_lane_topo, h_lane_sb;
-  bool dev_topo_dirty = false;           // a kernel may have rewritten topology rows (cascade trips, scheduled outages): the host mirrors are not the device rows any more
-  std::vector<int> lane_class;          // per lane: topology class (-1: no split substation / classes disabled)
-  DevArr<gpf::TopoClassDev> d_classes;  // device copy of classes[*].dev
-  size_t d_classes_count = 0;
-  bool no_classes = false;              // GRIDPF_NO_CLASSES=1: split lanes run the NB = n_busbar kernel
-  bool no_partition = false;     // GRIDPF_NO_PARTITION=1
-  int ipw_override = 0;        // GRIDPF_IPW=1|2|4 (developer override of the instances-per-wavefront heuristic)
-  int wpi_override = 0;        // GRIDPF_WPI=1|2 (developer override of the wavefronts-per-instance heuristic); 1 = deterministic
-  int wpi_env = 0;
-  bool no_yreg = false;        // GRIDPF_YREG=0: never keep the Ybus blocks in registers
-  int stage_max = 2;           // GRIDPF_STAGE=0|1|2: highest static-table staging tier the planner may pick (developer / tests)
-  int stage_force = -1;        // GRIDPF_FORCE_STAGE=0|1|2: take that tier whenever it fits the LDS, whatever it costs in residency (experiments)
-  int dcf_env = -1;            // GRIDPF_DCF=0|1 (-1: not set)
-  int cap_lanes = 0;           // lane buffers are padded to a multiple of 4 lanes (instance groups of a wavefront)
-  std::vector<int> lane_mb;    // max live busbars in one substation, per lane
-  int init_mb = 1;
-  bool plan_valid = false;      // cached launch plan of the whole batch (invalidated by every topology mutation)
-  LaunchPlan plan_cached{}, plan_b_cached{};   // plan_b: the split lanes of a mixed batch (sparse_nb == 0: none)
-  // profiling
-  bool profiling = false;      // per-launch event pairs (gpf_set_profiling(h, 2))
-  bool window = false;         // one event pair around a window of launches (gpf_set_profiling(h, 1))
-  hipEvent_t win_a = nullptr, win_b = nullptr;
-  bool win_marked = false;              // win_b was recorded by gpf_set_profiling(3) behind the last launch of the window
-  long long win_launches = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-  size_t ev_used = 0;
-  double acc_ms = 0.0;
-  long long acc_launches = 0;
-
-  gpf::Bufs bufs() const {
-    gpf::Bufs b{};
-    b.inj = inj.p; b.topo = topo.p; b.shunt_bus = shunt_bus.p; b.out = out.p; b.topo_out = topo_out.p;
-    b.shunt_bus_out = shunt_bus_out.p; b.line_status = line_status.p; b.status = status.p;
-    b.bus_vm = bus_vm.p; b.bus_va = bus_va.p; b.work = work.p; b.work_stride = 0;
-    b.chron = chron.p; b.lane_table = lane_table.p; b.lane_offset = lane_offset.p;
-    b.lane_scale = has_scale ? lane_scale.p : nullptr;
-    b.thermal_limit = thermal_limit.p; b.rho = rho.p; b.overflow_count = overflow_count.p; b.disc_round = disc_round.p;
-    b.lane_gen_delta = has_delta ? lane_gen_delta.p : nullptr;
-    b.maint = maint.n ? maint.p : nullptr;
-    b.cooldown = cooldown.p; b.maint_dur = maint_dur.n ? maint_dur.p : nullptr; b.traj_cool = (traj_cap && traj_cool.n) ? traj_cool.p : nullptr;
-    b.topo0 = topo0.p; b.done = done.p; b.episode = episode.p;
-    b.traj_rho = traj_cap ? traj_rho.p : nullptr; b.traj_status = traj_cap ? traj_status.p : nullptr; b.traj_cap = traj_cap;
-    const bool obs = traj_cap && (traj_what & GPF_TRAJ_OBS);
-    b.traj_out = obs ? traj_out.p : nullptr; b.traj_topo = obs ? traj_topo.p : nullptr; b.traj_shb = obs ? traj_shb.p : nullptr;
-    b.traj_lstat = obs ? traj_lstat.p : nullptr;
-    b.lane_stride = cap_lanes; b.n_real_lanes = n_lanes;
-    return b;
-  }
-};
-
-namespace {
+hipError_t rows_to_host(const gpf_engine* e, T* host, const DevArr<T>& arr, size_t stride, int lane0, int n) {
+  if (!host || stride == 0) return hipSuccess;
+  return hipMemcpyAsync(host, arr.p + (size_t)lane0 * stride, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToHost, e->stream);
+}
+template <typename T>
+hipError_t rows_to_device(const gpf_engine* e, const DevArr<T>& arr, const T* host, size_t stride, int lane0, int n) {
+  if (!host || stride == 0) return hipSuccess;
+  return hipMemcpyAsync(arr.p + (size_t)lane0 * stride, host, (size_t)n * stride * sizeof(T), hipMemcpyHostToDevice, e->stream);
+}
+// ... and rows [src, src + n) -> [dst, dst + n) of the same array
+template <typename T>
+hipError_t rows_copy(const gpf_engine* e, const DevArr<T>& arr, size_t stride, int src, int dst, int n) {
+  if (stride == 0) return hipSuccess;
+  return hipMemcpyAsync(arr.p + (size_t)dst * stride, arr.p + (size_t)src * stride, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToDevice, e->stream);
+}
 
 // the lanes' rows were sent by the host (their reset topology is their topology again)
 void topo_unmoved(gpf_engine* e, int lane0, int n) {
@@ -567,7 +303,7 @@ int topo_class_of(gpf_engine* e, const int* topo, const int* shunt_bus) {
   }
   gpf::Symbolic S = build_symbolic_resident(g, n_nodes, g.n_line, lo.data(), le.data(), true);
   if (S.nslot > 65535 || !gpf::flat_fits(S)) return -1;
-  auto* c = new gpf_engine::TopoClassHost();
+  auto c = std::make_unique<gpf_engine::TopoClassHost>();
   std::vector<int> fi;
   auto puti = [&fi](const int* v, size_t n) { int off = (int)fi.size(); fi.insert(fi.end(), v, v + n); while (fi.size() & 3) fi.push_back(0); return off; };
   const int o_prog = puti(S.prog.data(), S.prog.size());
@@ -578,7 +314,7 @@ int topo_class_of(gpf_engine* e, const int* topo, const int* shunt_bus) {
   const int o_up = puti(upv.data(), upv.size());
   const int o_br = puti(S.br_slot.data(), S.br_slot.size());
   const int o_no = puti(node_of.data(), node_of.size());
-  if (c->tables.upload(fi.data(), fi.size()) != hipSuccess) { delete c; return -1; }
+  if (c->tables.upload(fi.data(), fi.size()) != hipSuccess) return -1;
   c->n_nodes = n_nodes; c->nslot = S.nslot; c->nslot_y = S.nslot_y;
   gpf::SymDev& D = c->dev.sym;
   D = e->sym_dev;                                            // the grid's static blob pointers / offsets
@@ -601,17 +337,15 @@ int topo_class_of(gpf_engine* e, const int* topo, const int* shunt_bus) {
     D.static_connected = one ? 1 : 0;
   }
   D.prog = c->tables.p + o_prog;
-  if (!upload_flats(S, c->flat, D) || !D.fl[3].wave_closed) { c->tables.release(); c->flat.release(); delete c; return -1; }
+  if (!upload_flats(S, c->flat, D) || !D.fl[3].wave_closed) return -1;
   c->dev.pair_rc = c->tables.p + o_rc; c->dev.up = c->tables.p + o_up; c->dev.br_slot = c->tables.p + o_br; c->dev.node_of = c->tables.p + o_no;
   D.n_up = (int)upv.size() / 2;
   const int id = (int)e->classes.size();
-  e->classes.push_back(c);
+  e->classes.push_back(std::move(c));
   e->class_of_key.emplace(std::move(key), id);
   return id;
 }
 
-constexpr size_t LDS_SMALL_LIMIT = 64 * 1024;   // above this Y and J move to an HBM/L2 workspace
-constexpr size_t LDS_HARD_LIMIT = 160 * 1024 - 256;   // dynamic LDS budget (a few static bytes: block-wide reductions)
 
 // Symbolic analysis whose Gauss-Jordan tail (Symbolic::gj_lv0) does not cost a resident workgroup per CU.  The 2-wavefront kernels
 // of the large grids live on 4 workgroups of ~39 KB per CU: the tail's fill blocks (40 bytes each with the kept DC factors) are
@@ -710,7 +444,7 @@ int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchP
   const bool blocks_ok = e->g.n_busbar <= GPF_MAX_BUSBAR_BLOCKS;
   if (e->g.n_sub * mb <= 32000) {
 #ifdef GPF_TIMING
-    if (e->work.n < (size_t)e->cap_lanes * gpf::GPF_WORK_ROW) { e->work.release(); HIP_TRY(e->work.alloc((size_t)e->cap_lanes * gpf::GPF_WORK_ROW)); }
+    if (e->work.n < (size_t)e->cap_lanes * gpf::GPF_WORK_ROW) HIP_TRY(e->work.alloc((size_t)e->cap_lanes * gpf::GPF_WORK_ROW));
 #endif
     // lanes with split substations: (1) topology classes -- the single-busbar kernel on the lane's bus-level graph --, else
     // (2) the NB = n_busbar kernel; the lanes without a split keep the plain single-busbar kernel (mixed batch: two launches)
@@ -744,7 +478,7 @@ int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchP
         qb.tc = true; qb.sparse_nb = 1; qb.ipw = everyone ? tc_ipw : 1; qb.sparse_stage = 0; qb.minw = 2;
         qb.wpi = qb.ipw > 1 ? 1 : (e->wpi_override ? (e->wpi_override >= 2 ? 2 : 1) : (e->g.n_sub >= 64 ? 2 : 1));
         for (int cid : lc) {
-          const auto* c = e->classes[cid];
+          const auto& c = e->classes[cid];
           qb.tc_rows = std::max(qb.tc_rows, c->n_nodes); qb.tc_nslot = std::max(qb.tc_nslot, c->nslot); qb.tc_nslot_y = std::max(qb.tc_nslot_y, c->nslot_y);
         }
         // DC factors kept across the steps of a launch: alone (every lane has a class: ONE launch, its own parameter block) when
@@ -761,7 +495,6 @@ int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchP
         if (ok_b && e->d_classes_count != e->classes.size()) {
           std::vector<gpf::TopoClassDev> hc(e->classes.size());
           for (size_t i = 0; i < hc.size(); ++i) hc[i] = e->classes[i]->dev;
-          e->d_classes.release();
           HIP_TRY(e->d_classes.upload(hc.data(), hc.size()));
           e->d_classes_count = hc.size();
         }
@@ -775,7 +508,6 @@ int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchP
         while (lb.size() % 4) { lb.push_back(e->n_lanes); lc.push_back(lc.empty() ? 0 : lc.back()); }
         auto fit = [&](DevArr<int>& d, size_t need_n) -> hipError_t {
           if (d.n >= need_n) return hipSuccess;
-          d.release();
           return d.alloc(std::max<size_t>(need_n, (size_t)e->cap_lanes + 8) * 2);
         };
         HIP_TRY(fit(e->list_a, la.size() + 4)); HIP_TRY(fit(e->list_b, lb.size() + 4)); HIP_TRY(fit(e->list_c, lc.size() + 4));
@@ -811,17 +543,17 @@ int upload_params_s(gpf_engine* e, const gpf::Bufs& b, const LaunchPlan* tc, int
     E.on = 1; E.hold_storage = e->env_hold ? 1 : 0; E.loss_on = e->env_loss_on; E.coeff = e->env_coeff; E.eps_poly = e->rd_eps; E.tol_poly = e->env_tol;
     E.target = e->env_target.p; E.actual = e->env_actual.p; E.prev_p = e->env_prev.p; E.already = e->env_already.p; E.charge = e->env_charge.p;
     E.amount_prev = e->env_amount_prev.p; E.fresh = e->env_fresh.p;
-    E.act_redisp = e->env_act_r ? e->env_act_redisp.p : nullptr; E.act_storage = e->env_act_s ? e->env_act_storage.p : nullptr;
+    E.act_redisp = e->env_act_r ? e->env_act_redisp.p : nullptr; E.act_storage = e->env_act_s ? e->env_act_storage : nullptr;
     E.limit = e->env_limit.p; E.curt_prev = e->env_curt_prev.p; E.act_curtail = e->env_act_c ? e->env_act_curtail.p : nullptr;
     E.illegal = e->env_illegal.p;
     E.renewable = e->env_has_ren ? e->env_renewable.p : nullptr;
     E.pmin = e->rd_pmin.p; E.pmax = e->rd_pmax.p; E.ramp_up = e->rd_ru.p; E.ramp_down = e->rd_rd.p; E.redispatchable = e->rd_redisp.p;
     E.Emax = e->sto_emax.p; E.Emin = e->sto_emin.p; E.loss = e->sto_loss.p; E.eff_c = e->sto_effc.p; E.eff_d = e->sto_effd.p; E.charge0 = e->sto_charge0.p;
   }
-  if (!e->d_params_s) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&e->d_params_s), sizeof(gpf::DevParamsS)));
+  if (!e->d_params_s.p) HIP_TRY(e->d_params_s.alloc(1));
   if (!e->params_s_valid || std::memcmp(&hp, &e->h_params_s, sizeof(hp)) != 0) {
     e->h_params_s = hp;
-    HIP_TRY(hipMemcpyAsync(e->d_params_s, &e->h_params_s, sizeof(hp), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_params_s.p, &e->h_params_s, sizeof(hp), hipMemcpyHostToDevice, e->stream));
     e->params_s_valid = true;
   }
   return GPF_OK;
@@ -843,10 +575,10 @@ GpfJit* jit_for_launch(gpf_engine* e) {
 
 int prof_begin(gpf_engine* e, hipEvent_t& a, hipEvent_t& b) {
   if (e->ev_used == e->ev_pool.size()) {
-    hipEvent_t x, y;
-    HIP_TRY(hipEventCreate(&x));
-    HIP_TRY(hipEventCreate(&y));
-    e->ev_pool.emplace_back(x, y);
+    std::pair<Event, Event> ev;
+    HIP_TRY(ev.first.create());
+    HIP_TRY(ev.second.create());
+    e->ev_pool.push_back(std::move(ev));
   }
   a = e->ev_pool[e->ev_used].first;
   b = e->ev_pool[e->ev_used].second;
@@ -942,9 +674,14 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   return GPF_OK;
 }
 
-bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
-
 }  // namespace
+
+gpf_engine::~gpf_engine() {
+  if (dry) return;                      // (a header-only handle owns no device resource)
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  gpf_jit_release(jit);
+}
 
 extern "C" {
 
@@ -1027,7 +764,8 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
     if (device < 0 || device >= ndev) return fail(GPF_E_INVALID, "gpf_create: bad device index");
     HIP_TRY(hipSetDevice(device));
   }
-  gpf_engine* e = new gpf_engine();
+  std::unique_ptr<gpf_engine> own(new gpf_engine());   // frees what was allocated on every early return; the caller's on success
+  gpf_engine* e = own.get();
   e->device = device;
   e->dry = dry;
   {
@@ -1087,30 +825,28 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
       !in_range(e->h_load_sub, g.n_sub) || !in_range(e->h_sto_sub, g.n_sub) || !in_range(e->h_shunt_sub, g.n_sub) ||
       !in_range(e->h_line_or_pos, g.dim_topo) || !in_range(e->h_line_ex_pos, g.dim_topo) || !in_range(e->h_gen_pos, g.dim_topo) ||
       !in_range(e->h_load_pos, g.dim_topo) || !in_range(e->h_sto_pos, g.dim_topo)) {
-    delete e;
     return fail(GPF_E_INVALID, "gpf_create: index table out of range");
   }
 
-#define UP(arr, src, count)                                                  \
-  do {                                                                       \
-    hipError_t _e = e->arr.upload(src, (size_t)(count));                     \
-    if (_e != hipSuccess) { gpf_destroy(e); return fail(GPF_E_DEVICE, std::string("upload " #arr ": ") + hipGetErrorString(_e)); } \
-  } while (0)
-#define AL(arr, count)                                                       \
-  do {                                                                       \
-    hipError_t _e = e->arr.alloc((size_t)(count));                           \
-    if (_e != hipSuccess) { gpf_destroy(e); return fail(GPF_E_DEVICE, std::string("alloc " #arr ": ") + hipGetErrorString(_e)); } \
-  } while (0)
-  UP(sub_vn_kv, d->sub_vn_kv, g.n_sub);
-  UP(line_or_sub, d->line_or_sub, nl); UP(line_ex_sub, d->line_ex_sub, nl);
-  UP(line_or_pos, d->line_or_pos_topo_vect, nl); UP(line_ex_pos, d->line_ex_pos_topo_vect, nl);
-  UP(br_y, d->br_y, 8 * (size_t)nl); UP(br_bdc, d->br_bdc, nl);
-  UP(gen_sub, d->gen_sub, ng); UP(gen_pos, d->gen_pos_topo_vect, ng);
-  UP(gen_min_q, d->gen_min_q, ng); UP(gen_max_q, d->gen_max_q, ng); UP(gen_slack, d->gen_slack, ng);
-  UP(load_sub, d->load_sub, nd); UP(load_pos, d->load_pos_topo_vect, nd);
-  UP(sto_sub, d->storage_sub, ns); UP(sto_pos, d->storage_pos_topo_vect, ns);
-  UP(shunt_sub, d->shunt_sub, nsh); UP(shunt_fact, d->shunt_fact, nsh);
-  UP(d_init_inj, d->init_inj, g.n_inj); UP(d_init_topo, d->init_topo, g.dim_topo); UP(d_init_shunt_bus, d->init_shunt_bus, nsh);
+  // (the first failure stops the uploads and names its buffer)
+  hipError_t err = hipSuccess;
+  std::string what;
+  auto up = [&](const char* name, auto& arr, const auto* src, size_t count) {
+    if (err == hipSuccess && (err = arr.upload(src, count)) != hipSuccess) what = std::string("upload ") + name;
+  };
+  auto al = [&](const char* name, auto& arr, size_t count) {
+    if (err == hipSuccess && (err = arr.alloc(count)) != hipSuccess) what = std::string("alloc ") + name;
+  };
+  up("sub_vn_kv", e->sub_vn_kv, d->sub_vn_kv, g.n_sub); up("line_or_sub", e->line_or_sub, d->line_or_sub, nl);
+  up("line_ex_sub", e->line_ex_sub, d->line_ex_sub, nl); up("line_or_pos", e->line_or_pos, d->line_or_pos_topo_vect, nl);
+  up("line_ex_pos", e->line_ex_pos, d->line_ex_pos_topo_vect, nl); up("br_y", e->br_y, d->br_y, 8 * (size_t)nl);
+  up("br_bdc", e->br_bdc, d->br_bdc, nl); up("gen_sub", e->gen_sub, d->gen_sub, ng); up("gen_pos", e->gen_pos, d->gen_pos_topo_vect, ng);
+  up("gen_min_q", e->gen_min_q, d->gen_min_q, ng); up("gen_max_q", e->gen_max_q, d->gen_max_q, ng);
+  up("gen_slack", e->gen_slack, d->gen_slack, ng); up("load_sub", e->load_sub, d->load_sub, nd);
+  up("load_pos", e->load_pos, d->load_pos_topo_vect, nd); up("sto_sub", e->sto_sub, d->storage_sub, ns);
+  up("sto_pos", e->sto_pos, d->storage_pos_topo_vect, ns); up("shunt_sub", e->shunt_sub, d->shunt_sub, nsh);
+  up("shunt_fact", e->shunt_fact, d->shunt_fact, nsh); up("d_init_inj", e->d_init_inj, d->init_inj, g.n_inj);
+  up("d_init_topo", e->d_init_topo, d->init_topo, g.dim_topo); up("d_init_shunt_bus", e->d_init_shunt_bus, d->init_shunt_bus, nsh);
   g.sub_vn_kv = e->sub_vn_kv.p; g.line_or_sub = e->line_or_sub.p; g.line_ex_sub = e->line_ex_sub.p;
   g.line_or_pos = e->line_or_pos.p; g.line_ex_pos = e->line_ex_pos.p; g.br_y = e->br_y.p; g.br_bdc = e->br_bdc.p;
   g.gen_sub = e->gen_sub.p; g.gen_pos = e->gen_pos.p; g.gen_min_q = e->gen_min_q.p; g.gen_max_q = e->gen_max_q.p;
@@ -1118,17 +854,17 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
   g.sto_pos = e->sto_pos.p; g.shunt_sub = e->shunt_sub.p; g.shunt_fact = e->shunt_fact.p;
 
   const size_t B = (size_t)e->cap_lanes;   // padded: ghost lanes hold the pristine state and are never read back
-  AL(inj, B * g.n_inj); AL(topo, B * g.dim_topo); AL(shunt_bus, B * nsh);
-  AL(out, B * g.n_out); AL(topo_out, B * g.dim_topo); AL(shunt_bus_out, B * nsh); AL(line_status, B * nl);
-  AL(status, B * 4); AL(bus_vm, B * g.nb_tot); AL(bus_va, B * g.nb_tot);
-  AL(overflow_count, B * nl); AL(disc_round, B * nl); AL(rho, B * nl); AL(cooldown, B * nl);
-  AL(topo0, B * g.dim_topo); AL(done, B); AL(episode, B * 2);
-  AL(lane_table, B); AL(lane_offset, B); AL(thermal_limit, nl); AL(tmp_lines, std::max<size_t>(B, 1));
-#undef UP
-#undef AL
+  al("inj", e->inj, B * g.n_inj); al("topo", e->topo, B * g.dim_topo); al("shunt_bus", e->shunt_bus, B * nsh);
+  al("out", e->out, B * g.n_out); al("topo_out", e->topo_out, B * g.dim_topo); al("shunt_bus_out", e->shunt_bus_out, B * nsh);
+  al("line_status", e->line_status, B * nl); al("status", e->status, B * 4); al("bus_vm", e->bus_vm, B * g.nb_tot);
+  al("bus_va", e->bus_va, B * g.nb_tot); al("overflow_count", e->overflow_count, B * nl); al("disc_round", e->disc_round, B * nl);
+  al("rho", e->rho, B * nl); al("cooldown", e->cooldown, B * nl); al("topo0", e->topo0, B * g.dim_topo); al("done", e->done, B);
+  al("episode", e->episode, B * 2); al("lane_table", e->lane_table, B); al("lane_offset", e->lane_offset, B);
+  al("thermal_limit", e->thermal_limit, nl); al("tmp_lines", e->tmp_lines, std::max<size_t>(B, 1));
+  if (err != hipSuccess) return fail(GPF_E_DEVICE, what + ": " + hipGetErrorString(err));
   if (!dry) {
-    hipError_t es = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (es != hipSuccess) { gpf_destroy(e); return fail(GPF_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(es)); }
+    hipError_t es = e->stream.create(hipStreamNonBlocking);
+    if (es != hipSuccess) return fail(GPF_E_DEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(es));
   }
   count_lane(e, e->h_init_topo.data(), nsh ? e->h_init_shunt_bus.data() : nullptr, e->init_nb, e->init_nj, e->init_mb);
   e->lane_nb.assign(e->cap_lanes, e->init_nb);
@@ -1165,7 +901,7 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
       e->sym = it->second;
     }
     const gpf::Symbolic& S = e->sym;
-    if (S.nslot > 65535 || g.n_sub > 32767) { gpf_destroy(e); return fail(GPF_E_CAPACITY, "grid too large for the 16-bit packed symbolic program"); }
+    if (S.nslot > 65535 || g.n_sub > 32767) return fail(GPF_E_CAPACITY, "grid too large for the 16-bit packed symbolic program");
     // the static blob of kernel S (layout: gpf::StatOff): doubles, then ints
     gpf::SymDev& D = e->sym_dev;
     gpf::StatOff& so = D.so;
@@ -1243,7 +979,7 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
         const char* mx = std::getenv("GRIDPF_DCINV_MAX");
         if (n <= 24) so.dc_inv = putd(cm.data(), cm.size());
         else if (n <= (mx ? std::atoi(mx) : 63)) {
-          if (e->dc_inv_g.upload(cm.data(), cm.size()) != hipSuccess) { gpf_destroy(e); return fail(GPF_E_DEVICE, "upload dc_inv"); }
+          if (e->dc_inv_g.upload(cm.data(), cm.size()) != hipSuccess) return fail(GPF_E_DEVICE, "upload dc_inv");
           so.dc_inv = -2;
           D.dc_inv_g = e->dc_inv_g.p;
         }
@@ -1270,7 +1006,7 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
     so.n_dbl = (int)fd.size(); so.n_int = (int)fi.size();
     hipError_t eu = e->stat_dbl.upload(fd.data(), fd.size());
     if (eu == hipSuccess) eu = e->stat_int.upload(fi.data(), fi.size());
-    if (eu != hipSuccess) { gpf_destroy(e); return fail(GPF_E_DEVICE, std::string("upload static tables: ") + hipGetErrorString(eu)); }
+    if (eu != hipSuccess) return fail(GPF_E_DEVICE, std::string("upload static tables: ") + hipGetErrorString(eu));
     D.n = S.n; D.nslot = S.nslot; D.nslot_lu = S.nslot_lu; D.nslot_y = S.nslot_y; D.n_levels = S.n_levels; D.back_off = S.back_off; D.back_first = S.back_first;
       {   // connectivity of the static substation graph (all lines in service): lets the kernel skip the label propagation
       std::vector<int> comp(g.n_sub);
@@ -1286,7 +1022,7 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
     // GRIDPF_LANE_OPT=<iterations> overrides, 0 = sequential assignment); topology classes are built inside a step and skip it
     int lane_opt = 3000;
     if (const char* lo_ = std::getenv("GRIDPF_LANE_OPT")) lane_opt = std::max(0, atoi(lo_));
-    if (!upload_flats(S, e->flat_prog, D, lane_opt)) { gpf_destroy(e); return fail(GPF_E_DEVICE, "upload flat programs"); }
+    if (!upload_flats(S, e->flat_prog, D, lane_opt)) return fail(GPF_E_DEVICE, "upload flat programs");
   }
   {
     // keep the factored DC matrix in LDS across the steps of a launch when that does not cost residency: the blocks per CU
@@ -1309,7 +1045,7 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
     const char* fs_ = std::getenv("GRIDPF_FORCE_STAGE");
     if (fs_ && fs_[0] >= '0' && fs_[0] <= '2') e->stage_force = fs_[0] - '0';
   }
-  if (dry) { *out_h = e; return GPF_OK; }      // header-only handle: gpf_jit_source / gpf_get_plan / gpf_get_layout / gpf_destroy
+  if (dry) { *out_h = own.release(); return GPF_OK; }      // header-only handle: gpf_jit_source / gpf_get_plan / gpf_get_layout / gpf_destroy
   HIP_TRY(hipMemsetAsync(e->status.p, 0xFF, B * 4 * sizeof(int), e->stream));
   HIP_TRY(hipMemsetAsync(e->overflow_count.p, 0, B * nl * sizeof(int), e->stream));
   HIP_TRY(hipMemsetAsync(e->cooldown.p, 0, B * nl * sizeof(int), e->stream));
@@ -1325,64 +1061,15 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
   if (const char* j = getenv("GRIDPF_JIT")) {
     if (atoi(j) > 0 && gpf_jit_enable(e, nullptr, nullptr) != GPF_OK) fprintf(stderr, "[gridpf] GRIDPF_JIT: %s\n", g_err.c_str());
   }
-  *out_h = e;
   int rc = reset_lanes_unchecked(e, 0, e->cap_lanes);
-  if (rc != GPF_OK) { gpf_destroy(e); *out_h = nullptr; return rc; }
+  if (rc != GPF_OK) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
+  *out_h = own.release();
   return GPF_OK;
 }
 
 int gpf_destroy(gpf_handle e) {
   if (!e) return GPF_OK;
-  if (e->dry) { for (auto* c : e->classes) delete c; delete e; return GPF_OK; }      // (a header-only handle owns no device resource)
-  (void)hipSetDevice(e->device);
-  if (e->stream) { (void)hipStreamSynchronize(e->stream); (void)hipStreamDestroy(e->stream); }
-  if (e->win_a) { (void)hipEventDestroy(e->win_a); (void)hipEventDestroy(e->win_b); }
-  for (auto& pr : e->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  e->sub_vn_kv.release(); e->br_y.release(); e->br_bdc.release(); e->gen_min_q.release(); e->gen_max_q.release();
-  e->shunt_fact.release(); e->line_or_sub.release(); e->line_ex_sub.release(); e->line_or_pos.release();
-  e->line_ex_pos.release(); e->gen_sub.release(); e->gen_pos.release(); e->load_sub.release(); e->load_pos.release();
-  e->sto_sub.release(); e->sto_pos.release(); e->shunt_sub.release(); e->gen_slack.release();
-  e->inj.release(); e->bus_vm.release(); e->bus_va.release(); e->work.release(); e->topo.release(); e->shunt_bus.release();
-  e->topo_out.release(); e->shunt_bus_out.release(); e->status.release(); e->overflow_count.release(); e->disc_round.release(); e->cooldown.release(); e->keep.release(); e->maint_dur.release(); e->traj_cool.release();
-  e->ta_act.release(); e->ta_sub_cd.release(); e->ta_last_bus.release(); e->ta_ep_snap.release(); e->ta_list.release(); e->ta_list_rows.release();
-  e->ta_off.release(); e->ta_items.release(); e->ta_pos_sub.release(); e->ta_pos_other.release(); e->ta_flags.release(); e->ta_aff.release(); e->ta_amb.release();
-  if (e->ta_pin) (void)hipHostFree(e->ta_pin);
-  e->lane_table.release(); e->lane_offset.release(); e->tmp_lines.release(); e->out.release(); e->chron.release();
-  e->lane_scale.release(); e->thermal_limit.release(); e->rho.release(); e->line_status.release();
-  e->d_init_inj.release(); e->d_init_topo.release(); e->d_init_shunt_bus.release();
-  if (e->pin) (void)hipHostFree(e->pin);
-  if (e->sim_pin) (void)hipHostFree(e->sim_pin);
-  if (e->act_pin) (void)hipHostFree(e->act_pin);
-  if (e->res_pin) (void)hipHostFree(e->res_pin);
-  if (e->act_up) (void)hipEventDestroy(e->act_up);
-  if (e->ptdfb_ev_a) { (void)hipEventDestroy(e->ptdfb_ev_a); (void)hipEventDestroy(e->ptdfb_ev_b); }
-  if (e->ptdfb_status_pin) (void)hipHostFree(e->ptdfb_status_pin);
-  if (e->ptdfg_info_pin) (void)hipHostFree(e->ptdfg_info_pin);
-  if (e->ptdfg_back_pin) (void)hipHostFree(e->ptdfg_back_pin);
-  e->ptdfg_hash.release(); e->ptdfg_lane_class.release(); e->ptdfg_first.release(); e->ptdfg_c2b.release(); e->ptdfg_info.release();
-  e->maint.release(); e->forecast.release(); e->sim_src.release(); e->sim_rows.release();
-  e->env_target.release(); e->env_actual.release(); e->env_prev.release(); e->env_charge.release(); e->env_amount_prev.release();
-  e->env_act_storage.p = nullptr; e->env_act_storage.n = 0;       // (an alias into env_act_redisp)
-  e->env_act_redisp.release(); e->sto_charge0.release(); e->env_already.release(); e->env_fresh.release();
-  e->sto_emax.release(); e->sto_emin.release(); e->sto_loss.release(); e->sto_effc.release(); e->sto_effd.release();
-  e->env_limit.release(); e->env_curt_prev.release(); e->env_act_curtail.release(); e->env_renewable.release(); e->env_illegal.release();
-  e->rd_pmin.release(); e->rd_pmax.release(); e->rd_ru.release(); e->rd_rd.release(); e->rd_in.release(); e->rd_redisp.release();
-  e->rd_u8.release(); e->rd_after.release();
-  e->topo0.release(); e->done.release(); e->episode.release(); e->lane_gen_delta.release(); e->traj_rho.release(); e->traj_status.release();
-  e->traj_out.release(); e->traj_topo.release(); e->traj_shb.release(); e->traj_lstat.release();
-  gpf_jit_release(e->jit);
-  if (e->d_params_s) (void)hipFree(e->d_params_s);
-  e->stat_dbl.release(); e->dc_inv_g.release();
-  e->list_a.release(); e->list_b.release(); e->list_c.release(); e->d_classes.release();
-  for (auto* c : e->classes) { c->tables.release(); c->flat.release(); delete c; }
-  e->classes.clear();
-  e->ptdf_inj_bus.release(); e->ptdf_inj_w.release(); e->ptdf_t.release(); e->ptdf_flow.release();
-  e->lodf.release(); e->lodf_worst.release(); e->lodf_inv_cap.release(); e->ptdf_flow_rows.release();
-  e->ptdfb_desc.release(); e->ptdfb_order.release(); e->ptdfb_blk_class.release(); e->ptdfb_status.release();
-  e->ptdfb_work.release(); e->ptdfb_t.release(); e->ptdfb_lodf.release(); e->ptdfb_inj_w.release();
-  e->stat_int.release();
-  e->flat_prog.release();
   delete e;
   return GPF_OK;
 }
@@ -1406,8 +1093,7 @@ int gpf_lane_capacity(gpf_handle e) { return e ? e->cap_lanes : GPF_E_INVALID; }
 int gpf_set_injections(gpf_handle e, int32_t lane0, int32_t n, const double* inj) {
   if (!check_range(e, lane0, n) || !inj) return fail(GPF_E_INVALID, "gpf_set_injections: bad range");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(e->inj.p + (size_t)lane0 * e->g.n_inj, inj, (size_t)n * e->g.n_inj * sizeof(double),
-                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(rows_to_device(e, e->inj, inj, e->g.n_inj, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));   // the host buffer may be reused by the caller right away
   return GPF_OK;
 }
@@ -1482,8 +1168,7 @@ int gpf_set_topology(gpf_handle e, int32_t lane0, int32_t n, const int32_t* topo
 int gpf_get_injections(gpf_handle e, int32_t lane0, int32_t n, double* inj) {
   if (!check_range(e, lane0, n) || !inj) return fail(GPF_E_INVALID, "gpf_get_injections: bad range");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(inj, e->inj.p + (size_t)lane0 * e->g.n_inj, (size_t)n * e->g.n_inj * sizeof(double),
-                         hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, inj, e->inj, e->g.n_inj, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -1491,12 +1176,8 @@ int gpf_get_injections(gpf_handle e, int32_t lane0, int32_t n, double* inj) {
 int gpf_get_topology(gpf_handle e, int32_t lane0, int32_t n, int32_t* topo, int32_t* shunt_bus) {
   if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_get_topology: bad range");
   HIP_TRY(hipSetDevice(e->device));
-  if (topo)
-    HIP_TRY(hipMemcpyAsync(topo, e->topo.p + (size_t)lane0 * e->g.dim_topo, (size_t)n * e->g.dim_topo * sizeof(int),
-                           hipMemcpyDeviceToHost, e->stream));
-  if (shunt_bus && e->g.n_shunt)
-    HIP_TRY(hipMemcpyAsync(shunt_bus, e->shunt_bus.p + (size_t)lane0 * e->g.n_shunt, (size_t)n * e->g.n_shunt * sizeof(int),
-                           hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, topo, e->topo, e->g.dim_topo, lane0, n));
+  HIP_TRY(rows_to_host(e, shunt_bus, e->shunt_bus, e->g.n_shunt, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -1527,22 +1208,22 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
   if (std::abs(src - dst) < n) return fail(GPF_E_INVALID, "gpf_copy_lanes: overlapping ranges");
   HIP_TRY(hipSetDevice(e->device));
   const gpf::GridDev& g = e->g;
-#define CP(arr, stride)                                                                                                     \
-  if ((stride) > 0)                                                                                                         \
-  HIP_TRY(hipMemcpyAsync(e->arr.p + (size_t)dst * (stride), e->arr.p + (size_t)src * (stride),                              \
-                         (size_t)n * (stride) * sizeof(*e->arr.p), hipMemcpyDeviceToDevice, e->stream))
-  CP(inj, g.n_inj); CP(topo, g.dim_topo); CP(shunt_bus, g.n_shunt); CP(out, g.n_out); CP(topo_out, g.dim_topo);
-  CP(shunt_bus_out, g.n_shunt); CP(line_status, g.n_line); CP(status, 4); CP(bus_vm, g.nb_tot); CP(bus_va, g.nb_tot);
-  CP(overflow_count, g.n_line); CP(cooldown, g.n_line); CP(disc_round, g.n_line); CP(rho, g.n_line); CP(topo0, g.dim_topo); CP(done, 1); CP(episode, 2);
+  hipError_t err = hipSuccess;
+  auto cp = [&](const auto& arr, size_t stride) { if (err == hipSuccess) err = rows_copy(e, arr, stride, src, dst, n); };
+  cp(e->inj, g.n_inj); cp(e->topo, g.dim_topo); cp(e->shunt_bus, g.n_shunt); cp(e->out, g.n_out); cp(e->topo_out, g.dim_topo);
+  cp(e->shunt_bus_out, g.n_shunt); cp(e->line_status, g.n_line); cp(e->status, 4); cp(e->bus_vm, g.nb_tot); cp(e->bus_va, g.nb_tot);
+  cp(e->overflow_count, g.n_line); cp(e->cooldown, g.n_line); cp(e->disc_round, g.n_line); cp(e->rho, g.n_line); cp(e->topo0, g.dim_topo);
+  cp(e->done, 1); cp(e->episode, 2);
   if (e->env_on) {          // the environment's injection dynamics are part of the lane's state (Backend.copy / env.copy keep them)
-    CP(env_target, g.n_gen); CP(env_actual, g.n_gen); CP(env_prev, g.n_gen); CP(env_already, g.n_gen); CP(env_limit, g.n_gen);
-    CP(env_charge, g.n_sto); CP(env_amount_prev, 1); CP(env_curt_prev, 1); CP(env_fresh, 1); CP(env_illegal, 1);
+    cp(e->env_target, g.n_gen); cp(e->env_actual, g.n_gen); cp(e->env_prev, g.n_gen); cp(e->env_already, g.n_gen); cp(e->env_limit, g.n_gen);
+    cp(e->env_charge, g.n_sto); cp(e->env_amount_prev, 1); cp(e->env_curt_prev, 1); cp(e->env_fresh, 1); cp(e->env_illegal, 1);
   }
   if (e->ta_on) {                           // the acting path's state
-    CP(ta_sub_cd, g.n_sub); CP(ta_last_bus, g.dim_topo); CP(ta_flags, 2); CP(ta_act, 1);
+    cp(e->ta_sub_cd, g.n_sub); cp(e->ta_last_bus, g.dim_topo); cp(e->ta_flags, 2); cp(e->ta_act, 1);
+    HIP_TRY(err);
     for (int k = 0; k < n; ++k) { e->ta_n_moved += e->ta_moved[src + k] - e->ta_moved[dst + k]; e->ta_moved[dst + k] = e->ta_moved[src + k]; }
   }
-#undef CP
+  HIP_TRY(err);
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
     if (g.n_shunt) std::copy_n(e->h_lane_sb.begin() + (size_t)(src + k) * g.n_shunt, g.n_shunt, e->h_lane_sb.begin() + (size_t)(dst + k) * g.n_shunt); }
@@ -1555,12 +1236,12 @@ int gpf_fanout_n1(gpf_handle e, int32_t src, int32_t dst0, int32_t n_out, const 
   if (src >= dst0 && src < dst0 + n_out) return fail(GPF_E_INVALID, "gpf_fanout_n1: source inside destination range");
   if (n_out == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
-  if (e->tmp_lines.n < (size_t)n_out) { e->tmp_lines.release(); HIP_TRY(e->tmp_lines.alloc(n_out)); }
+  if (e->tmp_lines.n < (size_t)n_out) HIP_TRY(e->tmp_lines.alloc(n_out));
   HIP_TRY(hipMemcpyAsync(e->tmp_lines.p, out_lines, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(gpf::fanout_kernel, dim3(n_out), dim3(64), 0, e->stream, e->g, e->bufs(), src, dst0, n_out, e->tmp_lines.p);
   HIP_TRY(hipGetLastError());
   if (e->env_on) {                          // the contingency lanes start from the source's injection dynamics
-    if (e->sim_src.n < 1) { e->sim_src.release(); HIP_TRY(e->sim_src.alloc(1)); }
+    if (e->sim_src.n < 1) HIP_TRY(e->sim_src.alloc(1));
     HIP_TRY(hipMemcpyAsync(e->sim_src.p, &src, sizeof(int), hipMemcpyHostToDevice, e->stream));
     gpf::EnvDyn E{};
     E.target = e->env_target.p; E.actual = e->env_actual.p; E.prev_p = e->env_prev.p; E.already = e->env_already.p; E.charge = e->env_charge.p;
@@ -1595,8 +1276,8 @@ int gpf_runpf(gpf_handle e, int32_t lane0, int32_t n, int32_t is_dc, int32_t max
   if (e->profiling) { rc = prof_begin(e, ea, eb); if (rc != GPF_OK) return rc; }
   // (measured: forking the second launch onto its own stream costs more in cross-stream events than the overlap gains)
   p.jit = pb.jit = jit_for_launch(e);
-  HIP_TRY(gpf_launch_runpf_sparse(p, e->device, e->d_params_s, e->stream, lane0, n, is_dc, max_iter, tol_pu));
-  if (pb.sparse_nb) HIP_TRY(gpf_launch_runpf_sparse(pb, e->device, e->d_params_s, e->stream, lane0, n, is_dc, max_iter, tol_pu));
+  HIP_TRY(gpf_launch_runpf_sparse(p, e->device, e->d_params_s.p, e->stream, lane0, n, is_dc, max_iter, tol_pu));
+  if (pb.sparse_nb) HIP_TRY(gpf_launch_runpf_sparse(pb, e->device, e->d_params_s.p, e->stream, lane0, n, is_dc, max_iter, tol_pu));
   HIP_TRY(hipGetLastError());
   if (e->profiling) HIP_TRY(hipEventRecord(eb, e->stream));
   if (e->window) { ++e->win_launches; e->win_marked = false; }
@@ -1640,17 +1321,8 @@ int gpf_solve_lane(gpf_handle e, int32_t lane, const double* inj, const int32_t*
   const size_t o_out = o_sb + al((size_t)g.n_shunt * 4), o_tv = o_out + al((size_t)g.n_out * 4), o_sbo = o_tv + al((size_t)g.dim_topo * 4);
   const size_t o_ls = o_sbo + al((size_t)g.n_shunt * 4), o_st = o_ls + al((size_t)g.n_line), o_vm = o_st + 16, o_va = o_vm + al((size_t)g.nb_tot * 8);
   const size_t total = o_va + al((size_t)g.nb_tot * 8);
-  if (e->pin_bytes < total) {
-    if (e->pin) (void)hipHostFree(e->pin);
-    e->pin = nullptr; e->pin_bytes = 0;
-    // coherent (fine-grained) mapping: the device reads / writes it uncached, what the gather kernel wrote is in host memory when the
-    // stream has drained
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->pin), total, hipHostMallocMapped | hipHostMallocCoherent));
-    e->pin_bytes = total;
-    e->pin_dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->pin_dev), e->pin, 0));
-  }
-  unsigned char* P = e->pin;
+  HIP_TRY(e->pin.reserve(total));
+  unsigned char* P = e->pin.p;
   std::memcpy(P + o_inj, inj, (size_t)g.n_inj * 8);
   std::memcpy(P + o_topo, topo, (size_t)g.dim_topo * 4);
   if (g.n_shunt) std::memcpy(P + o_sb, shunt_bus, (size_t)g.n_shunt * 4);
@@ -1693,13 +1365,13 @@ int gpf_solve_lane(gpf_handle e, int32_t lane, const double* inj, const int32_t*
   HIP_TRY(hipMemcpyAsync(e->topo0.p + (size_t)lane * g.dim_topo, P + o_topo, (size_t)g.dim_topo * 4, hipMemcpyHostToDevice, st));
   if (g.n_shunt) HIP_TRY(hipMemcpyAsync(e->shunt_bus.p + (size_t)lane * g.n_shunt, P + o_sb, (size_t)g.n_shunt * 4, hipMemcpyHostToDevice, st));
   } else {
-    hipLaunchKernelGGL(gpf::lane_scatter_kernel, dim3(1), dim3(256), 0, st, g, bufs, (int)lane, (const unsigned char*)e->pin_dev, lb);
+    hipLaunchKernelGGL(gpf::lane_scatter_kernel, dim3(1), dim3(256), 0, st, g, bufs, (int)lane, (const unsigned char*)e->pin.dev, lb);
     HIP_TRY(hipGetLastError());
   }
   const double tol_pu = tol_mva / g.sn_mva;
   p.jit = pb.jit = jit_for_launch(e);
-  HIP_TRY(gpf_launch_runpf_sparse(p, e->device, e->d_params_s, st, lane, 1, is_dc, max_iter, tol_pu));
-  if (pb.sparse_nb) HIP_TRY(gpf_launch_runpf_sparse(pb, e->device, e->d_params_s, st, lane, 1, is_dc, max_iter, tol_pu));
+  HIP_TRY(gpf_launch_runpf_sparse(p, e->device, e->d_params_s.p, st, lane, 1, is_dc, max_iter, tol_pu));
+  if (pb.sparse_nb) HIP_TRY(gpf_launch_runpf_sparse(pb, e->device, e->d_params_s.p, st, lane, 1, is_dc, max_iter, tol_pu));
   if (e->window) { ++e->win_launches; e->win_marked = false; }
 #define DL1(off, arr, stride, bytes_per) \
   if ((stride) > 0) HIP_TRY(hipMemcpyAsync(P + (off), e->arr.p + (size_t)lane * (stride), (size_t)(stride) * (bytes_per), hipMemcpyDeviceToHost, st))
@@ -1707,7 +1379,7 @@ int gpf_solve_lane(gpf_handle e, int32_t lane, const double* inj, const int32_t*
   DL1(o_out, out, g.n_out, 4); DL1(o_tv, topo_out, g.dim_topo, 4); DL1(o_sbo, shunt_bus_out, g.n_shunt, 4); DL1(o_ls, line_status, g.n_line, 1);
   DL1(o_st, status, 4, 4); DL1(o_vm, bus_vm, g.nb_tot, 8); DL1(o_va, bus_va, g.nb_tot, 8);
   } else {
-    hipLaunchKernelGGL(gpf::lane_gather_kernel, dim3(1), dim3(256), 0, st, g, bufs, (int)lane, e->pin_dev, lb);
+    hipLaunchKernelGGL(gpf::lane_gather_kernel, dim3(1), dim3(256), 0, st, g, bufs, (int)lane, e->pin.dev, lb);
     HIP_TRY(hipGetLastError());
   }
 #undef DL1
@@ -1727,13 +1399,10 @@ int gpf_get_results(gpf_handle e, int32_t lane0, int32_t n, float* out, int32_t*
   if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_get_results: bad range");
   HIP_TRY(hipSetDevice(e->device));
   const gpf::GridDev& g = e->g;
-#define DL(dst, arr, stride)                                                                                   \
-  if ((dst) && (stride) > 0)                                                                                   \
-  HIP_TRY(hipMemcpyAsync(dst, e->arr.p + (size_t)lane0 * (stride), (size_t)n * (stride) * sizeof(*e->arr.p),   \
-                         hipMemcpyDeviceToHost, e->stream))
-  DL(out, out, g.n_out); DL(topo_vect, topo_out, g.dim_topo); DL(shunt_bus, shunt_bus_out, g.n_shunt);
-  DL(line_status, line_status, g.n_line); DL(status, status, 4); DL(bus_vm, bus_vm, g.nb_tot); DL(bus_va, bus_va, g.nb_tot);
-#undef DL
+  HIP_TRY(rows_to_host(e, out, e->out, g.n_out, lane0, n)); HIP_TRY(rows_to_host(e, topo_vect, e->topo_out, g.dim_topo, lane0, n));
+  HIP_TRY(rows_to_host(e, shunt_bus, e->shunt_bus_out, g.n_shunt, lane0, n)); HIP_TRY(rows_to_host(e, line_status, e->line_status, g.n_line, lane0, n));
+  HIP_TRY(rows_to_host(e, status, e->status, 4, lane0, n)); HIP_TRY(rows_to_host(e, bus_vm, e->bus_vm, g.nb_tot, lane0, n));
+  HIP_TRY(rows_to_host(e, bus_va, e->bus_va, g.nb_tot, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -1750,20 +1419,15 @@ int gpf_get_results_pinned(gpf_handle e, int32_t lane0, int32_t n, int32_t what,
   const size_t bytes[8] = {N * g.n_out * 4, N * g.dim_topo * 4, N * g.n_shunt * 4, N * g.n_line, N * 16, N * g.nb_tot * 8, N * g.nb_tot * 8, N * g.n_line * 4};
   size_t off[8], total = 0;
   for (int k = 0; k < 8; ++k) { off[k] = total; if ((what >> k) & 1) total += al(bytes[k]); }
-  if (e->res_pin_bytes < total) {
-    if (e->res_pin) (void)hipHostFree(e->res_pin);
-    e->res_pin = nullptr; e->res_pin_bytes = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->res_pin), total, hipHostMallocDefault));
-    e->res_pin_bytes = total;
-  }
+  HIP_TRY(e->res_pin.reserve(total));
   const void* src[8] = {e->out.p + (size_t)lane0 * g.n_out, e->topo_out.p + (size_t)lane0 * g.dim_topo, e->shunt_bus_out.p + (size_t)lane0 * g.n_shunt,
                         e->line_status.p + (size_t)lane0 * g.n_line, e->status.p + (size_t)lane0 * 4, e->bus_vm.p + (size_t)lane0 * g.nb_tot,
                         e->bus_va.p + (size_t)lane0 * g.nb_tot, e->rho.p + (size_t)lane0 * g.n_line};
   for (int k = 0; k < 8; ++k) {
     ptrs[k] = nullptr;
     if (!((what >> k) & 1) || bytes[k] == 0) continue;
-    HIP_TRY(hipMemcpyAsync(e->res_pin + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, e->stream));
-    ptrs[k] = e->res_pin + off[k];
+    HIP_TRY(hipMemcpyAsync(e->res_pin.p + off[k], src[k], bytes[k], hipMemcpyDeviceToHost, e->stream));
+    ptrs[k] = e->res_pin.p + off[k];
   }
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
@@ -1773,7 +1437,6 @@ int gpf_upload_chronics(gpf_handle e, int32_t n_tables, int32_t T, const float* 
   if (!e || n_tables <= 0 || T <= 0 || !data) return fail(GPF_E_INVALID, "gpf_upload_chronics: bad arguments");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->chron.release();
   e->maint.release();                       // belongs to the previous tables
   e->h_maint.clear(); e->h_hazard.clear();
   e->forecast.release(); e->fc_h = 0;
@@ -1958,8 +1621,8 @@ int step_range(gpf_engine* e, const gpf::Bufs& b_in, int lane0, int n, int t0, i
   p.env = pb.env = e->env_on;
   p.jit = pb.jit = jit_for_launch(e);
   int n_disp = 0;
-  HIP_TRY(gpf_launch_step_sparse(p, e->device, e->d_params_s, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
-  if (pb.sparse_nb) HIP_TRY(gpf_launch_step_sparse(pb, e->device, e->d_params_s, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
+  HIP_TRY(gpf_launch_step_sparse(p, e->device, e->d_params_s.p, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
+  if (pb.sparse_nb) HIP_TRY(gpf_launch_step_sparse(pb, e->device, e->d_params_s.p, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
   e->n_step_calls += 1; e->n_step_dispatches += n_disp;
   HIP_TRY(hipGetLastError());
   if (e->profiling) HIP_TRY(hipEventRecord(eb, e->stream));
@@ -1986,7 +1649,7 @@ int topo_prestep(gpf_engine* e, bool acts) {
   const gpf::TopoTab tab{e->ta_off.p, e->ta_items.p, e->ta_amb.p, e->ta_n_act};
   const size_t lds = acts ? gpf::topo_prestep_lds_ints(g.dim_topo, g.n_line, g.n_sub, g.n_shunt, g.n_busbar) * sizeof(int) : 0;
   hipLaunchKernelGGL(gpf::topo_prestep_kernel, dim3((unsigned)e->n_lanes), dim3(64), lds, e->stream, topo_dev(e), tab, topo_lanes(e),
-                     e->ta_rules, e->n_lanes, acts ? 1 : 0);
+                     *e->ta_rules, e->n_lanes, acts ? 1 : 0);
   HIP_TRY(hipGetLastError());
   if (!readback) return GPF_OK;
   return topo_readback(e, true);
@@ -1999,19 +1662,16 @@ int topo_readback(gpf_engine* e, bool moved) {
   const gpf::GridDev& g = e->g;
   const size_t w = (size_t)g.dim_topo + g.n_shunt;
   const size_t need = 1 + (size_t)e->n_lanes + (size_t)e->n_lanes * w;
-  if (e->ta_pin_n < need) {
+  if (e->ta_pin.n < need) {
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->ta_pin) (void)hipHostFree(e->ta_pin);
-    e->ta_pin = nullptr; e->ta_pin_n = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->ta_pin), need * sizeof(int), hipHostMallocDefault));
-    e->ta_pin_n = need;
+    HIP_TRY(e->ta_pin.reserve(need));
   }
-  HIP_TRY(hipMemcpyAsync(e->ta_pin, e->ta_list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->ta_pin.p, e->ta_list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  const int cnt = e->ta_pin[0];
+  const int cnt = e->ta_pin.p[0];
   if (cnt <= 0) return GPF_OK;
   if (cnt > e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back count)");
-  int* ids = e->ta_pin + 1;
+  int* ids = e->ta_pin.p + 1;
   int* rows = ids + e->n_lanes;
   HIP_TRY(hipMemcpyAsync(ids, e->ta_list.p + 1, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(rows, e->ta_list_rows.p, (size_t)cnt * w * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -2044,7 +1704,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if (acts && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: a launch that carries topology actions must be a one-step launch (the line-cooldown rule needs the "
                                "action step's trips and outages): use n_steps = 1");
-  if (acts && e->ta_rules.cd_line > 0 && !o->track_cooldown)
+  if (acts && e->ta_rules->cd_line > 0 && !o->track_cooldown)
     return fail(GPF_E_INVALID, "gpf_step_n: topology actions with cooldown_line > 0 need gpf_step_opts::track_cooldown (the agents' line "
                                "cooldowns are only counted down by a launch that maintains the line cooldowns)");
   if (e->ta_on && e->ta_n_moved > 0 && o->auto_reset && n_steps != 1)
@@ -2067,7 +1727,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     // lanes an action moved to another class than their reset topology's: an auto-reset puts them back, the host re-keys them
     const bool list_resets = o->auto_reset && e->ta_n_moved > 0;
     if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
-    hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), e->ta_rules,
+    hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), *e->ta_rules,
                        e->n_lanes, acts ? 1 : 0, n_steps, list_resets ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (list_resets) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
@@ -2109,6 +1769,7 @@ int topo_enable(gpf_engine* e) {
   HIP_TRY(hipMemsetAsync(e->ta_aff.p, 0, cap * ((size_t)g.n_line + g.n_sub), e->stream));
   e->ta_moved.assign(cap, 0);
   e->ta_n_moved = 0;
+  e->ta_rules = std::make_unique<gpf::TopoRules>();
   e->ta_on = true;
   for (int v : e->h_init_topo) e->ta_may_split |= v >= 2;
   return reset_topo_state(e, 0, (int)cap);
@@ -2123,7 +1784,7 @@ int gpf_set_topo_rules(gpf_handle e, int32_t on, int32_t max_sub_changed, int32_
     return fail(GPF_E_INVALID, "gpf_set_topo_rules: negative parameter");
   int rc = topo_enable(e);
   if (rc != GPF_OK) return rc;
-  e->ta_rules = gpf::TopoRules{on ? 1 : 0, max_sub_changed, max_line_status_changed, cooldown_sub, cooldown_line};
+  *e->ta_rules = gpf::TopoRules{on ? 1 : 0, max_sub_changed, max_line_status_changed, cooldown_sub, cooldown_line};
   return GPF_OK;
 }
 
@@ -2204,16 +1865,16 @@ int gpf_topo_actions_on_device(gpf_handle e, int32_t on) {
 }
 }  // extern "C"
 namespace {
+// the acting path's row accessors below: argument checks (the first call allocates the acting path's buffers), one row range, a
+// synchronisation (the caller may reuse its array at once)
 template <typename T>
-int topo_rows_io(gpf_engine* e, DevArr<T>& arr, size_t stride, int lane0, int n, T* host, bool to_device, const char* who) {
-  if (!check_range(e, lane0, n) || (!host && n)) return fail(GPF_E_INVALID, std::string(who) + ": bad range");
+int topo_rows(gpf_engine* e, DevArr<T>& arr, size_t stride, int lane0, int n, T* get, const T* set, const char* who) {
+  if (!check_range(e, lane0, n) || (!get && !set && n)) return fail(GPF_E_INVALID, std::string(who) + ": bad range");
   int rc = topo_enable(e);
-  if (rc != GPF_OK) return rc;
-  if (n == 0 || stride == 0) return GPF_OK;
+  if (rc != GPF_OK || n == 0) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  T* d = arr.p + (size_t)lane0 * stride;
-  if (to_device) HIP_TRY(hipMemcpyAsync(d, host, (size_t)n * stride * sizeof(T), hipMemcpyHostToDevice, e->stream));
-  else HIP_TRY(hipMemcpyAsync(host, d, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, get, arr, stride, lane0, n));
+  HIP_TRY(rows_to_device(e, arr, set, stride, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2222,17 +1883,17 @@ extern "C" {
 
 int gpf_get_sub_cooldown(gpf_handle e, int32_t lane0, int32_t n, int32_t* sub_cooldown) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_sub_cooldown: null");
-  return topo_rows_io<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, sub_cooldown, false, "gpf_get_sub_cooldown");
+  return topo_rows<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, sub_cooldown, nullptr, "gpf_get_sub_cooldown");
 }
 int gpf_set_sub_cooldown(gpf_handle e, int32_t lane0, int32_t n, const int32_t* sub_cooldown) {
   if (!e) return fail(GPF_E_INVALID, "gpf_set_sub_cooldown: null");
   if (sub_cooldown) for (size_t i = 0; i < (size_t)std::max(n, 0) * e->g.n_sub; ++i)
     if (sub_cooldown[i] < 0) return fail(GPF_E_INVALID, "gpf_set_sub_cooldown: negative cooldown");
-  return topo_rows_io<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, const_cast<int32_t*>(sub_cooldown), true, "gpf_set_sub_cooldown");
+  return topo_rows<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, nullptr, sub_cooldown, "gpf_set_sub_cooldown");
 }
 int gpf_get_last_bus(gpf_handle e, int32_t lane0, int32_t n, int32_t* last_bus) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_last_bus: null");
-  return topo_rows_io<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, last_bus, false, "gpf_get_last_bus");
+  return topo_rows<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, last_bus, nullptr, "gpf_get_last_bus");
 }
 int gpf_set_last_bus(gpf_handle e, int32_t lane0, int32_t n, const int32_t* last_bus) {
   if (!e) return fail(GPF_E_INVALID, "gpf_set_last_bus: null");
@@ -2240,11 +1901,11 @@ int gpf_set_last_bus(gpf_handle e, int32_t lane0, int32_t n, const int32_t* last
     if (last_bus[i] < 1 || last_bus[i] > e->g.n_busbar) return fail(GPF_E_INVALID, "gpf_set_last_bus: busbars must be 1..n_busbar");
     e->ta_may_split |= last_bus[i] >= 2;
   }
-  return topo_rows_io<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, const_cast<int32_t*>(last_bus), true, "gpf_set_last_bus");
+  return topo_rows<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, nullptr, last_bus, "gpf_set_last_bus");
 }
 int gpf_get_topo_flags(gpf_handle e, int32_t lane0, int32_t n, uint8_t* flags) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_topo_flags: null");
-  return topo_rows_io<unsigned char>(e, e->ta_flags, 2, lane0, n, flags, false, "gpf_get_topo_flags");
+  return topo_rows<unsigned char>(e, e->ta_flags, 2, lane0, n, flags, nullptr, "gpf_get_topo_flags");
 }
 
 int gpf_set_storage_params(gpf_handle e, const double* emax, const double* emin, const double* loss, const double* eff_charge,
@@ -2254,7 +1915,6 @@ int gpf_set_storage_params(gpf_handle e, const double* emax, const double* emin,
   if (ns && (!emax || !emin || !loss || !eff_charge || !eff_discharge || !charge0)) return fail(GPF_E_INVALID, "gpf_set_storage_params: null");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->sto_emax.release(); e->sto_emin.release(); e->sto_loss.release(); e->sto_effc.release(); e->sto_effd.release(); e->sto_charge0.release();
   HIP_TRY(e->sto_emax.upload(emax, ns)); HIP_TRY(e->sto_emin.upload(emin, ns)); HIP_TRY(e->sto_loss.upload(loss, ns));
   HIP_TRY(e->sto_effc.upload(eff_charge, ns)); HIP_TRY(e->sto_effd.upload(eff_discharge, ns)); HIP_TRY(e->sto_charge0.upload(charge0, ns));
   e->h_charge0.assign(charge0, charge0 + ns);
@@ -2279,9 +1939,9 @@ int gpf_set_env_dynamics(gpf_handle e, int32_t on, double tol_poly) {
     HIP_TRY(e->env_target.alloc(B * ng)); HIP_TRY(e->env_actual.alloc(B * ng)); HIP_TRY(e->env_prev.alloc(B * ng)); HIP_TRY(e->env_already.alloc(B * ng));
     HIP_TRY(e->env_charge.alloc(B * ns)); HIP_TRY(e->env_amount_prev.alloc(B)); HIP_TRY(e->env_fresh.alloc(B));
     // the redispatch and storage action rows of all lanes are ONE allocation ([B][n_gen] | [B][n_storage]): a host agent's two uploads per step are one DMA
-    HIP_TRY(e->env_act_redisp.alloc(B * ng + B * ns)); e->env_act_storage.p = e->env_act_redisp.p + B * ng; e->env_act_storage.n = B * ns;
+    HIP_TRY(e->env_act_redisp.alloc(B * ng + B * ns)); e->env_act_storage = e->env_act_redisp.p + B * ng;
     HIP_TRY(e->env_limit.alloc(B * ng)); HIP_TRY(e->env_curt_prev.alloc(B)); HIP_TRY(e->env_act_curtail.alloc(B * ng)); HIP_TRY(e->env_illegal.alloc(B));
-    HIP_TRY(hipMemset(e->env_act_redisp.p, 0, B * ng * sizeof(float))); HIP_TRY(hipMemset(e->env_act_storage.p, 0, B * ns * sizeof(float)));
+    HIP_TRY(hipMemset(e->env_act_redisp.p, 0, B * ng * sizeof(float))); HIP_TRY(hipMemset(e->env_act_storage, 0, B * ns * sizeof(float)));
     HIP_TRY(hipMemset(e->env_charge.p, 0, B * ns * sizeof(float)));
   }
   e->env_on = true;
@@ -2301,14 +1961,11 @@ namespace {
 int act_pin_begin(gpf_engine* e) {
   const size_t B = e->cap_lanes, ng = e->g.n_gen, ns = std::max(e->g.n_sto, 1), need = B * (2 * ng + ns);     // (the device layout: padded lane count)
   if (e->act_up) HIP_TRY(hipEventSynchronize(e->act_up));
-  if (e->act_pin_n < need) {
-    if (e->act_pin) (void)hipHostFree(e->act_pin);
-    e->act_pin = nullptr; e->act_pin_n = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->act_pin), need * sizeof(float), hipHostMallocDefault));
-    std::memset(e->act_pin, 0, need * sizeof(float));           // (the padding lanes' rows travel with the others)
-    e->act_pin_n = need;
+  if (e->act_pin.n < need) {
+    HIP_TRY(e->act_pin.reserve(need));
+    std::memset(e->act_pin.p, 0, need * sizeof(float));         // (the padding lanes' rows travel with the others)
   }
-  if (!e->act_up) HIP_TRY(hipEventCreateWithFlags(&e->act_up, hipEventDisableTiming));
+  if (!e->act_up) HIP_TRY(e->act_up.create(hipEventDisableTiming));
   return GPF_OK;
 }
 }  // namespace
@@ -2324,14 +1981,14 @@ int gpf_set_lane_actions(gpf_handle e, const float* redispatch, const float* sto
     if (rc != GPF_OK) return rc;
   }
   const size_t Bc = e->cap_lanes, so = Bc * ng;                  // storage rows: behind the (padded) redispatch rows, on the host block as on the device
-  if (redispatch) std::memcpy(e->act_pin, redispatch, B * ng * sizeof(float));
-  if (storage_power && ns) std::memcpy(e->act_pin + so, storage_power, B * ns * sizeof(float));
+  if (redispatch) std::memcpy(e->act_pin.p, redispatch, B * ng * sizeof(float));
+  if (storage_power && ns) std::memcpy(e->act_pin.p + so, storage_power, B * ns * sizeof(float));
   if (redispatch && storage_power && ns) {
-    HIP_TRY(hipMemcpyAsync(e->env_act_redisp.p, e->act_pin, (so + B * ns) * sizeof(float), hipMemcpyHostToDevice, e->stream));     // one DMA for both
+    HIP_TRY(hipMemcpyAsync(e->env_act_redisp.p, e->act_pin.p, (so + B * ns) * sizeof(float), hipMemcpyHostToDevice, e->stream));     // one DMA for both
   } else if (redispatch) {
-    HIP_TRY(hipMemcpyAsync(e->env_act_redisp.p, e->act_pin, B * ng * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->env_act_redisp.p, e->act_pin.p, B * ng * sizeof(float), hipMemcpyHostToDevice, e->stream));
   } else if (storage_power && ns) {
-    HIP_TRY(hipMemcpyAsync(e->env_act_storage.p, e->act_pin + so, B * ns * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->env_act_storage, e->act_pin.p + so, B * ns * sizeof(float), hipMemcpyHostToDevice, e->stream));
   }
   e->env_act_r = redispatch != nullptr;
   e->env_act_s = storage_power != nullptr && ns > 0;
@@ -2374,7 +2031,7 @@ int gpf_set_lane_curtailment(gpf_handle e, const float* limit) {
     const int rc = act_pin_begin(e);
     if (rc != GPF_OK) return rc;
   }
-  float* stage = e->act_pin + (size_t)e->cap_lanes * (e->g.n_gen + std::max(e->g.n_sto, 1));       // (behind the redispatch | storage rows: act_pin_begin)
+  float* stage = e->act_pin.p + (size_t)e->cap_lanes * (e->g.n_gen + std::max(e->g.n_sto, 1));       // (behind the redispatch | storage rows: act_pin_begin)
   std::memcpy(stage, limit, n * sizeof(float));
   HIP_TRY(hipMemcpyAsync(e->env_act_curtail.p, stage, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipEventRecord(e->act_up, e->stream));
@@ -2388,10 +2045,10 @@ int gpf_get_env_state(gpf_handle e, int32_t lane0, int32_t n, float* target, flo
   if (!e->env_on) return fail(GPF_E_INVALID, "gpf_get_env_state: the environment dynamics are off");
   HIP_TRY(hipSetDevice(e->device));
   const size_t ng = e->g.n_gen, ns = e->g.n_sto;
-#define DLE(dst, arr, stride) if ((dst) && (stride) > 0) HIP_TRY(hipMemcpyAsync(dst, e->arr.p + (size_t)lane0 * (stride), (size_t)n * (stride) * sizeof(*e->arr.p), hipMemcpyDeviceToHost, e->stream))
-  DLE(target, env_target, ng); DLE(actual, env_actual, ng); DLE(prev_p, env_prev, ng); DLE(already_modified, env_already, ng);
-  DLE(charge, env_charge, ns); DLE(amount_prev, env_amount_prev, 1); DLE(curtail_limit, env_limit, ng); DLE(curtail_prev, env_curt_prev, 1);
-#undef DLE
+  HIP_TRY(rows_to_host(e, target, e->env_target, ng, lane0, n)); HIP_TRY(rows_to_host(e, actual, e->env_actual, ng, lane0, n));
+  HIP_TRY(rows_to_host(e, prev_p, e->env_prev, ng, lane0, n)); HIP_TRY(rows_to_host(e, already_modified, e->env_already, ng, lane0, n));
+  HIP_TRY(rows_to_host(e, charge, e->env_charge, ns, lane0, n)); HIP_TRY(rows_to_host(e, amount_prev, e->env_amount_prev, 1, lane0, n));
+  HIP_TRY(rows_to_host(e, curtail_limit, e->env_limit, ng, lane0, n)); HIP_TRY(rows_to_host(e, curtail_prev, e->env_curt_prev, 1, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2400,7 +2057,7 @@ int gpf_get_env_illegal(gpf_handle e, int32_t lane0, int32_t n, int32_t* count) 
   if (!check_range(e, lane0, n) || !count) return fail(GPF_E_INVALID, "gpf_get_env_illegal: bad range / null");
   if (!e->env_on) return fail(GPF_E_INVALID, "gpf_get_env_illegal: the environment dynamics are off");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(count, e->env_illegal.p + lane0, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, count, e->env_illegal, 1, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2409,7 +2066,7 @@ int gpf_set_env_illegal(gpf_handle e, int32_t lane0, int32_t n, const int32_t* c
   if (!check_range(e, lane0, n) || !count) return fail(GPF_E_INVALID, "gpf_set_env_illegal: bad range / null");
   if (!e->env_on) return fail(GPF_E_INVALID, "gpf_set_env_illegal: the environment dynamics are off");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(e->env_illegal.p + lane0, count, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(rows_to_device(e, e->env_illegal, count, 1, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2421,10 +2078,10 @@ int gpf_set_env_state(gpf_handle e, int32_t lane0, int32_t n, const float* targe
   if (!e->env_on) return fail(GPF_E_INVALID, "gpf_set_env_state: the environment dynamics are off");
   HIP_TRY(hipSetDevice(e->device));
   const size_t ng = e->g.n_gen, ns = e->g.n_sto;
-#define ULE(src, arr, stride) if ((src) && (stride) > 0) HIP_TRY(hipMemcpyAsync(e->arr.p + (size_t)lane0 * (stride), src, (size_t)n * (stride) * sizeof(*e->arr.p), hipMemcpyHostToDevice, e->stream))
-  ULE(target, env_target, ng); ULE(actual, env_actual, ng); ULE(prev_p, env_prev, ng); ULE(already_modified, env_already, ng);
-  ULE(charge, env_charge, ns); ULE(amount_prev, env_amount_prev, 1); ULE(curtail_limit, env_limit, ng); ULE(curtail_prev, env_curt_prev, 1);
-#undef ULE
+  HIP_TRY(rows_to_device(e, e->env_target, target, ng, lane0, n)); HIP_TRY(rows_to_device(e, e->env_actual, actual, ng, lane0, n));
+  HIP_TRY(rows_to_device(e, e->env_prev, prev_p, ng, lane0, n)); HIP_TRY(rows_to_device(e, e->env_already, already_modified, ng, lane0, n));
+  HIP_TRY(rows_to_device(e, e->env_charge, charge, ns, lane0, n)); HIP_TRY(rows_to_device(e, e->env_amount_prev, amount_prev, 1, lane0, n));
+  HIP_TRY(rows_to_device(e, e->env_limit, curtail_limit, ng, lane0, n)); HIP_TRY(rows_to_device(e, e->env_curt_prev, curtail_prev, 1, lane0, n));
   if (prev_p) HIP_TRY(hipMemsetAsync(e->env_fresh.p + lane0, 0, (size_t)n, e->stream));     // previous set-points given: not a fresh episode
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
@@ -2478,8 +2135,8 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
   const double tm0 = sim_timing ? now_us() : 0.0;
   // 1. the source lanes' topology / shunt rows as they are on the device NOW (trips and maintenance included) -> host
   const int w = g.dim_topo + g.n_shunt;
-  if (e->sim_src.n < (size_t)n_src) { e->sim_src.release(); HIP_TRY(e->sim_src.alloc((size_t)n_src)); }
-  if (e->sim_rows.n < (size_t)n_src * w) { e->sim_rows.release(); HIP_TRY(e->sim_rows.alloc((size_t)n_src * w)); }
+  if (e->sim_src.n < (size_t)n_src) HIP_TRY(e->sim_src.alloc((size_t)n_src));
+  if (e->sim_rows.n < (size_t)n_src * w) HIP_TRY(e->sim_rows.alloc((size_t)n_src * w));
   HIP_TRY(hipMemcpyAsync(e->sim_src.p, src_lanes, (size_t)n_src * sizeof(int), hipMemcpyHostToDevice, e->stream));
   hipLaunchKernelGGL(gpf::gather_topo_kernel, dim3(n_src), dim3(64), 0, e->stream, e->g, e->bufs(), e->sim_src.p, n_src, e->sim_rows.p);
   HIP_TRY(hipGetLastError());
@@ -2487,19 +2144,16 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
   // rows, then the candidate topology / shunt rows.  It is only rewritten after the synchronisation below, i.e. when the uploads of
   // the previous call have long been consumed.
   const size_t n_rows = (size_t)n_src * w, n_topo = (size_t)n_dst * g.dim_topo, n_sb = (size_t)n_dst * std::max(g.n_shunt, 1);
-  if (e->sim_pin_n < n_rows + n_topo + n_sb) {
+  if (e->sim_pin.n < n_rows + n_topo + n_sb) {
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->sim_pin) (void)hipHostFree(e->sim_pin);
-    e->sim_pin = nullptr; e->sim_pin_n = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->sim_pin), (n_rows + n_topo + n_sb) * sizeof(int), hipHostMallocDefault));
-    e->sim_pin_n = n_rows + n_topo + n_sb;
+    HIP_TRY(e->sim_pin.reserve(n_rows + n_topo + n_sb));
   }
-  int* const rows = e->sim_pin;
+  int* const rows = e->sim_pin.p;
   HIP_TRY(hipMemcpyAsync(rows, e->sim_rows.p, n_rows * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   const double tm1 = sim_timing ? now_us() : 0.0;
   // 2. candidate topologies on the host (the launch planner needs them anyway: busbars per substation, topology classes)
-  int* const topo = e->sim_pin + n_rows;
+  int* const topo = e->sim_pin.p + n_rows;
   int* const sb = topo + n_topo;
   // Scheduled maintenance ahead of the observation (_ObsEnv.init, Environment/_obsEnv.py:361-385 with
   // BaseEnv._update_vector_with_timestep, baseEnv.py:4768-4825): a forecast `time_step` >= 1 steps ahead has the lines out whose
@@ -2614,7 +2268,6 @@ int gpf_set_gen_limits(gpf_handle e, const double* pmin, const double* pmax, con
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   const size_t ng = e->g.n_gen;
-  e->rd_pmin.release(); e->rd_pmax.release(); e->rd_ru.release(); e->rd_rd.release(); e->rd_redisp.release();
   HIP_TRY(e->rd_pmin.upload(pmin, ng)); HIP_TRY(e->rd_pmax.upload(pmax, ng)); HIP_TRY(e->rd_ru.upload(ramp_up, ng));
   HIP_TRY(e->rd_rd.upload(ramp_down, ng)); HIP_TRY(e->rd_redisp.upload(redispatchable, ng));
   e->rd_eps = eps_poly;
@@ -2630,9 +2283,9 @@ int gpf_redispatch(gpf_handle e, int32_t lane0, int32_t n, const double* new_p, 
   if (n == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
   const size_t ng = e->g.n_gen, row = (size_t)n * ng;
-  if (e->rd_in.n < 4 * row + (size_t)n) { e->rd_in.release(); HIP_TRY(e->rd_in.alloc(4 * row + n)); }
-  if (e->rd_u8.n < row + (size_t)n) { e->rd_u8.release(); HIP_TRY(e->rd_u8.alloc(row + n)); }
-  if (e->rd_after.n < row) { e->rd_after.release(); HIP_TRY(e->rd_after.alloc(row)); }
+  if (e->rd_in.n < 4 * row + (size_t)n) HIP_TRY(e->rd_in.alloc(4 * row + n));
+  if (e->rd_u8.n < row + (size_t)n) HIP_TRY(e->rd_u8.alloc(row + n));
+  if (e->rd_after.n < row) HIP_TRY(e->rd_after.alloc(row));
   double* d = e->rd_in.p;
   HIP_TRY(hipMemcpyAsync(d, new_p, row * 8, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(d + row, prev_p, row * 8, hipMemcpyHostToDevice, e->stream));
@@ -2722,7 +2375,7 @@ int gpf_get_trajectory_cooldown(gpf_handle e, int32_t step0, int32_t n_steps, in
 int gpf_get_cooldown(gpf_handle e, int32_t lane0, int32_t n, int32_t* line_cooldown) {
   if (!check_range(e, lane0, n) || !line_cooldown) return fail(GPF_E_INVALID, "gpf_get_cooldown: bad arguments");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(line_cooldown, e->cooldown.p + (size_t)lane0 * e->g.n_line, (size_t)n * e->g.n_line * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, line_cooldown, e->cooldown, e->g.n_line, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2731,7 +2384,7 @@ int gpf_set_cooldown(gpf_handle e, int32_t lane0, int32_t n, const int32_t* line
   if (!check_range(e, lane0, n) || !line_cooldown) return fail(GPF_E_INVALID, "gpf_set_cooldown: bad arguments");
   for (size_t i = 0; i < (size_t)n * e->g.n_line; ++i) if (line_cooldown[i] < 0) return fail(GPF_E_INVALID, "gpf_set_cooldown: negative counter");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(e->cooldown.p + (size_t)lane0 * e->g.n_line, line_cooldown, (size_t)n * e->g.n_line * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(rows_to_device(e, e->cooldown, line_cooldown, e->g.n_line, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2756,9 +2409,8 @@ int gpf_get_trajectory_obs(gpf_handle e, int32_t step0, int32_t n_steps, int32_t
 int gpf_get_episode(gpf_handle e, int32_t lane0, int32_t n, uint8_t* done, int32_t* steps_and_resets) {
   if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_get_episode: bad range");
   HIP_TRY(hipSetDevice(e->device));
-  if (done) HIP_TRY(hipMemcpyAsync(done, e->done.p + lane0, (size_t)n, hipMemcpyDeviceToHost, e->stream));
-  if (steps_and_resets)
-    HIP_TRY(hipMemcpyAsync(steps_and_resets, e->episode.p + (size_t)lane0 * 2, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, done, e->done, 1, lane0, n));
+  HIP_TRY(rows_to_host(e, steps_and_resets, e->episode, 2, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2767,8 +2419,7 @@ int gpf_set_overflow_count(gpf_handle e, int32_t lane0, int32_t n, const int32_t
   if (!check_range(e, lane0, n) || !overflow_count) return fail(GPF_E_INVALID, "gpf_set_overflow_count: bad arguments");
   for (size_t i = 0; i < (size_t)n * e->g.n_line; ++i) if (overflow_count[i] < 0) return fail(GPF_E_INVALID, "gpf_set_overflow_count: negative counter");
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(e->overflow_count.p + (size_t)lane0 * e->g.n_line, overflow_count, (size_t)n * e->g.n_line * sizeof(int),
-                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(rows_to_device(e, e->overflow_count, overflow_count, e->g.n_line, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2777,11 +2428,9 @@ int gpf_get_step_outputs(gpf_handle e, int32_t lane0, int32_t n, float* rho, int
   if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_get_step_outputs: bad range");
   HIP_TRY(hipSetDevice(e->device));
   const size_t nl = e->g.n_line;
-  if (rho) HIP_TRY(hipMemcpyAsync(rho, e->rho.p + lane0 * nl, n * nl * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-  if (overflow_count)
-    HIP_TRY(hipMemcpyAsync(overflow_count, e->overflow_count.p + lane0 * nl, n * nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  if (disc_round)
-    HIP_TRY(hipMemcpyAsync(disc_round, e->disc_round.p + lane0 * nl, n * nl * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(rows_to_host(e, rho, e->rho, nl, lane0, n));
+  HIP_TRY(rows_to_host(e, overflow_count, e->overflow_count, nl, lane0, n));
+  HIP_TRY(rows_to_host(e, disc_round, e->disc_round, nl, lane0, n));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
@@ -2810,7 +2459,7 @@ static int close_window(gpf_engine* e) {
 }
 
 static int open_window(gpf_engine* e) {
-  if (!e->win_a) { HIP_TRY(hipEventCreate(&e->win_a)); HIP_TRY(hipEventCreate(&e->win_b)); }
+  if (!e->win_a) { HIP_TRY(e->win_a.create()); HIP_TRY(e->win_b.create()); }
   HIP_TRY(hipEventRecord(e->win_a, e->stream));
   e->win_launches = 0;
   e->window = true;
@@ -2850,838 +2499,6 @@ int gpf_get_kernel_time(gpf_handle e, double* total_ms, int64_t* n_launches) {
 }
 
 
-/* ---- DC sensitivity (PTDF) path ------------------------------------------------------------------------------------ */
-int gpf_ptdf_build(gpf_handle e, int32_t lane) {
-  if (!check_range(e, lane, 1)) return fail(GPF_E_INVALID, "gpf_ptdf_build: bad lane");
-  HIP_TRY(hipSetDevice(e->device));
-  const gpf::GridDev& g = e->g;
-  const gpf::OutOff& oo = e->oo;
-  std::vector<int> topo(g.dim_topo), sb(std::max(g.n_shunt, 1));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(topo.data(), e->topo.p + (size_t)lane * g.dim_topo, (size_t)g.dim_topo * sizeof(int), hipMemcpyDeviceToHost));
-  if (g.n_shunt) HIP_TRY(hipMemcpy(sb.data(), e->shunt_bus.p + (size_t)lane * g.n_shunt, (size_t)g.n_shunt * sizeof(int), hipMemcpyDeviceToHost));
-  const int nbt = g.nb_tot;
-  auto bus_of = [&](int sub, int local) -> int { return (local >= 1 && local <= g.n_busbar) ? sub + (local - 1) * g.n_sub : -1; };
-  std::vector<char> act(nbt, 0), ref(nbt, 0);
-  std::vector<int> lf(g.n_line, -1), lt(g.n_line, -1);
-  for (int l = 0; l < g.n_line; ++l) {
-    const int bo = topo[e->h_line_or_pos[l]], be = topo[e->h_line_ex_pos[l]];
-    if (bo >= 1 && be >= 1) {
-      lf[l] = bus_of(e->h_line_or_sub[l], bo); lt[l] = bus_of(e->h_line_ex_sub[l], be);
-      if (lf[l] < 0 || lt[l] < 0) return fail(GPF_E_INVALID, "gpf_ptdf_build: bus id out of range");
-      act[lf[l]] = act[lt[l]] = 1;
-    }
-  }
-  std::vector<int> inj_bus(g.n_inj, -1);
-  std::vector<double> inj_w(g.n_inj, 0.0);
-  for (int i = 0; i < g.n_gen; ++i) {
-    const int b = bus_of(e->h_gen_sub[i], topo[e->h_gen_pos[i]]);
-    if (b < 0) continue;
-    act[b] = 1;
-    if (e->h_gen_slack[i]) ref[b] = 1; else { inj_bus[oo.inj_gen_p + i] = b; inj_w[oo.inj_gen_p + i] = 1.0; }
-  }
-  for (int i = 0; i < g.n_load; ++i) {
-    const int b = bus_of(e->h_load_sub[i], topo[e->h_load_pos[i]]);
-    if (b >= 0) { act[b] = 1; inj_bus[oo.inj_load_p + i] = b; inj_w[oo.inj_load_p + i] = -1.0; }
-  }
-  for (int i = 0; i < g.n_sto; ++i) {
-    const int b = bus_of(e->h_sto_sub[i], topo[e->h_sto_pos[i]]);
-    if (b >= 0) { act[b] = 1; inj_bus[oo.inj_sto_p + i] = b; inj_w[oo.inj_sto_p + i] = -1.0; }
-  }
-  for (int i = 0; i < g.n_shunt; ++i) {
-    const int b = bus_of(e->h_shunt_sub[i], sb[i]);
-    if (b >= 0) { act[b] = 1; inj_bus[oo.inj_sh_p + i] = b; inj_w[oo.inj_sh_p + i] = -e->h_shunt_fact[i]; }
-  }
-  // reduced B' over the active non-reference buses, inverted by Gauss-Jordan with partial pivoting (once per topology)
-  std::vector<int> idx(nbt, -1), buses;
-  bool any_ref = false;
-  for (int b = 0; b < nbt; ++b) { any_ref |= (act[b] && ref[b]); if (act[b] && !ref[b]) { idx[b] = (int)buses.size(); buses.push_back(b); } }
-  if (!any_ref) return fail(GPF_E_INVALID, "gpf_ptdf_build: no in-service slack generator in this topology");
-  const int nr = (int)buses.size();
-  std::vector<double> M((size_t)nr * 2 * nr, 0.0);
-  for (int r = 0; r < nr; ++r) M[(size_t)r * 2 * nr + nr + r] = 1.0;
-  for (int l = 0; l < g.n_line; ++l) {
-    if (lf[l] < 0 || lf[l] == lt[l]) continue;
-    const double bb = e->h_br_bdc[l];
-    const int a = idx[lf[l]], c = idx[lt[l]];
-    if (a >= 0) M[(size_t)a * 2 * nr + a] += bb;
-    if (c >= 0) M[(size_t)c * 2 * nr + c] += bb;
-    if (a >= 0 && c >= 0) { M[(size_t)a * 2 * nr + c] -= bb; M[(size_t)c * 2 * nr + a] -= bb; }
-  }
-  for (int k = 0; k < nr; ++k) {
-    int p = k;
-    for (int r = k + 1; r < nr; ++r) if (std::fabs(M[(size_t)r * 2 * nr + k]) > std::fabs(M[(size_t)p * 2 * nr + k])) p = r;
-    const double pv = M[(size_t)p * 2 * nr + k];
-    if (!(std::fabs(pv) > 1e-12)) return fail(GPF_E_INVALID, "gpf_ptdf_build: the topology is islanded (singular B')");
-    if (p != k) for (int q = 0; q < 2 * nr; ++q) std::swap(M[(size_t)k * 2 * nr + q], M[(size_t)p * 2 * nr + q]);
-    const double rp = 1.0 / pv;
-    for (int q = 0; q < 2 * nr; ++q) M[(size_t)k * 2 * nr + q] *= rp;
-    for (int r = 0; r < nr; ++r) {
-      if (r == k) continue;
-      const double mlt = M[(size_t)r * 2 * nr + k];
-      if (mlt == 0.0) continue;
-      for (int q = k; q < 2 * nr; ++q) M[(size_t)r * 2 * nr + q] -= mlt * M[(size_t)k * 2 * nr + q];
-    }
-  }
-  auto X = [&](int bus_row, int bus_col) -> double {
-    const int r = bus_row >= 0 ? idx[bus_row] : -1, c = idx[bus_col];
-    return (r >= 0 && c >= 0) ? M[(size_t)r * 2 * nr + nr + c] : 0.0;
-  };
-  e->h_ptdf.assign((size_t)g.n_line * nbt, 0.0);
-  // the device GEMM runs over the ACTIVE buses only (compact index: half of the n_sub * n_busbar ids are unused)
-  std::vector<int> compact(nbt, -1);
-  int n_act = 0;
-  for (int b = 0; b < nbt; ++b) if (act[b]) compact[b] = n_act++;
-  const int nb_pad = std::max(4, (n_act + 3) & ~3), line_pad = (g.n_line + 15) & ~15;
-  const int kpad = (nb_pad + 31) & ~31;                      // (rows behind nb_pad stay zero: gpf_ptdf_flows_rows runs whole trips of 8 k-steps)
-  std::vector<double> pt((size_t)kpad * line_pad, 0.0);
-  for (int l = 0; l < g.n_line; ++l) {
-    if (lf[l] < 0 || lf[l] == lt[l]) continue;
-    for (int b = 0; b < nbt; ++b) {
-      if (idx[b] < 0) continue;
-      const double v = e->h_br_bdc[l] * (X(lf[l], b) - X(lt[l], b));
-      e->h_ptdf[(size_t)l * nbt + b] = v;
-      pt[(size_t)compact[b] * line_pad + l] = v;
-    }
-  }
-  for (int i = 0; i < g.n_inj; ++i) if (inj_bus[i] >= 0) inj_bus[i] = compact[inj_bus[i]];
-  e->ptdf_ready = false;
-  e->ptdf_inj_bus.release(); e->ptdf_inj_w.release(); e->ptdf_t.release();
-  HIP_TRY(e->ptdf_inj_bus.upload(inj_bus.data(), inj_bus.size()));
-  HIP_TRY(e->ptdf_inj_w.upload(inj_w.data(), inj_w.size()));
-  HIP_TRY(e->ptdf_t.upload(pt.data(), pt.size()));
-  if (e->ptdf_nb_pad != nb_pad || e->ptdf_line_pad != line_pad || !e->ptdf_flow.p) {
-    e->ptdf_flow.release();
-    HIP_TRY(e->ptdf_flow.alloc((size_t)e->cap_lanes * line_pad));
-  }
-  {   // LODF[l][k] = H[l][k] / (1 - H[k][k]), H[l][k] = PTDF[l][from_k] - PTDF[l][to_k]; LODF[k][k] = -1
-    std::vector<double> lo_((size_t)g.n_line * line_pad, 0.0);
-    // elements on every bus: a line whose outage only removes a bus that carries nothing else (one line end, no injection) does not
-    // island anything -- the reference's DC power flow of that contingency converges with every other flow unchanged: column of zeros
-    std::vector<int> n_lines_at(nbt, 0), n_other_at(nbt, 0);
-    for (int l = 0; l < g.n_line; ++l) if (lf[l] >= 0) { ++n_lines_at[lf[l]]; ++n_lines_at[lt[l]]; }
-    for (int i = 0; i < g.n_gen; ++i) { const int b = bus_of(e->h_gen_sub[i], topo[e->h_gen_pos[i]]); if (b >= 0) ++n_other_at[b]; }
-    for (int i = 0; i < g.n_load; ++i) { const int b = bus_of(e->h_load_sub[i], topo[e->h_load_pos[i]]); if (b >= 0) ++n_other_at[b]; }
-    for (int i = 0; i < g.n_sto; ++i) { const int b = bus_of(e->h_sto_sub[i], topo[e->h_sto_pos[i]]); if (b >= 0) ++n_other_at[b]; }
-    for (int i = 0; i < g.n_shunt; ++i) { const int b = bus_of(e->h_shunt_sub[i], sb[i]); if (b >= 0) ++n_other_at[b]; }
-    for (int k = 0; k < g.n_line; ++k) {
-      if (lf[k] < 0 || lf[k] == lt[k]) continue;                 // an open line: its outage changes nothing
-      const double hkk = e->h_ptdf[(size_t)k * nbt + lf[k]] - e->h_ptdf[(size_t)k * nbt + lt[k]];
-      const double den = 1.0 - hkk;
-      const bool dangling = (n_lines_at[lf[k]] == 1 && n_other_at[lf[k]] == 0) || (n_lines_at[lt[k]] == 1 && n_other_at[lt[k]] == 0);
-      for (int l = 0; l < g.n_line; ++l) {
-        const double hlk = e->h_ptdf[(size_t)l * nbt + lf[k]] - e->h_ptdf[(size_t)l * nbt + lt[k]];
-        lo_[(size_t)l * line_pad + k] = std::fabs(den) < 1e-8 ? (dangling ? (l == k ? -1.0 : 0.0) : std::nan("")) : (l == k ? -1.0 : hlk / den);   // (diagonal -1 as in the batch builder)
-      }
-    }
-    e->lodf.release();
-    { std::vector<float> lof(lo_.begin(), lo_.end()); HIP_TRY(e->lodf.upload(lof.data(), lof.size())); }
-    e->lodf_worst.release();
-    HIP_TRY(e->lodf_worst.alloc((size_t)e->cap_lanes * line_pad));
-  }
-  e->ptdf_nb_pad = nb_pad; e->ptdf_line_pad = line_pad;
-  e->ptdf_ready = true;
-  e->ptdf_batch = false;
-  return GPF_OK;
-}
-
-// PtdfDev of the tables the flows / screening kernels run on: the single topology of gpf_ptdf_build or the class tables of gpf_ptdf_build_batch
-static gpf::PtdfDev ptdf_dev(gpf_engine* e) {
-  gpf::PtdfDev P{};
-  P.n_inj = e->g.n_inj; P.nb_pad = e->ptdf_nb_pad; P.line_pad = e->ptdf_line_pad; P.n_line = e->g.n_line;
-  if (e->ptdf_batch) {
-    P.inj_bus = nullptr; P.inj_w = e->ptdfb_inj_w.p; P.ptdf_t = e->ptdfb_t.p;
-    P.order = e->ptdfb_order.p; P.blk_class = e->ptdfb_blk_class.p; P.cls_desc = e->ptdfb_desc.p; P.cls_status = e->ptdfb_status.p;
-    P.desc_stride = e->ptdfb_desc_stride; P.inj_bus_off = gpf::PTDFB_HDR + 2 * e->g.n_line;
-    P.ptdf_stride = (long long)e->ptdfb_kpad * e->ptdf_line_pad;
-  } else {
-    P.inj_bus = e->ptdf_inj_bus.p; P.inj_w = e->ptdf_inj_w.p; P.ptdf_t = e->ptdf_t.p;
-  }
-  return P;
-}
-
-// A few PERSISTENT host threads for the table walks of gpf_ptdf_build_batch (row hashes / comparisons, descriptors of unseen classes): creating
-// threads per call cost more than the work it spread (measured on the MI355X box: no gain from 4 fresh std::threads on 0.8 ms of work).
-// Workers sleep on a condition variable between calls; they are detached at process exit (never joined: no ordering against the HIP runtime).
-namespace {
-class HostPool {
- public:
-  static HostPool& get() { static HostPool* p = new HostPool(); return *p; }      // (intentionally leaked)
-  int size() const { return n_workers_ + 1; }
-  // body(part, n_parts) for part = 0 .. n_parts - 1, part 0 on the caller's thread; returns when all parts are done
-  void run(int n_parts, const std::function<void(int, int)>& body) {
-    n_parts = std::max(1, std::min(n_parts, size()));
-    if (n_parts == 1) { body(0, 1); return; }
-    std::lock_guard<std::mutex> call_lk(call_mu_);          // one parallel region at a time
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      body_ = &body; parts_ = n_parts; next_ = 1; left_ = n_parts - 1; ++gen_;
-    }
-    cv_.notify_all();
-    body(0, n_parts);
-    std::unique_lock<std::mutex> lk(mu_);
-    done_.wait(lk, [&] { return left_ == 0; });
-    body_ = nullptr;
-  }
- private:
-  HostPool() {
-    const char* v = getenv("GRIDPF_PTDFB_THREADS");
-    int t = v ? atoi(v) : 4;
-    const int hw = (int)std::thread::hardware_concurrency();
-    if (hw > 0 && t > hw) t = hw;
-    n_workers_ = std::max(0, t - 1);
-    for (int w = 0; w < n_workers_; ++w) std::thread([this] { loop(); }).detach();
-  }
-  void loop() {
-    unsigned long long seen = 0;
-    for (;;) {
-      std::unique_lock<std::mutex> lk(mu_);
-      cv_.wait(lk, [&] { return gen_ != seen && next_ < parts_; });
-      const unsigned long long g = gen_;
-      while (gen_ == g && next_ < parts_) {
-        const int part = next_++;
-        const std::function<void(int, int)>* b = body_;
-        const int np = parts_;
-        lk.unlock();
-        (*b)(part, np);
-        lk.lock();
-        if (--left_ == 0) done_.notify_all();
-      }
-      seen = g;
-    }
-  }
-  std::mutex mu_, call_mu_;
-  std::condition_variable cv_, done_;
-  const std::function<void(int, int)>* body_ = nullptr;
-  int n_workers_ = 0, parts_ = 0, next_ = 0, left_ = 0;
-  unsigned long long gen_ = 0;
-};
-}  // namespace
-
-// completes the asynchronous tail of gpf_ptdf_build_batch: class status in h_ptdfb_status, kernel duration in ptdfb_kernel_ms
-static int ptdfb_finish(gpf_engine* e) {
-  if (!e->ptdfb_pending) return GPF_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  std::copy(e->ptdfb_status_pin, e->ptdfb_status_pin + e->h_ptdfb_status.size(), e->h_ptdfb_status.begin());
-  if (e->ptdfb_prefetched && e->ptdfb_host_stale) {            // (device path: the class map and the descriptor headers came back behind the status)
-    const int n = e->ptdfb_n, nc = e->ptdfb_classes;
-    e->h_ptdfb_lane_class.assign(e->ptdfg_back_pin, e->ptdfg_back_pin + n);
-    e->h_ptdfb_hdr.assign(e->ptdfg_back_pin + n, e->ptdfg_back_pin + n + (size_t)nc * 4);
-    e->ptdfb_host_stale = false;
-  }
-  e->ptdfb_prefetched = false;
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e->ptdfb_ev_a, e->ptdfb_ev_b);
-  e->ptdfb_kernel_ms = ms;
-  e->ptdfb_pending = false;
-  return GPF_OK;
-}
-
-// lane -> class map and descriptor headers of a build whose integer half ran on the device: to the host mirrors, on demand (12 KB for 2 048
-// lanes / 256 classes; the descriptors themselves stay on the device); with_bus: the compact -> bus maps too (gpf_ptdf_batch_get)
-static int ptdfb_fetch_host(gpf_engine* e, bool with_bus = false) {
-  if (!e->ptdfb_host_stale && !(with_bus && e->ptdfb_bus_stale)) return GPF_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int n = e->ptdfb_n, nc = e->ptdfb_classes, stride = e->ptdfb_desc_stride, nbt = e->g.nb_tot;
-  if (e->ptdfb_host_stale) {
-    e->h_ptdfb_lane_class.resize(n);
-    HIP_TRY(hipMemcpy(e->h_ptdfb_lane_class.data(), e->ptdfg_lane_class.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    e->h_ptdfb_hdr.resize((size_t)nc * 4);
-    HIP_TRY(hipMemcpy2D(e->h_ptdfb_hdr.data(), 4 * sizeof(int), e->ptdfb_desc.p, (size_t)stride * sizeof(int), 4 * sizeof(int), (size_t)nc, hipMemcpyDeviceToHost));
-    e->ptdfb_host_stale = false;
-  }
-  if (with_bus && e->ptdfb_bus_stale) {
-    std::vector<int> c2b((size_t)nc * nbt);
-    HIP_TRY(hipMemcpy(c2b.data(), e->ptdfg_c2b.p, c2b.size() * sizeof(int), hipMemcpyDeviceToHost));
-    e->h_ptdfb_bus.assign(nc, std::vector<int>());
-    for (int c = 0; c < nc; ++c) {
-      const int n_act = e->h_ptdfb_hdr[(size_t)c * 4 + 1];
-      e->h_ptdfb_bus[c].assign(c2b.begin() + (size_t)c * nbt, c2b.begin() + (size_t)c * nbt + n_act);
-    }
-    e->ptdfb_bus_stale = false;
-  }
-  return GPF_OK;
-}
-
-// The integer half of gpf_ptdf_build_batch on the device.  out[0..3] = classes, slots, largest n_pad, largest n_act.  Returns GPF_OK with
-// *done = false when the device path does not apply or flagged something (hash collision inside a class, bus id out of range, capacity):
-// the caller then takes the host path, which reports the error properly.
-static int ptdfb_group_on_device(gpf_engine* e, int lane0, int n, int stride, int out[4], bool* done) {
-  *done = false;
-  const gpf::GridDev& g = e->g;
-  if (n > gpf::PTDFG_MAX_LANES || g.nb_tot > gpf::PTDFG_MAX_BUS || g.n_line > 256 || getenv("GRIDPF_PTDFB_HOST")) return GPF_OK;
-  HIP_TRY(e->ptdfg_hash.ensure((size_t)n)); HIP_TRY(e->ptdfg_lane_class.ensure((size_t)n)); HIP_TRY(e->ptdfg_first.ensure((size_t)n));
-  HIP_TRY(e->ptdfb_order.ensure((size_t)16 * n)); HIP_TRY(e->ptdfb_blk_class.ensure((size_t)n));
-  HIP_TRY(e->ptdfb_desc.ensure((size_t)n * stride)); HIP_TRY(e->ptdfg_c2b.ensure((size_t)n * g.nb_tot)); HIP_TRY(e->ptdfg_info.ensure(8));
-  if (!e->ptdfg_info_pin) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->ptdfg_info_pin), 8 * sizeof(int), hipHostMallocDefault));
-  gpf::PtdfGroupDev D{};
-  D.topo = e->topo.p; D.shunt_bus = e->shunt_bus.p;
-  D.lane0 = lane0; D.n = n; D.dim_topo = g.dim_topo; D.n_shunt = g.n_shunt; D.n_sub = g.n_sub; D.n_busbar = g.n_busbar; D.n_line = g.n_line;
-  D.n_gen = g.n_gen; D.n_load = g.n_load; D.n_sto = g.n_sto; D.n_inj = g.n_inj;
-  D.inj_gen_p = e->oo.inj_gen_p; D.inj_load_p = e->oo.inj_load_p; D.inj_sto_p = e->oo.inj_sto_p; D.inj_sh_p = e->oo.inj_sh_p;
-  D.line_or_pos = e->line_or_pos.p; D.line_ex_pos = e->line_ex_pos.p; D.line_or_sub = e->line_or_sub.p; D.line_ex_sub = e->line_ex_sub.p;
-  D.gen_pos = e->gen_pos.p; D.gen_sub = e->gen_sub.p; D.load_pos = e->load_pos.p; D.load_sub = e->load_sub.p; D.sto_pos = e->sto_pos.p;
-  D.sto_sub = e->sto_sub.p; D.shunt_sub = e->shunt_sub.p; D.gen_slack = e->gen_slack.p;
-  D.desc_stride = stride;
-  D.hash = e->ptdfg_hash.p; D.lane_class = e->ptdfg_lane_class.p; D.first_lane = e->ptdfg_first.p; D.order = e->ptdfb_order.p;
-  D.blk_class = e->ptdfb_blk_class.p; D.desc = e->ptdfb_desc.p; D.c2b = e->ptdfg_c2b.p; D.info = e->ptdfg_info.p;
-  hipLaunchKernelGGL(gpf::ptdfg_hash_kernel, dim3(n), dim3(64), 0, e->stream, D);
-  int np2 = gpf::PTDFG_SORT_THREADS;                   // (ptdfg_group_kernel sorts a multiple of its workgroup)
-  while (np2 < n) np2 <<= 1;
-  const size_t lds_sort = (size_t)np2 * 20;
-  static size_t lds_sort_set[64] = {0};
-  if (lds_sort > lds_sort_set[e->device & 63]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gpf::ptdfg_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort));
-    lds_sort_set[e->device & 63] = lds_sort;
-  }
-  hipLaunchKernelGGL(gpf::ptdfg_group_kernel, dim3(1), dim3(gpf::PTDFG_SORT_THREADS), lds_sort, e->stream, D);
-  hipLaunchKernelGGL(gpf::ptdfg_verify_kernel, dim3(n), dim3(64), 0, e->stream, D);
-  hipLaunchKernelGGL(gpf::ptdfg_desc_kernel, dim3(n), dim3(gpf::PTDFG_DESC_THREADS), 0, e->stream, D);     // (blocks beyond the class count return at once)
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(e->ptdfg_info_pin, e->ptdfg_info.p, 8 * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int* info = e->ptdfg_info_pin;
-  if (info[4] || info[5] || info[0] <= 0) return GPF_OK;           // -> host path
-  out[0] = info[0]; out[1] = info[1]; out[2] = std::max(16, info[2]); out[3] = std::max(1, info[3]);
-  *done = true;
-  return GPF_OK;
-}
-
-/* ---- PTDF / LODF of every distinct topology of a lane range, built on the device (gridpf_ptdf_batch.hpp) --------------------------- */
-int gpf_ptdf_build_batch(gpf_handle e, int32_t lane0, int32_t n, int32_t with_lodf, int32_t* n_classes_out) {
-  if (!check_range(e, lane0, n) || n <= 0) return fail(GPF_E_INVALID, "gpf_ptdf_build_batch: bad lane range");
-  HIP_TRY(hipSetDevice(e->device));
-  // a rebuild overwrites the lane -> class map and may regrow the device tables before it can fail: from here until it has succeeded there
-  // are NO tables (gpf_ptdf_flows / gpf_ptdf_batch_get refuse), instead of new lane classes against old tables
-  e->ptdf_ready = false; e->ptdf_batch = false;
-  e->ptdfb_pending = false;                        // (a status nobody asked for: the stream orders the next build behind the last one)
-  const gpf::GridDev& g = e->g;
-  const gpf::OutOff& oo = e->oo;
-  const int nl = g.n_line, nbt = g.nb_tot, nsh = g.n_shunt;
-  static const bool stage_timing = getenv("GRIDPF_SIM_TIMING") != nullptr;      // developer: stage times of the call on stderr
-  auto now_us = [] { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3; };
-  double tm[6] = {0, 0, 0, 0, 0, 0};
-  // ---- the integer half: on the device (gridpf_ptdf_group.hpp) when the range allows it, else -- and whenever the device flagged something -- on the host
-  const int stride = (gpf::PTDFB_HDR + 3 * nl + g.n_inj + gpf::PTDFB_MAX_N + 1 + 2 * nl + 3) & ~3;
-  int nc = 0, npad_max = 16, nact_max = 1;
-  size_t n_slots = 0;
-  std::vector<int> desc, order, blk_class;
-  int grp[4] = {0, 0, 0, 0};
-  bool dev = false;
-  { const int rc_g = ptdfb_group_on_device(e, lane0, n, stride, grp, &dev); if (rc_g != GPF_OK) return rc_g; }
-  auto host_group = [&]() -> int {
-  // the lanes' topology rows as they are on the device (a cascade inside gpf_step_n may have tripped lines the host never saw)
-  // (when no kernel can have rewritten them -- no cascade, no outage tables since the engine was created -- and the host sent every row of the
-  //  range itself, the host mirrors ARE the device rows: no trip over PCIe, no synchronisation; 2 048 rows of 560 ints are 4.6 MB)
-  std::vector<int> topo_own, sb_own;
-  const int* topo_p = nullptr;
-  const int* sb_p = nullptr;
-  bool mirror_ok = !e->dev_topo_dirty && getenv("GRIDPF_PTDFB_NO_MIRROR") == nullptr;
-  for (int k = lane0; k < lane0 + n && mirror_ok; ++k)
-    mirror_ok = e->h_lane_topo[(size_t)k * g.dim_topo] != INT_MIN && (!nsh || e->h_lane_sb[(size_t)k * nsh] != INT_MIN);
-  if (stage_timing) tm[0] = now_us();
-  if (mirror_ok) {
-    topo_p = e->h_lane_topo.data() + (size_t)lane0 * g.dim_topo;
-    sb_p = e->h_lane_sb.data() + (size_t)lane0 * std::max(nsh, 1);
-  } else {
-    topo_own.resize((size_t)n * g.dim_topo); sb_own.resize((size_t)n * std::max(nsh, 1));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (stage_timing) tm[0] = now_us();
-    HIP_TRY(hipMemcpy(topo_own.data(), e->topo.p + (size_t)lane0 * g.dim_topo, topo_own.size() * sizeof(int), hipMemcpyDeviceToHost));
-    if (nsh) HIP_TRY(hipMemcpy(sb_own.data(), e->shunt_bus.p + (size_t)lane0 * nsh, (size_t)n * nsh * sizeof(int), hipMemcpyDeviceToHost));
-    topo_p = topo_own.data(); sb_p = sb_own.data();
-  }
-  struct RowView { const int* p; const int* data() const { return p; } int operator[](size_t i) const { return p[i]; } } topo{topo_p}, sb{sb_p};
-  if (stage_timing) tm[1] = now_us();
-  // ---- classes: lanes with identical (topology row, shunt buses) ----------------------------------------------------------------------
-  std::unordered_map<uint64_t, std::vector<int>> cls_of;     // row hash -> classes with that hash (rows compared on a hit)
-  std::vector<int> first_lane;                       // representative lane (index in the range) of each class
-  std::vector<uint64_t> first_hash;                  // its row hash (key of the descriptor cache)
-  e->h_ptdfb_lane_class.assign(n, -1);
-  auto same_rows = [&](int a, int b) {
-    return std::memcmp(topo.data() + (size_t)a * g.dim_topo, topo.data() + (size_t)b * g.dim_topo, (size_t)g.dim_topo * sizeof(int)) == 0 &&
-           (!nsh || std::memcmp(sb.data() + (size_t)a * nsh, sb.data() + (size_t)b * nsh, (size_t)nsh * sizeof(int)) == 0);
-  };
-  cls_of.reserve((size_t)n);
-  // host threads for the two table walks of this call (row hashes, descriptors of unseen classes): a few hundred microseconds of one core each
-  // for 2 048 lanes / 256 classes of a 118-substation grid, embarrassingly parallel
-  HostPool& pool = HostPool::get();
-  auto par_for = [&](int count, int min_per_thread, const std::function<void(int, int, int)>& body) {     // body(begin, end, part index)
-    const int nt = std::max(1, std::min(pool.size(), count / std::max(1, min_per_thread)));
-    pool.run(nt, [&](int part, int n_parts) { body((int)((long long)count * part / n_parts), (int)((long long)count * (part + 1) / n_parts), part); });
-  };
-  std::vector<uint64_t> row_hash((size_t)n);
-  par_for(n, 256, [&](int k0, int k1, int) {
-  for (int k = k0; k < k1; ++k) {
-    // row hash: four independent multiply-xor chains over the row (one dependent multiply per int was 1 ms for 2 048 rows of 560 ints);
-    // equal hashes are confirmed by comparing the rows, so the hash only has to spread
-    const int* tp = topo.data() + (size_t)k * g.dim_topo;
-    uint64_t h0 = 1469598103934665603ull, h1 = 0x9E3779B97F4A7C15ull, h2 = 0xC2B2AE3D27D4EB4Full, h3 = 0x165667B19E3779F9ull;
-    int i = 0;
-    for (; i + 8 <= g.dim_topo; i += 8) {
-      h0 = (h0 ^ ((uint64_t)(uint32_t)tp[i] | ((uint64_t)(uint32_t)tp[i + 1] << 32))) * 0x9FB21C651E98DF25ull;
-      h1 = (h1 ^ ((uint64_t)(uint32_t)tp[i + 2] | ((uint64_t)(uint32_t)tp[i + 3] << 32))) * 0xD6E8FEB86659FD93ull;
-      h2 = (h2 ^ ((uint64_t)(uint32_t)tp[i + 4] | ((uint64_t)(uint32_t)tp[i + 5] << 32))) * 0xA0761D6478BD642Full;
-      h3 = (h3 ^ ((uint64_t)(uint32_t)tp[i + 6] | ((uint64_t)(uint32_t)tp[i + 7] << 32))) * 0xE7037ED1A0B428DBull;
-    }
-    for (; i < g.dim_topo; ++i) h0 = (h0 ^ (uint32_t)tp[i]) * 1099511628211ull;
-    for (int q = 0; q < nsh; ++q) h1 = (h1 ^ ((uint32_t)sb[(size_t)k * nsh + q] + 0x9E3779B9u)) * 1099511628211ull;
-    uint64_t h = h0 ^ (h1 >> 29 | h1 << 35) ^ (h2 >> 17 | h2 << 47) ^ (h3 >> 41 | h3 << 23);
-    h ^= h >> 32;
-    row_hash[k] = h;
-  }
-  });
-  // classes by hash first (no row is touched), then every lane's row is compared with its class representative's -- in parallel: the two
-  // passes over the rows (hash, confirm) are what grouping costs (4.6 MB each for 2 048 lanes of a 118-substation grid, memory-bound on one core)
-  for (int k = 0; k < n; ++k) {
-    const uint64_t h = row_hash[k];
-    std::vector<int>& cand = cls_of[h];
-    if (cand.empty()) { cand.push_back((int)first_lane.size()); first_lane.push_back(k); first_hash.push_back(h); }
-    e->h_ptdfb_lane_class[k] = cand[0];
-  }
-  std::vector<char> differs((size_t)n, 0);
-  par_for(n, 256, [&](int k0, int k1, int) {
-    for (int k = k0; k < k1; ++k) { const int rep = first_lane[e->h_ptdfb_lane_class[k]]; differs[k] = (rep != k && !same_rows(rep, k)) ? 1 : 0; }
-  });
-  for (int k = 0; k < n; ++k) {                     // (a 64-bit hash collision between different rows: never seen; handled the slow way)
-    if (!differs[k]) continue;
-    const uint64_t h = row_hash[k];
-    std::vector<int>& cand = cls_of[h];
-    int c = -1;
-    for (size_t q = 1; q < cand.size(); ++q) if (same_rows(first_lane[cand[q]], k)) { c = cand[q]; break; }
-    if (c < 0) { c = (int)first_lane.size(); first_lane.push_back(k); first_hash.push_back(h); cand.push_back(c); }
-    e->h_ptdfb_lane_class[k] = c;
-  }
-  nc = (int)first_lane.size();
-  if (stage_timing) tm[2] = now_us();
-  // descriptor: header | lf | lt | inj_bus | lflag | row pointers of B' [PTDFB_MAX_N + 1] | row entries [2 n_line] (gridpf_ptdf_batch.hpp)
-  if (nl > 65535) return fail(GPF_E_CAPACITY, "gpf_ptdf_build_batch: more than 65535 lines");
-  desc.assign((size_t)nc * stride, -1);
-  e->h_ptdfb_bus.assign(nc, std::vector<int>());
-  auto bus_of = [&](int sub, int local) -> int { return (local >= 1 && local <= g.n_busbar) ? sub + (local - 1) * g.n_sub : -1; };
-  // One descriptor per class: ~3 us of table walks each (800 us for 256 classes of a 118-substation grid on one core)
-  struct ClsScratch { std::vector<char> act, ref, has_ref; std::vector<int> bf, bt, n_lines_at, n_other_at, ibus, compact, comp, cnt; int npad_max = 16, nact_max = 1; };
-  auto build_class = [&](int c, ClsScratch& S_) -> int {
-    std::vector<char>&act = S_.act, &ref = S_.ref, &has_ref = S_.has_ref;
-    std::vector<int>&bf = S_.bf, &bt = S_.bt, &n_lines_at = S_.n_lines_at, &n_other_at = S_.n_other_at, &ibus = S_.ibus, &compact = S_.compact, &comp = S_.comp, &cnt = S_.cnt;
-    const int* tp = topo.data() + (size_t)first_lane[c] * g.dim_topo;
-    const int* sbp = sb.data() + (size_t)first_lane[c] * std::max(nsh, 1);
-    int* d = desc.data() + (size_t)c * stride;
-    int* lf = d + gpf::PTDFB_HDR;
-    int* lt = lf + nl;
-    int* ib = lt + nl;
-    int* lflag = ib + g.n_inj;
-    act.assign(nbt, 0); ref.assign(nbt, 0);
-    bf.assign(nl, -1); bt.assign(nl, -1);
-    n_lines_at.assign(nbt, 0); n_other_at.assign(nbt, 0);      // in-service line ends / other elements on each bus
-    for (int l = 0; l < nl; ++l) {
-      const int bo = tp[e->h_line_or_pos[l]], be = tp[e->h_line_ex_pos[l]];
-      if (bo >= 1 && be >= 1) {
-        bf[l] = bus_of(e->h_line_or_sub[l], bo); bt[l] = bus_of(e->h_line_ex_sub[l], be);
-        if (bf[l] < 0 || bt[l] < 0) return 1;
-        act[bf[l]] = act[bt[l]] = 1;
-      }
-    }
-    ibus.assign(g.n_inj, -1);
-    for (int i = 0; i < g.n_gen; ++i) {
-      const int b = bus_of(e->h_gen_sub[i], tp[e->h_gen_pos[i]]);
-      if (b < 0) continue;
-      act[b] = 1;
-      ++n_other_at[b];
-      if (e->h_gen_slack[i]) ref[b] = 1; else ibus[oo.inj_gen_p + i] = b;
-    }
-    for (int i = 0; i < g.n_load; ++i) { const int b = bus_of(e->h_load_sub[i], tp[e->h_load_pos[i]]); if (b >= 0) { act[b] = 1; ++n_other_at[b]; ibus[oo.inj_load_p + i] = b; } }
-    for (int i = 0; i < g.n_sto; ++i) { const int b = bus_of(e->h_sto_sub[i], tp[e->h_sto_pos[i]]); if (b >= 0) { act[b] = 1; ++n_other_at[b]; ibus[oo.inj_sto_p + i] = b; } }
-    for (int i = 0; i < nsh; ++i) { const int b = bus_of(e->h_shunt_sub[i], sbp[i]); if (b >= 0) { act[b] = 1; ++n_other_at[b]; ibus[oo.inj_sh_p + i] = b; } }
-    for (int l = 0; l < nl; ++l) if (bf[l] >= 0) { ++n_lines_at[bf[l]]; ++n_lines_at[bt[l]]; }
-    // compact numbering: active non-reference buses first, then the active reference buses
-    compact.assign(nbt, -1);
-    std::vector<int>& c2b = e->h_ptdfb_bus[c];
-    c2b.reserve(nbt);
-    int nr = 0, n_act = 0;
-    for (int b = 0; b < nbt; ++b) if (act[b] && !ref[b]) { compact[b] = nr++; c2b.push_back(b); }
-    n_act = nr;
-    bool any_ref = false;
-    for (int b = 0; b < nbt; ++b) if (act[b] && ref[b]) { compact[b] = n_act++; c2b.push_back(b); any_ref = true; }
-    // connectivity (rundcpp(check_connectivity=True), pandaPowerBackend.py:1090): every active bus must reach a reference bus
-    int status = any_ref ? 0 : 3;
-    if (any_ref) {
-      comp.resize(nbt);
-      for (int b = 0; b < nbt; ++b) comp[b] = b;
-      auto find = [&](int x) { while (comp[x] != x) { comp[x] = comp[comp[x]]; x = comp[x]; } return x; };
-      for (int l = 0; l < nl; ++l) if (bf[l] >= 0 && bf[l] != bt[l]) comp[find(bf[l])] = find(bt[l]);
-      has_ref.assign(nbt, 0);
-      for (int b = 0; b < nbt; ++b) if (act[b] && ref[b]) has_ref[find(b)] = 1;
-      for (int b = 0; b < nbt; ++b) if (act[b] && !has_ref[find(b)]) { status = 2; break; }
-    }
-    const int n_pad = std::max(16, (nr + 15) & ~15);
-    if (n_pad > gpf::PTDFB_MAX_N) return 2;
-    d[0] = nr; d[1] = n_act; d[2] = n_pad; d[3] = status;
-    for (int l = 0; l < nl; ++l) {
-      const bool on = bf[l] >= 0 && bf[l] != bt[l];
-      lf[l] = on ? compact[bf[l]] : -1; lt[l] = on ? compact[bt[l]] : -1;
-      // a line end on a bus that carries nothing else: the outage of the line removes the bus (no islanding, the other flows stand)
-      lflag[l] = (on && ((n_lines_at[bf[l]] == 1 && n_other_at[bf[l]] == 0) || (n_lines_at[bt[l]] == 1 && n_other_at[bt[l]] == 0))) ? 1 : 0;
-    }
-    {   // rows of the reduced B': for every non-reference bus r the lines at it, ascending, as line | other end << 16
-      int* cptr = lflag + nl;
-      int* cent = cptr + gpf::PTDFB_MAX_N + 1;
-      cnt.assign(nr + 1, 0);
-      for (int l = 0; l < nl; ++l) { if (lf[l] < 0) continue; if (lf[l] < nr) ++cnt[lf[l]]; if (lt[l] < nr) ++cnt[lt[l]]; }
-      int acc = 0;
-      for (int r = 0; r < nr; ++r) { cptr[r] = acc; acc += cnt[r]; cnt[r] = cptr[r]; }
-      for (int r = nr; r <= gpf::PTDFB_MAX_N; ++r) cptr[r] = acc;
-      for (int i = 0; i < 2 * nl; ++i) cent[i] = 0;
-      for (int l = 0; l < nl; ++l) {
-        if (lf[l] < 0) continue;
-        if (lf[l] < nr) cent[cnt[lf[l]]++] = l | (lt[l] << 16);
-        if (lt[l] < nr) cent[cnt[lt[l]]++] = l | (lf[l] << 16);
-      }
-    }
-    for (int i = 0; i < g.n_inj; ++i) ib[i] = ibus[i] >= 0 ? compact[ibus[i]] : -1;
-    S_.npad_max = std::max(S_.npad_max, n_pad);
-    S_.nact_max = std::max(S_.nact_max, n_act);
-    return 0;
-  };
-  {
-    // Descriptors are cached by topology row (hash + the row itself, compared on a hit): a rebuild after some lanes changed their topology
-    // -- or the next contingency scan over the same family of topologies -- only walks the tables for classes it has not seen.
-    ClsScratch scr;
-    const size_t row_ints = (size_t)g.dim_topo + (size_t)nsh;
-    const bool no_cache = getenv("GRIDPF_PTDFB_NO_CACHE") != nullptr;      // developer / bench: every class counts as never seen (read at every call)
-    if (no_cache || e->ptdfb_cache_stride != stride || e->ptdfb_cache_n > 8192) { e->ptdfb_cache.clear(); e->ptdfb_cache_n = 0; e->ptdfb_cache_stride = stride; }
-    std::vector<int> miss;
-    for (int c = 0; c < nc; ++c) {
-      const int* tp = topo.data() + (size_t)first_lane[c] * g.dim_topo;
-      const int* sbp = sb.data() + (size_t)first_lane[c] * std::max(nsh, 1);
-      int* d = desc.data() + (size_t)c * stride;
-      auto it_b = e->ptdfb_cache.find(first_hash[c]);
-      const gpf_engine::PtdfbCached* hit = nullptr;
-      if (it_b != e->ptdfb_cache.end())
-        for (const auto& ce : it_b->second)
-          if (std::memcmp(ce.row.data(), tp, (size_t)g.dim_topo * sizeof(int)) == 0 && (!nsh || std::memcmp(ce.row.data() + g.dim_topo, sbp, (size_t)nsh * sizeof(int)) == 0)) { hit = &ce; break; }
-      if (hit) {
-        std::memcpy(d, hit->desc.data(), (size_t)stride * sizeof(int));
-        e->h_ptdfb_bus[c] = hit->c2b;
-      } else miss.push_back(c);
-    }
-    // the classes never seen before: their descriptors are independent table walks -- spread over the host threads
-    std::vector<int> miss_err(miss.size(), 0);
-    std::vector<gpf_engine::PtdfbCached> miss_ce(miss.size());      // (the cache entries too: three allocations + 9 KB of copies per class)
-    (void)scr;
-    par_for((int)miss.size(), 16, [&](int q0, int q1, int) {
-      ClsScratch scr_t;
-      for (int q = q0; q < q1; ++q) {
-        const int c = miss[q];
-        miss_err[q] = build_class(c, scr_t);
-        if (miss_err[q]) continue;
-        gpf_engine::PtdfbCached& ce = miss_ce[q];
-        ce.row.resize(row_ints);
-        std::memcpy(ce.row.data(), topo.data() + (size_t)first_lane[c] * g.dim_topo, (size_t)g.dim_topo * sizeof(int));
-        if (nsh) std::memcpy(ce.row.data() + g.dim_topo, sb.data() + (size_t)first_lane[c] * nsh, (size_t)nsh * sizeof(int));
-        const int* d = desc.data() + (size_t)c * stride;
-        ce.desc.assign(d, d + stride);
-        ce.c2b = e->h_ptdfb_bus[c];
-      }
-    });
-    for (size_t q = 0; q < miss.size(); ++q) {
-      const int c = miss[q];
-      const int err = miss_err[q];
-      if (err == 1) return fail(GPF_E_INVALID, "gpf_ptdf_build_batch: bus id out of range");
-      if (err == 2) return fail(GPF_E_CAPACITY, "gpf_ptdf_build_batch: more than 256 active non-reference buses in one topology");
-      e->ptdfb_cache[first_hash[c]].push_back(std::move(miss_ce[q]));
-      ++e->ptdfb_cache_n;
-    }
-    for (int c = 0; c < nc; ++c) {
-      const int* d = desc.data() + (size_t)c * stride;
-      npad_max = std::max(npad_max, d[2]);
-      nact_max = std::max(nact_max, d[1]);
-    }
-  }
-  if (stage_timing) tm[3] = now_us();
-  // ---- slots: lanes grouped by class, every group padded to a multiple of 16 ------------------------------------------------------------
-  std::vector<std::vector<int>> members(nc);
-  for (int k = 0; k < n; ++k) members[e->h_ptdfb_lane_class[k]].push_back(lane0 + k);
-  for (int c = 0; c < nc; ++c) {
-    for (int ln : members[c]) order.push_back(ln);
-    while (order.size() & 15) order.push_back(-1);
-    while (blk_class.size() * 16 < order.size()) blk_class.push_back(c);
-  }
-  n_slots = order.size();
-  return GPF_OK;
-  };
-  if (dev) { nc = grp[0]; n_slots = (size_t)grp[1]; npad_max = grp[2]; nact_max = grp[3]; }
-  else { const int rc_h = host_group(); if (rc_h != GPF_OK) return rc_h; }
-  const int line_pad = (nl + 15) & ~15;
-  const int nb_pad = std::max(4, (nact_max + 3) & ~3), kpad = (nb_pad + 31) & ~31;
-  e->ptdf_ready = false;
-  // (grow-only buffers: a rebuild after a few topology changes allocates nothing; uploads ride the engine's stream in front of the kernel)
-  if (!dev) {
-    HIP_TRY(e->ptdfb_desc.put(desc.data(), desc.size(), e->stream));
-    HIP_TRY(e->ptdfb_order.put(order.data(), order.size(), e->stream));
-    HIP_TRY(e->ptdfb_blk_class.put(blk_class.data(), blk_class.size(), e->stream));
-  }
-  HIP_TRY(e->ptdfb_status.ensure(nc));
-  HIP_TRY(e->ptdfb_work.ensure((size_t)nc * npad_max * npad_max));
-  HIP_TRY(e->ptdfb_t.ensure((size_t)nc * kpad * line_pad));
-  if (with_lodf) HIP_TRY(e->ptdfb_lodf.ensure((size_t)nc * nl * line_pad)); else e->ptdfb_lodf.release();
-  if (!e->ptdfb_inj_w.p) {
-    std::vector<double> w(g.n_inj, 0.0);
-    for (int i = 0; i < g.n_gen; ++i) w[oo.inj_gen_p + i] = 1.0;
-    for (int i = 0; i < g.n_load; ++i) w[oo.inj_load_p + i] = -1.0;
-    for (int i = 0; i < g.n_sto; ++i) w[oo.inj_sto_p + i] = -1.0;
-    for (int i = 0; i < nsh; ++i) w[oo.inj_sh_p + i] = -e->h_shunt_fact[i];
-    HIP_TRY(e->ptdfb_inj_w.upload(w.data(), w.size()));
-  }
-  if (e->ptdf_line_pad != line_pad || !e->ptdf_flow.p) { e->ptdf_flow.release(); HIP_TRY(e->ptdf_flow.alloc((size_t)e->cap_lanes * line_pad)); }
-  if (with_lodf && (e->ptdf_line_pad != line_pad || !e->lodf_worst.p)) { e->lodf_worst.release(); HIP_TRY(e->lodf_worst.alloc((size_t)e->cap_lanes * line_pad)); }
-  gpf::PtdfBuildDev D{};
-  D.n_line = nl; D.line_pad = line_pad; D.n_inj = g.n_inj; D.kpad = kpad; D.desc_stride = stride;
-  D.work_stride = (long long)npad_max * npad_max; D.ptdf_stride = (long long)kpad * line_pad; D.lodf_stride = (long long)nl * line_pad;
-  D.desc = e->ptdfb_desc.p; D.br_bdc = e->br_bdc.p; D.work = e->ptdfb_work.p; D.ptdf_t = e->ptdfb_t.p; D.lodf = with_lodf ? e->ptdfb_lodf.p : nullptr;
-  D.status = e->ptdfb_status.p;
-  DevArr<long long> dbg;
-  static const bool want_dbg = getenv("GRIDPF_PTDFB_DEBUG") != nullptr;     // developer: per-phase shader-clock stamps of class 0 on stderr
-  if (want_dbg) { HIP_TRY(dbg.alloc((size_t)nc * 8)); HIP_TRY(hipMemset(dbg.p, 0, (size_t)nc * 8 * sizeof(long long))); D.dbg = dbg.p; }
-  // reduced dimension <= 128 (118-substation grids): the matrix of a class lives in LDS (ptdf_build_lds_kernel), else in global memory
-  const bool no_resident = getenv("GRIDPF_PTDFB_GLOBAL") != nullptr;   // developer / tests: force the global-memory kernel (read at every call)
-  const bool resident = npad_max <= 128 && line_pad <= gpf::PTDFB_LDS_THREADS && !no_resident && gpf::ptdfb_lds_bytes_resident(npad_max, line_pad, nl) <= LDS_HARD_LIMIT;
-  const size_t lds = resident ? gpf::ptdfb_lds_bytes_resident(npad_max, line_pad, nl) : gpf::ptdfb_lds_bytes(npad_max, line_pad);
-  static size_t lds_set[64][2] = {{0}};
-  if (lds > lds_set[e->device & 63][resident]) {
-    HIP_TRY(hipFuncSetAttribute(resident ? reinterpret_cast<const void*>(&gpf::ptdf_build_lds_kernel) : reinterpret_cast<const void*>(&gpf::ptdf_build_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    lds_set[e->device & 63][resident] = lds;
-  }
-  if (stage_timing) tm[4] = now_us();
-  if (!e->ptdfb_ev_a) { HIP_TRY(hipEventCreate(&e->ptdfb_ev_a)); HIP_TRY(hipEventCreate(&e->ptdfb_ev_b)); }     // (the engine's: destroyed with it)
-  if (e->ptdfb_status_pin_n < (size_t)nc) {
-    if (e->ptdfb_status_pin) (void)hipHostFree(e->ptdfb_status_pin);
-    e->ptdfb_status_pin = nullptr; e->ptdfb_status_pin_n = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->ptdfb_status_pin), ((size_t)nc + nc / 4 + 64) * sizeof(int), hipHostMallocDefault));
-    e->ptdfb_status_pin_n = (size_t)nc + nc / 4 + 64;
-  }
-  struct { hipEvent_t a, b; } ev{e->ptdfb_ev_a, e->ptdfb_ev_b};
-  HIP_TRY(hipEventRecord(ev.a, e->stream));
-  if (resident) hipLaunchKernelGGL(gpf::ptdf_build_lds_kernel, dim3(nc), dim3(gpf::PTDFB_LDS_THREADS), lds, e->stream, D);
-  else hipLaunchKernelGGL(gpf::ptdf_build_kernel, dim3(nc), dim3(gpf::PTDFB_THREADS), lds, e->stream, D);
-  hipError_t le = hipGetLastError();
-  HIP_TRY(hipEventRecord(ev.b, e->stream));
-  if (le != hipSuccess) return fail(GPF_E_DEVICE, std::string("ptdf_build_kernel: ") + hipGetErrorString(le));
-  // the class status comes back by DMA into a pinned block behind the kernel; nobody waits here -- the flows / screening calls queue on the
-  // same stream, gpf_ptdf_batch_info (status, kernel time) synchronises when it is asked (ptdfb_finish)
-  e->h_ptdfb_status.assign(nc, 0);
-  HIP_TRY(hipMemcpyAsync(e->ptdfb_status_pin, e->ptdfb_status.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  e->ptdfb_n = n; e->ptdfb_classes = nc; e->ptdfb_desc_stride = stride;      // (what ptdfb_finish / ptdfb_fetch_host size their copies by)
-  e->ptdfb_host_stale = dev; e->ptdfb_bus_stale = dev;
-  e->ptdfb_prefetched = false;
-  if (dev) {                                        // what gpf_ptdf_batch_info will be asked for rides the same stream: one wait gets it all
-    const size_t need = (size_t)n + (size_t)nc * 4;
-    if (e->ptdfg_back_pin_n < need) {
-      if (e->ptdfg_back_pin) (void)hipHostFree(e->ptdfg_back_pin);
-      e->ptdfg_back_pin = nullptr; e->ptdfg_back_pin_n = 0;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->ptdfg_back_pin), (need + need / 4 + 256) * sizeof(int), hipHostMallocDefault));
-      e->ptdfg_back_pin_n = need + need / 4 + 256;
-    }
-    HIP_TRY(hipMemcpyAsync(e->ptdfg_back_pin, e->ptdfg_lane_class.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipMemcpy2DAsync(e->ptdfg_back_pin + n, 4 * sizeof(int), e->ptdfb_desc.p, (size_t)stride * sizeof(int), 4 * sizeof(int), (size_t)nc, hipMemcpyDeviceToHost, e->stream));
-    e->ptdfb_prefetched = true;
-  }
-  e->ptdfb_pending = true;
-  float ms = 0.f;
-  if (stage_timing || want_dbg) { int rc_f = ptdfb_finish(e); if (rc_f != GPF_OK) return rc_f; ms = (float)e->ptdfb_kernel_ms; }
-  if (stage_timing)
-    fprintf(stderr, "[gridpf] ptdf_build_batch %d lanes, %d classes: rows to the host %.0f us, grouping %.0f, descriptors %.0f, slots + uploads %.0f, kernel + status %.0f\n",
-            n, nc, tm[1] - tm[0], tm[2] - tm[1], tm[3] - tm[2], tm[4] - tm[3], now_us() - tm[4]);
-  if (want_dbg) {
-    std::vector<long long> h((size_t)nc * 8);
-    (void)hipMemcpy(h.data(), dbg.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-    int c_ok = 0;
-    while (c_ok < nc - 1 && e->h_ptdfb_status[c_ok] != 0) ++c_ok;
-    const long long* s_ = h.data() + (size_t)c_ok * 8;
-    fprintf(stderr, "[gridpf] ptdf_build_kernel class %d (n_pad %d), shader clocks: assemble %lld, gauss-jordan %lld (panel loads %lld, tile inversions %lld, trailing "
-                    "updates %lld), PTDF^T %lld, LODF %lld (row builds %lld); kernel %.1f us\n", c_ok, dev ? 0 : desc[(size_t)c_ok * stride + 2], s_[1] - s_[0], s_[3] - s_[1], s_[7], s_[2], s_[6],
-            s_[4] - s_[3], s_[5] ? s_[5] - s_[4] : 0LL, s_[7], ms * 1e3);
-    dbg.release();
-  }
-  if (e->window) { ++e->win_launches; e->win_marked = false; }
-  if (!dev) { e->h_ptdfb_desc = std::move(desc); e->h_ptdfb_hdr.clear(); }
-  e->ptdfb_host_stale = dev; e->ptdfb_bus_stale = dev;                       // (device path: lane -> class map, descriptors, compact -> bus maps are fetched when somebody asks)
-  e->ptdfb_lane0 = lane0; e->ptdfb_n = n; e->ptdfb_classes = nc; e->ptdfb_slots = (int)n_slots; e->ptdfb_kpad = kpad;
-  e->ptdfb_npad_max = npad_max; e->ptdfb_desc_stride = stride;
-  e->ptdf_nb_pad = nb_pad; e->ptdf_line_pad = line_pad;
-  e->ptdf_rows_valid = 0;
-  e->ptdf_batch = true;
-  e->ptdf_ready = true;
-  if (n_classes_out) *n_classes_out = nc;
-  return GPF_OK;
-}
-
-int gpf_ptdf_batch_info(gpf_handle e, int32_t* lane_class, int32_t* class_status, int32_t* class_n, double* kernel_ms) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_ptdf_batch_info: null");
-  if (!e->ptdf_ready || !e->ptdf_batch) return fail(GPF_E_INVALID, "gpf_ptdf_batch_info: call gpf_ptdf_build_batch first");
-  if (class_status || kernel_ms) { const int rc_f = ptdfb_finish(e); if (rc_f != GPF_OK) return rc_f; }
-  if (lane_class || class_n) { const int rc_m = ptdfb_fetch_host(e); if (rc_m != GPF_OK) return rc_m; }
-  if (lane_class) std::copy(e->h_ptdfb_lane_class.begin(), e->h_ptdfb_lane_class.end(), lane_class);
-  if (class_status) std::copy(e->h_ptdfb_status.begin(), e->h_ptdfb_status.end(), class_status);
-  if (class_n) for (int c = 0; c < e->ptdfb_classes; ++c) class_n[c] = e->h_ptdfb_hdr.empty() ? e->h_ptdfb_desc[(size_t)c * e->ptdfb_desc_stride] : e->h_ptdfb_hdr[(size_t)c * 4];
-  if (kernel_ms) *kernel_ms = e->ptdfb_kernel_ms;
-  return GPF_OK;
-}
-
-int gpf_ptdf_batch_get(gpf_handle e, int32_t cls, double* ptdf, double* lodf) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_ptdf_batch_get: null");
-  if (!e->ptdf_ready || !e->ptdf_batch) return fail(GPF_E_INVALID, "gpf_ptdf_batch_get: call gpf_ptdf_build_batch first");
-  if (cls < 0 || cls >= e->ptdfb_classes) return fail(GPF_E_INVALID, "gpf_ptdf_batch_get: bad class");
-  { const int rc_m = ptdfb_fetch_host(e, true); if (rc_m != GPF_OK) return rc_m; }
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int nl = e->g.n_line, lp = e->ptdf_line_pad, nbt = e->g.nb_tot, kpad = e->ptdfb_kpad;
-  if (ptdf) {
-    std::vector<double> pt((size_t)kpad * lp);
-    HIP_TRY(hipMemcpy(pt.data(), e->ptdfb_t.p + (size_t)cls * kpad * lp, pt.size() * sizeof(double), hipMemcpyDeviceToHost));
-    std::fill(ptdf, ptdf + (size_t)nl * nbt, 0.0);
-    const std::vector<int>& c2b = e->h_ptdfb_bus[cls];
-    for (size_t c = 0; c < c2b.size(); ++c)
-      for (int l = 0; l < nl; ++l) ptdf[(size_t)l * nbt + c2b[c]] = pt[c * lp + l];
-  }
-  if (lodf) {
-    if (!e->ptdfb_lodf.p) return fail(GPF_E_INVALID, "gpf_ptdf_batch_get: the batch was built without LODF tables");
-    std::vector<float> lof((size_t)nl * lp);
-    HIP_TRY(hipMemcpy(lof.data(), e->ptdfb_lodf.p + (size_t)cls * nl * lp, lof.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int m = 0; m < nl; ++m) for (int k = 0; k < nl; ++k) lodf[(size_t)m * nl + k] = (double)lof[(size_t)m * lp + k];
-  }
-  return GPF_OK;
-}
-
-int gpf_ptdf_get(gpf_handle e, double* ptdf) {
-  if (!e || !ptdf) return fail(GPF_E_INVALID, "gpf_ptdf_get: null");
-  if (!e->ptdf_ready || e->ptdf_batch) return fail(GPF_E_INVALID, "gpf_ptdf_get: call gpf_ptdf_build first (per-lane topologies: gpf_ptdf_batch_get)");
-  std::copy(e->h_ptdf.begin(), e->h_ptdf.end(), ptdf);
-  return GPF_OK;
-}
-
-int gpf_ptdf_flows(gpf_handle e, int32_t lane0, int32_t n) {
-  if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_ptdf_flows: bad range");
-  if (!e->ptdf_ready) return fail(GPF_E_INVALID, "gpf_ptdf_flows: call gpf_ptdf_build first");
-  if (n == 0) return GPF_OK;
-  if (e->ptdf_batch && (lane0 != e->ptdfb_lane0 || n != e->ptdfb_n))
-    return fail(GPF_E_INVALID, "gpf_ptdf_flows: per-lane topologies (gpf_ptdf_build_batch): the call must cover exactly the lane range that was built");
-  HIP_TRY(hipSetDevice(e->device));
-  const gpf::PtdfDev P = ptdf_dev(e);
-  const size_t lds_a = (size_t)16 * gpf::ptdf_a_stride(P.nb_pad) * sizeof(double);
-  const int n_blk = e->ptdf_batch ? e->ptdfb_slots / 16 : (n + 15) / 16;
-  hipLaunchKernelGGL(gpf::ptdf_flows_kernel, dim3(n_blk, (P.line_pad / 16 + 3) / 4), dim3(256), lds_a, e->stream, P, e->inj.p, lane0, n,
-                     e->ptdf_flow.p);
-  HIP_TRY(hipGetLastError());
-  if (e->window) { ++e->win_launches; e->win_marked = false; }
-  return GPF_OK;
-}
-
-int gpf_ptdf_flows_rows(gpf_handle e, int32_t t0, int32_t n_rows, double rebalance) {
-  if (!e || n_rows <= 0) return fail(GPF_E_INVALID, "gpf_ptdf_flows_rows: bad arguments");
-  if (!e->ptdf_ready) return fail(GPF_E_INVALID, "gpf_ptdf_flows_rows: call gpf_ptdf_build first");
-  if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_ptdf_flows_rows: no chronics uploaded");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t need = (size_t)n_rows * e->cap_lanes * e->ptdf_line_pad;
-  if (e->ptdf_flow_rows.n < need) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->ptdf_flow_rows.release();
-    HIP_TRY(e->ptdf_flow_rows.alloc(need));
-  }
-  if (e->ptdf_batch && (e->ptdfb_lane0 != 0 || e->ptdfb_n != e->n_lanes))
-    return fail(GPF_E_INVALID, "gpf_ptdf_flows_rows: per-lane topologies (gpf_ptdf_build_batch) must have been built for ALL lanes");
-  const gpf::PtdfDev P = ptdf_dev(e);
-  gpf::PtdfRowsDev R{};
-  R.chron = e->chron.p; R.lane_table = e->lane_table.p; R.lane_offset = e->lane_offset.p;
-  R.lane_scale = e->has_scale ? e->lane_scale.p : nullptr; R.lane_gen_delta = e->has_delta ? e->lane_gen_delta.p : nullptr;
-  R.gen_slack = e->gen_slack.p; R.T = e->chron_T; R.n_chron = e->g.n_chron; R.n_load = e->g.n_load; R.n_gen = e->g.n_gen;
-  R.inj_gen_p = e->oo.inj_gen_p; R.inj_load_p = e->oo.inj_load_p; R.inj_sto_p = e->oo.inj_sto_p; R.n_inj_tail = e->g.n_inj - e->oo.inj_sto_p;
-  R.rebalance = rebalance;
-  R.kpad = (P.nb_pad + 31) & ~31;
-  static const int mt_env = std::getenv("GRIDPF_PTDF_MT") ? std::atoi(std::getenv("GRIDPF_PTDF_MT")) : 0;      // developer override (1 | 2 | 4)
-  const int mt = (mt_env == 1 || mt_env == 2 || mt_env == 4) ? mt_env : 2;
-  const int NP = 16 * mt;
-  const size_t lds_a = (size_t)NP * gpf::ptdf_rows_stride(R.kpad) * sizeof(double);
-  const long long n_pairs = (long long)e->n_lanes * n_rows;
-  // per-lane topologies: one block per (group of 16 slots, mt consecutive rows), see ptdf_rows_kernel
-  const int n_units = e->ptdf_batch ? e->ptdfb_slots : e->n_lanes;
-  const dim3 grid(e->ptdf_batch ? (unsigned)((size_t)(e->ptdfb_slots / 16) * ((n_rows + mt - 1) / mt)) : (unsigned)((n_pairs + NP - 1) / NP));
-  static size_t lds_set[64][3] = {{0}};
-#define GPF_PTDF_ROWS(MT_, SLOT_)                                                                                                      \
-  do {                                                                                                                                 \
-    if (lds_a > lds_set[e->device & 63][SLOT_]) {                                                                                      \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&gpf::ptdf_rows_kernel<MT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a)); \
-      lds_set[e->device & 63][SLOT_] = lds_a;                                                                                          \
-    }                                                                                                                                  \
-    hipLaunchKernelGGL(gpf::ptdf_rows_kernel<MT_>, grid, dim3(256), lds_a, e->stream, P, R, e->inj.p, n_units, (long long)e->cap_lanes, t0, \
-                       n_rows, e->ptdf_flow_rows.p);                                                                                   \
-  } while (0)
-  if (mt == 4) GPF_PTDF_ROWS(4, 2); else if (mt == 2) GPF_PTDF_ROWS(2, 1); else GPF_PTDF_ROWS(1, 0);
-#undef GPF_PTDF_ROWS
-  HIP_TRY(hipGetLastError());
-  e->ptdf_rows_valid = n_rows;
-  if (e->window) { ++e->win_launches; e->win_marked = false; }
-  return GPF_OK;
-}
-
-int gpf_get_ptdf_flows_rows(gpf_handle e, int32_t row0, int32_t n_rows, int32_t lane0, int32_t n, float* p_or) {
-  if (!check_range(e, lane0, n) || !p_or || row0 < 0 || n_rows < 0 || row0 + n_rows > e->ptdf_rows_valid)
-    return fail(GPF_E_INVALID, "gpf_get_ptdf_flows_rows: bad range (only the rows of the last gpf_ptdf_flows_rows are retrievable)");
-  HIP_TRY(hipSetDevice(e->device));
-  for (int r = 0; r < n_rows; ++r)
-    HIP_TRY(hipMemcpy2DAsync(p_or + (size_t)r * n * e->g.n_line, (size_t)e->g.n_line * sizeof(float),
-                             e->ptdf_flow_rows.p + ((size_t)(row0 + r) * e->cap_lanes + lane0) * e->ptdf_line_pad,
-                             (size_t)e->ptdf_line_pad * sizeof(float), (size_t)e->g.n_line * sizeof(float), (size_t)n, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
-int gpf_get_ptdf_flows(gpf_handle e, int32_t lane0, int32_t n, float* p_or) {
-  if (!check_range(e, lane0, n) || !p_or) return fail(GPF_E_INVALID, "gpf_get_ptdf_flows: bad arguments");
-  if (!e->ptdf_ready) return fail(GPF_E_INVALID, "gpf_get_ptdf_flows: call gpf_ptdf_build first");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpy2DAsync(p_or, (size_t)e->g.n_line * sizeof(float), e->ptdf_flow.p + (size_t)lane0 * e->ptdf_line_pad,
-                           (size_t)e->ptdf_line_pad * sizeof(float), (size_t)e->g.n_line * sizeof(float), (size_t)n,
-                           hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
-int gpf_lodf_screen(gpf_handle e, int32_t lane0, int32_t n, const float* cap_mw, float* worst) {
-  if (!check_range(e, lane0, n) || !worst) return fail(GPF_E_INVALID, "gpf_lodf_screen: bad arguments");
-  if (!e->ptdf_ready) return fail(GPF_E_INVALID, "gpf_lodf_screen: call gpf_ptdf_build and gpf_ptdf_flows first");
-  if (n == 0) return GPF_OK;
-  if (e->ptdf_batch && (lane0 != e->ptdfb_lane0 || n != e->ptdfb_n || !e->ptdfb_lodf.p))
-    return fail(GPF_E_INVALID, "gpf_lodf_screen: per-lane topologies: build them with LODF tables and screen exactly the lane range that was built");
-  HIP_TRY(hipSetDevice(e->device));
-  const int nl = e->g.n_line, lp = e->ptdf_line_pad;
-  const float* ic = nullptr;
-  if (cap_mw) {
-    std::vector<float> inv(nl);
-    for (int l = 0; l < nl; ++l) inv[l] = cap_mw[l] > 0.f ? 1.0f / cap_mw[l] : 0.f;
-    if (!e->lodf_inv_cap.p) HIP_TRY(e->lodf_inv_cap.alloc(nl));
-    HIP_TRY(hipMemcpyAsync(e->lodf_inv_cap.p, inv.data(), (size_t)nl * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    ic = e->lodf_inv_cap.p;
-  }
-  const size_t lds = ((size_t)5 * gpf::LODF_LPW + 1) * lp * sizeof(float);
-  if (e->ptdf_batch)
-    hipLaunchKernelGGL(gpf::lodf_screen_kernel, dim3(e->ptdfb_slots / gpf::LODF_LPW), dim3(256), lds, e->stream, nl, lp, e->ptdfb_lodf.p, ic, e->ptdf_flow.p,
-                       lane0, n, e->lodf_worst.p, e->ptdfb_order.p, e->ptdfb_blk_class.p, (long long)nl * lp, e->ptdfb_status.p);
-  else
-    hipLaunchKernelGGL(gpf::lodf_screen_kernel, dim3((n + gpf::LODF_LPW - 1) / gpf::LODF_LPW), dim3(256), lds, e->stream, nl, lp, e->lodf.p, ic,
-                       e->ptdf_flow.p, lane0, n, e->lodf_worst.p, nullptr, nullptr, 0LL, nullptr);
-  HIP_TRY(hipGetLastError());
-  if (e->window) { ++e->win_launches; e->win_marked = false; }
-  HIP_TRY(hipMemcpy2DAsync(worst, (size_t)nl * sizeof(float), e->lodf_worst.p + (size_t)lane0 * lp, (size_t)lp * sizeof(float),
-                           (size_t)nl * sizeof(float), (size_t)n, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
 #ifdef GPF_TIMING
 int gpf_debug_read_work(gpf_handle e, double* out, int64_t n) {
   HIP_TRY(hipSetDevice(e->device));
@@ -3720,7 +2537,7 @@ int gpf_device_pointers_n(gpf_handle e, void** out, int32_t n_ptrs, void** strea
   const bool obs = e->traj_cap && (e->traj_what & GPF_TRAJ_OBS);
   ptrs[18] = obs ? e->traj_out.p : nullptr; ptrs[19] = obs ? e->traj_topo.p : nullptr; ptrs[20] = obs ? e->traj_shb.p : nullptr;
   ptrs[21] = obs ? e->traj_lstat.p : nullptr;
-  ptrs[22] = e->env_on ? e->env_act_redisp.p : nullptr; ptrs[23] = e->env_on ? e->env_act_storage.p : nullptr;
+  ptrs[22] = e->env_on ? e->env_act_redisp.p : nullptr; ptrs[23] = e->env_on ? e->env_act_storage : nullptr;
   ptrs[24] = e->env_on ? e->env_act_curtail.p : nullptr; ptrs[25] = e->env_on ? e->env_target.p : nullptr;
   ptrs[26] = e->env_on ? e->env_actual.p : nullptr; ptrs[27] = e->env_on ? e->env_charge.p : nullptr;
   ptrs[28] = e->ta_on ? e->ta_act.p : nullptr; ptrs[29] = e->ta_on ? e->ta_sub_cd.p : nullptr;

@@ -1,0 +1,341 @@
+// gridpf_engine.hpp -- what the C ABI units (gridpf_capi*.hip) share: the engine behind a gpf_handle, the owners of its device memory, pinned
+// blocks, stream and events, the error plumbing.  Host-only: no header that defines a non-template kernel (each has exactly one unit).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/gridpf.h"
+#include "gridpf_common.hpp"
+#include "gridpf_host.hpp"
+#include "gridpf_symbolic.hpp"
+
+namespace gpf { struct TopoRules; }        // gridpf_topo.hpp (next to the topology kernels: gridpf_capi.hip only)
+
+#pragma GCC visibility push(hidden)         // internal to libgridpf.so: only the gpf_* entry points are its interface
+
+inline thread_local std::string g_err;      // gpf_last_error
+
+inline int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+#define HIP_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t _e = (expr);                                                                 \
+    if (_e != hipSuccess)                                                                   \
+      return fail(GPF_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));         \
+  } while (0)
+
+// gpf_create(device = GPF_DEVICE_NONE): a HEADER-ONLY handle is being built -- every host-side step of gpf_create runs (symbolic analysis, static
+// tables, launch planning), nothing is allocated on or copied to a device (there may be none).  Thread-local: set for the duration of that call.
+inline thread_local bool g_dry_create = false;
+
+constexpr size_t LDS_HARD_LIMIT = 160 * 1024 - 256;   // dynamic LDS budget (a few static bytes: block-wide reductions)
+
+// `n` elements of T in device memory, freed with the owner (move-only)
+template <typename T>
+struct DevArr {
+  T* p = nullptr;
+  size_t n = 0;
+  size_t cap = 0;                          // elements allocated (ensure / put: grow-only buffers reused across calls)
+  DevArr() = default;
+  DevArr(const DevArr&) = delete; DevArr& operator=(const DevArr&) = delete;
+  DevArr(DevArr&& o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr; o.n = o.cap = 0; }
+  ~DevArr() { release(); }
+  hipError_t alloc(size_t count) {         // a new block (the old one is freed first)
+    release();
+    n = count;
+    if (count == 0 || g_dry_create) return hipSuccess;
+    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+  }
+  hipError_t upload(const T* src, size_t count) {
+    hipError_t e = alloc(count);
+    if (e != hipSuccess || count == 0 || g_dry_create) return e;
+    return hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+    cap = 0;
+  }
+  hipError_t ensure(size_t count) {        // room for `count` elements; contents undefined afterwards when it had to grow
+    if (count <= cap && p) { n = count; return hipSuccess; }
+    release();
+    const size_t want = count + count / 4;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(want, 1) * sizeof(T));
+    cap = e == hipSuccess ? std::max<size_t>(want, 1) : 0;
+    n = e == hipSuccess ? count : 0;
+    return e;
+  }
+  hipError_t put(const T* src, size_t count, hipStream_t stream) {   // ensure + asynchronous upload on `stream` (src must stay alive until it ran)
+    hipError_t e = ensure(count);
+    if (e != hipSuccess || count == 0) return e;
+    return hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, stream);
+  }
+};
+
+// grow-only pinned host block of `n` elements of T (hipHostMalloc with `flags`), freed with the owner.  Mapped blocks also hold their
+// device-side address (`dev`).
+template <typename T>
+struct HostPin {
+  T* p = nullptr;
+  T* dev = nullptr;
+  size_t n = 0;
+  const unsigned flags;
+  explicit HostPin(unsigned flags_ = hipHostMallocDefault) : flags(flags_) {}
+  HostPin(const HostPin&) = delete; HostPin& operator=(const HostPin&) = delete;
+  ~HostPin() { if (p) (void)hipHostFree(p); }
+  // room for `need` elements: a block of need + slack when it has to grow (contents undefined afterwards)
+  hipError_t reserve(size_t need, size_t slack = 0) {
+    if (need <= n) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = dev = nullptr; n = 0;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), (need + slack) * sizeof(T), flags);
+    if (e != hipSuccess) return e;
+    n = need + slack;
+    if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), p, 0);
+    return e;
+  }
+};
+
+// a HIP stream / event destroyed with the owner; both convert to the raw handle
+struct Stream {
+  hipStream_t h = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+  ~Stream() { if (h) (void)hipStreamDestroy(h); }
+  hipError_t create(unsigned flags) { return hipStreamCreateWithFlags(&h, flags); }
+  operator hipStream_t() const { return h; }
+};
+
+struct Event {
+  hipEvent_t h = nullptr;
+  Event() = default;
+  Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+  Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+  ~Event() { if (h) (void)hipEventDestroy(h); }
+  hipError_t create() { return hipEventCreate(&h); }
+  hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&h, flags); }
+  operator hipEvent_t() const { return h; }
+};
+
+struct gpf_engine {
+  ~gpf_engine();                        // (gridpf_capi.hip: waits for the stream; the members free themselves)
+  int device = 0;
+  bool dry = false;                     // header-only handle (gpf_create with GPF_DEVICE_NONE): no device resources, no launches
+  int n_lanes = 0;
+  Stream stream;
+  gpf::GridDev g{};
+  gpf::OutOff oo{};
+  gpf_layout layout{};
+  // static tables (device)
+  DevArr<double> sub_vn_kv, br_y, br_bdc, gen_min_q, gen_max_q, shunt_fact;
+  DevArr<int> line_or_sub, line_ex_sub, line_or_pos, line_ex_pos, gen_sub, gen_pos, load_sub, load_pos, sto_sub, sto_pos,
+      shunt_sub;
+  DevArr<unsigned char> gen_slack;
+  // host copies needed to size launches
+  std::vector<int> h_line_or_sub, h_line_ex_sub, h_line_or_pos, h_line_ex_pos, h_gen_sub, h_gen_pos, h_load_sub, h_load_pos,
+      h_sto_sub, h_sto_pos, h_shunt_sub;
+  std::vector<unsigned char> h_gen_slack;
+  std::vector<double> h_init_inj;
+  std::vector<int> h_init_topo, h_init_shunt_bus;
+  // per-lane state (device)
+  DevArr<double> inj, bus_vm, bus_va, work;
+  DevArr<int> topo, shunt_bus, topo_out, shunt_bus_out, status, overflow_count, disc_round, lane_table, lane_offset, tmp_lines;
+  DevArr<int> cooldown;                 // [B][n_line] line cooldowns of the environment (gpf::Bufs::cooldown)
+  // topology actions of the batched acting path (gridpf_topo.hpp): allocated by the first gpf_set_topo_rules / gpf_upload_topo_actions
+  bool ta_on = false;
+  std::unique_ptr<gpf::TopoRules> ta_rules;   // (allocated with the buffers: the type is complete in gridpf_capi.hip only)
+  DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_list, ta_list_rows, ta_off, ta_items, ta_pos_sub, ta_pos_other;
+  DevArr<unsigned char> ta_flags, ta_aff, ta_amb;
+  int ta_n_act = 0;
+  bool ta_bus_items = false;            // an entry of the table sets / changes a bus: the read-back of class changes is needed
+  bool ta_may_split = false;            // some row or last-bus entry was on a busbar >= 2 (then line-status actions can change a class key too)
+  bool ta_host = false, ta_dev = false; // the next launch carries indices set by the host / written on the device
+  std::vector<char> ta_moved;           // per lane: an action moved it to another topology class than its reset topology's (auto-reset re-keys it)
+  int ta_n_moved = 0;
+  HostPin<int> ta_pin;                  // pinned read-back block: count | lane ids | rows
+  // topology-derived state of the reference topology shared by the lanes of one-step launches (gpf::KeepArgs): two blobs (Ybus in LDS /
+  // in registers), allocated and keyed by the first gpf_step_n with n_steps = 1; GRIDPF_KEEP=0 at gpf_create turns it off
+  DevArr<unsigned char> keep;
+  gpf::KeepArgs keep_args{};
+  int keep_launch = 0;
+  bool keep_enabled = true;
+  DevArr<unsigned short> maint_dur;     // [chron_tables][chron_T][n_line] remaining duration of the maintenance / hazard under way, or empty
+  DevArr<short> traj_cool;              // [traj_cap][cap_lanes][n_line]
+  DevArr<float> out, chron, lane_scale, thermal_limit, rho;
+  DevArr<unsigned char> line_status, done;
+  DevArr<int> topo0, episode;           // topology last sent by the host (auto-reset target); {steps survived, resets} per lane
+  DevArr<float> lane_gen_delta, traj_rho;
+  DevArr<unsigned char> maint;          // [chron_tables][chron_T][n_line] scheduled maintenance OR hazards (forced outages), or empty
+  std::vector<unsigned char> h_maint, h_hazard;   // host copies of the two tables (the device holds their union)
+  std::vector<unsigned short> h_outage_dur;       // gpf_upload_outage_durations: remaining durations given by the caller (else derived from the tables)
+  std::vector<int> h_lane_table, h_lane_offset;   // host mirror of lane_table / lane_offset (gpf_simulate_batch: maintenance ahead of a source lane)
+  std::vector<char> h_lane_forecast;              // 1: the lane is a scratch lane of gpf_simulate_batch (its offset is an absolute row, of the forecast tables for time_step > 0)
+  // injection dynamics of the environment (gpf::EnvDyn)
+  bool env_on = false, env_hold = false, env_act_r = false, env_act_s = false, sto_ready = false;
+  int env_loss_on = 1;
+  double env_coeff = 300.0 / 3600.0, env_tol = 1e-2;
+  DevArr<float> env_target, env_actual, env_prev, env_charge, env_amount_prev, env_act_redisp, sto_charge0;
+  float* env_act_storage = nullptr;     // [B][n_storage]: the tail of env_act_redisp (one allocation, one DMA for both action rows)
+  DevArr<float> env_limit, env_curt_prev, env_act_curtail;
+  DevArr<int> env_illegal;              // [B] cancelled (illegal) actions since the reset
+  DevArr<unsigned char> env_already, env_fresh, env_renewable;
+  bool env_act_c = false, env_has_ren = false;
+  DevArr<double> sto_emax, sto_emin, sto_loss, sto_effc, sto_effd;
+  std::vector<float> h_charge0;
+  DevArr<float> forecast;               // [chron_tables][chron_T][fc_h][n_chron] *_forecasted tables (gpf_upload_forecasts), or empty
+  int fc_h = 0;
+  DevArr<int> sim_src, sim_rows;        // gpf_simulate_batch staging: source lane list, gathered topology rows
+  struct PtdfbCached { std::vector<int> row, desc, c2b; };      // gpf_ptdf_build_batch: descriptor of a topology row seen before
+  std::unordered_map<uint64_t, std::vector<PtdfbCached>> ptdfb_cache;
+  size_t ptdfb_cache_n = 0;
+  int ptdfb_cache_stride = 0;
+  HostPin<unsigned char> res_pin;       // pinned block of gpf_get_results_pinned
+  HostPin<float> act_pin;               // pinned staging of gpf_set_lane_actions / gpf_set_lane_curtailment (redispatch | storage | curtailment)
+  Event act_up;                         // recorded behind the uploads that read it: the next call waits for it before rewriting the block
+  HostPin<int> sim_pin;                 // its pinned host block (grow-only): gathered source rows | candidate topology rows | candidate shunt rows
+  DevArr<signed char> traj_status;
+  DevArr<float> traj_out;               // per-step observation trajectory (GPF_TRAJ_OBS): [traj_cap][cap_lanes][n_out] ...
+  DevArr<int> traj_topo, traj_shb;
+  DevArr<unsigned char> traj_lstat;
+  int traj_cap = 0;
+  int traj_what = 0;                    // GPF_TRAJ_* bits of the current buffers
+  int traj_valid = 0;                   // steps of the trajectory written by the last gpf_step_n
+  bool has_delta = false;
+  DevArr<double> rd_pmin, rd_pmax, rd_ru, rd_rd, rd_in;      // generator limits + staging of gpf_redispatch
+  DevArr<unsigned char> rd_redisp, rd_u8;
+  DevArr<float> rd_after;
+  double rd_eps = 1e-4;
+  bool rd_ready = false;
+  // pinned host block of gpf_solve_lane (one lane in, one lane out), mapped into the device (coherent: the device reads / writes it
+  // uncached, what the gather kernel wrote is in host memory when the stream has drained)
+  HostPin<unsigned char> pin{hipHostMallocMapped | hipHostMallocCoherent};
+  GpfJit jit;                           // grid-specialised step kernels (gpf_jit_enable; gridpf_jit.hip)
+  gpf::GridDev jit_g;                   // the grid-level part of the parameter block the specialisation was generated from
+  gpf::OutOff jit_oo;
+  gpf::SymDev jit_sym;
+  int dcf = 0;                          // the NB == 1 LDS layout has room for the factored DC matrix (decided once at gpf_create)
+  DevArr<double> d_init_inj;
+  DevArr<int> d_init_topo, d_init_shunt_bus;
+  int chron_T = 0, chron_tables = 0;
+  bool has_scale = false;
+  // per-lane capacity bookkeeping (host): number of active buses / NR unknowns of each lane
+  std::vector<int> lane_nb, lane_nj;
+  int init_nb = 0, init_nj = 0;
+  // block-sparse path (kernel S)
+  gpf::Symbolic sym;
+  // DC sensitivity path (gridpf_ptdf.hpp, gridpf_capi_ptdf.hip)
+  DevArr<int> ptdf_inj_bus;
+  DevArr<double> ptdf_inj_w, ptdf_t;
+  DevArr<float> ptdf_flow, lodf_worst, lodf_inv_cap;
+  DevArr<float> ptdf_flow_rows;    // [rows][cap_lanes][line_pad] flows of the last gpf_ptdf_flows_rows
+  int ptdf_rows_valid = 0;
+  DevArr<float> lodf;              // [n_line][line_pad] line outage distribution factors of the PTDF topology, float32 (NaN column: islanding outage)
+  std::vector<double> h_ptdf;      // [n_line][nb_tot]
+  std::vector<double> h_br_bdc, h_shunt_fact;
+  std::vector<int> h_gen_cnt;
+  int ptdf_nb_pad = 0, ptdf_line_pad = 0;
+  bool ptdf_ready = false;
+  // per-lane topologies (gpf_ptdf_build_batch, gridpf_ptdf_batch.hpp): one PTDF^T / LODF block per distinct topology class of a lane range
+  long long n_step_calls = 0, n_step_dispatches = 0;   // gpf_step_n calls / kernel dispatches they issued (gpf_get_counters)
+  bool ptdf_batch = false;                 // the flows / screening calls run on the class tables of the last gpf_ptdf_build_batch
+  int ptdfb_lane0 = 0, ptdfb_n = 0, ptdfb_classes = 0, ptdfb_slots = 0, ptdfb_kpad = 0, ptdfb_npad_max = 0, ptdfb_desc_stride = 0;
+  DevArr<int> ptdfb_desc, ptdfb_order, ptdfb_blk_class, ptdfb_status;
+  DevArr<double> ptdfb_work, ptdfb_t, ptdfb_inj_w;
+  DevArr<float> ptdfb_lodf;
+  std::vector<int> h_ptdfb_lane_class, h_ptdfb_status, h_ptdfb_desc;
+  std::vector<std::vector<int>> h_ptdfb_bus;   // per class: compact bus index -> bus id (sub + (local - 1) * n_sub)
+  double ptdfb_kernel_ms = 0.0;            // duration of the last build kernel (HIP events)
+  // the build call returns once its kernel is QUEUED: class status + kernel time are fetched when somebody asks (gpf_ptdf_batch_info)
+  Event ptdfb_ev_a, ptdfb_ev_b;
+  HostPin<int> ptdfb_status_pin;
+  bool ptdfb_pending = false;
+  // device-side grouping + descriptors (gridpf_ptdf_group.hpp): their outputs, and the host mirrors fetched on demand
+  DevArr<unsigned long long> ptdfg_hash;
+  DevArr<int> ptdfg_lane_class, ptdfg_first, ptdfg_c2b, ptdfg_info;
+  HostPin<int> ptdfg_info_pin;
+  HostPin<int> ptdfg_back_pin;             // lane -> class map + descriptor headers, queued behind the factorisation
+  bool ptdfb_prefetched = false;
+  bool ptdfb_host_stale = false;           // h_ptdfb_lane_class / h_ptdfb_hdr are not what the device holds: ptdfb_fetch_host
+  bool ptdfb_bus_stale = false;            // ... nor h_ptdfb_bus (only gpf_ptdf_batch_get reads it)
+  std::vector<int> h_ptdfb_hdr;            // device path: the 4-int headers of the class descriptors (nr, n_act, n_pad, status); empty: h_ptdfb_desc has them
+  DevArr<double> dc_inv_g;     // static DC inverse of the larger grids (gpf::SymDev::dc_inv_g)
+  DevArr<double> stat_dbl;     // static blob of kernel S (gpf::StatOff)
+  DevArr<int> stat_int;
+  DevArr<int> flat_prog;       // flat programs of the substation graph (4 group widths)
+  gpf::SymDev sym_dev{};
+  gpf::DevParamsS h_params_s{};
+  DevArr<gpf::DevParamsS> d_params_s;
+  bool params_s_valid = false;
+  // mixed batches: lanes without / with split substations are launched separately (single-busbar kernel / NB = n_busbar)
+  DevArr<int> list_a, list_b, list_c;   // list_c: topology class of every lane of list_b
+  // topology classes (gpf::TopoClassDev): bus-level graphs of the split topologies seen so far, each with its own symbolic program
+  struct TopoClassHost { DevArr<int> tables, flat; gpf::TopoClassDev dev; int n_nodes, nslot, nslot_y; };
+  std::vector<std::unique_ptr<TopoClassHost>> classes;
+  std::unordered_map<std::string, int> class_of_key;
+  // host mirror of the topology last SENT for every lane (gpf_set_topology skips the per-lane bookkeeping when a lane is
+  // re-sent unchanged: agents resend whole batches with few changes); first entry INT_MIN = unknown
+  std::vector<int> h_lane_topo, h_lane_sb;
+  bool dev_topo_dirty = false;           // a kernel may have rewritten topology rows (cascade trips, scheduled outages): the host mirrors are not the device rows any more
+  std::vector<int> lane_class;          // per lane: topology class (-1: no split substation / classes disabled)
+  DevArr<gpf::TopoClassDev> d_classes;  // device copy of classes[*].dev
+  size_t d_classes_count = 0;
+  bool no_classes = false;              // GRIDPF_NO_CLASSES=1: split lanes run the NB = n_busbar kernel
+  bool no_partition = false;     // GRIDPF_NO_PARTITION=1
+  int ipw_override = 0;        // GRIDPF_IPW=1|2|4 (developer override of the instances-per-wavefront heuristic)
+  int wpi_override = 0;        // GRIDPF_WPI=1|2 (developer override of the wavefronts-per-instance heuristic); 1 = deterministic
+  int wpi_env = 0;
+  bool no_yreg = false;        // GRIDPF_YREG=0: never keep the Ybus blocks in registers
+  int stage_max = 2;           // GRIDPF_STAGE=0|1|2: highest static-table staging tier the planner may pick (developer / tests)
+  int stage_force = -1;        // GRIDPF_FORCE_STAGE=0|1|2: take that tier whenever it fits the LDS, whatever it costs in residency (experiments)
+  int dcf_env = -1;            // GRIDPF_DCF=0|1 (-1: not set)
+  int cap_lanes = 0;           // lane buffers are padded to a multiple of 4 lanes (instance groups of a wavefront)
+  std::vector<int> lane_mb;    // max live busbars in one substation, per lane
+  int init_mb = 1;
+  bool plan_valid = false;      // cached launch plan of the whole batch (invalidated by every topology mutation)
+  LaunchPlan plan_cached{}, plan_b_cached{};   // plan_b: the split lanes of a mixed batch (sparse_nb == 0: none)
+  // profiling
+  bool profiling = false;      // per-launch event pairs (gpf_set_profiling(h, 2))
+  bool window = false;         // one event pair around a window of launches (gpf_set_profiling(h, 1))
+  Event win_a, win_b;
+  bool win_marked = false;              // win_b was recorded by gpf_set_profiling(3) behind the last launch of the window
+  long long win_launches = 0;
+  std::vector<std::pair<Event, Event>> ev_pool;
+  size_t ev_used = 0;
+  double acc_ms = 0.0;
+  long long acc_launches = 0;
+
+  gpf::Bufs bufs() const {
+    gpf::Bufs b{};
+    b.inj = inj.p; b.topo = topo.p; b.shunt_bus = shunt_bus.p; b.out = out.p; b.topo_out = topo_out.p;
+    b.shunt_bus_out = shunt_bus_out.p; b.line_status = line_status.p; b.status = status.p;
+    b.bus_vm = bus_vm.p; b.bus_va = bus_va.p; b.work = work.p; b.work_stride = 0;
+    b.chron = chron.p; b.lane_table = lane_table.p; b.lane_offset = lane_offset.p;
+    b.lane_scale = has_scale ? lane_scale.p : nullptr;
+    b.thermal_limit = thermal_limit.p; b.rho = rho.p; b.overflow_count = overflow_count.p; b.disc_round = disc_round.p;
+    b.lane_gen_delta = has_delta ? lane_gen_delta.p : nullptr;
+    b.maint = maint.n ? maint.p : nullptr;
+    b.cooldown = cooldown.p; b.maint_dur = maint_dur.n ? maint_dur.p : nullptr; b.traj_cool = (traj_cap && traj_cool.n) ? traj_cool.p : nullptr;
+    b.topo0 = topo0.p; b.done = done.p; b.episode = episode.p;
+    b.traj_rho = traj_cap ? traj_rho.p : nullptr; b.traj_status = traj_cap ? traj_status.p : nullptr; b.traj_cap = traj_cap;
+    const bool obs = traj_cap && (traj_what & GPF_TRAJ_OBS);
+    b.traj_out = obs ? traj_out.p : nullptr; b.traj_topo = obs ? traj_topo.p : nullptr; b.traj_shb = obs ? traj_shb.p : nullptr;
+    b.traj_lstat = obs ? traj_lstat.p : nullptr;
+    b.lane_stride = cap_lanes; b.n_real_lanes = n_lanes;
+    return b;
+  }
+};
+
+inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
+
+#pragma GCC visibility pop

@@ -6,8 +6,9 @@ name=$1; rev=${2:-HEAD}
 R=$(cd $(dirname $0)/.. && pwd); W=$R/tools/_build/$name
 rm -rf $W; mkdir -p $W/obj
 git -C $R archive $rev grid2op_amd/csrc include | tar -x -C $W
-for u in gridpf_capi gridpf_jit gridpf_launch_runpf gridpf_launch_step; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $W/grid2op_amd/csrc/$u.hip -o $W/obj/$u.o &
+for f in $W/grid2op_amd/csrc/*.hip; do
+  u=$(basename $f .hip)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $f -o $W/obj/$u.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $W/obj/*.o -o $W/grid2op_amd/libgridpf.so && rm -rf $W/obj && echo built $W/grid2op_amd/libgridpf.so

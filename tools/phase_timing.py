@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Developer tool: per-phase cycle counts of the small-grid step kernel (needs a -DGPF_TIMING build of the library).
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DGPF_TIMING grid2op_amd/csrc/gridpf_capi.hip -o /tmp/libgridpf_timing.so
-    GRIDPF_LIB=/tmp/libgridpf_timing.so python tools/phase_timing.py [batch]
+    python -c "import __graft_entry__ as g; g.build_timing_lib()"      # -> grid2op_amd/libgridpf_timing.so
+    GRIDPF_LIB=grid2op_amd/libgridpf_timing.so python tools/phase_timing.py [batch]
 """
 import ctypes as C
 import os
