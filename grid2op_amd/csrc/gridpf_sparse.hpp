@@ -154,7 +154,8 @@ struct Stamps { long long v[GPF_NSTAMP]; };
 #define GPF_STAMPS(k) do { stamps.v[(k)] = (long long)__builtin_readcyclecounter(); } while (0)
 #define GPF_STAMPS_PARAM , Stamps& stamps
 #define GPF_STAMPS_ARG , stamps
-#define GPF_STAMPS_DECL Stamps stamps; for (int k_ = 0; k_ < GPF_NSTAMP; ++k_) stamps.v[k_] = 0
+#define GPF_STAMPS_DECL Stamps stamps; for (int k_ = 0; k_ < GPF_NSTAMP; ++k_) stamps.v[k_] = 0; \
+  for (int k_ = threadIdx.x; k_ < GPF_NPASS_T; k_ += blockDim.x) gpf_pass_t[k_] = 0      /* (unstamped slots read as zero, not as what LDS held) */
 #define GPF_STAMPS_FLUSH(inst_) do { if (tid == 0) { for (int k_ = 0; k_ < GPF_NSTAMP; ++k_) P->b.work[(size_t)(inst_) * GPF_WORK_ROW + k_] = (double)stamps.v[k_]; \
     for (int k_ = 0; k_ < GPF_NPASS_T; ++k_) P->b.work[(size_t)(inst_) * GPF_WORK_ROW + GPF_NSTAMP + k_] = (double)gpf_pass_t[k_]; } } while (0)
 #else
@@ -685,6 +686,45 @@ __device__ inline bool block_lu_solve(const SymDev& S, PP prog, double* __restri
   return ok;
 }
 
+// ---- item words of the flat program RESIDENT in registers (instance-group kernels) ---------------------------------------------
+// Lane t executes item t of pass k of the same flat program in every sweep of every Newton iteration of every step of a launch, and
+// the instance-group kernels (IPW > 1: the small grids) read those words from global memory (see solve_instance_sparse: PROG_LDS): a
+// dependent L2 round trip at the head of both sweeps, 8 times per env step, and a vmcnt wait in front of every pass.  Their programs
+// are a handful of passes (14 substations: 5 forward + 1 back at group width 32), so the lane's words of EVERY pass are loaded ONCE per launch, before the
+// step loop, and the sweeps take them from registers: no global load is left in the Newton loop.  Grid-specialised build: the pass
+// counts are literals, the walk unrolls to exactly the passes of the grid and the words are 2 VGPRs per pass.  Shipped build:
+// GPF_WR_CAP_F forward and GPF_WR_CAP_B back passes are held (16 VGPRs: the back substitution of these grids is one pass; with 8 + 8 the
+// shipped kernels with the injection dynamics went to 256 VGPRs and 24 ... 40 bytes of scratch); a program with more passes in either
+// sweep (block-uniform) streams as before.
+// The two variants issue the same arithmetic on the same operands in the same order.  -DGPF_NO_WORDS_RES: developer A/B build, streaming only.
+constexpr int GPF_WR_CAP_F = 6, GPF_WR_CAP_B = 2;
+template <bool ON> struct FlatWords { };
+template <> struct FlatWords<true> { unsigned f[2 * GPF_WR_CAP_F], b[2 * GPF_WR_CAP_B]; };
+#ifdef GPF_NO_WORDS_RES
+template <int NB, int IPW, int WPI> constexpr bool flat_words_ct() { return false; }
+#else
+template <int NB, int IPW, int WPI> constexpr bool flat_words_ct() { return NB == 1 && IPW > 1 && WPI == 1; }
+#endif
+__device__ __forceinline__ bool flat_words_fit(const FlatDev& F) { return F.n_fwd <= GPF_WR_CAP_F && F.n_back <= GPF_WR_CAP_B; }
+template <int GW, class PP>
+__device__ __forceinline__ void flat_words_load(FlatWords<false>&, const FlatDev&, PP, int) {}
+template <int GW, class PP>
+__device__ __forceinline__ void flat_words_load(FlatWords<true>& W, const FlatDev& F, PP prog, int tid) {
+  const bool fit = flat_words_fit(F);
+#pragma unroll
+  for (int k = 0; k < GPF_WR_CAP_F; ++k) {             // (every pass is GW items of two words, 0xffffffff: no item for this lane)
+    const bool on_f = fit && k < F.n_fwd;
+    W.f[2 * k] = on_f ? (unsigned)prog[2 * tid + 2 * GW * k] : 0xffffffffu;
+    W.f[2 * k + 1] = on_f ? (unsigned)prog[2 * tid + 2 * GW * k + 1] : 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < GPF_WR_CAP_B; ++k) {
+    const bool on_b = fit && k < F.n_back;
+    W.b[2 * k] = on_b ? (unsigned)prog[F.back_off + 2 * tid + 2 * GW * k] : 0xffffffffu;
+    W.b[2 * k + 1] = on_b ? (unsigned)prog[F.back_off + 2 * tid + 2 * GW * k + 1] : 0u;
+  }
+}
+
 // ---- flat-program sweeps (gridpf_symbolic.hpp: FlatProg) -------------------------------------------------------------------
 // Block LU + solve with 2x2 blocks on the flat program.  A: row 0 of every (pseudo-)slot at A + slot * 2, row 1 at
 // A + HS + slot * 2 (HS = (rslot0 + n) * 2 doubles); the right-hand side lives in the pseudo-slots and holds s = D x on return
@@ -693,8 +733,10 @@ __device__ inline bool block_lu_solve(const SymDev& S, PP prog, double* __restri
 // deferred scaling pass is gone): the back substitution accumulates s_p -= A_pj inv(D_j) s_j with ds_add_f64 and the caller forms
 // x_p = inv(D_p) s_p where it consumes the solution (flat_solution).  What a phase costs is its instruction count: no level headers,
 // no bounds / clamps, no "trailing update or right-hand side?" selects, byte offsets instead of slot indices.
-template <int GW, class PP = const int*>
-__device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restrict__ A, size_t HS, int tid, long long* dbg = nullptr) {
+// RES: the lane's item words come from W (flat_words_load, registers) instead of `prog`: no load in the sweeps.
+template <int GW, class PP = const int*, bool RES = false>
+__device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restrict__ A, size_t HS, int tid, long long* dbg = nullptr,
+                                     const FlatWords<RES>* W = nullptr) {
 #ifdef GPF_TIMING
   const long long t_lu0 = __builtin_readcyclecounter();
 #endif
@@ -746,7 +788,7 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
   //    latency (LDS round trip -> arithmetic -> LDS round trip, tools/lds_pass_bench.hip: 450 cycles for one wavefront alone, 630 -- 800
   //    for two wavefronts with the barrier and 4 instances per CU): the narrow tail levels and the back substitution of the
   //    118-substation grids (12 of 19 passes per factorisation) pay the single-wavefront price.
-#define GPF_WALK(n_, at0_, MASK_, NEXT_SOLO_, ITEM_, TB_)                                                                                   \
+#define GPF_WALK(n_, at0_, MASK_, NEXT_SOLO_, ITEM_, TB_, WR_, CAP_)                                                                                 \
   {                                                                                                                                \
     const unsigned solo_ = GW > WAVE ? (unsigned)(MASK_) : 0u;                                                                     \
     const int n_pass_ = (n_);                                                                                                      \
@@ -758,6 +800,11 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
       else GPF_LSYNC();                                                                                                            \
       GPF_PASS_T((TB_) + k);                                                                                                       \
     };                                                                                                                             \
+    if constexpr (RES) {             /* resident words: a fully unrolled walk over register pairs, no load */                      \
+      _Pragma("unroll")                                                                                                            \
+      for (int k = 0; k < (CAP_); ++k)                                                                                             \
+        if (k < n_pass_) step_(W->WR_[2 * k], W->WR_[2 * k + 1], k);                                                               \
+    } else {                                                                                                                       \
     int at = (at0_) + 2 * tid;                                                                                                     \
     unsigned p0 = (unsigned)prog[at], p1 = (unsigned)prog[at + 1];                                                                 \
     if (PF2) {                                                                                                                     \
@@ -781,8 +828,9 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
         p0 = n0; p1 = n1;                                                                                                          \
       }                                                                                                                            \
     }                                                                                                                              \
+    }                                                                                                                              \
   }
-  GPF_WALK(F.n_fwd, 0, F.solo_fwd, F.n_back > 0 && (F.solo_back & 1), fwd_item, 1)   // (the first back pass continues a solo run)
+  GPF_WALK(F.n_fwd, 0, F.solo_fwd, F.n_back > 0 && (F.solo_back & 1), fwd_item, 1, f, GPF_WR_CAP_F)   // (the first back pass continues a solo run)
 #ifdef GPF_TIMING
   const long long t_lu1 = __builtin_readcyclecounter();
 #endif
@@ -800,7 +848,7 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
       atomicAdd(FL_D(a1, w1), -fma(uB.x, x0, uB.y * x1));
     }
   };
-  GPF_WALK(F.n_back, F.back_off, F.solo_back, false, back_item, 1 + F.n_fwd)
+  GPF_WALK(F.n_back, F.back_off, F.solo_back, false, back_item, 1 + F.n_fwd, b, GPF_WR_CAP_B)
 #ifdef GPF_TIMING
   if (dbg) { dbg[0] = t_lu1 - t_lu0; dbg[1] = (long long)__builtin_readcyclecounter() - t_lu1; }
 #endif
@@ -813,9 +861,9 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
 // the forward sweep), COMPACT: as one double per slot (CarveP::Adc) instead of element [0][0] of the row-0 half; only the
 // right-hand-side items of the forward sweep and the back substitution run.  On return the first entry of pseudo-slot p holds
 // s_p = d_p * theta_p (the caller divides by the pivot, like the 2x2 sweep's callers apply inv(D_p)).
-template <int GW, bool FACTOR, bool COMPACT, class PP = const int*>
+template <int GW, bool FACTOR, bool COMPACT, class PP = const int*, bool RES = false>
 __device__ inline bool scalar_lu_flat(const FlatDev& F, PP prog, double* __restrict__ A, double* __restrict__ fac, int tid,
-                                      long long* dbg = nullptr) {
+                                      long long* dbg = nullptr, const FlatWords<RES>* W = nullptr) {
 #ifdef GPF_TIMING
   const long long t_lu0 = __builtin_readcyclecounter();
 #endif
@@ -840,7 +888,7 @@ __device__ inline bool scalar_lu_flat(const FlatDev& F, PP prog, double* __restr
   };
 #undef GPF_PASS_T
 #define GPF_PASS_T(i_) do {} while (0)
-  GPF_WALK(F.n_fwd, 0, F.solo_fwd, F.n_back > 0 && (F.solo_back & 1), fwd_item, 0)
+  GPF_WALK(F.n_fwd, 0, F.solo_fwd, F.n_back > 0 && (F.solo_back & 1), fwd_item, 0, f, GPF_WR_CAP_F)
 #ifdef GPF_TIMING
   const long long t_lu1 = __builtin_readcyclecounter();
 #endif
@@ -850,7 +898,7 @@ __device__ inline bool scalar_lu_flat(const FlatDev& F, PP prog, double* __restr
       atomicAdd(FL_D(a0, w1), -(*facp(w0 & 0xffffu) * *FL_D(a0, fj)) * fast_rcp(*facp(fj - (unsigned)F.rhs_field0)));
     }
   };
-  GPF_WALK(F.n_back, F.back_off, F.solo_back, false, back_item, 0)
+  GPF_WALK(F.n_back, F.back_off, F.solo_back, false, back_item, 0, b, GPF_WR_CAP_B)
 #ifdef GPF_TIMING
   if (dbg) { dbg[0] = t_lu1 - t_lu0; dbg[1] = (long long)__builtin_readcyclecounter() - t_lu1; }
 #endif
@@ -905,7 +953,8 @@ struct TopoState {
 // factored DC matrix (CarveP::Adc) instead, which no longer has to be rebuilt and refactored by every step of a launch.
 constexpr int YR_PASSES = 4;
 template <int NB, int STAGE, int IPW, int WPI, bool TC, bool YR = false>
-__device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, const SymDev& S, const FlatDev& FL, const StatView<STAGE>& sv, CarveP<NB>& c, double2* yreg, unsigned* rcreg, int inst, int is_dc, int max_iter,
+__device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, const SymDev& S, const FlatDev& FL, const StatView<STAGE>& sv, CarveP<NB>& c, double2* yreg, unsigned* rcreg,
+                                            const FlatWords<flat_words_ct<NB, IPW, WPI>()>& FW, int inst, int is_dc, int max_iter,
                                             double tol_pu, int tid, const SolveCtl& ctl, TopoState& ts, int& n_iter_out, int& nb_out, float& a_or_first GPF_STAMPS_PARAM) {
   typedef Grp<IPW, WPI> G;
   constexpr int GW = G::GW;
@@ -1277,8 +1326,12 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
   // 4 096 lanes -- so a staged program (tier >= 1) is read from LDS there.
   const int* const flat_g = STAGE == 0 ? sv.prog.p : S.flat[gw_index(GW)];     // (tier 0: the view already points at the global copy)
   constexpr bool PROG_LDS = STAGE >= 1 && IPW == 1;
+  // (instance-group kernels: the words are in registers for the whole launch, FlatWords, unless the program has too many passes)
+  constexpr bool WRES = flat_words_ct<NB, IPW, WPI>();
+  const bool wres = WRES && flat_words_fit(FL);                 // block-uniform; a literal in the grid-specialised build
   auto lu_ac = [&](long long* dbg) -> bool {
     if (BS == 2) {
+      if (WRES && wres) return block_lu_flat<GW, decltype(gptr(flat_g)), WRES>(FL, gptr(flat_g), c.A, HS, tid, dbg, &FW);
       if (PROG_LDS) return block_lu_flat<GW>(FL, sv.prog.p, c.A, HS, tid, dbg);
       return block_lu_flat<GW>(FL, gptr(flat_g), c.A, HS, tid, dbg);
     }
@@ -1287,9 +1340,11 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
   };
   auto lu_dc = [&](long long* dbg) -> bool {       // single-busbar layout only
     if (dc_kept) {
+      if (WRES && wres) return scalar_lu_flat<GW, false, true, decltype(gptr(flat_g)), WRES>(FL, gptr(flat_g), c.A, c.Adc, tid, dbg, &FW);
       if (PROG_LDS) return scalar_lu_flat<GW, false, true>(FL, sv.prog.p, c.A, c.Adc, tid, dbg);
       return scalar_lu_flat<GW, false, true>(FL, gptr(flat_g), c.A, c.Adc, tid, dbg);
     }
+    if (WRES && wres) return scalar_lu_flat<GW, true, false, decltype(gptr(flat_g)), WRES>(FL, gptr(flat_g), c.A, c.A, tid, dbg, &FW);
     if (PROG_LDS) return scalar_lu_flat<GW, true, false>(FL, sv.prog.p, c.A, c.A, tid, dbg);
     return scalar_lu_flat<GW, true, false>(FL, gptr(flat_g), c.A, c.A, tid, dbg);
   };
@@ -1465,6 +1520,8 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
       for (int i = S.nslot_y * 2 + tid; i < S.nslot * 2; i += GW) { c.A[i] = 0.0; c.A[HS + i] = 0.0; }      // fill blocks start at zero
       GPF_LSYNC();
       GPF_STAMPS(10);
+      // (assembler comments, no instruction: tests/test_step_kernel_words_resident.py finds the loop in the disassembly by them)
+      asm volatile("; GPF_NEWTON_NWR_BEGIN" ::: "memory");
       while (true) {
         // ---- pair phase: T_uv, T_vu -> the two off-diagonal Jacobian blocks, S_u += T_uv, S_v += T_vu
         if (p_on) {
@@ -1514,7 +1571,11 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
         if (G::block_all_u(done)) break;
         GPF_LSYNC();
         if (it == 1) GPF_STAMPS(12);
+#ifdef GPF_TIMING
+        const bool ok = lu_ac(it == 1 ? &stamps.v[32] : nullptr);     // (per-pass stamps of the first factorisation: GPF_PASS_T)
+#else
         const bool ok = lu_ac(nullptr);
+#endif
         if (it == 1) GPF_STAMPS(13);
         // ---- update (groups that are done keep their state) + preparation of the next pair phase
         bool fin = true, piv_ok = true;
@@ -1544,6 +1605,7 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
         GPF_LSYNC();
         if (!done && G::template any2<1>(!ok || !piv_ok, !fin) != 0u) { status = 4; done = true; }
         if (it == 1) GPF_STAMPS(14);
+        asm volatile("; GPF_NEWTON_NWR_BACKEDGE" ::: "memory");
       }
       // what the results phase reads from LDS: the bus injections of the final state, va, |V|
       if (b_on) { *SreP(ib) = Sr; *SimP(ib) = Si; c.va[ib] = va; c.vm[ib] = vm; }
@@ -2157,7 +2219,9 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void runpf_sparse_kerne
   ctl.otraj = false; ctl.orow = inst; ctl.write_topo = true; ctl.inj_regs = false; ctl.tc_rebuild = false;
   TopoState ts;
   ts.status = 0; ts.nb = 0; ts.dc_base = false; ts.dc_out = -1; ts.gen_base = false; ts.tc[0] = ts.tc[1] = -1;
-  const int st = solve_instance_sparse<NB, STAGE, IPW, WPI, TC, YR>(P, S, FL, sv, c, yreg, rcreg, inst, is_dc, max_iter, tol_pu, tid, ctl, ts, n_iter, nb, a_first GPF_STAMPS_ARG);
+  FlatWords<flat_words_ct<NB, IPW, WPI>()> FW;
+  flat_words_load<GW>(FW, FL, gptr(S.flat[GWI]), tid);
+  const int st = solve_instance_sparse<NB, STAGE, IPW, WPI, TC, YR>(P, S, FL, sv, c, yreg, rcreg, FW, inst, is_dc, max_iter, tol_pu, tid, ctl, ts, n_iter, nb, a_first GPF_STAMPS_ARG);
   GPF_SYNC();
   if (st != 0) write_nan_results<GW>(g, P->b, inst, tid, inst, false);
   if (tid == 0) {
@@ -2631,6 +2695,10 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
   } while (0)
   // per-step observation trajectory (block-uniform): every step's rows go to [step][lane] of Bufs::traj_*, else to the lane's rows
   const bool tobs = b.traj_out != nullptr;
+  // the lane's item words of the flat program, once per launch (the block's program is the same for every step: the grid's, or the one of
+  // the topology class the host packed the block's lanes by)
+  FlatWords<flat_words_ct<NB, IPW, WPI>()> FW;
+  flat_words_load<GW>(FW, FL, gptr(S.flat[GWI]), tid0);
   for (int step = 0; step < sa.n_steps; ++step) {
     GPF_REDERIVE();
     const bool last = step + 1 == sa.n_steps;
@@ -2814,7 +2882,7 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
       ctl.tc_rebuild = keep_hit && step == 0;
       ctl.inj_regs = skip_inj; ctl.r_lp0 = k9_lp0; ctl.r_lq0 = k9_lq0; ctl.r_lp1 = k9_lp1; ctl.r_lq1 = k9_lq1; ctl.r_pp = k9_pp; ctl.r_vm = k9_vm;
       GPF_STAMPS(31);
-      const int st_k = solve_instance_sparse<NB, STAGE, IPW, WPI, TC, YR>(P, S, FL, sv, c, yreg, rcreg, inst, sa.is_dc, max_iter, tol_pu, tid, ctl, ts, it_k, nb_k, a_first GPF_STAMPS_ARG);
+      const int st_k = solve_instance_sparse<NB, STAGE, IPW, WPI, TC, YR>(P, S, FL, sv, c, yreg, rcreg, FW, inst, sa.is_dc, max_iter, tol_pu, tid, ctl, ts, it_k, nb_k, a_first GPF_STAMPS_ARG);
       first = false;
       GPF_SYNC_IF(sa.cascade != 0 && g.n_line > GW);   // (every line loop maps line l to lane l % GW: lanes read their own rows)
       if (more) { st = st_k; n_iter = it_k; nb = nb_k; }

@@ -57,7 +57,8 @@ if SPARSE:
     if med[39] > 0 and NS == 1:
         print(f"  prologue detail: before the kept-state block {med[34] - m8:.0f}, loads + key comparison {med[36] - med[34]:.0f}, state -> LDS {med[37] - med[36]:.0f}, "
               f"block verdict {med[38] - med[37]:.0f}, barrier {med[39] - med[38]:.0f}, rest {med[19] - med[39]:.0f}")
-    print(f"  DC block-LU: elimination levels + scaling {med[20]:.0f}, back substitution {med[21]:.0f} cycles")
+    if med[20] < 1e9 and med[21] < 1e9:      # (the register-resident path reuses slots 20 / 21 for raw stamps: not durations there)
+        print(f"  DC block-LU: elimination levels + scaling {med[20]:.0f}, back substitution {med[21]:.0f} cycles")
     print(f"  first Newton iteration: initial sincos {med[10] - med[4]:.0f}, Jacobian blocks + S {med[11] - med[10]:.0f}, "
           f"diag + mismatch + test {med[12] - med[11]:.0f}, block LU {med[13] - med[12]:.0f}, update + sincos {med[14] - med[13]:.0f}")
     print(f"  K9 detail: topo row + first loads {med[16] - med[8]:.0f}, load rows + sums {med[17] - med[16]:.0f}, reductions {med[18] - med[17]:.0f}, "
@@ -73,7 +74,7 @@ if SPARSE:
     ok = pt[:, 0] > 0
     if ok.any():
         d = np.diff(pt[ok], axis=1)
-        d = np.where((pt[ok][:, 1:] > 0) & (d > 0), d, np.nan)
+        d = np.where((pt[ok][:, 1:] > 0) & (pt[ok][:, :-1] > 0) & (d > 0) & (d < 1e7), d, np.nan)      # stamped slots only (unstamped ones read as zero)
         print("  first factorisation, cycles per pass (forward then back; median / min / max over lanes):")
         for k in range(min(d.shape[1], 20)):
             if np.isfinite(d[:, k]).any():
