@@ -1439,6 +1439,7 @@ int gpf_upload_chronics(gpf_handle e, int32_t n_tables, int32_t T, const float* 
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->maint.release();                       // belongs to the previous tables
   e->h_maint.clear(); e->h_hazard.clear();
+  ++e->maint_gen;
   e->forecast.release(); e->fc_h = 0;
   HIP_TRY(e->chron.upload(data, (size_t)n_tables * T * e->g.n_chron));
   e->chron_T = T;
@@ -1465,6 +1466,7 @@ int upload_outage_tables(gpf_engine* e) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->maint.release();
   e->maint_dur.release();
+  ++e->maint_gen;
   if (e->h_maint.empty() && e->h_hazard.empty()) return GPF_OK;
   std::vector<unsigned char> u = e->h_maint.empty() ? e->h_hazard : e->h_maint;
   if (!e->h_maint.empty() && !e->h_hazard.empty()) for (size_t i = 0; i < u.size(); ++i) u[i] = (u[i] || e->h_hazard[i]) ? 1 : 0;
@@ -1733,6 +1735,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     if (list_resets) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
   }
   e->traj_valid = e->traj_cap ? n_steps : 0;
+  e->last_t0 = t0; e->last_n_steps = n_steps; e->last_track_cooldown = o->track_cooldown != 0;
   if (e->env_on) {                          // the actions were consumed by this launch (a held storage action stays)
     // (the kernels only read an action buffer whose flag is set -- EnvDyn::act_* is NULL otherwise --, so "consumed" is the flag: no
     //  clearing dispatch behind every launch of an agent that acts at every step)
@@ -2529,6 +2532,7 @@ int gpf_device_pointers(gpf_handle e, void** ptrs, void** stream) { return gpf_d
 int gpf_device_pointers_n(gpf_handle e, void** out, int32_t n_ptrs, void** stream) {
   if (!e || !out || n_ptrs < 0) return fail(GPF_E_INVALID, "gpf_device_pointers: null");
   void* ptrs[GPF_N_DEVICE_POINTERS];
+  ptrs[32] = e->obs_spec_on ? e->obs_vec.p : nullptr;
   ptrs[0] = e->inj.p; ptrs[1] = e->topo.p; ptrs[2] = e->shunt_bus.p; ptrs[3] = e->out.p; ptrs[4] = e->topo_out.p;
   ptrs[5] = e->line_status.p; ptrs[6] = e->status.p; ptrs[7] = e->chron.p;
   ptrs[8] = e->rho.p; ptrs[9] = e->overflow_count.p; ptrs[10] = e->done.p; ptrs[11] = e->episode.p; ptrs[12] = e->bus_vm.p;

@@ -162,6 +162,14 @@ struct StepArgs {
   KeepArgs keep;     // (gpf_step_n, n_steps = 1, single-busbar kernels without topology classes)
 };
 
+// K9: the chronics row a lane reads at time index t -- (t + lane_offset) mod T, non-negative (gpf_step_n; the observation clock of
+// gridpf_obs.hpp dates the lane's last step with the same row)
+__host__ __device__ __forceinline__ int chron_row_index(int t, int off, int T) {
+  int row = (t + off) % T;
+  if (row < 0) row += T;
+  return row;
+}
+
 // results-row offsets (must match gpf_layout in include/gridpf.h)
 struct OutOff {
   int p_or, q_or, v_or, a_or, th_or, p_ex, q_ex, v_ex, a_ex, th_ex;

@@ -211,6 +211,19 @@ struct gpf_engine {
   int traj_cap = 0;
   int traj_what = 0;                    // GPF_TRAJ_* bits of the current buffers
   int traj_valid = 0;                   // steps of the trajectory written by the last gpf_step_n
+  // observation vectors assembled on the device (gridpf_obs.hpp, gridpf_capi_obs.hip): the spec's segment table, the per-element affine map,
+  // the calendar of the chronics tables and the maintenance look-ahead derived from the uploaded maintenance table
+  bool obs_spec_on = false, obs_clock_on = false, obs_gof = true;
+  int obs_dim = 0, obs_n_seg = 0;
+  std::vector<int> h_obs_seg;           // [n_seg][5] {kind, source offset, length, destination offset, flags}
+  DevArr<int> obs_seg;
+  DevArr<float> obs_sub, obs_div, obs_vec;   // [dim], [dim], engine-owned output [cap_lanes][dim]
+  DevArr<long long> obs_clock;          // [chron_tables] minutes since 1970-01-01 00:00 of row 0 of each table
+  int obs_clock_tables = 0, obs_step_minutes = 5, obs_max_step = 0;
+  DevArr<int> obs_maint_next, obs_maint_durn;   // [chron_tables][chron_T][n_line] time_next_maintenance / duration_next_maintenance at every row
+  long long obs_maint_gen = -1, maint_gen = 0;  // generation of the outage tables the look-ahead was derived from / current generation
+  bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
+  int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
   DevArr<double> rd_pmin, rd_pmax, rd_ru, rd_rd, rd_in;      // generator limits + staging of gpf_redispatch
   DevArr<unsigned char> rd_redisp, rd_u8;

@@ -2559,8 +2559,7 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
   // ---- per-lane constants of the launch --------------------------------------------------------------------------------------
   const int tab = b.lane_table ? gptr(b.lane_table)[inst] : 0;
   const int off = b.lane_offset ? gptr(b.lane_offset)[inst] : 0;
-  int row = (sa.t + off) % sa.T;
-  if (row < 0) row += sa.T;
+  int row = chron_row_index(sa.t, off, sa.T);
   const bool has_sc = b.lane_scale != nullptr;
   const bool has_delta = b.lane_gen_delta != nullptr;
   // jitter factors and redispatch delta of the elements this thread handles first stay in registers for the whole launch

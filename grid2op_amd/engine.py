@@ -709,12 +709,13 @@ class PowerFlowEngine:
         ``act_curtail`` ``[n_lanes, n_gen]``, ``act_storage`` ``[n_lanes, n_storage]`` (`lane_actions_on_device`) and
         ``target_dispatch`` / ``actual_dispatch`` / ``storage_charge`` float32 (obs.target_dispatch, ...); once topology actions are enabled
         (`set_topo_rules` / `upload_topo_actions`) also ``act_topo`` int32 ``[n_lanes, 1]`` (`topo_actions_on_device`), ``sub_cooldown``
-        ``[n_lanes, n_sub]``, ``topo_flags`` uint8 ``[n_lanes, 2]`` and ``last_bus`` ``[n_lanes, dim_topo]``.  The engine works on its own HIP stream: call `sync` (or make the consumer's
+        ``[n_lanes, n_sub]``, ``topo_flags`` uint8 ``[n_lanes, 2]`` and ``last_bus`` ``[n_lanes, dim_topo]``; once an observation spec is set
+        (`set_obs_spec`) also ``obs`` float32 ``[n_lanes, dim]`` (what `observation_vector` without ``out`` writes).  The engine works on its own HIP stream: call `sync` (or make the consumer's
         stream wait on ``views["stream"]``, a ``torch.cuda.ExternalStream``) before reading."""
         import torch
-        ptrs = (C.c_void_p * 32)()
+        ptrs = (C.c_void_p * _capi.N_DEVICE_POINTERS)()
         stream = C.c_void_p()
-        check(self._lib.gpf_device_pointers_n(self._h, ptrs, 32, C.byref(stream)), "gpf_device_pointers_n")
+        check(self._lib.gpf_device_pointers_n(self._h, ptrs, _capi.N_DEVICE_POINTERS, C.byref(stream)), "gpf_device_pointers_n")
         cap = self._lib.gpf_lane_capacity(self._h)
         m = self.model
         dev = torch.device("cuda", self.device)
@@ -738,7 +739,8 @@ class PowerFlowEngine:
              "target_dispatch": view(25, m.n_gen, "<f4"), "actual_dispatch": view(26, m.n_gen, "<f4"),
              "storage_charge": view(27, m.n_storage, "<f4"),
              "act_topo": view(28, 1, "<i4"), "sub_cooldown": view(29, m.n_sub, "<i4"), "topo_flags": view(30, 2, "|u1"),
-             "last_bus": view(31, m.dim_topo, "<i4")}
+             "last_bus": view(31, m.dim_topo, "<i4"),
+             "obs": view(32, self._obs_spec.dim if getattr(self, "_obs_spec", None) is not None else 0, "<f4")}
 
         def tview(idx, cols, typestr):       # trajectory buffers: [cap_steps][cap][cols]
             if cols == 0 or not ptrs[idx] or not getattr(self, "_traj_cap", 0):
@@ -750,6 +752,95 @@ class PowerFlowEngine:
                   "traj_line_status": tview(21, m.n_line, "|u1")})
         v["stream"] = torch.cuda.ExternalStream(stream.value, device=dev)
         return v
+
+    # ---- observation vectors assembled on the device (include/gridpf.h: gpf_set_obs_spec; grid2op_amd/obs_spec.py) ----------------------
+    def set_obs_clock(self, start, step_minutes: int = 5, max_step: Optional[int] = None):
+        """The calendar of row 0 of each chronics table: ``start`` is a naive ``datetime`` (or a list with one per table); ``step_minutes``
+        is the length of a step (obs.delta_time), ``max_step`` what obs.max_step reports (default: the rows of the uploaded tables - 1,
+        as the reference's ``max_episode_duration`` of a chronics of that length)."""
+        import datetime as _dt
+        starts = list(start) if isinstance(start, (list, tuple)) else [start]
+        mins = []
+        for s_ in starts:
+            if not isinstance(s_, _dt.datetime):
+                raise TypeError("set_obs_clock: start must be a datetime (or a list of them)")
+            d = s_.replace(tzinfo=None) - _dt.datetime(1970, 1, 1)
+            if d.seconds % 60 or d.microseconds:
+                raise ValueError("set_obs_clock: start must fall on a whole minute")
+            mins.append(d.days * 1440 + d.seconds // 60)
+        if max_step is None:
+            max_step = max(int(getattr(self, "chron_T", 1)) - 1, 0)
+        a = np.ascontiguousarray(mins, dtype=np.int64)
+        check(self._lib.gpf_set_obs_clock(self._h, a.size, a.ctypes.data_as(C.POINTER(C.c_int64)), int(step_minutes), int(max_step)),
+              "gpf_set_obs_clock")
+
+    def set_obs_spec(self, spec, game_over_fill: bool = True):
+        """The layout of the observation vectors (`grid2op_amd.obs_spec.ObsSpec`).  ``game_over_fill``: a lane whose last step ended its
+        episode gets the reference's game-over vector (``BaseObservation.set_game_over``: zeros, topo_vect / _shunt_bus /
+        time_next_maintenance -1, curtailment_limit 1, calendar and counters kept) instead of the NaN rows of the failed power flow."""
+        from .obs_spec import out_offsets
+        oo = out_offsets(self.model)
+        assert all(self.out_slices[k].start == v for k, v in oo.items()), "obs_spec.out_offsets disagrees with the library's layout"
+        seg = np.ascontiguousarray(spec.segments, dtype=np.int32)
+        sub = np.ascontiguousarray(spec.subtract, dtype=np.float32)
+        div = np.ascontiguousarray(spec.divide, dtype=np.float32)
+        assert sub.size == spec.dim and div.size == spec.dim
+        check(self._lib.gpf_set_obs_spec(self._h, seg.shape[0], ptr(seg, C.c_int32), int(spec.dim), ptr(sub, C.c_float), ptr(div, C.c_float),
+                                         int(bool(game_over_fill))), "gpf_set_obs_spec")
+        self._obs_spec = spec
+        self._obs_view = None
+
+    def _obs_dim(self):
+        spec = getattr(self, "_obs_spec", None)
+        if spec is None:
+            raise GridPFError("no observation spec is set (set_obs_spec)")
+        return spec.dim
+
+    def observation_vector(self, lane0: int = 0, n: Optional[int] = None, out=None):
+        """The observation vectors of lanes ``[lane0, lane0 + n)`` as a float32 torch tensor ``[n, dim]`` in device memory, written by one
+        gather kernel queued on the engine's stream (asynchronous: order the consumer on ``device_views()["stream"]``, or `sync`).
+        Without ``out`` the tensor ALIASES the engine-owned buffer ``device_views()["obs"]`` (rewritten by the next call); ``out`` may be
+        a caller's float32 CUDA tensor ``[n, >= dim]`` with unit column stride and any row stride >= dim -- only the first ``dim``
+        columns of its rows are written."""
+        lane0, n = self._range(lane0, n)
+        dim = self._obs_dim()
+        if out is None:
+            check(self._lib.gpf_obs_vector(self._h, lane0, n, None, 0), "gpf_obs_vector")
+            if getattr(self, "_obs_view", None) is None:
+                self._obs_view = self.device_views()["obs"]
+            return self._obs_view[lane0:lane0 + n]
+        import torch
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2):
+            raise ValueError("observation_vector: out must be a 2-d float32 CUDA tensor")
+        if out.device.index != self.device or out.shape[0] != n or out.shape[1] < dim or out.stride(1) != 1 or (n > 1 and out.stride(0) < dim):
+            raise ValueError(f"observation_vector: out must live on cuda:{self.device}, have {n} rows of >= {dim} contiguous columns and a row stride >= {dim}")
+        check(self._lib.gpf_obs_vector(self._h, lane0, n, C.c_void_p(out.data_ptr()), int(out.stride(0)) if n > 1 else max(int(out.stride(0)), dim)),
+              "gpf_obs_vector")
+        return out[:, :dim]
+
+    def observation_trajectory(self, n_steps: int, step0: int = 0, lane0: int = 0, n: Optional[int] = None, out=None):
+        """The observation vectors of steps ``[step0, step0 + n_steps)`` of the last multi-step launch, ``[n_steps, n, dim]`` float32 on the
+        device, from the per-step copies of `set_trajectory(cap, TRAJ_OBS)`.  Calendar and maintenance attributes advance with the
+        steps; attributes without a per-step copy (timestep_overflow, time_before_cooldown_sub, the dispatch / charge / curtailment
+        state, current_step) must not be in the spec.  Asynchronous, as `observation_vector`."""
+        import torch
+        lane0, n = self._range(lane0, n)
+        dim = self._obs_dim()
+        if out is None:
+            out = torch.empty((int(n_steps), n, dim), dtype=torch.float32, device=torch.device("cuda", self.device))
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (int(n_steps), n, dim)):
+            raise ValueError(f"observation_trajectory: out must be a contiguous float32 CUDA tensor of shape {(int(n_steps), n, dim)}")
+        torch.cuda.current_stream(out.device).synchronize()      # (a fresh allocation may still be in use by work queued on torch's stream)
+        check(self._lib.gpf_obs_vector_trajectory(self._h, int(step0), int(n_steps), lane0, n, C.c_void_p(out.data_ptr())),
+              "gpf_obs_vector_trajectory")
+        return out
+
+    def observation_vector_host(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """`observation_vector` copied to the host: float32 ``[n, dim]`` (synchronous)."""
+        lane0, n = self._range(lane0, n)
+        out = np.empty((n, self._obs_dim()), dtype=np.float32)
+        check(self._lib.gpf_get_obs_vector(self._h, lane0, n, ptr(out, C.c_float)), "gpf_get_obs_vector")
+        return out
 
     def set_overflow_count(self, counts, lane0: int = 0):
         """The protection counters (consecutive steps above the thermal limit, ``obs.timestep_overflow``) of lanes

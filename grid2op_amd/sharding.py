@@ -207,6 +207,29 @@ class ShardedEngine:
         for eng, l0, k, off in self._parts(lane0, c.shape[0]):
             eng.set_cooldown(c[off:off + k], lane0=l0)
 
+    # ---- observation vectors (PowerFlowEngine.set_obs_spec ...): per-shard tensors on each device, host copies concatenated ----------
+    def set_obs_clock(self, *a, **kw):
+        for eng in self.engines:
+            eng.set_obs_clock(*a, **kw)
+
+    def set_obs_spec(self, spec, game_over_fill: bool = True):
+        for eng in self.engines:
+            eng.set_obs_spec(spec, game_over_fill)
+
+    def observation_vector(self, lane0: int = 0, n=None, out=None):
+        """One tensor per shard that intersects the range (each on its own device and stream); ``out``: a list with one tensor per such shard."""
+        parts = self._parts(lane0, n)
+        outs = [None] * len(parts) if out is None else list(out)
+        if len(outs) != len(parts):
+            raise ValueError(f"ShardedEngine.observation_vector: {len(parts)} shards intersect the range, {len(outs)} output tensors given")
+        return [eng.observation_vector(l0, k, out=o) for (eng, l0, k, _), o in zip(parts, outs)]
+
+    def observation_trajectory(self, n_steps: int, step0: int = 0, lane0: int = 0, n=None):
+        return [eng.observation_trajectory(n_steps, step0, l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
+
+    def observation_vector_host(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.observation_vector_host(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
     def step_outputs(self, lane0: int = 0, n=None):
         parts = [eng.step_outputs(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))

@@ -105,8 +105,9 @@ const char* gpf_last_error(void);
  * call (grid2op_amd/_capi.py does): 300 = round 4 (gpf_set_trajectory(h, cap, what), 22 device pointers, GPF_ST_REDISPATCH,
  * gpf_device_pointers_n); 310 = + gpf_jit_*, GPF_E_UNSUPPORTED, gpf_set_profiling mode 3; 321 = 28 device pointers (action buffers and
  * dispatch / charge state of the environment dynamics), gpf_lane_actions_on_device; 322 = + gpf_get_results_pinned; 323 = gpf_step_opts::track_cooldown,
- * GPF_DEVICE_NONE (header-only handles); 324 = 32 device pointers, topology actions in the batched step (gpf_upload_topo_actions ...). */
-#define GPF_ABI_VERSION 324
+ * GPF_DEVICE_NONE (header-only handles); 324 = 32 device pointers, topology actions in the batched step (gpf_upload_topo_actions ...);
+ * 325 = 33 device pointers, observation vectors assembled on the device (gpf_set_obs_spec ...). */
+#define GPF_ABI_VERSION 325
 int gpf_version(void);
 /* Bitwise run-to-run reproducibility is the DEFAULT on every grid: the same lane inputs give bit-identical results from run to
  * run and whatever the lane's position in the batch (grid2op's determinism contract: same seeds -> same episode,
@@ -426,6 +427,77 @@ int gpf_get_last_bus(gpf_handle h, int32_t lane0, int32_t n, int32_t* last_bus);
 int gpf_set_last_bus(gpf_handle h, int32_t lane0, int32_t n, const int32_t* last_bus);
 int gpf_get_topo_flags(gpf_handle h, int32_t lane0, int32_t n, uint8_t* flags);
 
+/* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
+ * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
+ * Observation/baseObservation.py:4464-4540; with subtract / divide what gym_compat.BoxGymObsSpace(attr_to_keep, subtract, divide) puts on
+ * top of it, gym_compat/box_gym_obsspace.py) -- one float32 row per lane, gathered from the engine's buffers by ONE side kernel on the
+ * engine's stream (grid2op_amd/csrc/gridpf_obs.hpp); the step and power-flow kernels are not involved.
+ *   gpf_set_obs_clock : the calendar of row 0 of each chronics table, start_minutes[n_tables] minutes since 1970-01-01 00:00 (>= 0), the step
+ *                       length in minutes (> 0) and the episode length obs.max_step reports.  A lane's date is that of the chronics row its
+ *                       last step read -- (t + lane_offset) mod T of its table, the row index of gpf_step_n for the last time index of the last
+ *                       launch (t = 0 before any launch).
+ *   gpf_set_obs_spec  : n_seg <= 64 segments[n_seg][5] = {source kind (GPF_OBS_*), source offset, length, destination offset, flags}
+ *                       and the per-element affine map value = (x - subtract[i]) / divide[i] in float32 (arrays of `dim` floats; NULL: 0 / 1;
+ *                       a segment whose elements all have 0 and 1 is a plain cast, bit for bit).  Source offsets are columns of the results row
+ *                       (GPF_OBS_OUT), the calendar field 0..5 = year, month, day, hour, minute, weekday (GPF_OBS_CALENDAR), the float bits of
+ *                       the value (GPF_OBS_CONST), an element offset otherwise.  flags bits 0-1: what a lane whose last step ended its episode
+ *                       writes when game_over_fill != 0 (BaseObservation.set_game_over, baseObservation.py:1551-1700): 0 zeros, 1 the value as
+ *                       computed (calendar, counters, constants), 2 minus one, 3 one.  Everything is validated on the host before the device is
+ *                       touched: kinds, source ranges against the grid's sizes, destination ranges that tile [0, dim) without overlap or gap,
+ *                       divide != 0.  Sources: GPF_OBS_RHO / GPF_OBS_OVERFLOW are the buffers gpf_step / gpf_step_n maintain (gpf_runpf does NOT
+ *                       refresh them); buffers that were never allocated (line / substation cooldowns, the state of the injection dynamics)
+ *                       read as zeros, the curtailment limit as 1; the generator margins (baseObservation.py:4393-4410, float32) are zeros until
+ *                       gpf_set_gen_limits was called, renewables from gpf_set_gen_renewable; time / duration of the next maintenance are
+ *                       GridValue.get_maintenance_time_1d / get_maintenance_duration_1d (Chronics/gridValue.py:264-410) of the uploaded
+ *                       MAINTENANCE table at the lane's row (-1 / 0 without a table); current_step is the lane's steps survived, plus one on a
+ *                       lane whose last step ended its episode (BaseEnv.nb_time_step counts the failing step); gen_p_before_curtail /
+ *                       gen_p_delta read the generator set-points of the lane's injection row as the last launch left them (the reference's
+ *                       values while no curtailment limit is acting on the lane).
+ *   gpf_obs_vector    : rows of lanes [lane0, lane0 + n) -> out_dev (device memory, row k at out_dev + k * row_stride floats, row_stride >= dim;
+ *                       only the first dim floats of a row are written) or, out_dev = NULL, rows lane0.. of the engine-owned [lane capacity][dim]
+ *                       buffer (gpf_device_pointers_n entry 32).  Asynchronous on the engine's stream.
+ *   gpf_obs_vector_trajectory : [n_steps][n][dim] (dense) of steps [step0, step0 + n_steps) of the last multi-step launch from the per-step
+ *                       copies of GPF_TRAJ_OBS (GPF_E_INVALID without them); out_dev must not be NULL.  Calendar and maintenance attributes advance
+ *                       with the steps; a step whose status is not converged counts as game over.  Attributes without a per-step copy
+ *                       (GPF_OBS_OVERFLOW, GPF_OBS_COOLDOWN_SUB, the dispatch / charge / curtailment state, GPF_OBS_CURRENT_STEP, the two set-point
+ *                       attributes) are refused by name.
+ *                       GPF_OBS_COOLDOWN_LINE reads the int16 per-step copy of a launch that maintained the line cooldowns
+ *                       (gpf_step_opts::track_cooldown) and the lanes' own counters, which then stand for all its steps, of one that did not; a
+ *                       failed step has no copy, so with game_over_fill off the attribute is refused in this mode after a tracking launch.
+ *   gpf_get_obs_vector: gpf_obs_vector into the engine-owned buffer, then the rows on the host ([n][dim]); synchronous. */
+#define GPF_OBS_CONST 0
+#define GPF_OBS_OUT 1
+#define GPF_OBS_RHO 2
+#define GPF_OBS_LINE_STATUS 3
+#define GPF_OBS_TOPO_VECT 4
+#define GPF_OBS_SHUNT_BUS 5
+#define GPF_OBS_OVERFLOW 6
+#define GPF_OBS_COOLDOWN_LINE 7
+#define GPF_OBS_COOLDOWN_SUB 8
+#define GPF_OBS_TARGET_DISPATCH 9
+#define GPF_OBS_ACTUAL_DISPATCH 10
+#define GPF_OBS_STORAGE_CHARGE 11
+#define GPF_OBS_CURTAILMENT_LIMIT 12
+#define GPF_OBS_MARGIN_UP 13
+#define GPF_OBS_MARGIN_DOWN 14
+#define GPF_OBS_CALENDAR 15
+#define GPF_OBS_CURRENT_STEP 16
+#define GPF_OBS_MAX_STEP 17
+#define GPF_OBS_DELTA_TIME 18
+#define GPF_OBS_TIME_NEXT_MAINTENANCE 19
+#define GPF_OBS_DURATION_NEXT_MAINTENANCE 20
+#define GPF_OBS_THERMAL_LIMIT 21
+#define GPF_OBS_GEN_P_BEFORE_CURTAIL 22   /* renewables: the generator set-point the last launch left in the injection row, others 0 */
+#define GPF_OBS_GEN_P_DELTA 23            /* gen_p of the power flow minus that set-point (what the slack absorbed), float32 */
+#define GPF_OBS_N_KINDS 24
+#define GPF_OBS_MAX_SEGMENTS 64
+int gpf_set_obs_clock(gpf_handle h, int32_t n_tables, const int64_t* start_minutes, int32_t step_minutes, int32_t max_step);
+int gpf_set_obs_spec(gpf_handle h, int32_t n_seg, const int32_t* segments, int32_t dim, const float* subtract, const float* divide,
+                     int32_t game_over_fill);
+int gpf_obs_vector(gpf_handle h, int32_t lane0, int32_t n, float* out_dev, int64_t row_stride);
+int gpf_obs_vector_trajectory(gpf_handle h, int32_t step0, int32_t n_steps, int32_t lane0, int32_t n, float* out_dev);
+int gpf_get_obs_vector(gpf_handle h, int32_t lane0, int32_t n, float* host_out);
+
 /* Trajectory buffers of multi-step launches (n_steps_cap = 0 or what = 0 releases them).
  *   GPF_TRAJ_RHO: rho [cap][n_lanes][n_line] and status [cap][n_lanes] of every step of the last gpf_step_n.
  *   GPF_TRAJ_OBS: in addition the complete backend observation of every step -- results row out [cap][n_lanes][n_out]
@@ -535,9 +607,10 @@ int gpf_get_plan(gpf_handle h, int32_t out[8]);
  * [lanes][n_gen], storage power [lanes][n_storage], curtailment [lanes][n_gen] (gpf_lane_actions_on_device), then target dispatch,
  * actual dispatch [lanes][n_gen] and state of charge [lanes][n_storage] (obs.target_dispatch / actual_dispatch / storage_charge);
  * 28..31 = the acting path of the topology actions (NULL until it is enabled): act_topo int32 [lanes], sub_cooldown int32 [lanes][n_sub],
- * topo_flags uint8 [lanes][2], last_bus int32 [lanes][dim_topo] (gpf_upload_topo_actions);
+ * topo_flags uint8 [lanes][2], last_bus int32 [lanes][dim_topo] (gpf_upload_topo_actions); 32 = the engine-owned observation vectors
+ * float32 [lanes][dim] (NULL until gpf_set_obs_spec; gpf_obs_vector with out_dev = NULL writes them);
  * stream = hipStream_t */
-#define GPF_N_DEVICE_POINTERS 32
+#define GPF_N_DEVICE_POINTERS 33
 int gpf_device_pointers(gpf_handle h, void** ptrs /* [GPF_N_DEVICE_POINTERS] */, void** stream);
 /* The same with the length of the caller's array: entries beyond n_ptrs are not written, entries beyond the library's count are
  * NULL -- a caller built against an older / newer header cannot be overrun. */
