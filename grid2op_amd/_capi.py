@@ -16,7 +16,7 @@ __all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
-ABI_VERSION = 325          # include/gridpf.h GPF_ABI_VERSION
+ABI_VERSION = 326          # include/gridpf.h GPF_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "gpf_last_error", "gpf_version", "gpf_set_deterministic", "gpf_device_count", "gpf_create", "gpf_destroy", "gpf_get_layout", "gpf_n_lanes",
@@ -29,10 +29,10 @@ EXPORTED_SYMBOLS = [
     "gpf_get_counters", "gpf_upload_outage_durations", "gpf_get_cooldown", "gpf_set_cooldown", "gpf_get_trajectory_cooldown", "gpf_ptdf_build", "gpf_ptdf_build_batch", "gpf_ptdf_batch_info", "gpf_ptdf_batch_get", "gpf_ptdf_get", "gpf_ptdf_flows", "gpf_get_ptdf_flows", "gpf_ptdf_flows_rows", "gpf_get_ptdf_flows_rows", "gpf_lodf_screen",
     "gpf_jit_enable", "gpf_jit_disable", "gpf_jit_info", "gpf_jit_source",
     "gpf_set_topo_rules", "gpf_upload_topo_actions", "gpf_set_lane_topo_actions", "gpf_topo_actions_on_device", "gpf_get_sub_cooldown",
-    "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags",
+    "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags", "gpf_topo_action_mask", "gpf_get_topo_action_mask",
     "gpf_set_obs_clock", "gpf_set_obs_spec", "gpf_obs_vector", "gpf_obs_vector_trajectory", "gpf_get_obs_vector",
 ]
-N_DEVICE_POINTERS = 33     # include/gridpf.h GPF_N_DEVICE_POINTERS
+N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
 
 class GridPFError(RuntimeError):
@@ -183,6 +183,8 @@ def lib() -> C.CDLL:
     L.gpf_get_last_bus.argtypes = [h, i32, i32, _ip]
     L.gpf_set_last_bus.argtypes = [h, i32, i32, _ip]
     L.gpf_get_topo_flags.argtypes = [h, i32, i32, _bp]
+    L.gpf_topo_action_mask.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]
+    L.gpf_get_topo_action_mask.argtypes = [h, i32, i32, _bp]
     L.gpf_set_obs_clock.argtypes = [h, i32, C.POINTER(C.c_int64), i32, i32]
     L.gpf_set_obs_spec.argtypes = [h, i32, _ip, i32, _fp, _fp, i32]
     L.gpf_obs_vector.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]

@@ -18,6 +18,7 @@
 #include "gridpf_engine.hpp"
 #include "gridpf_redispatch.hpp"
 #include "gridpf_topo.hpp"
+#include "gridpf_topo_mask.hpp"
 
 namespace gpf {
 // device-side lane utilities ------------------------------------------------------------------------------------------
@@ -1765,6 +1766,7 @@ int topo_enable(gpf_engine* e) {
   for (int i = 0; i < g.n_load; ++i) pos_sub[e->h_load_pos[i]] = e->h_load_sub[i];
   for (int i = 0; i < g.n_sto; ++i) pos_sub[e->h_sto_pos[i]] = e->h_sto_sub[i];
   HIP_TRY(e->ta_pos_sub.upload(pos_sub.data(), pos_sub.size()));
+  e->h_ta_pos_sub = pos_sub;
   HIP_TRY(e->ta_pos_other.upload(pos_other.data(), pos_other.size()));
   HIP_TRY(e->ta_act.alloc(cap)); HIP_TRY(e->ta_sub_cd.alloc(cap * g.n_sub)); HIP_TRY(e->ta_last_bus.alloc(cap * g.dim_topo));
   HIP_TRY(e->ta_ep_snap.alloc(cap)); HIP_TRY(e->ta_list.alloc(cap + 1)); HIP_TRY(e->ta_list_rows.alloc(cap * ((size_t)g.dim_topo + g.n_shunt)));
@@ -1807,38 +1809,27 @@ int gpf_upload_topo_actions(gpf_handle e, int32_t n_act, const int32_t* act_off,
       return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action item (kind, id or bus; change_bus needs exactly 2 busbars per substation)");
     bus_items |= kind == GPF_ACT_CHANGE_BUS || kind == GPF_ACT_SET_SHUNT_BUS || (kind == GPF_ACT_SET_BUS && v != 0);
   }
-  // static ambiguity of every entry (BaseAction._check_for_ambiguity, Action/baseAction.py:3668-3760 -- the topology kinds)
-  std::vector<unsigned char> amb((size_t)n_act, 0);
-  std::vector<int> setv(g.dim_topo), chg(g.dim_topo), setl(g.n_line), swl(g.n_line);
-  for (int k = 0; k < n_act; ++k) {
-    std::fill(setv.begin(), setv.end(), 0); std::fill(chg.begin(), chg.end(), 0); std::fill(setl.begin(), setl.end(), 0); std::fill(swl.begin(), swl.end(), 0);
-    for (int q = act_off[k]; q < act_off[k + 1]; ++q) {
-      const int kind = act_items[3 * q], id = act_items[3 * q + 1], v = act_items[3 * q + 2];
-      if (kind == GPF_ACT_SET_BUS) setv[id] = v;
-      else if (kind == GPF_ACT_CHANGE_BUS) chg[id] = 1;
-      else if (kind == GPF_ACT_SET_LINE_STATUS) setl[id] = v;
-      else if (kind == GPF_ACT_CHANGE_LINE_STATUS) swl[id] = 1;
-    }
-    bool a = false;
-    for (int p = 0; p < g.dim_topo && !a; ++p) a = chg[p] && setv[p] != 0;              // set_bus and change_bus of one element
-    for (int l = 0; l < g.n_line && !a; ++l) {
-      const int po = e->h_line_or_pos[l], pe = e->h_line_ex_pos[l];
-      a = (swl[l] && setl[l] != 0)                                                       // set and change of one line status
-          || (setv[po] == -1 && setv[pe] > 0) || (setv[pe] == -1 && setv[po] > 0)         // one end set to -1, the other to a bus
-          || (setl[l] == -1 && (setv[po] > 0 || setv[pe] > 0 || chg[po] || chg[pe]))       // disconnected and (re)assigned / changed
-          || (setl[l] == 1 && (setv[po] == -1 || setv[pe] == -1 || chg[po] || chg[pe]));   // reconnected and disconnected / changed
-    }
-    amb[k] = a ? 1 : 0;
-  }
   int rc = topo_enable(e);
   if (rc != GPF_OK) return rc;
+  // static ambiguity of every entry and the static summary the legality masks are evaluated from (gridpf_topo_mask.hpp)
+  std::vector<unsigned char> amb((size_t)n_act, 0);
+  const gpf::TopoMaskGrid mg{g.dim_topo, g.n_line, g.n_sub, e->h_line_or_pos.data(), e->h_line_ex_pos.data(), e->h_ta_pos_sub.data()};
+  gpf::topo_static_ambiguity(mg, n_act, act_off, act_items, amb.data());
+  gpf::TopoMaskSummary ms;
+  if (!gpf::build_topo_mask_summary(mg, n_act, act_off, act_items, amb.data(), ms))
+    return fail(GPF_E_CAPACITY, "gpf_upload_topo_actions: more than 2^20 - 1 lines or substations (the summary words of the legality masks)");
   HIP_TRY(hipStreamSynchronize(e->stream));                 // (a launch in flight may read the old table)
   e->ta_off.release(); e->ta_items.release(); e->ta_amb.release();
+  e->ta_m_off.release(); e->ta_m_line.release(); e->ta_m_sub.release(); e->ta_m_end.release(); e->ta_mask.release();
   e->ta_n_act = 0;
   if (n_act) {
     HIP_TRY(e->ta_off.upload(act_off, (size_t)n_act + 1));
     if (n_items_total) HIP_TRY(e->ta_items.upload(act_items, 3 * (size_t)n_items_total));
     HIP_TRY(e->ta_amb.upload(amb.data(), amb.size()));
+    HIP_TRY(e->ta_m_off.upload(ms.off.data(), ms.off.size())); HIP_TRY(e->ta_m_line.upload(ms.line.data(), ms.line.size()));
+    HIP_TRY(e->ta_m_sub.upload(ms.sub.data(), ms.sub.size())); HIP_TRY(e->ta_m_end.upload(ms.end.data(), ms.end.size()));
+    HIP_TRY(e->ta_mask.alloc((size_t)e->cap_lanes * n_act));
+    HIP_TRY(hipMemset(e->ta_mask.p, 0, (size_t)e->cap_lanes * n_act));
     e->ta_n_act = n_act;
   }
   e->ta_bus_items = bus_items;
@@ -1909,6 +1900,38 @@ int gpf_set_last_bus(gpf_handle e, int32_t lane0, int32_t n, const int32_t* last
 int gpf_get_topo_flags(gpf_handle e, int32_t lane0, int32_t n, uint8_t* flags) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_topo_flags: null");
   return topo_rows<unsigned char>(e, e->ta_flags, 2, lane0, n, flags, nullptr, "gpf_get_topo_flags");
+}
+
+int gpf_topo_action_mask(gpf_handle e, int32_t lane0, int32_t n, uint8_t* out_dev, int64_t row_stride) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_topo_action_mask: null");
+  if (e->dry) return fail(GPF_E_INVALID, "gpf_topo_action_mask: header-only handle");
+  if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_topo_action_mask: bad lane range");
+  if (!e->ta_on || e->ta_n_act == 0) return fail(GPF_E_INVALID, "gpf_topo_action_mask: no action table (gpf_upload_topo_actions)");
+  if (out_dev && row_stride < e->ta_n_act) return fail(GPF_E_INVALID, "gpf_topo_action_mask: row_stride is smaller than the table's number of entries");
+  if (n == 0) return GPF_OK;
+  const gpf::GridDev& g = e->g;
+  const size_t lds = (2 * (size_t)gpf::tm_words(g.n_line) + gpf::tm_words(g.n_sub)) * sizeof(unsigned long long);
+  if (lds > 64 * 1024) return fail(GPF_E_CAPACITY, "gpf_topo_action_mask: the grid's line and substation bit sets do not fit 64 KiB of LDS");
+  HIP_TRY(hipSetDevice(e->device));
+  const gpf::TopoMaskTab tab{e->ta_m_off.p, e->ta_m_line.p, e->ta_m_sub.p, e->ta_m_end.p, e->ta_amb.p, e->ta_n_act};
+  const gpf::TopoMaskLanes s{e->topo.p, e->cooldown.p, e->ta_sub_cd.p, e->line_or_pos.p, e->line_ex_pos.p, g.dim_topo, g.n_line, g.n_sub};
+  const gpf::TopoRules& r = *e->ta_rules;
+  unsigned char* dst = out_dev ? out_dev : e->ta_mask.p + (size_t)lane0 * e->ta_n_act;
+  const unsigned chunks = (unsigned)std::min((e->ta_n_act + gpf::TM_CHUNK - 1) / gpf::TM_CHUNK, 65535);
+  hipLaunchKernelGGL(gpf::topo_mask_kernel, dim3((unsigned)n, chunks), dim3(64), lds, e->stream, tab, s, r.on, r.max_line, r.max_sub, lane0, n, dst,
+                     out_dev ? (long long)row_stride : (long long)e->ta_n_act);
+  HIP_TRY(hipGetLastError());
+  return GPF_OK;
+}
+
+int gpf_get_topo_action_mask(gpf_handle e, int32_t lane0, int32_t n, uint8_t* host_out) {
+  int rc = gpf_topo_action_mask(e, lane0, n, nullptr, 0);      // (its refusals first: they say what is missing)
+  if (rc != GPF_OK) return rc;
+  if (n > 0 && !host_out) return fail(GPF_E_INVALID, "gpf_get_topo_action_mask: null output");
+  if (n > 0)
+    HIP_TRY(hipMemcpyAsync(host_out, e->ta_mask.p + (size_t)lane0 * e->ta_n_act, (size_t)n * e->ta_n_act, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return GPF_OK;
 }
 
 int gpf_set_storage_params(gpf_handle e, const double* emax, const double* emin, const double* loss, const double* eff_charge,
@@ -2533,6 +2556,7 @@ int gpf_device_pointers_n(gpf_handle e, void** out, int32_t n_ptrs, void** strea
   if (!e || !out || n_ptrs < 0) return fail(GPF_E_INVALID, "gpf_device_pointers: null");
   void* ptrs[GPF_N_DEVICE_POINTERS];
   ptrs[32] = e->obs_spec_on ? e->obs_vec.p : nullptr;
+  ptrs[33] = e->ta_on && e->ta_n_act ? e->ta_mask.p : nullptr;
   ptrs[0] = e->inj.p; ptrs[1] = e->topo.p; ptrs[2] = e->shunt_bus.p; ptrs[3] = e->out.p; ptrs[4] = e->topo_out.p;
   ptrs[5] = e->line_status.p; ptrs[6] = e->status.p; ptrs[7] = e->chron.p;
   ptrs[8] = e->rho.p; ptrs[9] = e->overflow_count.p; ptrs[10] = e->done.p; ptrs[11] = e->episode.p; ptrs[12] = e->bus_vm.p;

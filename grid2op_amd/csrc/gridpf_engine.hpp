@@ -158,7 +158,11 @@ struct gpf_engine {
   DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_list, ta_list_rows, ta_off, ta_items, ta_pos_sub, ta_pos_other;
   DevArr<unsigned char> ta_flags, ta_aff, ta_amb;
   int ta_n_act = 0;
-  bool ta_bus_items = false;            // an entry of the table sets / changes a bus: the read-back of class changes is needed
+  // legality masks of the table (gridpf_topo_mask.hpp): its static summary, uploaded with it, and the engine-owned masks [cap_lanes][ta_n_act]
+  DevArr<int> ta_m_off, ta_m_line, ta_m_sub, ta_m_end;
+  DevArr<unsigned char> ta_mask;
+  std::vector<int> h_ta_pos_sub;        // substation of every topo_vect position (host copy of ta_pos_sub)
+  bool ta_bus_items = false;           // an entry of the table sets / changes a bus: the read-back of class changes is needed
   bool ta_may_split = false;            // some row or last-bus entry was on a busbar >= 2 (then line-status actions can change a class key too)
   bool ta_host = false, ta_dev = false; // the next launch carries indices set by the host / written on the device
   std::vector<char> ta_moved;           // per lane: an action moved it to another topology class than its reset topology's (auto-reset re-keys it)

@@ -20,7 +20,8 @@ from . import _capi
 from ._capi import GpfGridDesc, GpfLayout, GpfStepOpts, GridPFError, check, ptr
 from .grid_model import GridModel
 
-__all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT"]
+__all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT", "MASK_TOO_MANY_LINES", "MASK_TOO_MANY_SUBS",
+           "MASK_LINE_COOLDOWN", "MASK_SUB_COOLDOWN", "MASK_AMBIGUOUS"]
 
 ST_CONVERGED = 0
 STATUS_TEXT = {
@@ -33,6 +34,8 @@ STATUS_TEXT = {
     6: "infeasible redispatching (ImpossibleRedispatching: game over)",
     -1: "power flow not run",
 }
+# reason bits of `PowerFlowEngine.topo_action_mask` (include/gridpf.h GPF_MASK_*); 0: the entry would be applied
+MASK_TOO_MANY_LINES, MASK_TOO_MANY_SUBS, MASK_LINE_COOLDOWN, MASK_SUB_COOLDOWN, MASK_AMBIGUOUS = 0x01, 0x02, 0x04, 0x08, 0x10
 
 _OUT_FIELDS = [
     ("p_or", "n_line"), ("q_or", "n_line"), ("v_or", "n_line"), ("a_or", "n_line"), ("theta_or", "n_line"),
@@ -567,6 +570,8 @@ class PowerFlowEngine:
         items = np.ascontiguousarray(items, dtype=np.int32)
         check(self._lib.gpf_upload_topo_actions(self._h, n, ptr(off, C.c_int32), ptr(items if items.size else None, C.c_int32),
                                                 ptr(amb, C.c_uint8)), "gpf_upload_topo_actions")
+        self._n_topo_act = n
+        self._mask_view = None               # (the engine-owned mask buffer is re-allocated with the table)
         return amb[:n].astype(bool)
 
     def set_lane_topo_actions(self, index):
@@ -605,6 +610,37 @@ class PowerFlowEngine:
         """(is_illegal, is_ambiguous) bool ``[n]`` of the last launch that carried topology actions."""
         f = self._topo_rows("gpf_get_topo_flags", 2, np.uint8, C.c_uint8, lane0, n)
         return f[:, 0].astype(bool), f[:, 1].astype(bool)
+
+    def topo_action_mask(self, lane0: int = 0, n: Optional[int] = None, out=None):
+        """Which entries of the uploaded action table lanes ``[lane0, lane0 + n)`` may play right now: a uint8 torch tensor
+        ``[n, n_act]`` in device memory, 0 where a launch that carried the entry would apply it, else the OR of the reasons
+        (`MASK_TOO_MANY_LINES` ... `MASK_AMBIGUOUS`).  One kernel queued on the engine's stream (asynchronous: order the consumer on
+        ``device_views()["stream"]``, or `sync`); it only reads the lanes' state.  Without ``out`` the tensor ALIASES the engine-owned buffer
+        ``device_views()["topo_mask"]`` (rewritten by the next call); ``out`` may be a caller's uint8 CUDA tensor ``[n, >= n_act]`` with unit
+        column stride and any row stride >= n_act -- only the first ``n_act`` columns of its rows are written."""
+        lane0, n = self._range(lane0, n)
+        n_act = int(getattr(self, "_n_topo_act", 0))
+        if out is None:
+            check(self._lib.gpf_topo_action_mask(self._h, lane0, n, None, 0), "gpf_topo_action_mask")
+            if getattr(self, "_mask_view", None) is None:
+                self._mask_view = self.device_views()["topo_mask"]
+            return self._mask_view[lane0:lane0 + n]
+        import torch
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2):
+            raise ValueError("topo_action_mask: out must be a 2-d uint8 CUDA tensor")
+        if out.device.index != self.device or out.shape[0] != n or out.stride(1) != 1:
+            raise ValueError(f"topo_action_mask: out must live on cuda:{self.device} and have {n} rows with unit column stride")
+        # rows narrower than the table: the library refuses their width as the stride, with its message
+        stride = int(out.stride(0)) if n > 1 and out.shape[1] >= n_act else int(out.shape[1])
+        check(self._lib.gpf_topo_action_mask(self._h, lane0, n, C.c_void_p(out.data_ptr()), stride), "gpf_topo_action_mask")
+        return out[:, :n_act]
+
+    def topo_action_mask_host(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """`topo_action_mask` copied to the host: uint8 ``[n, n_act]`` (synchronous)."""
+        lane0, n = self._range(lane0, n)
+        out = np.empty((n, int(getattr(self, "_n_topo_act", 0))), dtype=np.uint8)
+        check(self._lib.gpf_get_topo_action_mask(self._h, lane0, n, ptr(out if out.size else None, C.c_uint8)), "gpf_get_topo_action_mask")
+        return out
 
     def set_gen_renewable(self, renewable):
         """``gen_renewable`` mask (curtailment only acts on these generators); None switches curtailment off."""
@@ -710,7 +746,8 @@ class PowerFlowEngine:
         ``target_dispatch`` / ``actual_dispatch`` / ``storage_charge`` float32 (obs.target_dispatch, ...); once topology actions are enabled
         (`set_topo_rules` / `upload_topo_actions`) also ``act_topo`` int32 ``[n_lanes, 1]`` (`topo_actions_on_device`), ``sub_cooldown``
         ``[n_lanes, n_sub]``, ``topo_flags`` uint8 ``[n_lanes, 2]`` and ``last_bus`` ``[n_lanes, dim_topo]``; once an observation spec is set
-        (`set_obs_spec`) also ``obs`` float32 ``[n_lanes, dim]`` (what `observation_vector` without ``out`` writes).  The engine works on its own HIP stream: call `sync` (or make the consumer's
+        (`set_obs_spec`) also ``obs`` float32 ``[n_lanes, dim]`` (what `observation_vector` without ``out`` writes); once an action table is
+        uploaded also ``topo_mask`` uint8 ``[n_lanes, n_act]`` (what `topo_action_mask` without ``out`` writes).  The engine works on its own HIP stream: call `sync` (or make the consumer's
         stream wait on ``views["stream"]``, a ``torch.cuda.ExternalStream``) before reading."""
         import torch
         ptrs = (C.c_void_p * _capi.N_DEVICE_POINTERS)()
@@ -740,7 +777,8 @@ class PowerFlowEngine:
              "storage_charge": view(27, m.n_storage, "<f4"),
              "act_topo": view(28, 1, "<i4"), "sub_cooldown": view(29, m.n_sub, "<i4"), "topo_flags": view(30, 2, "|u1"),
              "last_bus": view(31, m.dim_topo, "<i4"),
-             "obs": view(32, self._obs_spec.dim if getattr(self, "_obs_spec", None) is not None else 0, "<f4")}
+             "obs": view(32, self._obs_spec.dim if getattr(self, "_obs_spec", None) is not None else 0, "<f4"),
+             "topo_mask": view(33, int(getattr(self, "_n_topo_act", 0)), "|u1")}
 
         def tview(idx, cols, typestr):       # trajectory buffers: [cap_steps][cap][cols]
             if cols == 0 or not ptrs[idx] or not getattr(self, "_traj_cap", 0):

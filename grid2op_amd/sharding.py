@@ -410,6 +410,17 @@ class ShardedEngine:
         parts = [eng.topo_action_flags(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(2))
 
+    def topo_action_mask(self, lane0: int = 0, n=None, out=None):
+        """One tensor per shard that intersects the range (each on its own device and stream); ``out``: a list with one tensor per such shard."""
+        parts = self._parts(lane0, n)
+        outs = [None] * len(parts) if out is None else list(out)
+        if len(outs) != len(parts):
+            raise ValueError(f"ShardedEngine.topo_action_mask: {len(parts)} shards intersect the range, {len(outs)} output tensors given")
+        return [eng.topo_action_mask(l0, k, out=o) for (eng, l0, k, _), o in zip(parts, outs)]
+
+    def topo_action_mask_host(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.topo_action_mask_host(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

@@ -107,7 +107,7 @@ const char* gpf_last_error(void);
  * dispatch / charge state of the environment dynamics), gpf_lane_actions_on_device; 322 = + gpf_get_results_pinned; 323 = gpf_step_opts::track_cooldown,
  * GPF_DEVICE_NONE (header-only handles); 324 = 32 device pointers, topology actions in the batched step (gpf_upload_topo_actions ...);
  * 325 = 33 device pointers, observation vectors assembled on the device (gpf_set_obs_spec ...). */
-#define GPF_ABI_VERSION 325
+#define GPF_ABI_VERSION 326
 int gpf_version(void);
 /* Bitwise run-to-run reproducibility is the DEFAULT on every grid: the same lane inputs give bit-identical results from run to
  * run and whatever the lane's position in the batch (grid2op's determinism contract: same seeds -> same episode,
@@ -427,6 +427,34 @@ int gpf_get_last_bus(gpf_handle h, int32_t lane0, int32_t n, int32_t* last_bus);
 int gpf_set_last_bus(gpf_handle h, int32_t lane0, int32_t n, const int32_t* last_bus);
 int gpf_get_topo_flags(gpf_handle h, int32_t lane0, int32_t n, uint8_t* flags);
 
+/* ---- legality masks of the action table (what a policy with a discrete head over the table needs before every step) -- for lane k
+ * and table entry a one byte, 0 exactly when a launch that carried act_topo[k] = a right now would apply the entry (is_illegal =
+ * is_ambiguous = 0 in gpf_get_topo_flags), else the OR of ALL the reasons that hold (the reference reports the first):
+ *   GPF_MASK_TOO_MANY_LINES  aff_lines.sum() > max_line_status_changed            (Rules/LookParam.py:28-53)
+ *   GPF_MASK_TOO_MANY_SUBS   aff_subs.sum() > max_sub_changed                     (Rules/LookParam.py:28-53)
+ *   GPF_MASK_LINE_COOLDOWN   an affected line has a line cooldown > 0             (Rules/PreventReconnection.py:23-60)
+ *   GPF_MASK_SUB_COOLDOWN    an affected substation has a substation cooldown > 0 (Rules/PreventReconnection.py:23-60)
+ *   GPF_MASK_AMBIGUOUS       the entry's static ambiguity flag; such an entry carries this bit alone (no impact is computed for it)
+ * aff_lines / aff_subs are BaseAction.get_topological_impact (Action/baseAction.py:1782-2020) with the lane's line status (both ends of
+ * its current topology row > 0) -- the arithmetic of the pre-step of gpf_step_n, evaluated for every entry by ONE side kernel
+ * (grid2op_amd/csrc/gridpf_topo_mask.hpp) from a static per-entry summary built by gpf_upload_topo_actions.  With gpf_set_topo_rules(on = 0)
+ * only GPF_MASK_AMBIGUOUS occurs.  The inputs are the lanes' topology rows, line cooldowns and substation cooldowns as they stand when the
+ * call is ordered on the engine's stream; the call only reads: no lane state, pending index, flag or affected row changes; a lane whose
+ * episode is done is evaluated from its rows like any other.
+ *   gpf_topo_action_mask     : rows of lanes [lane0, lane0 + n) -> out_dev (device memory, row k at out_dev + k * row_stride bytes,
+ *                              row_stride >= n_act; only the first n_act bytes of a row are written) or, out_dev = NULL, rows lane0.. of the
+ *                              engine-owned [lane capacity][n_act] buffer (gpf_device_pointers_n entry 33, re-allocated with the table).
+ *                              Asynchronous on the engine's stream.
+ *   gpf_get_topo_action_mask : the same into the engine-owned buffer, then the rows on the host ([n][n_act], dense); synchronous.
+ * GPF_E_INVALID: no table (or an empty one), a lane range outside the engine, row_stride < n_act, a header-only handle. */
+#define GPF_MASK_TOO_MANY_LINES 0x01
+#define GPF_MASK_TOO_MANY_SUBS 0x02
+#define GPF_MASK_LINE_COOLDOWN 0x04
+#define GPF_MASK_SUB_COOLDOWN 0x08
+#define GPF_MASK_AMBIGUOUS 0x10
+int gpf_topo_action_mask(gpf_handle h, int32_t lane0, int32_t n, uint8_t* out_dev, int64_t row_stride);
+int gpf_get_topo_action_mask(gpf_handle h, int32_t lane0, int32_t n, uint8_t* host_out);
+
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
  * Observation/baseObservation.py:4464-4540; with subtract / divide what gym_compat.BoxGymObsSpace(attr_to_keep, subtract, divide) puts on
@@ -608,9 +636,10 @@ int gpf_get_plan(gpf_handle h, int32_t out[8]);
  * actual dispatch [lanes][n_gen] and state of charge [lanes][n_storage] (obs.target_dispatch / actual_dispatch / storage_charge);
  * 28..31 = the acting path of the topology actions (NULL until it is enabled): act_topo int32 [lanes], sub_cooldown int32 [lanes][n_sub],
  * topo_flags uint8 [lanes][2], last_bus int32 [lanes][dim_topo] (gpf_upload_topo_actions); 32 = the engine-owned observation vectors
- * float32 [lanes][dim] (NULL until gpf_set_obs_spec; gpf_obs_vector with out_dev = NULL writes them);
+ * float32 [lanes][dim] (NULL until gpf_set_obs_spec; gpf_obs_vector with out_dev = NULL writes them); 33 = the engine-owned legality
+ * masks uint8 [lanes][n_act] (NULL without an action table; gpf_topo_action_mask with out_dev = NULL writes them);
  * stream = hipStream_t */
-#define GPF_N_DEVICE_POINTERS 33
+#define GPF_N_DEVICE_POINTERS 34
 int gpf_device_pointers(gpf_handle h, void** ptrs /* [GPF_N_DEVICE_POINTERS] */, void** stream);
 /* The same with the length of the caller's array: entries beyond n_ptrs are not written, entries beyond the library's count are
  * NULL -- a caller built against an older / newer header cannot be overrun. */
