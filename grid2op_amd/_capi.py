@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "gpf_jit_enable", "gpf_jit_disable", "gpf_jit_info", "gpf_jit_source",
     "gpf_set_topo_rules", "gpf_upload_topo_actions", "gpf_set_lane_topo_actions", "gpf_topo_actions_on_device", "gpf_get_sub_cooldown",
     "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags", "gpf_topo_action_mask", "gpf_get_topo_action_mask",
+    "gpf_set_topo_areas", "gpf_set_topo_slots", "gpf_get_topo_action_areas",
     "gpf_set_obs_clock", "gpf_set_obs_spec", "gpf_obs_vector", "gpf_obs_vector_trajectory", "gpf_get_obs_vector",
 ]
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
@@ -185,6 +186,9 @@ def lib() -> C.CDLL:
     L.gpf_get_topo_flags.argtypes = [h, i32, i32, _bp]
     L.gpf_topo_action_mask.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]
     L.gpf_get_topo_action_mask.argtypes = [h, i32, i32, _bp]
+    L.gpf_set_topo_areas.argtypes = [h, i32, _ip]
+    L.gpf_set_topo_slots.argtypes = [h, i32]
+    L.gpf_get_topo_action_areas.argtypes = [h, C.POINTER(C.c_uint32)]
     L.gpf_set_obs_clock.argtypes = [h, i32, C.POINTER(C.c_int64), i32, i32]
     L.gpf_set_obs_spec.argtypes = [h, i32, _ip, i32, _fp, _fp, i32]
     L.gpf_obs_vector.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]

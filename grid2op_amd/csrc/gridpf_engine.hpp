@@ -162,6 +162,14 @@ struct gpf_engine {
   DevArr<int> ta_m_off, ta_m_line, ta_m_sub, ta_m_end;
   DevArr<unsigned char> ta_mask;
   std::vector<int> h_ta_pos_sub;        // substation of every topo_vect position (host copy of ta_pos_sub)
+  // composite actions and rules by area (gpf_set_topo_slots / gpf_set_topo_areas): areas belong to the rules, not to lanes
+  int ta_n_slot = 1;                    // table entries per lane and step: ta_act is [cap_lanes][ta_n_slot]
+  int ta_max_items = 0;                 // ta_n_slot x the items of the table's longest entry (the gathered item list of the pre-step)
+  int ta_n_area = 0;                    // 0: whole-grid limits
+  std::vector<int> h_ta_sub_area;       // [n_sub] area of every substation (empty without areas)
+  DevArr<int> ta_sub_area;
+  std::vector<int> h_ta_off, h_ta_items;        // host copy of the table (a header-only handle has nothing else; areas set later re-derive the summary)
+  std::vector<unsigned char> h_ta_amb;
   bool ta_bus_items = false;           // an entry of the table sets / changes a bus: the read-back of class changes is needed
   bool ta_may_split = false;            // some row or last-bus entry was on a busbar >= 2 (then line-status actions can change a class key too)
   bool ta_host = false, ta_dev = false; // the next launch carries indices set by the host / written on the device

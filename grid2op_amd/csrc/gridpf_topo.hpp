@@ -10,8 +10,15 @@
 //   4. application (_BackendAction.__iadd__, Action/_backendAction.py:836-919): apply_topo_action below -- the ONE implementation,
 //      called by gpf_simulate_batch on the host and by topo_prestep_kernel on the device;
 //   5. bookkeeping after the step (Environment/baseEnv.py:3346-3395, _BackendAction.update_state :1533-1555): topo_poststep_kernel.
+//
+// Composite actions (gpf_set_topo_slots) and rules by area (gpf_set_topo_areas; Rules/rulesByArea.py:120-140): a lane plays the
+// concatenation, in slot order, of the item lists of its non-empty slots as ONE action -- dense arrays, run-time ambiguity
+// (topo_dense_ambiguity, gridpf_topo_mask.hpp), impact, legality with the limits held per area, ONE call of apply_topo_action.  That is the
+// GEN instantiation of topo_prestep_kernel; with one slot and no areas the engine launches the other one, which is the kernel as it was.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "gridpf_topo_mask.hpp"
 
 namespace gpf {
 
@@ -71,7 +78,7 @@ __host__ __device__ inline void apply_topo_action(const TopoMaps& m, int* row, i
 struct TopoTab { const int* off; const int* items; const unsigned char* amb; int n_act; };
 // per-lane state of the acting path (rows padded to the engine's lane capacity)
 struct TopoLanes {
-  int* act;               // [lanes] action index of the next launch, -1 = do nothing
+  int* act;               // [lanes][n_slot] action indices of the next launch, -1 = empty slot
   int* sub_cd;            // [lanes][n_sub] times_before_topology_actionable
   int* last_bus;          // [lanes][dim_topo] last known busbar (_BackendAction.last_topo_registered)
   unsigned char* flags;   // [lanes][2] {is_illegal, is_ambiguous} of the last action launch
@@ -81,7 +88,10 @@ struct TopoLanes {
   int* list_rows;         // [lanes][dim_topo + n_shunt] their new rows (slot order of `list`)
   const int* pos_sub;     // [dim_topo] substation of every topo_vect position
   const int* pos_other;   // [dim_topo] the other end's position for a line end, else -1
+  int n_slot;             // table entries per lane and step (gpf_set_topo_slots)
 };
+// composite actions and areas: sub_area [n_sub] (NULL: the whole grid is one area), max_items: n_slot x the items of the longest table entry
+struct TopoComp { const int* sub_area; int n_area, max_items; };
 // the grid maps and lane rows the three kernels touch (a small argument block: GridDev + Bufs by value cost SGPR spills)
 struct TopoDev {
   int dim_topo, n_line, n_sub, n_shunt, n_busbar;
@@ -91,13 +101,18 @@ struct TopoDev {
 // rules (Parameters MAX_SUB_CHANGED / MAX_LINE_STATUS_CHANGED / NB_TIMESTEP_COOLDOWN_SUB / NB_TIMESTEP_COOLDOWN_LINE); on = 0: AlwaysLegal
 struct TopoRules { int on, max_sub, max_line, cd_sub, cd_line; };
 
-// LDS ints of topo_prestep_kernel
-__host__ __device__ inline size_t topo_prestep_lds_ints(int dim_topo, int n_line, int n_sub, int n_shunt, int n_busbar) {
-  return 4 * (size_t)dim_topo + 3 * (size_t)n_line + (size_t)n_sub + 2 * (size_t)n_shunt + 4 * (size_t)n_sub * n_busbar + 8;
+// LDS ints of topo_prestep_kernel.  max_items < 0: the instantiation for one slot and no areas; else the GEN one, with the gathered item
+// list [max_items][3], change_bus kept apart from eff [dim_topo], the two line-status arrays of the ambiguity rules [2][n_line] and the
+// per-area counters [2][TM_MAX_AREAS].
+__host__ __device__ inline size_t topo_prestep_lds_ints(int dim_topo, int n_line, int n_sub, int n_shunt, int n_busbar, int max_items = -1) {
+  const size_t base = 4 * (size_t)dim_topo + 3 * (size_t)n_line + (size_t)n_sub + 2 * (size_t)n_shunt + 4 * (size_t)n_sub * n_busbar + 8;
+  return max_items < 0 ? base : base + 3 * (size_t)max_items + (size_t)dim_topo + 2 * (size_t)n_line + 2 * TM_MAX_AREAS;
 }
 
 // Steps 1-4 for one lane per 64-thread block (one wavefront), its rows staged in LDS.  act_on = 0: only the auto-reset snapshot.
-__global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab, TopoLanes s, TopoRules r, int n_lanes, int act_on) {
+// GEN: composite actions of s.n_slot entries and limits per area (`c`); else one entry per lane, whole-grid limits, `c` unused.
+template <bool GEN>
+__global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab, TopoLanes s, TopoRules r, TopoComp c, int n_lanes, int act_on) {
   extern __shared__ int lds[];
   const int lane = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
   if (lane >= n_lanes) return;
@@ -106,8 +121,22 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
   if (!act_on) return;
   unsigned char* aff = s.aff + (size_t)lane * (L + S);
   for (int i = tid; i < L + S; i += nth) aff[i] = 0;
-  const int a = s.act[lane];
-  const bool amb = a < -1 || a >= tab.n_act || (a >= 0 && tab.amb[a]);
+  int a = -1, n_items = 0;
+  bool amb = false;
+  if constexpr (GEN) {                                         // an index outside the table in any slot: ambiguous; all slots empty: nothing
+    for (int k = 0; k < s.n_slot; ++k) {
+      const int ak = s.act[(size_t)lane * s.n_slot + k];
+      amb = amb || ak < -1 || ak >= tab.n_act;
+      if (ak >= 0 && ak < tab.n_act) { a = ak; n_items += tab.off[ak + 1] - tab.off[ak]; }
+    }
+    amb = amb || n_items > c.max_items;                        // (the bound of `gath`; the engine sizes it n_slot x the longest entry, so an
+                                                               //  index repeated over slots fits too and this never fires on a table it uploaded)
+    // tab.amb is not consulted, even with one slot (areas only), where it would answer: the run-time pass below is the one rule for
+    // every GEN launch, an ambiguous single entry costs one gather and one pass over the dense arrays before the lane stops
+  } else {
+    a = s.act[lane];
+    amb = a < -1 || a >= tab.n_act || (a >= 0 && tab.amb[a]);
+  }
   if (a == -1 || amb) {                                        // (uniform over the block)
     if (tid == 0) { s.flags[(size_t)lane * 2] = 0; s.flags[(size_t)lane * 2 + 1] = amb ? 1 : 0; }
     return;
@@ -126,9 +155,29 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
   int* used1 = used0 + S * NBB;
   int* act0 = used1 + S * NBB;
   int* act1 = act0 + S * NBB;
-  int* cnt = act1 + S * NBB;      // [8] aff lines, aff subs, cooldown hit, key changed, busbar count before / after, list slot
+  int* cnt = act1 + S * NBB;      // [8] aff lines, aff subs, cooldown hit, key changed, busbar count before / after, list slot, ambiguous
+  int* chg = cnt + 8;             // GEN: [D] change_bus
+  int* setl = chg + D;            //      [L] set_line_status value
+  int* swl = setl + L;            //      [L] change_line_status
+  int* acnt = swl + L;            //      [2][TM_MAX_AREAS] aff lines / aff subs per area
+  int* gath = acnt + 2 * TM_MAX_AREAS;   // [max_items][3] the concatenated item list
   const int* items = tab.items + 3 * (size_t)tab.off[a];
-  const int n_items = tab.off[a + 1] - tab.off[a];
+  if constexpr (GEN) {
+    int at = 0;
+    for (int k = 0; k < s.n_slot; ++k) {                       // (uniform) slot after slot, every thread a stride of the slot's ints
+      const int ak = s.act[(size_t)lane * s.n_slot + k];
+      if (ak < 0) continue;
+      const int o0 = tab.off[ak], n3 = 3 * (tab.off[ak + 1] - o0);
+      for (int i = tid; i < n3; i += nth) gath[at + i] = tab.items[3 * (size_t)o0 + i];
+      at += n3;
+    }
+    for (int i = tid; i < D; i += nth) chg[i] = 0;
+    for (int i = tid; i < L; i += nth) { setl[i] = 0; swl[i] = 0; }
+    if (tid < 2 * TM_MAX_AREAS) acnt[tid] = 0;
+    items = gath;
+  } else {
+    n_items = tab.off[a + 1] - tab.off[a];
+  }
   const int* trow = g.topo + (size_t)lane * D;
   for (int i = tid; i < D; i += nth) { const int v = trow[i]; row[i] = v; prev[i] = v; setv[i] = 0; eff[i] = 0; }
   for (int i = tid; i < NS; i += nth) { const int v = g.shunt_bus[(size_t)lane * NS + i]; sbr[i] = v; sbp[i] = v; }
@@ -144,8 +193,21 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
       if (kind == TA_SET_BUS) setv[id] = v;
       else if (kind == TA_CHANGE_BUS) eff[id] = 1;
       else if (kind == TA_CHANGE_LINE_STATUS || (kind == TA_SET_LINE_STATUS && v != 0)) imp[id] = 1;
+      if constexpr (GEN) {
+        if (kind == TA_CHANGE_BUS) chg[id] = 1;
+        else if (kind == TA_SET_LINE_STATUS) setl[id] = v;
+        else if (kind == TA_CHANGE_LINE_STATUS) swl[id] = 1;
+      }
     }
   __syncthreads();
+  if constexpr (GEN) {                                         // 1. ambiguity of the composite, on its dense arrays
+    if (topo_dense_ambiguity(D, L, g.line_or_pos, g.line_ex_pos, setv, chg, setl, swl, tid, nth)) cnt[7] = 1;
+    __syncthreads();
+    if (cnt[7]) {
+      if (tid == 0) { s.flags[(size_t)lane * 2] = 0; s.flags[(size_t)lane * 2 + 1] = 1; }
+      return;
+    }
+  }
   for (int i = tid; i < D; i += nth) eff[i] = (eff[i] || setv[i] != 0) ? 1 : 0;
   __syncthreads();
   for (int l = tid; l < L; l += nth) {
@@ -161,10 +223,26 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
   for (int i = tid; i < D; i += nth) if (eff[i]) subf[s.pos_sub[i]] = 1;
   __syncthreads();
   // 3. legality (LookParam + PreventReconnection)
-  for (int l = tid; l < L; l += nth) if (imp[l]) { atomicAdd(&cnt[0], 1); if (g.cooldown[(size_t)lane * L + l] > 0) cnt[2] = 1; }
-  for (int i = tid; i < S; i += nth) if (subf[i]) { atomicAdd(&cnt[1], 1); if (s.sub_cd[(size_t)lane * S + i] > 0) cnt[2] = 1; }
-  __syncthreads();
-  const bool illegal = r.on && (cnt[0] > r.max_line || cnt[1] > r.max_sub || cnt[2] != 0);
+  bool illegal;
+  if constexpr (GEN) {                                         // the limits per area; a line counts in the area of its origin substation
+    for (int l = tid; l < L; l += nth) if (imp[l]) {
+      atomicAdd(&acnt[c.sub_area ? c.sub_area[s.pos_sub[g.line_or_pos[l]]] : 0], 1);
+      if (g.cooldown[(size_t)lane * L + l] > 0) cnt[2] = 1;
+    }
+    for (int i = tid; i < S; i += nth) if (subf[i]) {
+      atomicAdd(&acnt[TM_MAX_AREAS + (c.sub_area ? c.sub_area[i] : 0)], 1);
+      if (s.sub_cd[(size_t)lane * S + i] > 0) cnt[2] = 1;
+    }
+    __syncthreads();
+    bool over = false;
+    for (int k = 0; k < TM_MAX_AREAS; ++k) over = over || acnt[k] > r.max_line || acnt[TM_MAX_AREAS + k] > r.max_sub;
+    illegal = r.on && (over || cnt[2] != 0);
+  } else {
+    for (int l = tid; l < L; l += nth) if (imp[l]) { atomicAdd(&cnt[0], 1); if (g.cooldown[(size_t)lane * L + l] > 0) cnt[2] = 1; }
+    for (int i = tid; i < S; i += nth) if (subf[i]) { atomicAdd(&cnt[1], 1); if (s.sub_cd[(size_t)lane * S + i] > 0) cnt[2] = 1; }
+    __syncthreads();
+    illegal = r.on && (cnt[0] > r.max_line || cnt[1] > r.max_sub || cnt[2] != 0);
+  }
   if (tid == 0) { s.flags[(size_t)lane * 2] = illegal ? 1 : 0; s.flags[(size_t)lane * 2 + 1] = 0; }
   if (illegal) return;
   for (int l = tid; l < L; l += nth) aff[l] = (unsigned char)imp[l];
@@ -256,7 +334,7 @@ __global__ void topo_fanout_kernel(TopoDev g, TopoLanes s, int src, int dst0, in
   for (int i = threadIdx.x; i < S; i += blockDim.x) s.sub_cd[(size_t)dst * S + i] = s.sub_cd[(size_t)src * S + i];
   for (int i = threadIdx.x; i < D; i += blockDim.x) s.last_bus[(size_t)dst * D + i] = s.last_bus[(size_t)src * D + i];
   if (threadIdx.x < 2) s.flags[(size_t)dst * 2 + threadIdx.x] = s.flags[(size_t)src * 2 + threadIdx.x];
-  if (threadIdx.x == 0) s.act[dst] = s.act[src];
+  if (threadIdx.x < s.n_slot) s.act[(size_t)dst * s.n_slot + threadIdx.x] = s.act[(size_t)src * s.n_slot + threadIdx.x];
 }
 
 }  // namespace gpf

@@ -5,8 +5,14 @@
 //   impact     BaseAction.get_topological_impact (Action/baseAction.py:1782-2020) with the lane's line status;
 //   legality   Rules/LookParam.py:28-53 + Rules/PreventReconnection.py:23-60 against the lane's line and substation cooldowns.
 // Three parts: the static per-entry summary built on the host at upload (build_topo_mask_summary), the rule core of one (lane, entry)
-// (topo_mask_eval: plain C++, the ONE statement of the mask's rules, run by the kernel and by the host emulator of
-// tests/native/topo_mask_emul.cpp), and the kernel.  Without hipcc only the first two exist: the header then needs no HIP header.
+// (topo_mask_eval, topo_mask_eval_area over topo_mask_rules: plain C++, the ONE statement of the mask's rules, run by the kernel and by
+// the host emulators of tests/native/), and the kernel.  Without hipcc only the first two exist: the header then needs no HIP header.
+//
+// Areas (gpf_set_topo_areas; Rules/rulesByArea.py:120-140, _lookparam_byarea): every substation carries one area, a line the area of its
+// ORIGIN substation (rulesByArea.py:91), and the two limits hold per area.  The summary then carries the area in bits 26-29 of every line
+// word and substation word, and topo_mask_eval_area runs the same rules (topo_mask_rules) with a counter per area: sixteen saturating
+// 8-bit counters held in two 64-bit registers.
+// The ambiguity rules are stated once (topo_dense_ambiguity) for the upload and for the composite actions of topo_prestep_kernel.
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -35,6 +41,8 @@ constexpr int TM_STATUS = 1 << 20, TM_OR_POS = 1 << 21, TM_OR_NEG = 1 << 22, TM_
 // A substation word: bits 0-19 the substation; ALWAYS: affected whatever the line status (a set_bus / change_bus on an element that is
 // not a line end).
 constexpr int TM_SUB_ALWAYS = 1 << 20;
+// Bits 26-29 of a line word / substation word: the area of the line (of its origin substation) / of the substation; 0 without areas.
+constexpr int TM_AREA_SHIFT = 26, TM_MAX_AREAS = 16, TM_AREA_MAX_LIMIT = 254;
 
 // The static summary of the table.  off [n_act + 1][3]: first line word, first substation record, first line-end candidate of every
 // entry (an ambiguous entry has none).  line: one word per line the entry can put into aff_lines (status item, or set_bus != 0 on an
@@ -55,20 +63,42 @@ GPF_TM_HD inline void tm_line_impact(int w, bool st, bool& im, bool& clr) {
   clr = clr || hit;
 }
 
-// The mask byte of entry `a` for one lane.  live / line_cd / sub_cd: the lane's bit sets (line in service = both ends > 0, line
-// cooldown > 0, substation cooldown > 0; bit i of word i / 64).  rules_on = 0: AlwaysLegal.
-GPF_TM_HD inline unsigned topo_mask_eval(const TopoMaskTab& t, int a, const unsigned long long* live, const unsigned long long* line_cd,
-                                         const unsigned long long* sub_cd, int rules_on, int max_line, int max_sub) {
-  if (t.amb[a]) return TM_AMBIGUOUS;
-  if (!rules_on) return 0;
+// The two counters of the limits: one count over the whole grid, or one per area.  bump(word): a line / substation word is counted
+// (in its area, bits 26-29 of the word); over(limit): the count, or some area's, exceeds the limit.
+struct TmGridCount {
+  int n = 0;
+  GPF_TM_HD void bump(int) { ++n; }
+  GPF_TM_HD bool over(int limit) const { return n > limit; }
+};
+// Sixteen saturating 8-bit counters in two 64-bit words: counter k is byte k & 7 of word k >> 3 (limit <= TM_AREA_MAX_LIMIT: exact).
+struct TmAreaCount {
+  unsigned long long lo = 0, hi = 0;
+  GPF_TM_HD void bump(int word) {
+    const int area = (word >> TM_AREA_SHIFT) & (TM_MAX_AREAS - 1), sh = (area & 7) * 8;
+    const bool up = (area & 8) != 0;
+    const unsigned long long w = up ? hi : lo;
+    const unsigned long long nw = ((w >> sh) & 0xFFull) != 0xFFull ? w + (1ull << sh) : w;
+    if (up) hi = nw; else lo = nw;
+  }
+  GPF_TM_HD bool over(int limit) const {
+    bool o = false;
+    for (int k = 0; k < 8; ++k) o = o || (int)((lo >> (8 * k)) & 0xFFull) > limit || (int)((hi >> (8 * k)) & 0xFFull) > limit;
+    return o;
+  }
+};
+
+// The rules of a mask byte, stated once for both counters: entry `a` (not ambiguous) of one lane under rules that are on.
+template <class Count>
+GPF_TM_HD inline unsigned topo_mask_rules(const TopoMaskTab& t, int a, const unsigned long long* live, const unsigned long long* line_cd,
+                                          const unsigned long long* sub_cd, int max_line, int max_sub) {
   unsigned m = 0;
-  int n_lines = 0, n_subs = 0;
+  Count n_lines, n_subs;
   const int* o = t.off + 3 * a;
   for (int q = o[0]; q < o[3]; ++q) {
     const int w = t.line[q], l = w & TM_LINE_MASK;
     bool im, clr;
     tm_line_impact(w, tm_bit(live, l), im, clr);
-    if (im) { ++n_lines; if (tm_bit(line_cd, l)) m |= TM_LINE_COOLDOWN; }
+    if (im) { n_lines.bump(w); if (tm_bit(line_cd, l)) m |= TM_LINE_COOLDOWN; }
   }
   int c = o[2];
   for (int q = o[1]; q < o[4]; ++q) {
@@ -81,11 +111,47 @@ GPF_TM_HD inline unsigned topo_mask_eval(const TopoMaskTab& t, int a, const unsi
       aff = aff || !clr;
     }
     c += nc;
-    if (aff) { ++n_subs; if (tm_bit(sub_cd, w & TM_LINE_MASK)) m |= TM_SUB_COOLDOWN; }
+    if (aff) { n_subs.bump(w); if (tm_bit(sub_cd, w & TM_LINE_MASK)) m |= TM_SUB_COOLDOWN; }
   }
-  if (n_lines > max_line) m |= TM_TOO_MANY_LINES;
-  if (n_subs > max_sub) m |= TM_TOO_MANY_SUBS;
+  if (n_lines.over(max_line)) m |= TM_TOO_MANY_LINES;
+  if (n_subs.over(max_sub)) m |= TM_TOO_MANY_SUBS;
   return m;
+}
+
+// The mask byte of entry `a` for one lane.  live / line_cd / sub_cd: the lane's bit sets (line in service = both ends > 0, line
+// cooldown > 0, substation cooldown > 0; bit i of word i / 64).  rules_on = 0: AlwaysLegal.
+GPF_TM_HD inline unsigned topo_mask_eval(const TopoMaskTab& t, int a, const unsigned long long* live, const unsigned long long* line_cd,
+                                         const unsigned long long* sub_cd, int rules_on, int max_line, int max_sub) {
+  if (t.amb[a]) return TM_AMBIGUOUS;
+  if (!rules_on) return 0;
+  return topo_mask_rules<TmGridCount>(t, a, live, line_cd, sub_cd, max_line, max_sub);
+}
+
+// The same byte with the two limits held per area (rules on; the words of `t` carry their areas): TOO_MANY_LINES / TOO_MANY_SUBS mean
+// "in some area".  max_line, max_sub <= TM_AREA_MAX_LIMIT.
+GPF_TM_HD inline unsigned topo_mask_eval_area(const TopoMaskTab& t, int a, const unsigned long long* live, const unsigned long long* line_cd,
+                                              const unsigned long long* sub_cd, int max_line, int max_sub) {
+  if (t.amb[a]) return TM_AMBIGUOUS;
+  return topo_mask_rules<TmAreaCount>(t, a, live, line_cd, sub_cd, max_line, max_sub);
+}
+
+// The ambiguity rules of the topology kinds (BaseAction._check_for_ambiguity, Action/baseAction.py:3668-3760) on the dense arrays of one
+// action -- setv [dim_topo] set_bus value, chg [dim_topo] change_bus, setl [n_line] set_line_status value, swl [n_line]
+// change_line_status, each filled item by item (a later item of a position / line replaces an earlier one).  The ONE statement of these
+// rules: run per table entry at upload (topo_static_ambiguity) and per lane on a composite action (topo_prestep_kernel, gridpf_topo.hpp).
+// Looks at positions and lines tid, tid + nth, ...; the action is ambiguous when any of the nth calls says so.
+GPF_TM_HD inline bool topo_dense_ambiguity(int dim_topo, int n_line, const int* or_pos, const int* ex_pos, const int* setv, const int* chg,
+                                           const int* setl, const int* swl, int tid, int nth) {
+  bool a = false;
+  for (int p = tid; p < dim_topo; p += nth) a = a || (chg[p] && setv[p] != 0);              // set_bus and change_bus of one element
+  for (int l = tid; l < n_line; l += nth) {
+    const int po = or_pos[l], pe = ex_pos[l];
+    a = a || (swl[l] && setl[l] != 0)                                                      // set and change of one line status
+        || (setv[po] == -1 && setv[pe] > 0) || (setv[pe] == -1 && setv[po] > 0)             // one end set to -1, the other to a bus
+        || (setl[l] == -1 && (setv[po] > 0 || setv[pe] > 0 || chg[po] || chg[pe]))           // disconnected and (re)assigned / changed
+        || (setl[l] == 1 && (setv[po] == -1 || setv[pe] == -1 || chg[po] || chg[pe]));       // reconnected and disconnected / changed
+  }
+  return a;
 }
 
 // ---- host: static ambiguity + summary of a table, once per upload ---------------------------------------------------------------
@@ -104,15 +170,7 @@ inline void topo_static_ambiguity(const TopoMaskGrid& g, int n_act, const int* a
       else if (kind == TM_SET_LINE_STATUS) setl[id] = v;
       else if (kind == TM_CHANGE_LINE_STATUS) swl[id] = 1;
     }
-    bool a = false;
-    for (int p = 0; p < g.dim_topo && !a; ++p) a = chg[p] && setv[p] != 0;              // set_bus and change_bus of one element
-    for (int l = 0; l < g.n_line && !a; ++l) {
-      const int po = g.or_pos[l], pe = g.ex_pos[l];
-      a = (swl[l] && setl[l] != 0)                                                       // set and change of one line status
-          || (setv[po] == -1 && setv[pe] > 0) || (setv[pe] == -1 && setv[po] > 0)         // one end set to -1, the other to a bus
-          || (setl[l] == -1 && (setv[po] > 0 || setv[pe] > 0 || chg[po] || chg[pe]))       // disconnected and (re)assigned / changed
-          || (setl[l] == 1 && (setv[po] == -1 || setv[pe] == -1 || chg[po] || chg[pe]));   // reconnected and disconnected / changed
-    }
+    const bool a = topo_dense_ambiguity(g.dim_topo, g.n_line, g.or_pos, g.ex_pos, setv.data(), chg.data(), setl.data(), swl.data(), 0, 1);
     amb[k] = a ? 1 : 0;
   }
 }
@@ -124,9 +182,10 @@ struct TopoMaskSummary {
 
 // The dense per-entry arrays are those of step 2 of topo_prestep_kernel, filled item by item in the same way (a later set_bus of a
 // position replaces an earlier one; a line-status item with a value != 0 marks its line for good).  false: a line or substation id
-// does not fit the 20 bits of a word.
+// does not fit the 20 bits of a word.  sub_area [n_sub] (NULL: no areas): the area, < TM_MAX_AREAS, every line word and substation word
+// carries (a line: its origin substation's).
 inline bool build_topo_mask_summary(const TopoMaskGrid& g, int n_act, const int* act_off, const int* act_items, const unsigned char* amb,
-                                    TopoMaskSummary& s) {
+                                    TopoMaskSummary& s, const int* sub_area = nullptr) {
   if (g.n_line > TM_LINE_MASK || g.n_sub > TM_LINE_MASK) return false;
   std::vector<int> setv(g.dim_topo, 0), eff(g.dim_topo, 0), imp(g.n_line, 0), other(g.dim_topo, -1), line_of(g.dim_topo, -1);
   for (int l = 0; l < g.n_line; ++l) {
@@ -154,7 +213,8 @@ inline bool build_topo_mask_summary(const TopoMaskGrid& g, int n_act, const int*
       return l | (imp[l] ? TM_STATUS : 0) | (setv[po] > 0 ? TM_OR_POS : 0) | (setv[po] < 0 ? TM_OR_NEG : 0) | (setv[pe] > 0 ? TM_EX_POS : 0) |
              (setv[pe] < 0 ? TM_EX_NEG : 0);
     };
-    for (int l : lines) { const int w = word(l); if (w & ~TM_LINE_MASK) s.line.push_back(w); }
+    auto area = [&](int sub) { return sub_area ? sub_area[sub] << TM_AREA_SHIFT : 0; };
+    for (int l : lines) { const int w = word(l); if (w & ~TM_LINE_MASK) s.line.push_back(w | area(g.pos_sub[g.or_pos[l]])); }
     for (int p : poss) if (eff[p]) {
       const int l = line_of[p];
       cand.emplace_back(g.pos_sub[p], l < 0 ? -1 : word(l) | (p == g.ex_pos[l] ? TM_END : 0));
@@ -166,7 +226,7 @@ inline bool build_topo_mask_summary(const TopoMaskGrid& g, int n_act, const int*
       for (; j < cand.size() && cand[j].first == cand[i].first; ++j) {
         if (cand[j].second < 0) always = TM_SUB_ALWAYS; else { s.end.push_back(cand[j].second); ++n_end; }
       }
-      s.sub.push_back(cand[i].first | always); s.sub.push_back(n_end);
+      s.sub.push_back(cand[i].first | always | area(cand[i].first)); s.sub.push_back(n_end);
       i = j;
     }
     for (int p : poss) { setv[p] = 0; eff[p] = 0; }
@@ -174,6 +234,27 @@ inline bool build_topo_mask_summary(const TopoMaskGrid& g, int n_act, const int*
   }
   s.off[3 * (size_t)n_act] = (int)s.line.size(); s.off[3 * (size_t)n_act + 1] = (int)(s.sub.size() / 2); s.off[3 * (size_t)n_act + 2] = (int)s.end.size();
   return true;
+}
+
+// Bit k of areas[a]: entry `a` can touch area k -- the area of every substation it names and of BOTH end substations of every line it
+// names (a status item, or a set_bus / change_bus on a line end), ambiguous entries included.  sub_area NULL: one area, bit 0.
+// shunt_sub [n_shunt] (may be NULL: shunt items are skipped).
+inline void topo_action_areas(const TopoMaskGrid& g, int n_act, const int* act_off, const int* act_items, const int* sub_area,
+                              const int* shunt_sub, unsigned* areas) {
+  std::vector<int> line_of(g.dim_topo, -1);
+  for (int l = 0; l < g.n_line; ++l) { line_of[g.or_pos[l]] = l; line_of[g.ex_pos[l]] = l; }
+  auto bit = [&](int sub) { return 1u << (sub_area ? sub_area[sub] : 0); };
+  auto ends = [&](int l) { return bit(g.pos_sub[g.or_pos[l]]) | bit(g.pos_sub[g.ex_pos[l]]); };
+  for (int a = 0; a < n_act; ++a) {
+    unsigned m = 0;
+    for (int q = act_off[a]; q < act_off[a + 1]; ++q) {
+      const int kind = act_items[3 * q], id = act_items[3 * q + 1];
+      if (kind == TM_SET_BUS || kind == TM_CHANGE_BUS) { m |= bit(g.pos_sub[id]); if (line_of[id] >= 0) m |= ends(line_of[id]); }
+      else if (kind == TM_SET_LINE_STATUS || kind == TM_CHANGE_LINE_STATUS) m |= ends(id);
+      else if (shunt_sub) m |= bit(shunt_sub[id]);
+    }
+    areas[a] = m;
+  }
 }
 
 // 64-bit words of a bit set over n elements
@@ -191,9 +272,10 @@ constexpr int TM_CHUNK = 256;      // table entries of one wavefront (4 per thre
 // One wavefront per (lane, chunk of TM_CHUNK entries): blockIdx.x = lane - lane0, blockIdx.y strides over the chunks.  The lane's state
 // is reduced once to three bit sets in LDS (one __ballot per 64 lines / substations), thread t then evaluates entries t, t + 64, ...
 // of the chunk, so that the wavefront's 64 byte stores to the lane's row are contiguous.  Dynamic LDS: (2 * tm_words(n_line) +
-// tm_words(n_sub)) * 8 bytes.  Reads only; writes bytes [0, n_act) of rows [0, n) of `out`.
+// tm_words(n_sub)) * 8 bytes.  Reads only; writes bytes [0, n_act) of rows [0, n) of `out`.  by_area (uniform): the rules are on and
+// areas are set -- the limits hold per area.
 __global__ __launch_bounds__(64) void topo_mask_kernel(TopoMaskTab tab, TopoMaskLanes s, int rules_on, int max_line, int max_sub, int lane0,
-                                                       int n, unsigned char* __restrict__ out, long long row_stride) {
+                                                       int n, unsigned char* __restrict__ out, long long row_stride, int by_area) {
   extern __shared__ unsigned long long tm_sets[];
   const int k = blockIdx.x, tid = threadIdx.x;
   if (k >= n) return;
@@ -222,7 +304,10 @@ __global__ __launch_bounds__(64) void topo_mask_kernel(TopoMaskTab tab, TopoMask
   unsigned char* orow = out + (long long)k * row_stride;
   for (long long a0 = (long long)blockIdx.y * TM_CHUNK; a0 < tab.n_act; a0 += (long long)gridDim.y * TM_CHUNK) {
     const int a1 = (int)(a0 + TM_CHUNK < tab.n_act ? a0 + TM_CHUNK : tab.n_act);
-    for (int a = (int)a0 + tid; a < a1; a += 64) orow[a] = (unsigned char)topo_mask_eval(tab, a, live, lcd, scd, rules_on, max_line, max_sub);
+    if (by_area)
+      for (int a = (int)a0 + tid; a < a1; a += 64) orow[a] = (unsigned char)topo_mask_eval_area(tab, a, live, lcd, scd, max_line, max_sub);
+    else
+      for (int a = (int)a0 + tid; a < a1; a += 64) orow[a] = (unsigned char)topo_mask_eval(tab, a, live, lcd, scd, rules_on, max_line, max_sub);
   }
 }
 #endif  // __HIPCC__

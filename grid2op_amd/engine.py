@@ -574,10 +574,46 @@ class PowerFlowEngine:
         self._mask_view = None               # (the engine-owned mask buffer is re-allocated with the table)
         return amb[:n].astype(bool)
 
+    def set_topo_areas(self, areas=None):
+        """The areas of the reference's ``RulesByArea``: ``sub_area`` (int ``[n_sub]``, the area of every substation) or a list of lists
+        of substation ids, one per area (at most 16).  The two limits of `set_topo_rules` then hold per area, a line counting in the
+        area of its origin substation.  None: whole-grid limits again (the default)."""
+        n_sub = self.model.n_sub
+        if areas is None or len(areas) == 0:
+            check(self._lib.gpf_set_topo_areas(self._h, 0, None), "gpf_set_topo_areas")
+            return
+        if np.ndim(areas[0]) == 0:
+            sub_area = np.ascontiguousarray(areas, dtype=np.int32)
+            if sub_area.shape != (n_sub,):
+                raise ValueError(f"set_topo_areas: sub_area must have {n_sub} entries")
+            n_area = int(sub_area.max()) + 1 if (sub_area >= 0).all() else 1     # (the library refuses a negative id)
+        else:
+            sub_area = np.full(n_sub, -1, dtype=np.int32)
+            for k, subs in enumerate(areas):
+                subs = np.asarray(subs, dtype=np.int64)
+                if ((subs < 0) | (subs >= n_sub)).any() or (sub_area[subs] >= 0).any():
+                    raise ValueError("set_topo_areas: a substation id is out of range or listed twice")
+                sub_area[subs] = k
+            n_area = len(areas)
+        check(self._lib.gpf_set_topo_areas(self._h, n_area, ptr(sub_area, C.c_int32)), "gpf_set_topo_areas")
+
+    def set_topo_slots(self, n_slot: int = 1):
+        """Table entries a lane plays per step (1..8): the concatenation, in slot order, of the non-empty slots' item lists is played as
+        ONE action.  Changing it drops pending indices; ``device_views()["act_topo"]`` becomes ``[n_lanes, n_slot]``."""
+        check(self._lib.gpf_set_topo_slots(self._h, int(n_slot)), "gpf_set_topo_slots")
+        self._n_topo_slot = int(n_slot)
+
+    def topo_action_areas(self) -> np.ndarray:
+        """uint32 ``[n_act]``: bit k set when the table entry can touch area k (every substation it names, both ends of every line it
+        names).  Entries of the slots of one lane with pairwise disjoint area sets are applied exactly when each has mask byte 0."""
+        out = np.zeros(max(int(getattr(self, "_n_topo_act", 0)), 1), dtype=np.uint32)
+        check(self._lib.gpf_get_topo_action_areas(self._h, ptr(out, C.c_uint32)), "gpf_get_topo_action_areas")
+        return out[:int(getattr(self, "_n_topo_act", 0))]
+
     def set_lane_topo_actions(self, index):
-        """Entry of the action table every lane plays at the NEXT launch (int ``[n_lanes]``, -1 = do nothing; None: none) -- that launch
-        must be a one-step launch."""
-        a = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(self.n_lanes)
+        """Entries of the action table every lane plays at the NEXT launch (int ``[n_lanes]`` with one slot, ``[n_lanes, n_slot]`` else;
+        -1 = empty slot, all empty = do nothing; None: none) -- that launch must be a one-step launch."""
+        a = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(self.n_lanes * int(getattr(self, "_n_topo_slot", 1)))
         check(self._lib.gpf_set_lane_topo_actions(self._h, ptr(a, C.c_int32)), "gpf_set_lane_topo_actions")
 
     def topo_actions_on_device(self, on: bool = True):
@@ -744,7 +780,7 @@ class PowerFlowEngine:
         float64, ``bus_vm`` / ``bus_va`` float64; with the environment dynamics on also the action buffers ``act_redispatch`` /
         ``act_curtail`` ``[n_lanes, n_gen]``, ``act_storage`` ``[n_lanes, n_storage]`` (`lane_actions_on_device`) and
         ``target_dispatch`` / ``actual_dispatch`` / ``storage_charge`` float32 (obs.target_dispatch, ...); once topology actions are enabled
-        (`set_topo_rules` / `upload_topo_actions`) also ``act_topo`` int32 ``[n_lanes, 1]`` (`topo_actions_on_device`), ``sub_cooldown``
+        (`set_topo_rules` / `upload_topo_actions`) also ``act_topo`` int32 ``[n_lanes, n_slot]`` (`topo_actions_on_device`), ``sub_cooldown``
         ``[n_lanes, n_sub]``, ``topo_flags`` uint8 ``[n_lanes, 2]`` and ``last_bus`` ``[n_lanes, dim_topo]``; once an observation spec is set
         (`set_obs_spec`) also ``obs`` float32 ``[n_lanes, dim]`` (what `observation_vector` without ``out`` writes); once an action table is
         uploaded also ``topo_mask`` uint8 ``[n_lanes, n_act]`` (what `topo_action_mask` without ``out`` writes).  The engine works on its own HIP stream: call `sync` (or make the consumer's
@@ -775,7 +811,7 @@ class PowerFlowEngine:
              "act_redispatch": view(22, m.n_gen, "<f4"), "act_storage": view(23, m.n_storage, "<f4"), "act_curtail": view(24, m.n_gen, "<f4"),
              "target_dispatch": view(25, m.n_gen, "<f4"), "actual_dispatch": view(26, m.n_gen, "<f4"),
              "storage_charge": view(27, m.n_storage, "<f4"),
-             "act_topo": view(28, 1, "<i4"), "sub_cooldown": view(29, m.n_sub, "<i4"), "topo_flags": view(30, 2, "|u1"),
+             "act_topo": view(28, int(getattr(self, "_n_topo_slot", 1)), "<i4"), "sub_cooldown": view(29, m.n_sub, "<i4"), "topo_flags": view(30, 2, "|u1"),
              "last_bus": view(31, m.dim_topo, "<i4"),
              "obs": view(32, self._obs_spec.dim if getattr(self, "_obs_spec", None) is not None else 0, "<f4"),
              "topo_mask": view(33, int(getattr(self, "_n_topo_act", 0)), "|u1")}

@@ -378,6 +378,17 @@ class ShardedEngine:
         for eng in self.engines:
             eng.set_topo_rules(*a, **kw)
 
+    def set_topo_areas(self, areas=None):
+        for eng in self.engines:
+            eng.set_topo_areas(areas)
+
+    def set_topo_slots(self, n_slot: int = 1):
+        for eng in self.engines:
+            eng.set_topo_slots(n_slot)
+
+    def topo_action_areas(self):
+        return self.engines[0].topo_action_areas()
+
     def upload_topo_actions(self, actions):
         return [eng.upload_topo_actions(actions) for eng in self.engines][0]
 

@@ -106,7 +106,10 @@ const char* gpf_last_error(void);
  * gpf_device_pointers_n); 310 = + gpf_jit_*, GPF_E_UNSUPPORTED, gpf_set_profiling mode 3; 321 = 28 device pointers (action buffers and
  * dispatch / charge state of the environment dynamics), gpf_lane_actions_on_device; 322 = + gpf_get_results_pinned; 323 = gpf_step_opts::track_cooldown,
  * GPF_DEVICE_NONE (header-only handles); 324 = 32 device pointers, topology actions in the batched step (gpf_upload_topo_actions ...);
- * 325 = 33 device pointers, observation vectors assembled on the device (gpf_set_obs_spec ...). */
+ * 325 = 33 device pointers, observation vectors assembled on the device (gpf_set_obs_spec ...).
+ * gpf_set_topo_areas / gpf_set_topo_slots / gpf_get_topo_action_areas were added under 326 without raising it: three new symbols, no
+ * struct, argument list or default behaviour changed, so a binding written against the earlier 326 header works unchanged (a binding
+ * that needs them finds out by looking the symbols up). */
 #define GPF_ABI_VERSION 326
 int gpf_version(void);
 /* Bitwise run-to-run reproducibility is the DEFAULT on every grid: the same lane inputs give bit-identical results from run to
@@ -401,7 +404,8 @@ int gpf_simulate_batch(gpf_handle h, int32_t t_obs, int32_t time_step, int32_t n
  *     auto_reset while any lane is on a moved class is refused (GPF_E_INVALID: the plan of a launch cannot follow a reset inside it);
  *   - the pending indices are consumed by the launch that takes them, also when it fails after the pre-step (the rows may already be
  *     rewritten: reset or re-send the lanes after a failed launch);
- *   - also out of scope: RulesByArea (l2rpn_idf_2023), the opponent, PreventDiscoStorageModif.
+ *   - also out of scope: the opponent, PreventDiscoStorageModif (it cannot fire on a pure topology action) and combined topology +
+ *     injection actions.  RulesByArea (l2rpn_idf_2023) is covered by gpf_set_topo_areas / gpf_set_topo_slots below.
  * The launch planner needs every lane's topology class: the pre-step kernel lists the lanes whose class key or busbar count changed
  * and the host reads that one compact list back (skipped when no entry of the table can change a class).  The auto-reset target
  * (the rows last sent with gpf_set_topology) is not changed by an action.
@@ -409,7 +413,7 @@ int gpf_simulate_batch(gpf_handle h, int32_t t_obs, int32_t time_step, int32_t n
  *                               cooldown_sub / cooldown_line: NB_TIMESTEP_COOLDOWN_SUB / NB_TIMESTEP_COOLDOWN_LINE (0: not booked).
  *   gpf_upload_topo_actions   : the table in the encoding of gpf_simulate_batch (act_off[n_act + 1], act_items[][3], validated the same
  *                               way); ambiguous[n_act] (may be NULL) receives the static ambiguity flags.  n_act = 0 empties it.
- *   gpf_set_lane_topo_actions : index[n_lanes] of the NEXT launch from the host (NULL: none); consumed by that launch.
+ *   gpf_set_lane_topo_actions : index[n_lanes][n_slot] of the NEXT launch from the host (NULL: none); consumed by that launch.
  *   gpf_topo_actions_on_device: on != 0: the next launch takes the indices written into the device buffer act_topo (gpf_device_pointers
  *                               entry 28) on the engine's stream or ordered before the launch; consumed by that launch.
  *   gpf_get/set_sub_cooldown  : [n][n_sub] obs.time_before_cooldown_sub.      gpf_get/set_last_bus: [n][dim_topo] busbars 1..n_busbar.
@@ -426,6 +430,44 @@ int gpf_set_sub_cooldown(gpf_handle h, int32_t lane0, int32_t n, const int32_t* 
 int gpf_get_last_bus(gpf_handle h, int32_t lane0, int32_t n, int32_t* last_bus);
 int gpf_set_last_bus(gpf_handle h, int32_t lane0, int32_t n, const int32_t* last_bus);
 int gpf_get_topo_flags(gpf_handle h, int32_t lane0, int32_t n, uint8_t* flags);
+
+/* ---- rules by area and composite actions (Rules/rulesByArea.py: RulesByArea, the rules l2rpn_idf_2023 is played under: the limits hold
+ * per area and an agent acts in every area at the same step) ------------------------------------------------------------------------
+ *   gpf_set_topo_areas : sub_area[n_sub], the area in [0, n_area) of every substation, 1 <= n_area <= 16, every area holding at least one
+ *                        substation (GPF_E_INVALID otherwise).  n_area = 0 or sub_area = NULL: whole-grid limits again (the default).  A line
+ *                        belongs to the area of its ORIGIN substation (rulesByArea.py:91), tie lines too.  With gpf_set_topo_rules(on = 1)
+ *                        an action is then illegal when in ANY area the affected lines of that area exceed max_line_status_changed, or the
+ *                        affected substations of that area exceed max_sub_changed (_lookparam_byarea, rulesByArea.py:120-140);
+ *                        PreventReconnection stays per element.  With areas set the two limits must not exceed 254 (GPF_E_INVALID).  Areas
+ *                        belong to the rules, not to lanes: resets and lane copies do not touch them.  May be called before or after the
+ *                        upload of the table.
+ *   gpf_set_topo_slots : 1 <= n_slot <= 8 (default 1) table entries per lane and step: act_topo becomes [lane capacity][n_slot] (another
+ *                        buffer: fetch gpf_device_pointers again), all slots empty; pending indices are dropped.  A lane's action is the
+ *                        CONCATENATION, in slot order, of the item lists of its non-empty slots (-1: empty; all empty: do nothing), treated
+ *                        exactly as a single table entry with that item list would be: the dense arrays are filled item by item (a later
+ *                        set_bus of a position replaces an earlier one), ambiguity is decided at run time on them by the rules of the
+ *                        upload (an index outside the table in any slot: ambiguous), impact, legality and the cooldown booking are those
+ *                        of the union, and the list is applied ONCE (every line-status item before any bus item -- applying slot after
+ *                        slot would be another action).  One index may sit in several slots of a lane: its items then stand
+ *                        several times in the list, as they would in such an entry.  GPF_E_INVALID (here or from
+ *                        gpf_upload_topo_actions) when n_slot times the longest entry of the table does not fit the pre-step kernel's
+ *                        64 KiB of LDS.
+ *   gpf_get_topo_action_areas : areas[n_act], bit k set when the entry can touch area k: the area of every substation it names and of BOTH
+ *                        end substations of every line it names through a status item or a line-end set_bus / change_bus (an ambiguous
+ *                        entry: everything it names).  Without areas every non-empty entry has bit 0.  Static; works on a header-only handle.
+ * With areas set GPF_MASK_TOO_MANY_LINES / GPF_MASK_TOO_MANY_SUBS of the legality masks below mean "in some area".  The mask stays one byte
+ * per (lane, ENTRY).  Factorisation guarantee: if the non-empty slots of a lane hold entries with pairwise disjoint area sets
+ * (gpf_get_topo_action_areas), the composite is applied (is_illegal = is_ambiguous = 0) EXACTLY WHEN every one of those entries has mask
+ * byte 0 for that lane.  Proof: disjoint area sets mean the entries name disjoint elements, lines and substations (an entry's set holds
+ * the areas of both ends of every line it names).  So (1) no item of one entry overwrites or meets an item of another in the dense
+ * arrays, and every ambiguity rule looks at one element or at one line and its two ends: the composite is ambiguous iff one entry is;
+ * (2) a line's impact depends on its own items and status, a substation's on its own elements and their lines: the composite's
+ * aff_lines / aff_subs are the disjoint unions of the entries'; (3) an affected line or substation of an entry lies in one of that
+ * entry's areas, so each area's counts come from one entry only: a limit is exceeded in some area iff it is for one entry alone;
+ * (4) the cooldown rules are per element.  A policy with one head per area can therefore mask each head by its own columns. */
+int gpf_set_topo_areas(gpf_handle h, int32_t n_area, const int32_t* sub_area /* [n_sub] */);
+int gpf_set_topo_slots(gpf_handle h, int32_t n_slot);
+int gpf_get_topo_action_areas(gpf_handle h, uint32_t* areas /* [n_act] */);
 
 /* ---- legality masks of the action table (what a policy with a discrete head over the table needs before every step) -- for lane k
  * and table entry a one byte, 0 exactly when a launch that carried act_topo[k] = a right now would apply the entry (is_illegal =
@@ -634,7 +676,7 @@ int gpf_get_plan(gpf_handle h, int32_t out[8]);
  * [cap][gpf_lane_capacity][row]); 22..27 = the environment dynamics (NULL while they are off): the action buffers redispatch
  * [lanes][n_gen], storage power [lanes][n_storage], curtailment [lanes][n_gen] (gpf_lane_actions_on_device), then target dispatch,
  * actual dispatch [lanes][n_gen] and state of charge [lanes][n_storage] (obs.target_dispatch / actual_dispatch / storage_charge);
- * 28..31 = the acting path of the topology actions (NULL until it is enabled): act_topo int32 [lanes], sub_cooldown int32 [lanes][n_sub],
+ * 28..31 = the acting path of the topology actions (NULL until it is enabled): act_topo int32 [lanes][n_slot], sub_cooldown int32 [lanes][n_sub],
  * topo_flags uint8 [lanes][2], last_bus int32 [lanes][dim_topo] (gpf_upload_topo_actions); 32 = the engine-owned observation vectors
  * float32 [lanes][dim] (NULL until gpf_set_obs_spec; gpf_obs_vector with out_dev = NULL writes them); 33 = the engine-owned legality
  * masks uint8 [lanes][n_act] (NULL without an action table; gpf_topo_action_mask with out_dev = NULL writes them);
