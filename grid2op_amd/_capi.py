@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "library_path", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags", "gpf_topo_action_mask", "gpf_get_topo_action_mask",
     "gpf_set_topo_areas", "gpf_set_topo_slots", "gpf_get_topo_action_areas",
     "gpf_set_obs_clock", "gpf_set_obs_spec", "gpf_obs_vector", "gpf_obs_vector_trajectory", "gpf_get_obs_vector",
+    "gpf_set_opponent", "gpf_upload_opponent_draws", "gpf_upload_opponent_schedule", "gpf_get_opponent_state", "gpf_set_opponent_state",
 ]
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
@@ -64,6 +65,17 @@ class GpfGridDesc(C.Structure):
         ("storage_sub", _ip), ("storage_pos_topo_vect", _ip),
         ("shunt_sub", _ip), ("shunt_fact", _dp),
         ("init_inj", _dp), ("init_topo", _ip), ("init_shunt_bus", _ip),
+    ]
+
+
+class GpfOpponentDesc(C.Structure):
+    """include/gridpf.h gpf_opponent_desc"""
+    _fields_ = [
+        ("kind", C.c_int32), ("n_lines", C.c_int32), ("line_ids", _ip), ("rho_normalization", _dp), ("attack_period", C.c_int32),
+        ("attack_hazard_rate", C.c_double), ("recovery_rate", C.c_double), ("recovery_minimum_duration", C.c_int32),
+        ("pmax_pmin_ratio", C.c_double), ("episode_max_time", C.c_int32), ("init_budget", C.c_float), ("budget_per_ts", C.c_float),
+        ("attack_duration", C.c_int32), ("attack_cooldown", C.c_int32), ("draw_source", C.c_int32), ("seed_lo", C.c_uint32),
+        ("seed_hi", C.c_uint32), ("lane_base", C.c_int32), ("schedule_cap", C.c_int32),
     ]
 
 
@@ -194,6 +206,11 @@ def lib() -> C.CDLL:
     L.gpf_obs_vector.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]
     L.gpf_obs_vector_trajectory.argtypes = [h, i32, i32, i32, i32, C.c_void_p]
     L.gpf_get_obs_vector.argtypes = [h, i32, i32, _fp]
+    L.gpf_set_opponent.argtypes = [h, C.POINTER(GpfOpponentDesc)]
+    L.gpf_upload_opponent_draws.argtypes = [h, i32, _dp]
+    L.gpf_upload_opponent_schedule.argtypes = [h, _ip, _ip]
+    L.gpf_get_opponent_state.argtypes = [h, i32, i32, _dp, _ip]
+    L.gpf_set_opponent_state.argtypes = [h, i32, i32, _dp, _ip]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

@@ -1225,6 +1225,7 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
     HIP_TRY(err);
     for (int k = 0; k < n; ++k) { e->ta_n_moved += e->ta_moved[src + k] - e->ta_moved[dst + k]; e->ta_moved[dst + k] = e->ta_moved[src + k]; }
   }
+  if (e->opp_kind && err == hipSuccess) err = opponent_copy_lanes(e, src, dst, n);
   HIP_TRY(err);
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
@@ -1736,11 +1737,21 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if (acts && e->env_on && (e->env_act_r || e->env_act_s || e->env_act_c))
     return fail(GPF_E_INVALID, "gpf_step_n: topology actions and injection actions (redispatch / storage / curtailment) are pending for the same "
                                "launch: combined actions are not supported (in the reference the illegality of either part cancels both)");
+  if (e->opp_kind && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: with an opponent set (gpf_set_opponent) a launch must be a one-step launch (the opponent's choice "
+                               "needs the previous step's rho and line status): use n_steps = 1");
+  if (e->opp_kind && !o->track_cooldown)
+    return fail(GPF_E_INVALID, "gpf_step_n: an opponent (gpf_set_opponent) needs gpf_step_opts::track_cooldown (the attacked line's cooldown is "
+                               "only counted down by a launch that maintains the line cooldowns)");
   HIP_TRY(hipSetDevice(e->device));
   int rc = GPF_OK;
   if (e->ta_on) {
     if (acts) { e->ta_host = e->ta_dev = false; e->dev_topo_dirty = true; }   // consumed by this launch, whatever happens below
     rc = topo_prestep(e, acts);
+    if (rc != GPF_OK) return rc;
+  }
+  if (e->opp_kind) {                        // after the agent's action, before the step: the attack wins
+    rc = opponent_prestep(e);
     if (rc != GPF_OK) return rc;
   }
   rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);

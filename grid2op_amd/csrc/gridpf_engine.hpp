@@ -234,6 +234,13 @@ struct gpf_engine {
   int obs_clock_tables = 0, obs_step_minutes = 5, obs_max_step = 0;
   DevArr<int> obs_maint_next, obs_maint_durn;   // [chron_tables][chron_T][n_line] time_next_maintenance / duration_next_maintenance at every row
   long long obs_maint_gen = -1, maint_gen = 0;  // generation of the outage tables the look-ahead was derived from / current generation
+  // the opponent of the batched acting path (gridpf_opponent.hpp, gridpf_capi_opp.hip): its configuration (host), the attackable lines and
+  // their normalisation, the per-lane state, the draws table and the Geometric schedules
+  int opp_kind = 0;                     // GPF_OPP_*; 0: off -- gpf_step_n launches nothing for it
+  gpf_opponent_desc opp_desc{};         // as validated (its pointers are not kept)
+  int opp_n_draw = 0;
+  DevArr<int> opp_lines, opp_state, opp_sched;
+  DevArr<double> opp_norm, opp_budget, opp_draws;
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
@@ -360,6 +367,10 @@ struct gpf_engine {
     return b;
   }
 };
+
+// gridpf_capi_opp.hip: the opponent's pre-step of a one-step launch (queued on the engine's stream) and its share of gpf_copy_lanes
+int opponent_prestep(gpf_engine* e);
+hipError_t opponent_copy_lanes(gpf_engine* e, int src, int dst, int n);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

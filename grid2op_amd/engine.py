@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import GpfGridDesc, GpfLayout, GpfStepOpts, GridPFError, check, ptr
+from ._capi import GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
 from .grid_model import GridModel
 
 __all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT", "MASK_TOO_MANY_LINES", "MASK_TOO_MANY_SUBS",
@@ -36,6 +36,94 @@ STATUS_TEXT = {
 }
 # reason bits of `PowerFlowEngine.topo_action_mask` (include/gridpf.h GPF_MASK_*); 0: the entry would be applied
 MASK_TOO_MANY_LINES, MASK_TOO_MANY_SUBS, MASK_LINE_COOLDOWN, MASK_SUB_COOLDOWN, MASK_AMBIGUOUS = 0x01, 0x02, 0x04, 0x08, 0x10
+
+# the opponent of `PowerFlowEngine.set_opponent` (include/gridpf.h GPF_OPP_*)
+OPP_NONE, OPP_RANDOM_LINE, OPP_WEIGHTED_RANDOM, OPP_GEOMETRIC = 0, 1, 2, 3
+OPP_DRAWS_TABLE, OPP_DRAWS_PHILOX = 0, 1
+OPP_STATE_INTS = 14
+OPP_TIME_NONE = -2 ** 31
+OPP_FLAG_DRAWS_EXHAUSTED, OPP_FLAG_SCHEDULE_CAPPED = 1, 2
+OPP_KIND_OF_CLASS = {"RandomLineOpponent": OPP_RANDOM_LINE, "WeightedRandomOpponent": OPP_WEIGHTED_RANDOM, "GeometricOpponent": OPP_GEOMETRIC}
+
+
+@dataclass
+class OpponentState:
+    """Per-lane state of the opponent (`PowerFlowEngine.opponent_state`): the five values of ``OpponentSpace._get_state`` (the budget as
+    float64 with the flag that it is still a numpy.float32), the opponent's own counters, and the two ``info`` values of the last launch.
+    ``next_attack_time`` is `OPP_TIME_NONE` for None."""
+    budget: np.ndarray
+    budget_is_f32: np.ndarray
+    attack_duration: np.ndarray
+    attack_cooldown: np.ndarray
+    attack_line: np.ndarray
+    previous_fails: np.ndarray
+    next_attack_time: np.ndarray
+    attack_counter: np.ndarray
+    n_schedule: np.ndarray
+    cursor: np.ndarray
+    episode: np.ndarray
+    flags: np.ndarray
+    opponent_attack_line: np.ndarray
+    opponent_attack_duration: np.ndarray
+
+    _COLS = ("budget_is_f32", "attack_duration", "attack_cooldown", "attack_line", "previous_fails", "next_attack_time", "attack_counter",
+             "n_schedule", "cursor", "episode", "flags", "opponent_attack_line", "opponent_attack_duration")
+
+    @classmethod
+    def from_rows(cls, budget, rows):
+        return cls(budget, *(rows[:, k].copy() for k in range(len(cls._COLS))))
+
+    def rows(self) -> np.ndarray:
+        out = np.zeros((len(self.budget), OPP_STATE_INTS), dtype=np.int32)
+        for k, name in enumerate(self._COLS):
+            out[:, k] = getattr(self, name)
+        return out
+
+
+def opponent_config(model, opponent_class, kwargs_opponent=None, opponent_init_budget=0.0, opponent_budget_per_ts=0.0,
+                    opponent_attack_duration=0, opponent_attack_cooldown=99999, delta_time_seconds=300.0, max_episode_duration=None,
+                    draw_source=OPP_DRAWS_PHILOX, seed=0, lane_base=0, schedule_cap=None) -> dict:
+    """The keyword arguments of `PowerFlowEngine.set_opponent` from a reference-style configuration: the ``opponent_class`` (the class or
+    its name), ``kwargs_opponent`` and the four ``opponent_*`` numbers of ``grid2op.make``; line names are resolved through the model's
+    ``name_line`` (BaseOpponent._set_line_id, Opponent/baseOpponent.py:139-161), the Geometric rates are derived as
+    GeometricOpponent.init does (Opponent/geometricOpponent.py:111-135) and its errors are raised with its reasons."""
+    name = opponent_class if isinstance(opponent_class, str) else getattr(opponent_class, "__name__", str(opponent_class))
+    if name not in OPP_KIND_OF_CLASS:
+        raise ValueError(f"opponent_config: {name} is not one of {sorted(OPP_KIND_OF_CLASS)} (the single-area line opponents)")
+    kw = dict(kwargs_opponent or {})
+    names = [str(x) for x in np.asarray(model.name_line)]
+    lines = []
+    for l_name in kw.get("lines_attacked", ()):
+        if str(l_name) not in names:
+            raise ValueError(f'opponent_config: unable to find the powerline named "{l_name}" on the grid')
+        lines.append(names.index(str(l_name)))
+    out = dict(kind=OPP_KIND_OF_CLASS[name], lines=lines, init_budget=opponent_init_budget, budget_per_ts=opponent_budget_per_ts,
+               attack_duration=int(opponent_attack_duration), attack_cooldown=int(opponent_attack_cooldown), draw_source=draw_source,
+               seed=seed, lane_base=lane_base)
+    if name == "WeightedRandomOpponent":
+        norm = list(kw.get("rho_normalization", ()))
+        if norm and len(norm) != len(lines):
+            raise ValueError("opponent_config: the usage rate normalization must have the same length as the number of attacked lines")
+        out.update(rho_normalization=norm or None, attack_period=int(kw.get("attack_period", 12 * 24)))
+    if name == "GeometricOpponent":
+        every, avg = kw.get("attack_every_xxx_hour", 24), kw.get("average_attack_duration_hour", 4)
+        mini = kw.get("minimum_attack_duration_hour", 2)
+        ts_per_hour = 3600.0 / float(delta_time_seconds)
+        if avg < mini:
+            raise ValueError("opponent_config: the average duration of an attack cannot be lower than the minimum time of an attack")
+        if avg == mini:
+            raise ValueError("opponent_config: average_attack_duration_hour == minimum_attack_duration_hour is not supported")
+        if every <= avg:
+            raise ValueError("opponent_config: attack_every_xxx_hour <= average_attack_duration_hour is not supported")
+        if max_episode_duration is None or not np.isfinite(max_episode_duration):
+            raise ValueError("opponent_config: the Geometric opponent only works with a known finite episode duration (max_episode_duration)")
+        hazard = 1.0 / (ts_per_hour * (every - avg))
+        if schedule_cap is None:            # expected attacks of an episode with a wide margin (the schedule ends where the capacity does)
+            schedule_cap = int(min(max(16, 4 * int(max_episode_duration) * hazard + 16), int(max_episode_duration)))
+        out.update(attack_hazard_rate=hazard, recovery_rate=1.0 / (ts_per_hour * (avg - mini)),
+                   recovery_minimum_duration=int(mini * ts_per_hour), pmax_pmin_ratio=float(kw.get("pmax_pmin_ratio", 4)),
+                   episode_max_time=int(max_episode_duration), schedule_cap=int(schedule_cap))
+    return out
 
 _OUT_FIELDS = [
     ("p_or", "n_line"), ("q_or", "n_line"), ("v_or", "n_line"), ("a_or", "n_line"), ("theta_or", "n_line"),
@@ -677,6 +765,61 @@ class PowerFlowEngine:
         out = np.empty((n, int(getattr(self, "_n_topo_act", 0))), dtype=np.uint8)
         check(self._lib.gpf_get_topo_action_mask(self._h, lane0, n, ptr(out if out.size else None, C.c_uint8)), "gpf_get_topo_action_mask")
         return out
+
+    # ---- the opponent (include/gridpf.h gpf_set_opponent; grid2op_amd/csrc/gridpf_opponent.hpp) -------
+    def set_opponent(self, kind=OPP_NONE, lines=(), *, init_budget=0.0, budget_per_ts=0.0, attack_duration=0, attack_cooldown=0,
+                     rho_normalization=None, attack_period=12 * 24, attack_hazard_rate=0.0, recovery_rate=0.0, recovery_minimum_duration=0,
+                     pmax_pmin_ratio=4.0, episode_max_time=0, draw_source=OPP_DRAWS_PHILOX, seed=0, lane_base=0, schedule_cap=64):
+        """The reference's OpponentSpace with a RandomLine / WeightedRandom / Geometric opponent on every lane of the one-step launches
+        (`opponent_config` builds these arguments from a ``grid2op.make``-style configuration).  ``kind`` None or `OPP_NONE`: off.
+        ``lines``: attackable line ids in the order of ``lines_attacked``.  ``seed``: 64-bit key of the Philox source; ``lane_base``: the
+        global index of lane 0.  Launches then need ``n_steps = 1`` and ``track_cooldown``."""
+        if kind is None or int(kind) == OPP_NONE:
+            check(self._lib.gpf_set_opponent(self._h, None), "gpf_set_opponent")
+            self._opp_cap = 0
+            return
+        ids = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1)
+        norm = None if rho_normalization is None else np.ascontiguousarray(rho_normalization, dtype=np.float64).reshape(-1)
+        if norm is not None and norm.size != ids.size:
+            raise ValueError("set_opponent: rho_normalization must have one entry per attackable line")
+        d = GpfOpponentDesc()
+        d.kind, d.n_lines, d.line_ids, d.rho_normalization = int(kind), int(ids.size), ptr(ids if ids.size else None, C.c_int32), ptr(norm, C.c_double)
+        d.attack_period, d.attack_hazard_rate, d.recovery_rate = int(attack_period), float(attack_hazard_rate), float(recovery_rate)
+        d.recovery_minimum_duration, d.pmax_pmin_ratio, d.episode_max_time = int(recovery_minimum_duration), float(pmax_pmin_ratio), int(episode_max_time)
+        d.init_budget, d.budget_per_ts = float(np.float32(init_budget)), float(np.float32(budget_per_ts))
+        d.attack_duration, d.attack_cooldown, d.draw_source = int(attack_duration), int(attack_cooldown), int(draw_source)
+        d.seed_lo, d.seed_hi, d.lane_base, d.schedule_cap = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(lane_base), int(schedule_cap)
+        check(self._lib.gpf_set_opponent(self._h, C.byref(d)), "gpf_set_opponent")
+        self._opp_cap = int(schedule_cap) if int(kind) == OPP_GEOMETRIC else 0
+
+    def upload_opponent_draws(self, draws):
+        """Table source: float64 ``[n_lanes, n_draw]`` uniforms in [0, 1), consumed per lane in event order; the cursors go back to 0."""
+        u = np.ascontiguousarray(draws, dtype=np.float64).reshape(self.n_lanes, -1)
+        check(self._lib.gpf_upload_opponent_draws(self._h, u.shape[1], ptr(u if u.size else None, C.c_double)), "gpf_upload_opponent_draws")
+
+    def upload_opponent_schedule(self, schedule, count):
+        """Geometric opponent, table source: int32 ``[n_lanes, k, 2]`` {waiting time, duration} (``k`` <= the schedule capacity) and the
+        number of entries of every lane -- what the opponent's reset sampled."""
+        cap = int(getattr(self, "_opp_cap", 0))
+        sch = np.asarray(schedule, dtype=np.int32).reshape(self.n_lanes, -1, 2)
+        if sch.shape[1] > cap:
+            raise ValueError(f"upload_opponent_schedule: {sch.shape[1]} entries per lane exceed the schedule capacity {cap}")
+        full = np.zeros((self.n_lanes, max(cap, 1), 2), dtype=np.int32)
+        full[:, :sch.shape[1]] = sch
+        cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(count, dtype=np.int32), (self.n_lanes,)))
+        check(self._lib.gpf_upload_opponent_schedule(self._h, ptr(full, C.c_int32), ptr(cnt, C.c_int32)), "gpf_upload_opponent_schedule")
+
+    def opponent_state(self, lane0: int = 0, n: Optional[int] = None) -> "OpponentState":
+        """The lanes' opponent state with ``opponent_attack_line`` (-1: none) / ``opponent_attack_duration`` of the last launch (synchronous)."""
+        lane0, n = self._range(lane0, n)
+        bud, rows = np.zeros(n, dtype=np.float64), np.zeros((n, OPP_STATE_INTS), dtype=np.int32)
+        check(self._lib.gpf_get_opponent_state(self._h, lane0, n, ptr(bud, C.c_double), ptr(rows, C.c_int32)), "gpf_get_opponent_state")
+        return OpponentState.from_rows(bud, rows)
+
+    def set_opponent_state(self, state: "OpponentState", lane0: int = 0):
+        bud = np.ascontiguousarray(state.budget, dtype=np.float64)
+        rows = np.ascontiguousarray(state.rows())
+        check(self._lib.gpf_set_opponent_state(self._h, int(lane0), len(bud), ptr(bud, C.c_double), ptr(rows, C.c_int32)), "gpf_set_opponent_state")
 
     def set_gen_renewable(self, renewable):
         """``gen_renewable`` mask (curtailment only acts on these generators); None switches curtailment off."""

@@ -432,6 +432,37 @@ class ShardedEngine:
     def topo_action_mask_host(self, lane0: int = 0, n=None):
         return np.concatenate([eng.topo_action_mask_host(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
 
+    # the opponent: the configuration goes to every device with the shard's lane_base, tables and per-lane state are cut by block
+    def set_opponent(self, kind=0, lines=(), **kw):
+        base = int(kw.pop("lane_base", 0))
+        for eng, (b0, _) in zip(self.engines, self.blocks):
+            if kind is None or int(kind) == 0:
+                eng.set_opponent(None)
+            else:
+                eng.set_opponent(kind, lines, lane_base=base + b0, **kw)
+
+    def upload_opponent_draws(self, draws):
+        u = np.asarray(draws).reshape(self.n_lanes, -1)
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.upload_opponent_draws(u[b0:b0 + bn])
+
+    def upload_opponent_schedule(self, schedule, count):
+        sch = np.asarray(schedule).reshape(self.n_lanes, -1, 2)
+        cnt = np.broadcast_to(np.asarray(count), (self.n_lanes,))
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.upload_opponent_schedule(sch[b0:b0 + bn], cnt[b0:b0 + bn])
+
+    def opponent_state(self, lane0: int = 0, n=None):
+        from .engine import OpponentState
+        parts = [eng.opponent_state(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
+        return OpponentState.from_rows(np.concatenate([p.budget for p in parts]), np.concatenate([p.rows() for p in parts]))
+
+    def set_opponent_state(self, state, lane0: int = 0):
+        from .engine import OpponentState
+        bud, rows = np.asarray(state.budget), state.rows()
+        for eng, l0, k, off in self._parts(lane0, len(bud)):
+            eng.set_opponent_state(OpponentState.from_rows(bud[off:off + k], rows[off:off + k]), lane0=l0)
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

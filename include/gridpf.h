@@ -497,6 +497,97 @@ int gpf_get_topo_action_areas(gpf_handle h, uint32_t* areas /* [n_act] */);
 int gpf_topo_action_mask(gpf_handle h, int32_t lane0, int32_t n, uint8_t* out_dev, int64_t row_stride);
 int gpf_get_topo_action_mask(gpf_handle h, int32_t lane0, int32_t n, uint8_t* host_out);
 
+/* ---- the opponent of the batched acting path (grid2op_amd/csrc/gridpf_opponent.hpp): the reference's OpponentSpace
+ * (Opponent/opponentSpace.py:144-249: budget, attack duration and attack cooldown) with one of its three single-area line opponents --
+ * RandomLineOpponent (Opponent/randomLineOpponent.py:94-106), WeightedRandomOpponent (Opponent/weightedRandomOpponent.py:139-164),
+ * GeometricOpponent (Opponent/geometricOpponent.py:169-293) -- run for every lane by ONE side kernel (opponent_prestep_kernel) queued after the
+ * topology pre-step and before the step of a ONE-STEP gpf_step_n launch, so that the attack is added after the agent's action and wins
+ * (Environment/baseEnv.py:3148-3170, called at :3839): the attacked line is forced out of the lane's topology row (both ends -1) at every
+ * step of the attack's duration, its line cooldown is raised to max(remaining duration, cooldown) before the step's own decrement (a fresh
+ * attack of duration 3 shows 2 in the next observation); the agent's legality was decided on the cooldowns from before the attack.
+ * The opponent reads the lane's rho and line_status RESULT rows of its last step (the observation at time t).  A lane with no completed
+ * step in its episode (steps survived = 0: a fresh lane, after gpf_reset_lanes, after an auto-reset) is the reference's `observation is
+ * None` call of env.reset(): its opponent is reset (OpponentSpace.reset, :96-106), nothing else happens, not even the budget increment.  A
+ * done lane without auto-reset is left alone.  The budget restates numpy's arithmetic: float32 until the first paid attack step, whose
+ * integer cost widens it to float64; float32 increments are then added in float64; a reset goes back to float32.
+ * Random numbers: the automaton consumes uniforms u in [0, 1) of a per-lane stream, one per event in event order:
+ *   WeightedRandom draws _next_attack_time : 1 + floor(u * attack_period);   RandomLine picks among n connected lines : the floor(u * n)-th
+ *   in attackable-list order;   WeightedRandom / Geometric pick a line : the first index whose cumulative float64 weight is > u * total
+ *   (RandomState.choice's cdf.searchsorted(u, side="right"));   Geometric samples its schedule (GPF_OPP_DRAWS_PHILOX only) :
+ *   max(1, ceil(log1p(-u) / log1p(-p))), waiting time and duration alternating (sample_attack_times_and_durations, :169-197).
+ *   GPF_OPP_DRAWS_TABLE  : gpf_upload_opponent_draws uploads draws[lanes][n_draw]; every lane has a cursor, set to 0 by the upload and NOT by
+ *                          a reset (a recorded run goes on across its resets); a lane whose cursor runs past the table stops attacking and
+ *                          raises the sticky GPF_OPP_FLAG_DRAWS_EXHAUSTED.  The Geometric schedule comes from gpf_upload_opponent_schedule.
+ *   GPF_OPP_DRAWS_PHILOX : Philox4x32-10, key (seed_lo, seed_hi), counter (draw index in the episode, the lane's opponent resets so far,
+ *                          lane + lane_base, 0), u = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53.  The kernel fills the lane's Geometric schedule
+ *                          itself when it resets the lane, up to schedule_cap attacks: if the capacity is reached the schedule ENDS there
+ *                          (sticky GPF_OPP_FLAG_SCHEDULE_CAPPED) -- size it for the episode (episode_max_time * hazard rate, with margin).
+ *   gpf_set_opponent         : NULL or kind GPF_OPP_NONE turns the opponent off (gpf_step_n then launches nothing for it).  Everything is
+ *                              validated before the device is touched: line ids in [0, n_line) and distinct, at least one line, init_budget
+ *                              >= 0 (opponentSpace.py:77), attack_period > 0 (weightedRandomOpponent.py:93), rho_normalization finite and > 0,
+ *                              hazard and recovery rates in (0, 1] (the rates of geometricOpponent.py:117-135 exist), pmax_pmin_ratio > 0,
+ *                              a finite episode_max_time > 0 (geometricOpponent.py:149-155), attack_duration / attack_cooldown >= 0,
+ *                              schedule_cap > 0.  Every lane's opponent starts reset; the sticky flags are cleared.
+ *   gpf_upload_opponent_draws    : table source; draws[n_lanes][n_draw] doubles in [0, 1); cursors back to 0.
+ *   gpf_upload_opponent_schedule : Geometric, table source; schedule[n_lanes][schedule_cap][2] = {waiting time, duration} and count[n_lanes]
+ *                                  entries (<= schedule_cap): what the opponent's reset sampled, for the lanes' NEXT resets too until replaced.
+ *   gpf_get_opponent_state   : budget[n] and state[n][GPF_OPP_STATE_INTS] of lanes [lane0, lane0 + n) (either may be NULL); entries
+ *                              GPF_OPP_S_INFO_LINE / _DURATION are info["opponent_attack_line"] (a line id, -1: none) and
+ *                              info["opponent_attack_duration"] of the last launch (baseEnv.py:3890-3892).  Synchronous.
+ *   gpf_set_opponent_state   : the same rows written (tests start from arbitrary states).
+ * gpf_step_n with an opponent set refuses n_steps != 1 (the choice needs the previous step's rho) and track_cooldown == 0 (the attacked
+ * line's cooldown is only counted down by a launch that maintains the line cooldowns).  gpf_copy_lanes copies the opponent state;
+ * gpf_fanout_n1 and gpf_simulate_batch never run the opponent and leave its state alone. */
+#define GPF_OPP_NONE 0
+#define GPF_OPP_RANDOM_LINE 1
+#define GPF_OPP_WEIGHTED_RANDOM 2
+#define GPF_OPP_GEOMETRIC 3
+#define GPF_OPP_DRAWS_TABLE 0
+#define GPF_OPP_DRAWS_PHILOX 1
+#define GPF_OPP_STATE_INTS 14
+#define GPF_OPP_S_BUDGET_IS_F32 0  /* the budget is still a numpy.float32 */
+#define GPF_OPP_S_DURATION 1       /* current_attack_duration */
+#define GPF_OPP_S_COOLDOWN 2       /* current_attack_cooldown */
+#define GPF_OPP_S_LINE 3           /* last_attack: the attacked line, -1 for None */
+#define GPF_OPP_S_PREVIOUS_FAILS 4
+#define GPF_OPP_S_NEXT_TIME 5      /* _next_attack_time; GPF_OPP_TIME_NONE for None (the reference counts it below zero after a refused attack) */
+#define GPF_OPP_S_COUNTER 6        /* Geometric: _attack_counter */
+#define GPF_OPP_S_N_SCHEDULE 7     /* Geometric: _number_of_attacks */
+#define GPF_OPP_S_CURSOR 8         /* draws consumed */
+#define GPF_OPP_S_EPISODE 9        /* resets of the lane's opponent so far */
+#define GPF_OPP_S_FLAGS 10         /* sticky GPF_OPP_FLAG_* */
+#define GPF_OPP_S_INFO_LINE 11
+#define GPF_OPP_S_INFO_DURATION 12
+#define GPF_OPP_TIME_NONE (-2147483647 - 1)
+#define GPF_OPP_FLAG_DRAWS_EXHAUSTED 1
+#define GPF_OPP_FLAG_SCHEDULE_CAPPED 2
+typedef struct gpf_opponent_desc {
+  int32_t kind;                        /* GPF_OPP_* */
+  int32_t n_lines;
+  const int32_t* line_ids;             /* [n_lines] attackable lines, in the order of the reference's lines_attacked */
+  const double* rho_normalization;     /* [n_lines] or NULL (ones): WeightedRandom */
+  int32_t attack_period;               /* WeightedRandom */
+  double attack_hazard_rate;           /* Geometric: 1 / (ts_per_hour * (attack_every_xxx_hour - average_attack_duration_hour)) */
+  double recovery_rate;                /*            1 / (ts_per_hour * (average_attack_duration_hour - minimum_attack_duration_hour)) */
+  int32_t recovery_minimum_duration;   /*            int(minimum_attack_duration_hour * ts_per_hour) */
+  double pmax_pmin_ratio;
+  int32_t episode_max_time;            /*            env.max_episode_duration() */
+  float init_budget;                   /* opponent_init_budget (numpy.float32 in the reference) */
+  float budget_per_ts;                 /* opponent_budget_per_ts */
+  int32_t attack_duration;             /* opponent_attack_duration */
+  int32_t attack_cooldown;             /* opponent_attack_cooldown */
+  int32_t draw_source;                 /* GPF_OPP_DRAWS_* */
+  uint32_t seed_lo;
+  uint32_t seed_hi;
+  int32_t lane_base;                   /* global index of lane 0 (a sharded engine draws what one engine would) */
+  int32_t schedule_cap;                /* Geometric: attacks per episode the lane's schedule can hold */
+} gpf_opponent_desc;
+int gpf_set_opponent(gpf_handle h, const gpf_opponent_desc* desc);
+int gpf_upload_opponent_draws(gpf_handle h, int32_t n_draw, const double* draws);
+int gpf_upload_opponent_schedule(gpf_handle h, const int32_t* schedule, const int32_t* count);
+int gpf_get_opponent_state(gpf_handle h, int32_t lane0, int32_t n, double* budget, int32_t* state);
+int gpf_set_opponent_state(gpf_handle h, int32_t lane0, int32_t n, const double* budget, const int32_t* state);
+
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
  * Observation/baseObservation.py:4464-4540; with subtract / divide what gym_compat.BoxGymObsSpace(attr_to_keep, subtract, divide) puts on
