@@ -33,6 +33,8 @@ EXPORTED_SYMBOLS = [
     "gpf_set_topo_areas", "gpf_set_topo_slots", "gpf_get_topo_action_areas",
     "gpf_set_obs_clock", "gpf_set_obs_spec", "gpf_obs_vector", "gpf_obs_vector_trajectory", "gpf_get_obs_vector",
     "gpf_set_opponent", "gpf_upload_opponent_draws", "gpf_upload_opponent_schedule", "gpf_get_opponent_state", "gpf_set_opponent_state",
+    "gpf_set_opponent_areas", "gpf_upload_opponent_area_schedule", "gpf_get_opponent_area_state", "gpf_set_opponent_area_state",
+    "gpf_get_opponent_attack_lines",
 ]
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
@@ -211,6 +213,11 @@ def lib() -> C.CDLL:
     L.gpf_upload_opponent_schedule.argtypes = [h, _ip, _ip]
     L.gpf_get_opponent_state.argtypes = [h, i32, i32, _dp, _ip]
     L.gpf_set_opponent_state.argtypes = [h, i32, i32, _dp, _ip]
+    L.gpf_set_opponent_areas.argtypes = [h, i32, _ip]
+    L.gpf_upload_opponent_area_schedule.argtypes = [h, _ip, _ip]
+    L.gpf_get_opponent_area_state.argtypes = [h, i32, i32, _ip]
+    L.gpf_set_opponent_area_state.argtypes = [h, i32, i32, _ip]
+    L.gpf_get_opponent_attack_lines.argtypes = [h, i32, i32, C.POINTER(C.c_uint8)]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

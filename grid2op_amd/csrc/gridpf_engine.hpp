@@ -241,6 +241,12 @@ struct gpf_engine {
   int opp_n_draw = 0;
   DevArr<int> opp_lines, opp_state, opp_sched;
   DevArr<double> opp_norm, opp_budget, opp_draws;
+  // ... and its areas (gpf_set_opponent_areas): the last validated descriptor's kind and lines on the host (kept on a header-only handle
+  // too, so that everything about areas can be refused there), the lines grouped by area with each area's offset, and the per-(lane, area)
+  // state and schedules.  opp_n_area 0: the single-area opponent.
+  int opp_host_kind = 0, opp_n_area = 0;
+  std::vector<int> opp_host_lines, opp_area_lines_host, opp_area_off;   // opp_area_off: [n_area + 1]
+  DevArr<int> opp_area_lines, opp_area_tab, opp_area_state, opp_area_sched;   // opp_area_tab: [2][n_area] offsets, counts
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;

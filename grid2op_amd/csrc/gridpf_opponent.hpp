@@ -15,6 +15,9 @@
 //   RandomLine picks among n connected lines      the floor(u * n)-th in attackable-list order
 //   WeightedRandom / Geometric pick a line        the first index whose cumulative float64 weight is > u * total
 //   Geometric samples its schedule (Philox only)  max(1, ceil(log1p(-u) / log1p(-p))), waiting time and duration alternating
+// With areas set (gpf_set_opponent_areas) the lane plays GeometricOpponentMultiArea (Opponent/geometricOpponentMultiArea.py:88-149): one
+// Geometric sub-opponent per area, each with its slice of the attackable list, its schedule and a row of OPP_AREA_STATE_INTS ints; all
+// areas draw from the lane's ONE stream, in area order (opp_area_*, opponent_area_prestep_kernel).
 // Three parts: the scalar rules (plain C++, the ONE statement of each rule, run by the kernel on one thread per lane and by the host
 // emulator of tests/native/), the line choice (opp_weight + the threshold rule, summed by a wavefront scan on the device and by a plain
 // loop in the emulator), and the kernel.  Without hipcc only the first two exist: the header then needs no HIP header.
@@ -51,6 +54,16 @@ constexpr int OS_INFO_LINE = 11;     // info["opponent_attack_line"] of the last
 constexpr int OS_INFO_DURATION = 12; // info["opponent_attack_duration"] of the last launch
 constexpr int OPP_TIME_NONE = INT32_MIN;
 constexpr int OPP_FLAG_DRAWS_EXHAUSTED = 1, OPP_FLAG_SCHEDULE_CAPPED = 2;
+// per (lane, area) state with areas set (= GPF_OPP_AS_* of include/gridpf.h); the lane's row then keeps OS_F32, OS_DURATION, OS_COOLDOWN,
+// OS_PREV_FAILS, OS_CURSOR, OS_EPISODE, OS_FLAGS; OS_LINE / OS_INFO_LINE hold the accepted line of the lowest attacking area, OS_INFO_DURATION 1 or 0
+constexpr int OPP_MAX_AREAS = 16;
+constexpr int OPP_AREA_STATE_INTS = 8;
+constexpr int OAS_COUNTER = 0;        // _new_attack_time_counters[a] (-1: the area is free)
+constexpr int OAS_LINE = 1;           // _previous_attacks[a]: the line, -1 for None
+constexpr int OAS_NEXT_TIME = 2;      // the sub-opponent's _next_attack_time
+constexpr int OAS_ATTACK_COUNTER = 3; //                    _attack_counter
+constexpr int OAS_N_SCHED = 4;        //                    _number_of_attacks
+constexpr int OAS_INFO_LINE = 5;      // the area's line in the ACCEPTED attack of the last launch (-1: none)
 
 struct OppCfg {
   int kind, n_att;
@@ -113,7 +126,7 @@ GPF_OPP_HD inline int opp_geometric(double u, double p) {
 
 // GeometricOpponent.sample_attack_times_and_durations (geometricOpponent.py:169-197) from the lane's own stream, up to sched_cap attacks:
 // when the capacity is reached the schedule ends there (sticky OPP_FLAG_SCHEDULE_CAPPED)
-GPF_OPP_HD inline void opp_sample_schedule(const OppCfg& c, const OppLane& L) {
+GPF_OPP_HD inline void opp_sample_schedule_into(const OppCfg& c, const OppLane& L, int* sched, int* n_sched) {
   int n = 0;
   long long t = 0;
   while (t < c.episode_len) {
@@ -125,27 +138,29 @@ GPF_OPP_HD inline void opp_sample_schedule(const OppCfg& c, const OppLane& L) {
     if (t < c.episode_len) {
       if (!opp_draw(c, L, u)) break;
       const int dur = c.min_dur + opp_geometric(u, c.recovery);
-      L.sched[2 * n] = wait; L.sched[2 * n + 1] = dur;
+      sched[2 * n] = wait; sched[2 * n + 1] = dur;
       ++n;
       t += dur;
     }
   }
-  L.st[OS_N_SCHED] = n;
+  *n_sched = n;
 }
+GPF_OPP_HD inline void opp_sample_schedule(const OppCfg& c, const OppLane& L) { opp_sample_schedule_into(c, L, L.sched, &L.st[OS_N_SCHED]); }
 
 // OpponentSpace.reset (opponentSpace.py:96-106) + the opponent's reset: what env.reset() leaves.  The table cursor and an uploaded schedule
 // stay (the recorded draws of a run go on across its resets); the Philox stream starts its next episode.
-GPF_OPP_HD inline void opp_reset(const OppCfg& c, const OppLane& L) {
+GPF_OPP_HD inline void opp_reset_space(const OppCfg& c, const OppLane& L) {
   int* s = L.st;
   *L.budget = (double)c.init_budget; s[OS_F32] = 1;
   s[OS_DURATION] = 0; s[OS_COOLDOWN] = c.attack_cooldown; s[OS_LINE] = -1; s[OS_PREV_FAILS] = 0;
   s[OS_NEXT_TIME] = OPP_TIME_NONE; s[OS_COUNTER] = 0;
   s[OS_EPISODE] += 1;
   s[OS_INFO_LINE] = -1; s[OS_INFO_DURATION] = 0;
-  if (c.source == OPP_DRAWS_PHILOX) {
-    s[OS_CURSOR] = 0;
-    if (c.kind == OPP_GEOMETRIC) opp_sample_schedule(c, L);
-  }
+  if (c.source == OPP_DRAWS_PHILOX) s[OS_CURSOR] = 0;
+}
+GPF_OPP_HD inline void opp_reset(const OppCfg& c, const OppLane& L) {
+  opp_reset_space(c, L);
+  if (c.source == OPP_DRAWS_PHILOX && c.kind == OPP_GEOMETRIC) opp_sample_schedule(c, L);
 }
 
 // what the scalar part asks of the line choice
@@ -154,15 +169,38 @@ constexpr int OPP_SEL_KTH = 1;       // the first index at which the count of co
 constexpr int OPP_SEL_CDF = 2;       // the first index at which the cumulative weight exceeds u * total
 struct OppAsk { int asked, sel, line, duration; double u; };    // duration -1: None
 
+// OpponentSpace.attack's update of its variables (opponentSpace.py:183-185) on a budget and a lane row
+GPF_OPP_HD inline void opp_space_tick(const OppCfg& c, double* budget, int* s) {
+  // budget += budget_per_timestep: float32 + float32 while the budget is one (the double sum rounded once), float64 + float32 afterwards
+  const double sum = *budget + (double)c.budget_per_ts;
+  *budget = s[OS_F32] ? (double)(float)sum : sum;
+  s[OS_DURATION] = s[OS_DURATION] > 1 ? s[OS_DURATION] - 1 : 0;
+  s[OS_COOLDOWN] = s[OS_COOLDOWN] > 1 ? s[OS_COOLDOWN] - 1 : 0;
+}
+
+// GeometricOpponent.attack up to its draw of a line (geometricOpponent.py:234-293) on one opponent's _next_attack_time, _attack_counter
+// and schedule of n entries (the lane's own, or an area's); c.lines / c.n_att are that opponent's attackable list
+GPF_OPP_HD inline void opp_geometric_attack(const OppCfg& c, const OppLane& L, int prev_fails, int* next_time, int* counter, int n, const int* sched,
+                                            int n_conn, OppAsk& a) {
+  const int k = *counter;
+  if (k >= n) return;
+  if (prev_fails) *next_time = sched[2 * k] + sched[2 * (k > 0 ? k - 1 : n - 1) + 1];   // (index -1 of the reference's array: its last entry)
+  if (*next_time == OPP_TIME_NONE) *next_time = 1 + sched[2 * k];
+  const int dur = sched[2 * k + 1];
+  *next_time -= 1;
+  if (*next_time > 0) return;
+  *counter = k + 1;                                                  // the attack is launched
+  if (n_conn != c.n_att) return;                                     // `~status.all()`: given up when ANY attackable line is out
+  if (c.n_att == 1) { a.line = c.lines[0]; a.duration = dur; return; }
+  if (!opp_draw(c, L, a.u)) return;
+  a.sel = OPP_SEL_CDF; a.duration = dur;
+}
+
 // OpponentSpace.attack up to the opponent's choice (opponentSpace.py:183-201) and the opponent's attack() up to its draw of a line.
 // n_conn: connected attackable lines in the observation; w_pos: WeightedRandom's sum of weights is > 0.
 GPF_OPP_HD inline void opp_decide(const OppCfg& c, const OppLane& L, int n_conn, bool w_pos, OppAsk& a) {
   int* s = L.st;
-  // budget += budget_per_timestep: float32 + float32 while the budget is one (the double sum rounded once), float64 + float32 afterwards
-  const double sum = *L.budget + (double)c.budget_per_ts;
-  *L.budget = s[OS_F32] ? (double)(float)sum : sum;
-  s[OS_DURATION] = s[OS_DURATION] > 1 ? s[OS_DURATION] - 1 : 0;
-  s[OS_COOLDOWN] = s[OS_COOLDOWN] > 1 ? s[OS_COOLDOWN] - 1 : 0;
+  opp_space_tick(c, L.budget, s);
   a.asked = 0; a.sel = OPP_SEL_NONE; a.line = -1; a.duration = -1; a.u = 0.0;
   if (s[OS_DURATION] > 0) { a.line = s[OS_LINE]; return; }           // the last attack continues
   if (s[OS_COOLDOWN] > c.attack_cooldown) return;                    // minimum time between two attacks not met
@@ -182,18 +220,7 @@ GPF_OPP_HD inline void opp_decide(const OppCfg& c, const OppLane& L, int n_conn,
     if (s[OS_NEXT_TIME] > 0 || n_conn == 0 || !w_pos || !opp_draw(c, L, a.u)) return;
     a.sel = OPP_SEL_CDF; a.duration = -1;
   } else if (c.kind == OPP_GEOMETRIC) {
-    const int k = s[OS_COUNTER], n = s[OS_N_SCHED];
-    if (k >= n) return;
-    if (s[OS_PREV_FAILS]) s[OS_NEXT_TIME] = L.sched[2 * k] + L.sched[2 * (k > 0 ? k - 1 : n - 1) + 1];   // (index -1 of the reference's array: its last entry)
-    if (s[OS_NEXT_TIME] == OPP_TIME_NONE) s[OS_NEXT_TIME] = 1 + L.sched[2 * k];
-    const int dur = L.sched[2 * k + 1];
-    s[OS_NEXT_TIME] -= 1;
-    if (s[OS_NEXT_TIME] > 0) return;
-    s[OS_COUNTER] = k + 1;                                           // the attack is launched
-    if (n_conn != c.n_att) return;                                   // `~status.all()`: given up when ANY attackable line is out
-    if (c.n_att == 1) { a.line = c.lines[0]; a.duration = dur; return; }
-    if (!opp_draw(c, L, a.u)) return;
-    a.sel = OPP_SEL_CDF; a.duration = dur;
+    opp_geometric_attack(c, L, s[OS_PREV_FAILS], &s[OS_NEXT_TIME], &s[OS_COUNTER], s[OS_N_SCHED], L.sched, n_conn, a);
   }
 }
 
@@ -272,6 +299,140 @@ inline int opp_prestep_serial(const OppCfg& c, const OppLane& L, int steps_survi
   return 1;
 }
 
+// ---- GeometricOpponentMultiArea (geometricOpponentMultiArea.py:88-149) under OpponentSpace.attack ------------------------------------
+// the areas of a launch: area a attacks lines[offset[a] .. offset[a] + count[a]) (its entries of the descriptor's list, in that order)
+struct OppAreas {
+  int n_area;
+  const int* lines;          // [n_att] the attackable lines grouped by area
+  const int* offset;         // [n_area]
+  const int* count;          // [n_area]
+};
+// one lane's area rows
+struct OppAreaLane {
+  int* st;                   // [n_area][OPP_AREA_STATE_INTS]
+  int* sched;                // [n_area][sched_cap][2]
+};
+
+// area a's view of the configuration: the sub-opponent's attackable list
+GPF_OPP_HD inline OppCfg opp_area_cfg(const OppCfg& c, const OppAreas& A, int a) {
+  OppCfg ca = c;
+  ca.lines = A.lines + A.offset[a]; ca.n_att = A.count[a];
+  return ca;
+}
+
+// GeometricOpponentMultiArea.reset (:88-92) under OpponentSpace.reset: counters to -1, every sub-opponent reset (with the Philox source the
+// areas sample their schedules in area order from the lane's stream); _previous_attacks (OAS_LINE) stays as it is, as in the reference
+GPF_OPP_HD inline void opp_area_reset(const OppCfg& c, const OppLane& L, const OppAreas& A, const OppAreaLane& R) {
+  opp_reset_space(c, L);
+  for (int a = 0; a < A.n_area; ++a) {
+    int* r = R.st + a * OPP_AREA_STATE_INTS;
+    r[OAS_COUNTER] = -1; r[OAS_NEXT_TIME] = OPP_TIME_NONE; r[OAS_ATTACK_COUNTER] = 0; r[OAS_INFO_LINE] = -1;
+    if (c.source == OPP_DRAWS_PHILOX) opp_sample_schedule_into(c, L, R.sched + (size_t)a * c.sched_cap * 2, &r[OAS_N_SCHED]);
+  }
+}
+
+// OpponentSpace.attack up to its call of the opponent; returns 1 when the opponent is asked.  The returned duration of the multi-area
+// opponent is always 1, so the space asks at every step; the other two branches are the reference's `tell_attack_continues` of the
+// multi-area opponent ("I should not get there !"): here no area moves and nothing is attacked.
+GPF_OPP_HD inline int opp_area_begin(const OppCfg& c, const OppLane& L) {
+  opp_space_tick(c, L.budget, L.st);
+  return L.st[OS_DURATION] == 0 && L.st[OS_COOLDOWN] <= c.attack_cooldown ? 1 : 0;
+}
+
+// one area's turn of GeometricOpponentMultiArea.attack (:127-148) up to its sub-opponent's draw of a line; ca: opp_area_cfg.
+// a.asked: the area was free and its sub-opponent was called (else a.line is the line it goes on holding)
+GPF_OPP_HD inline void opp_area_decide(const OppCfg& ca, const OppLane& L, int* r, const int* sched, int n_conn, OppAsk& a) {
+  a.asked = 0; a.sel = OPP_SEL_NONE; a.line = -1; a.duration = -1; a.u = 0.0;
+  r[OAS_COUNTER] = r[OAS_COUNTER] >= 0 ? r[OAS_COUNTER] - 1 : -1;
+  if (r[OAS_COUNTER] >= 0) { r[OAS_NEXT_TIME] = OPP_TIME_NONE; a.line = r[OAS_LINE]; return; }   // the sub-opponent's tell_attack_continues
+  a.asked = 1;
+  opp_geometric_attack(ca, L, L.st[OS_PREV_FAILS], &r[OAS_NEXT_TIME], &r[OAS_ATTACK_COUNTER], r[OAS_N_SCHED], sched, n_conn, a);
+}
+
+// ... and from the sub-opponent's answer on: an attack of duration d books the area for d more steps (the line is held d + 1 steps)
+GPF_OPP_HD inline void opp_area_book(int* r, const OppAsk& a) {
+  if (!a.asked) return;
+  if (a.line >= 0) r[OAS_COUNTER] = a.duration;
+  r[OAS_LINE] = a.line;
+}
+
+// OpponentSpace.attack from the multi-area opponent's answer on (opponentSpace.py:202-249): the answer is the union of the areas' lines with
+// duration 1, its cost one unit per line (baseActionBudget.py:55-56); a refused attack leaves the areas' bookings as they are
+GPF_OPP_HD inline void opp_area_finish(const OppCfg& c, const OppLane& L, const OppAreas& A, const OppAreaLane& R, int asked) {
+  int* s = L.st;
+  int n = 0, first = -1;
+  if (asked) {
+    for (int a = 0; a < A.n_area; ++a) {
+      const int l = R.st[a * OPP_AREA_STATE_INTS + OAS_LINE];
+      if (l >= 0) { if (first < 0) first = l; ++n; }
+    }
+    int fails = 0;
+    if (1 > c.max_duration) { n = 0; fails = 1; }
+    if ((double)n > *L.budget) { n = 0; fails = 1; }
+    if (n > 0) { s[OS_DURATION] = 1; s[OS_COOLDOWN] += c.attack_cooldown; }
+    s[OS_PREV_FAILS] = fails;
+  } else {
+    s[OS_PREV_FAILS] = 0;
+  }
+  if (n > 0) { *L.budget -= (double)n; s[OS_F32] = 0; }               // the integer cost of an attack widens the budget to float64
+  for (int a = 0; a < A.n_area; ++a) {
+    int* r = R.st + a * OPP_AREA_STATE_INTS;
+    r[OAS_INFO_LINE] = n > 0 ? r[OAS_LINE] : -1;
+  }
+  if (n == 0) first = -1;
+  s[OS_LINE] = first;
+  s[OS_INFO_LINE] = first;
+  s[OS_INFO_DURATION] = n > 0 ? 1 : 0;
+}
+
+// BaseEnv._aux_handle_attack (baseEnv.py:3158-3169) for every line of the accepted union: out of the topology row, cooldown max(1, cooldown)
+GPF_OPP_HD inline void opp_area_apply(const OppAreas& A, const OppAreaLane& R, int* topo_row, int* cooldown_row, const int* or_pos, const int* ex_pos) {
+  for (int a = 0; a < A.n_area; ++a) {
+    const int line = R.st[a * OPP_AREA_STATE_INTS + OAS_INFO_LINE];
+    if (line < 0) continue;
+    topo_row[or_pos[line]] = -1; topo_row[ex_pos[line]] = -1;
+    if (cooldown_row[line] < 1) cooldown_row[line] = 1;
+  }
+}
+
+// One lane's pre-step with areas, with plain loops (the host emulator; opponent_area_prestep_kernel runs the same rules with the sums on a
+// wavefront).  Returns 1 when the lane's opponent ran.
+inline int opp_area_prestep_serial(const OppCfg& c, const OppLane& L, const OppAreas& A, const OppAreaLane& R, int steps_survived, int done,
+                                   const float* rho, const unsigned char* status, int* topo_row, int* cooldown_row, const int* or_pos,
+                                   const int* ex_pos) {
+  if (steps_survived == 0) { opp_area_reset(c, L, A, R); return 0; }
+  if (done) return 0;
+  const int asked = opp_area_begin(c, L);
+  for (int ar = 0; asked && ar < A.n_area; ++ar) {
+    const OppCfg ca = opp_area_cfg(c, A, ar);
+    int* r = R.st + ar * OPP_AREA_STATE_INTS;
+    int n_conn = 0;
+    for (int i = 0; i < ca.n_att; ++i) n_conn += status[ca.lines[i]] ? 1 : 0;
+    OppAsk a;
+    opp_area_decide(ca, L, r, R.sched + (size_t)ar * c.sched_cap * 2, n_conn, a);
+    if (a.sel != OPP_SEL_NONE) {
+      double total = 0.0;
+      for (int i = 0; i < ca.n_att; ++i) total += opp_weight(ca, a.sel, rho, status, i);
+      const double thr = opp_threshold(a, total);
+      double cum = 0.0;
+      int last = -1;
+      a.line = -1;
+      for (int i = 0; i < ca.n_att && a.line < 0; ++i) {
+        const double w = opp_weight(ca, a.sel, rho, status, i);
+        cum += w;
+        if (w > 0.0) last = i;
+        if (cum > thr) a.line = ca.lines[i];
+      }
+      if (a.line < 0 && last >= 0) a.line = ca.lines[last];
+    }
+    opp_area_book(r, a);
+  }
+  opp_area_finish(c, L, A, R, asked);
+  opp_area_apply(A, R, topo_row, cooldown_row, or_pos, ex_pos);
+  return 1;
+}
+
+
 #ifdef __HIPCC__
 // the lanes' rows the kernel touches
 struct OppDev {
@@ -345,6 +506,58 @@ __global__ __launch_bounds__(64 * OPP_WPB) void opponent_prestep_kernel(OppCfg c
   if (tid == 0) {
     opp_finish(c, L, a.asked, a.line, a.duration);
     opp_apply(L, d.topo + (size_t)lane * d.dim_topo, d.cooldown + (size_t)lane * d.n_line, d.or_pos, d.ex_pos);
+  }
+}
+// the lanes' area rows
+struct OppAreaDev { int* state; int* sched; };
+
+// The pre-step with areas: the same shape (one wavefront per lane, OPP_WPB lanes per block, no LDS, one launch per step whatever the number
+// of areas).  The wavefront walks the areas in a wave-uniform loop, in area order -- the order in which they consume the lane's stream:
+// count and scan on the area's slice of the attackable list, the scalar rules on thread 0; thread 0 then applies the space's combination
+// and forces every accepted line out.  Reads and writes what opponent_prestep_kernel does, plus the lane's area rows.
+__global__ __launch_bounds__(64 * OPP_WPB) void opponent_area_prestep_kernel(OppCfg c, OppDev d, OppAreas A, OppAreaDev ad, int n_lanes) {
+  const int tid = threadIdx.x & 63;
+  const int lane = blockIdx.x * OPP_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (lane >= n_lanes) return;                                       // (no block-wide barrier below)
+  OppLane L;
+  L.budget = d.budget + lane; L.st = d.state + (size_t)lane * OPP_STATE_INTS;
+  L.draws = d.draws ? d.draws + (size_t)lane * c.n_draw : nullptr;
+  L.sched = nullptr;
+  L.global_lane = lane + c.lane_base;
+  OppAreaLane R;
+  R.st = ad.state + (size_t)lane * A.n_area * OPP_AREA_STATE_INTS;
+  R.sched = ad.sched + (size_t)lane * A.n_area * c.sched_cap * 2;
+  if (d.episode[(size_t)lane * 2] == 0) { if (tid == 0) opp_area_reset(c, L, A, R); return; }
+  if (d.done[lane]) return;
+  const float* rho = d.rho + (size_t)lane * d.n_line;
+  const unsigned char* status = d.line_status + (size_t)lane * d.n_line;
+  int asked = 0;
+  if (tid == 0) asked = opp_area_begin(c, L);
+  asked = __shfl(asked, 0);
+  if (asked)
+    for (int ar = 0; ar < A.n_area; ++ar) {
+      const OppCfg ca = opp_area_cfg(c, A, ar);
+      int* r = R.st + ar * OPP_AREA_STATE_INTS;
+      int n_conn = 0;
+      for (int c0 = 0; c0 < ca.n_att; c0 += 64) {
+        const int idx = c0 + tid;
+        n_conn += __popcll(__ballot(idx < ca.n_att && status[ca.lines[idx]] != 0));
+      }
+      OppAsk a;
+      a.asked = 0; a.sel = OPP_SEL_NONE; a.line = -1; a.duration = -1; a.u = 0.0;
+      if (tid == 0) opp_area_decide(ca, L, r, R.sched + (size_t)ar * c.sched_cap * 2, n_conn, a);
+      a.sel = __shfl(a.sel, 0); a.u = __shfl(a.u, 0);
+      if (a.sel != OPP_SEL_NONE) {
+        const double total = opp_wave_scan(ca, a.sel, rho, status, tid, false, 0.0, nullptr);
+        int idx = -1;
+        opp_wave_scan(ca, a.sel, rho, status, tid, true, opp_threshold(a, total), &idx);
+        a.line = idx >= 0 ? ca.lines[idx] : -1;
+      }
+      if (tid == 0) opp_area_book(r, a);
+    }
+  if (tid == 0) {
+    opp_area_finish(c, L, A, R, asked);
+    opp_area_apply(A, R, d.topo + (size_t)lane * d.dim_topo, d.cooldown + (size_t)lane * d.n_line, d.or_pos, d.ex_pos);
   }
 }
 #endif  // __HIPCC__

@@ -43,6 +43,7 @@ OPP_DRAWS_TABLE, OPP_DRAWS_PHILOX = 0, 1
 OPP_STATE_INTS = 14
 OPP_TIME_NONE = -2 ** 31
 OPP_FLAG_DRAWS_EXHAUSTED, OPP_FLAG_SCHEDULE_CAPPED = 1, 2
+OPP_MAX_AREAS, OPP_AREA_STATE_INTS = 16, 8
 OPP_KIND_OF_CLASS = {"RandomLineOpponent": OPP_RANDOM_LINE, "WeightedRandomOpponent": OPP_WEIGHTED_RANDOM, "GeometricOpponent": OPP_GEOMETRIC}
 
 
@@ -80,6 +81,32 @@ class OpponentState:
         return out
 
 
+@dataclass
+class OpponentAreaState:
+    """Per-(lane, area) state of the multi-area opponent (`PowerFlowEngine.opponent_area_state`), every field ``[n, n_area]``: the area's
+    ``_new_attack_time_counters`` entry (-1: free), its ``_previous_attacks`` line (-1: None), its sub-opponent's ``_next_attack_time``
+    (`OPP_TIME_NONE` for None), ``_attack_counter`` and ``_number_of_attacks``, and the area's line in the accepted attack of the last
+    launch (-1: none)."""
+    counter: np.ndarray
+    line: np.ndarray
+    next_attack_time: np.ndarray
+    attack_counter: np.ndarray
+    n_schedule: np.ndarray
+    opponent_attack_line: np.ndarray
+
+    _COLS = ("counter", "line", "next_attack_time", "attack_counter", "n_schedule", "opponent_attack_line")
+
+    @classmethod
+    def from_rows(cls, rows):
+        return cls(*(rows[:, :, k].copy() for k in range(len(cls._COLS))))
+
+    def rows(self) -> np.ndarray:
+        out = np.zeros(np.shape(self.counter) + (OPP_AREA_STATE_INTS,), dtype=np.int32)
+        for k, name in enumerate(self._COLS):
+            out[:, :, k] = getattr(self, name)
+        return out
+
+
 def opponent_config(model, opponent_class, kwargs_opponent=None, opponent_init_budget=0.0, opponent_budget_per_ts=0.0,
                     opponent_attack_duration=0, opponent_attack_cooldown=99999, delta_time_seconds=300.0, max_episode_duration=None,
                     draw_source=OPP_DRAWS_PHILOX, seed=0, lane_base=0, schedule_cap=None) -> dict:
@@ -89,7 +116,8 @@ def opponent_config(model, opponent_class, kwargs_opponent=None, opponent_init_b
     GeometricOpponent.init does (Opponent/geometricOpponent.py:111-135) and its errors are raised with its reasons."""
     name = opponent_class if isinstance(opponent_class, str) else getattr(opponent_class, "__name__", str(opponent_class))
     if name not in OPP_KIND_OF_CLASS:
-        raise ValueError(f"opponent_config: {name} is not one of {sorted(OPP_KIND_OF_CLASS)} (the single-area line opponents)")
+        raise ValueError(f"opponent_config: {name} is not one of {sorted(OPP_KIND_OF_CLASS)} (the single-area line opponents; "
+                         "GeometricOpponentMultiArea: opponent_area_config)")
     kw = dict(kwargs_opponent or {})
     names = [str(x) for x in np.asarray(model.name_line)]
     lines = []
@@ -124,6 +152,29 @@ def opponent_config(model, opponent_class, kwargs_opponent=None, opponent_init_b
                    recovery_minimum_duration=int(mini * ts_per_hour), pmax_pmin_ratio=float(kw.get("pmax_pmin_ratio", 4)),
                    episode_max_time=int(max_episode_duration), schedule_cap=int(schedule_cap))
     return out
+
+
+def opponent_area_config(model, kwargs_opponent=None, opponent_init_budget=0.0, opponent_budget_per_ts=0.0, opponent_attack_duration=0,
+                         opponent_attack_cooldown=99999, **kw):
+    """A reference-style configuration of ``GeometricOpponentMultiArea`` (``lines_attacked``: a list of lists, one per area) as
+    ``(set_opponent keywords, area_of_line)``: the lines of all areas in area order with the rates `opponent_config` derives for a
+    GeometricOpponent, and the area of each of them for `PowerFlowEngine.set_opponent_areas`.  ``lines_attacked`` None is the reference's
+    warning case (Opponent/geometricOpponentMultiArea.py:69-71): the opponent is deactivated, ``(dict(kind=OPP_NONE), None)``.  Further
+    keywords are those of `opponent_config`."""
+    kwo = dict(kwargs_opponent or {})
+    areas = kwo.get("lines_attacked")
+    if areas is None:
+        import warnings
+        warnings.warn("opponent_area_config: GeometricOpponentMultiArea: no area provided, the opponent will be deactivated.")
+        return dict(kind=OPP_NONE), None
+    areas = [list(a) for a in areas]
+    if any(isinstance(a, str) for a in kwo["lines_attacked"]):
+        raise ValueError("opponent_area_config: lines_attacked must be a list of lists of line names, one list per area")
+    kwo["lines_attacked"] = [l for a in areas for l in a]
+    out = opponent_config(model, "GeometricOpponent", kwo, opponent_init_budget, opponent_budget_per_ts, opponent_attack_duration,
+                          opponent_attack_cooldown, **kw)
+    return out, [a for a, names in enumerate(areas) for _ in names]
+
 
 _OUT_FIELDS = [
     ("p_or", "n_line"), ("q_or", "n_line"), ("v_or", "n_line"), ("a_or", "n_line"), ("theta_or", "n_line"),
@@ -776,7 +827,7 @@ class PowerFlowEngine:
         global index of lane 0.  Launches then need ``n_steps = 1`` and ``track_cooldown``."""
         if kind is None or int(kind) == OPP_NONE:
             check(self._lib.gpf_set_opponent(self._h, None), "gpf_set_opponent")
-            self._opp_cap = 0
+            self._opp_cap = self._opp_n_area = 0
             return
         ids = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1)
         norm = None if rho_normalization is None else np.ascontiguousarray(rho_normalization, dtype=np.float64).reshape(-1)
@@ -790,7 +841,7 @@ class PowerFlowEngine:
         d.attack_duration, d.attack_cooldown, d.draw_source = int(attack_duration), int(attack_cooldown), int(draw_source)
         d.seed_lo, d.seed_hi, d.lane_base, d.schedule_cap = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(lane_base), int(schedule_cap)
         check(self._lib.gpf_set_opponent(self._h, C.byref(d)), "gpf_set_opponent")
-        self._opp_cap = int(schedule_cap) if int(kind) == OPP_GEOMETRIC else 0
+        self._opp_cap, self._opp_n_area = (int(schedule_cap) if int(kind) == OPP_GEOMETRIC else 0), 0
 
     def upload_opponent_draws(self, draws):
         """Table source: float64 ``[n_lanes, n_draw]`` uniforms in [0, 1), consumed per lane in event order; the cursors go back to 0."""
@@ -820,6 +871,46 @@ class PowerFlowEngine:
         bud = np.ascontiguousarray(state.budget, dtype=np.float64)
         rows = np.ascontiguousarray(state.rows())
         check(self._lib.gpf_set_opponent_state(self._h, int(lane0), len(bud), ptr(bud, C.c_double), ptr(rows, C.c_int32)), "gpf_set_opponent_state")
+
+    # ---- the multi-area opponent (include/gridpf.h gpf_set_opponent_areas) ----------------------------
+    def set_opponent_areas(self, area_of_line):
+        """GeometricOpponentMultiArea: ``area_of_line[i]`` is the area of entry ``i`` of the ``lines`` of `set_opponent` (kind
+        `OPP_GEOMETRIC`); every area is a Geometric opponent of its own on the lane's one stream of draws (`opponent_area_config` builds
+        both from a reference-style configuration).  None (or empty): back to the single-area opponent.  Every lane's opponent starts reset."""
+        a = np.zeros(0, np.int32) if area_of_line is None else np.ascontiguousarray(area_of_line, dtype=np.int32).reshape(-1)
+        n_area = int(a.max()) + 1 if a.size else 0
+        check(self._lib.gpf_set_opponent_areas(self._h, n_area, ptr(a if a.size else None, C.c_int32)), "gpf_set_opponent_areas")
+        self._opp_n_area = n_area
+
+    def upload_opponent_area_schedule(self, schedule, count):
+        """Table source: int32 ``[n_lanes, n_area, k, 2]`` {waiting time, duration} (``k`` <= the schedule capacity) and ``[n_lanes, n_area]``
+        entries -- what every area's reset sampled."""
+        cap, na = int(getattr(self, "_opp_cap", 0)), int(getattr(self, "_opp_n_area", 0))
+        sch = np.asarray(schedule, dtype=np.int32)
+        sch = np.broadcast_to(sch, (self.n_lanes,) + sch.shape[-3:]) if sch.ndim == 3 else sch.reshape(self.n_lanes, na, -1, 2)
+        if sch.shape[2] > cap:
+            raise ValueError(f"upload_opponent_area_schedule: {sch.shape[2]} entries per area exceed the schedule capacity {cap}")
+        full = np.zeros((self.n_lanes, na, max(cap, 1), 2), dtype=np.int32)
+        full[:, :, :sch.shape[2]] = sch
+        cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(count, dtype=np.int32), (self.n_lanes, na)))
+        check(self._lib.gpf_upload_opponent_area_schedule(self._h, ptr(full, C.c_int32), ptr(cnt, C.c_int32)), "gpf_upload_opponent_area_schedule")
+
+    def opponent_area_state(self, lane0: int = 0, n: Optional[int] = None) -> "OpponentAreaState":
+        lane0, n = self._range(lane0, n)
+        rows = np.zeros((n, max(int(getattr(self, "_opp_n_area", 0)), 1), OPP_AREA_STATE_INTS), dtype=np.int32)
+        check(self._lib.gpf_get_opponent_area_state(self._h, lane0, n, ptr(rows, C.c_int32)), "gpf_get_opponent_area_state")
+        return OpponentAreaState.from_rows(rows)
+
+    def set_opponent_area_state(self, state: "OpponentAreaState", lane0: int = 0):
+        rows = np.ascontiguousarray(state.rows())
+        check(self._lib.gpf_set_opponent_area_state(self._h, int(lane0), rows.shape[0], ptr(rows, C.c_int32)), "gpf_set_opponent_area_state")
+
+    def opponent_attack_lines(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """bool ``[n, n_line]``: ``info["opponent_attack_line"]`` of the last launch, with or without areas (synchronous)."""
+        lane0, n = self._range(lane0, n)
+        out = np.zeros((n, self.model.n_line), dtype=np.uint8)
+        check(self._lib.gpf_get_opponent_attack_lines(self._h, lane0, n, ptr(out, C.c_uint8)), "gpf_get_opponent_attack_lines")
+        return out.astype(bool)
 
     def set_gen_renewable(self, renewable):
         """``gen_renewable`` mask (curtailment only acts on these generators); None switches curtailment off."""

@@ -463,6 +463,32 @@ class ShardedEngine:
         for eng, l0, k, off in self._parts(lane0, len(bud)):
             eng.set_opponent_state(OpponentState.from_rows(bud[off:off + k], rows[off:off + k]), lane0=l0)
 
+    # the multi-area opponent: the areas go to every device, area schedules and area state are cut by block
+    def set_opponent_areas(self, area_of_line):
+        for eng in self.engines:
+            eng.set_opponent_areas(area_of_line)
+
+    def upload_opponent_area_schedule(self, schedule, count):
+        sch, cnt = np.asarray(schedule), np.asarray(count)
+        if sch.ndim == 3:
+            sch = np.broadcast_to(sch, (self.n_lanes,) + sch.shape)
+        cnt = np.broadcast_to(cnt, (self.n_lanes, sch.shape[1]))
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.upload_opponent_area_schedule(sch[b0:b0 + bn], cnt[b0:b0 + bn])
+
+    def opponent_area_state(self, lane0: int = 0, n=None):
+        from .engine import OpponentAreaState
+        return OpponentAreaState.from_rows(np.concatenate([eng.opponent_area_state(l0, k).rows() for eng, l0, k, _ in self._parts(lane0, n)]))
+
+    def set_opponent_area_state(self, state, lane0: int = 0):
+        from .engine import OpponentAreaState
+        rows = state.rows()
+        for eng, l0, k, off in self._parts(lane0, rows.shape[0]):
+            eng.set_opponent_area_state(OpponentAreaState.from_rows(rows[off:off + k]), lane0=l0)
+
+    def opponent_attack_lines(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.opponent_attack_lines(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

@@ -588,6 +588,58 @@ int gpf_upload_opponent_schedule(gpf_handle h, const int32_t* schedule, const in
 int gpf_get_opponent_state(gpf_handle h, int32_t lane0, int32_t n, double* budget, int32_t* state);
 int gpf_set_opponent_state(gpf_handle h, int32_t lane0, int32_t n, const double* budget, const int32_t* state);
 
+/* ---- the multi-area opponent: GeometricOpponentMultiArea (Opponent/geometricOpponentMultiArea.py:18-204), the opponent l2rpn_idf_2023
+ * ships.  gpf_set_opponent_areas cuts the attackable list of a GPF_OPP_GEOMETRIC opponent into areas; every area is one GeometricOpponent
+ * with the descriptor's rates, its own slice of the list (its entries in descriptor order: that order decides the cdf), its own schedule
+ * and a row of GPF_OPP_AREA_STATE_INTS ints.  ONE side kernel (opponent_area_prestep_kernel) runs them for every lane, one launch per step
+ * whatever the number of areas.  What a step does (attack(), :126-149, under OpponentSpace.attack, opponentSpace.py:177-249):
+ *   - every area's counter goes down by one, clamped at -1; the areas are visited in area order;
+ *   - a free area (counter -1) calls its sub-opponent's attack() (geometricOpponent.py:230-293) with the space's previous_fails -- the same
+ *     flag for every area of the step; a line with duration d sets counter = d and _previous_attacks = that line, no line sets None;
+ *   - any other area gets tell_attack_continues (geometricOpponent.py:199-200: _next_attack_time = None) and contributes its line again:
+ *     an attack of duration d holds its line for d + 1 steps;
+ *   - the answer is the union of the contributed lines with duration 1, so the space asks at every step: 1 > attack_duration drops the
+ *     attack and sets previous_fails (even when there was none); the cost is one unit per line (baseActionBudget.py:46-57); cost > budget
+ *     drops the attack and sets previous_fails, but the areas have booked their counters and lines, which therefore come back at the next
+ *     step; an accepted attack sets current_attack_duration = 1, current_attack_cooldown += attack_cooldown, budget -= cost;
+ *   - every line of the accepted union is forced out and its cooldown raised to max(1, cooldown) before the step (baseEnv.py:3148-3170).
+ *   - reset() (:88-92): counters to -1, every sub-opponent reset (counter 0, _next_attack_time None, schedule resampled); _previous_attacks
+ *     is LEFT as it is.
+ * attack_cooldown > 1 cannot be played: with cooldown c two consecutive attacking steps leave current_attack_cooldown = 2 c, and after the
+ * next decrement 2 c - 1 > c for every c >= 2 sends the space into its minimum-time-between-attacks branch, which calls the multi-area
+ * opponent's own tell_attack_continues: RuntimeError("I should not get there !") (:152-153).  A state written by hand can still reach that
+ * branch (GPF_OPP_S_COOLDOWN above attack_cooldown + 1): then no area moves and nothing is attacked at that step.
+ * Draws: the lane's ONE stream, one uniform per event in event order -- within a step, area order; on a Philox reset the areas sample their
+ * schedules in area order; a sub-opponent with a single line draws nothing.  The two sticky flags stay per lane.
+ * The lane's row with areas set: BUDGET_IS_F32, DURATION (0 or 1), COOLDOWN, PREVIOUS_FAILS, CURSOR, EPISODE, FLAGS keep their meaning; LINE and
+ * INFO_LINE hold the accepted line of the lowest attacking area (-1: none), INFO_DURATION 1 or 0; NEXT_TIME, COUNTER, N_SCHEDULE are unused.
+ *   gpf_set_opponent_areas  : after gpf_set_opponent with kind GPF_OPP_GEOMETRIC; area_of_line[i] in [0, n_area) is the area of entry i of
+ *                             the descriptor's line_ids.  n_area = 0 goes back to the single-area opponent; gpf_set_opponent itself clears
+ *                             the areas.  Every lane's opponent starts reset.  Refused before the device is touched (on a header-only handle
+ *                             too): no opponent or not Geometric, n_area outside [0, GPF_OPP_MAX_AREAS], an entry outside [0, n_area), an
+ *                             empty area, attack_cooldown > 1.
+ *   gpf_upload_opponent_area_schedule : table source; schedule[n_lanes][n_area][schedule_cap][2] and count[n_lanes][n_area].
+ *   gpf_get_opponent_area_state / gpf_set_opponent_area_state : state[n][n_area][GPF_OPP_AREA_STATE_INTS].  The setter refuses a line outside
+ *                             the area's list (unless -1), a counter below -1, N_SCHEDULE outside [0, schedule_cap]; with areas set
+ *                             gpf_set_opponent_state refuses DURATION > 1.
+ *   gpf_get_opponent_attack_lines : attacked[n][n_line], info["opponent_attack_line"] of the last launch (with or without areas).
+ * gpf_copy_lanes copies area state and area schedules; gpf_step_n keeps its two refusals; gpf_fanout_n1 and gpf_simulate_batch never run
+ * the opponent. */
+#define GPF_OPP_MAX_AREAS 16
+#define GPF_OPP_AREA_STATE_INTS 8
+#define GPF_OPP_AS_COUNTER 0         /* _new_attack_time_counters[a]; -1: the area is free */
+#define GPF_OPP_AS_LINE 1            /* _previous_attacks[a]: the line, -1 for None */
+#define GPF_OPP_AS_NEXT_TIME 2       /* the sub-opponent's _next_attack_time; GPF_OPP_TIME_NONE for None */
+#define GPF_OPP_AS_ATTACK_COUNTER 3  /*                    _attack_counter */
+#define GPF_OPP_AS_N_SCHEDULE 4      /*                    _number_of_attacks */
+#define GPF_OPP_AS_INFO_LINE 5       /* the area's line in the ACCEPTED attack of the last launch, -1 for none */
+                                     /* 6, 7: reserved, always 0 */
+int gpf_set_opponent_areas(gpf_handle h, int32_t n_area, const int32_t* area_of_line);
+int gpf_upload_opponent_area_schedule(gpf_handle h, const int32_t* schedule, const int32_t* count);
+int gpf_get_opponent_area_state(gpf_handle h, int32_t lane0, int32_t n, int32_t* state);
+int gpf_set_opponent_area_state(gpf_handle h, int32_t lane0, int32_t n, const int32_t* state);
+int gpf_get_opponent_attack_lines(gpf_handle h, int32_t lane0, int32_t n, uint8_t* attacked);
+
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
  * Observation/baseObservation.py:4464-4540; with subtract / divide what gym_compat.BoxGymObsSpace(attr_to_keep, subtract, divide) puts on
