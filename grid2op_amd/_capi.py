@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "library_path", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
@@ -35,7 +35,10 @@ EXPORTED_SYMBOLS = [
     "gpf_set_opponent", "gpf_upload_opponent_draws", "gpf_upload_opponent_schedule", "gpf_get_opponent_state", "gpf_set_opponent_state",
     "gpf_set_opponent_areas", "gpf_upload_opponent_area_schedule", "gpf_get_opponent_area_state", "gpf_set_opponent_area_state",
     "gpf_get_opponent_attack_lines",
+    "gpf_set_alerts", "gpf_set_lane_alerts", "gpf_alerts_on_device", "gpf_alert_state_ints", "gpf_get_alert_state", "gpf_set_alert_state",
+    "gpf_get_alert_reward", "gpf_alert_device_pointers",
 ]
+N_ALERT_POINTERS = 3       # include/gridpf.h GPF_N_ALERT_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
 
@@ -79,6 +82,12 @@ class GpfOpponentDesc(C.Structure):
         ("attack_duration", C.c_int32), ("attack_cooldown", C.c_int32), ("draw_source", C.c_int32), ("seed_lo", C.c_uint32),
         ("seed_hi", C.c_uint32), ("lane_base", C.c_int32), ("schedule_cap", C.c_int32),
     ]
+
+
+class GpfAlertDesc(C.Structure):
+    """include/gridpf.h gpf_alert_desc"""
+    _fields_ = [("time_window", C.c_int32), ("reward_min_no_blackout", C.c_float), ("reward_min_blackout", C.c_float),
+                ("reward_max_no_blackout", C.c_float), ("reward_max_blackout", C.c_float)]
 
 
 class GpfLayout(C.Structure):
@@ -218,6 +227,14 @@ def lib() -> C.CDLL:
     L.gpf_get_opponent_area_state.argtypes = [h, i32, i32, _ip]
     L.gpf_set_opponent_area_state.argtypes = [h, i32, i32, _ip]
     L.gpf_get_opponent_attack_lines.argtypes = [h, i32, i32, C.POINTER(C.c_uint8)]
+    L.gpf_set_alerts.argtypes = [h, C.POINTER(GpfAlertDesc)]
+    L.gpf_set_lane_alerts.argtypes = [h, C.POINTER(C.c_uint64)]
+    L.gpf_alerts_on_device.argtypes = [h, i32]
+    L.gpf_alert_state_ints.argtypes = [h, _ip]
+    L.gpf_get_alert_state.argtypes = [h, i32, i32, _ip]
+    L.gpf_set_alert_state.argtypes = [h, i32, i32, _ip]
+    L.gpf_get_alert_reward.argtypes = [h, i32, i32, _fp]
+    L.gpf_alert_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

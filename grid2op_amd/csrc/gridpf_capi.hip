@@ -664,6 +664,7 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   HIP_TRY(hipMemsetAsync(e->status.p + (size_t)lane0 * 4, 0xFF, (size_t)n * 4 * sizeof(int), e->stream));
   if (e->env_on) { int rc_e = reset_env_state(e, lane0, n); if (rc_e != GPF_OK) return rc_e; }
   if (e->ta_on) { int rc_t = reset_topo_state(e, lane0, n); if (rc_t != GPF_OK) return rc_t; }
+  if (e->al_on) { int rc_a = alert_reset_lanes(e, lane0, n); if (rc_a != GPF_OK) return rc_a; }
   topo_unmoved(e, lane0, n);
   HIP_TRY(hipStreamSynchronize(e->stream));
   const int init_class = topo_class_of(e, e->h_init_topo.data(), g.n_shunt ? e->h_init_shunt_bus.data() : nullptr);
@@ -1226,6 +1227,7 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
     for (int k = 0; k < n; ++k) { e->ta_n_moved += e->ta_moved[src + k] - e->ta_moved[dst + k]; e->ta_moved[dst + k] = e->ta_moved[src + k]; }
   }
   if (e->opp_kind && err == hipSuccess) err = opponent_copy_lanes(e, src, dst, n);
+  if (e->al_on && err == hipSuccess) err = alert_copy_lanes(e, src, dst, n);
   HIP_TRY(err);
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
@@ -1754,6 +1756,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = opponent_prestep(e);
     if (rc != GPF_OK) return rc;
   }
+  if (e->al_on) {                           // after the opponent, before the power flow (baseEnv.py:3295)
+    rc = alert_prestep(e);
+    if (rc != GPF_OK) return rc;
+  }
   rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
   if (rc != GPF_OK) return rc;
   if (e->ta_on) {
@@ -1764,6 +1770,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
                        e->n_lanes, acts ? 1 : 0, n_steps, list_resets ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (list_resets) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
+  }
+  if (e->al_on) {                           // the reward of the step, on its done flag
+    rc = alert_poststep(e);
+    if (rc != GPF_OK) return rc;
   }
   e->traj_valid = e->traj_cap ? n_steps : 0;
   e->last_t0 = t0; e->last_n_steps = n_steps; e->last_track_cooldown = o->track_cooldown != 0;

@@ -13,10 +13,17 @@ namespace {
 const char* const kKindName[GPF_OBS_N_KINDS] = {
     "const", "out", "rho", "line_status", "topo_vect", "_shunt_bus", "timestep_overflow", "time_before_cooldown_line", "time_before_cooldown_sub",
     "target_dispatch", "actual_dispatch", "storage_charge", "curtailment_limit", "gen_margin_up", "gen_margin_down", "calendar", "current_step",
-    "max_step", "delta_time", "time_next_maintenance", "duration_next_maintenance", "thermal_limit", "gen_p_before_curtail", "gen_p_delta"};
+    "max_step", "delta_time", "time_next_maintenance", "duration_next_maintenance", "thermal_limit", "gen_p_before_curtail", "gen_p_delta",
+    "active_alert", "time_since_last_alert", "alert_duration", "total_number_of_alert", "time_since_last_attack", "attack_under_alert",
+    "was_alert_used_after_attack"};
+
+bool alert_kind(int kind) { return kind >= GPF_OBS_ACTIVE_ALERT && kind <= GPF_OBS_WAS_ALERT_USED_AFTER_ATTACK; }
 
 // width of the source a segment of `kind` reads (-1: any offset, the segment is a fill)
-int source_width(const gpf::GridDev& g, int kind) {
+int source_width(const gpf_engine* e, int kind) {
+  const gpf::GridDev& g = e->g;
+  if (kind == GPF_OBS_TOTAL_NUMBER_OF_ALERT) return 1;
+  if (alert_kind(kind)) return e->al_A;
   switch (kind) {
     case GPF_OBS_OUT: return g.n_out;
     case GPF_OBS_RHO: case GPF_OBS_LINE_STATUS: case GPF_OBS_OVERFLOW: case GPF_OBS_COOLDOWN_LINE: case GPF_OBS_TIME_NEXT_MAINTENANCE:
@@ -93,6 +100,15 @@ int launch_obs(gpf_engine* e, bool traj, int step0, int n_steps, int lane0, int 
   S.maint_next = maint && e->obs_maint_next.n ? e->obs_maint_next.p : nullptr;
   S.maint_durn = maint && e->obs_maint_durn.n ? e->obs_maint_durn.p : nullptr;
   S.thermal_limit = e->thermal_limit.p;
+  for (int kind = GPF_OBS_ACTIVE_ALERT; kind <= GPF_OBS_WAS_ALERT_USED_AFTER_ATTACK; ++kind)
+    if (spec_uses(e, kind) && !e->al_on)
+      return fail(GPF_E_INVALID, std::string(who) + ": " + kKindName[kind] + " is in the spec but alerts were turned off since (gpf_set_alerts)");
+  for (int s = 0; s < e->obs_n_seg; ++s) {                 // (alerts set again on another opponent: the spec's ranges may not fit any more)
+    const int* q = &e->h_obs_seg[gpf::OBS_SEG_INTS * s];
+    if (alert_kind(q[0]) && q[1] + q[2] > source_width(e, q[0]))
+      return fail(GPF_E_INVALID, std::string(who) + ": " + kKindName[q[0]] + ": the spec was set for more alertable lines than there are now: set it again");
+  }
+  S.alert = e->al_on ? e->al_obs.p : nullptr; S.alert_A = e->al_A;
   S.T = e->chron.p ? e->chron_T : 0;
   S.t = traj ? e->last_t0 : e->last_t0 + e->last_n_steps - 1;
   S.step_minutes = e->obs_step_minutes; S.max_step = e->obs_max_step;
@@ -140,7 +156,9 @@ int gpf_set_obs_spec(gpf_handle e, int32_t n_seg, const int32_t* segments, int32
     const std::string at = "gpf_set_obs_spec: segment " + std::to_string(s);
     if (kind < 0 || kind >= GPF_OBS_N_KINDS) return fail(GPF_E_INVALID, at + ": unknown source kind " + std::to_string(kind));
     if (len <= 0) return fail(GPF_E_INVALID, at + " (" + kKindName[kind] + "): length must be positive");
-    const int w = source_width(g, kind);
+    if (alert_kind(kind) && !e->al_on && !(e->dry && e->al_host_A > 0))
+      return fail(GPF_E_INVALID, at + " (" + kKindName[kind] + "): alerts are off (gpf_set_alerts)");
+    const int w = alert_kind(kind) && e->dry ? (kind == GPF_OBS_TOTAL_NUMBER_OF_ALERT ? 1 : e->al_host_A) : source_width(e, kind);
     if (w >= 0 && (so < 0 || (long long)so + len > w))
       return fail(GPF_E_INVALID, at + " (" + kKindName[kind] + "): source range [" + std::to_string(so) + ", " + std::to_string((long long)so + len) +
                                      ") is outside the " + std::to_string(w) + " elements this grid has");
@@ -190,7 +208,9 @@ int gpf_obs_vector_trajectory(gpf_handle e, int32_t step0, int32_t n_steps, int3
   if (step0 < 0 || n_steps < 0 || step0 + n_steps > e->traj_valid)
     return fail(GPF_E_INVALID, "gpf_obs_vector_trajectory: bad step range (only the steps of the last gpf_step_n are retrievable)");
   for (int kind : {GPF_OBS_OVERFLOW, GPF_OBS_COOLDOWN_SUB, GPF_OBS_TARGET_DISPATCH, GPF_OBS_ACTUAL_DISPATCH, GPF_OBS_STORAGE_CHARGE,
-                   GPF_OBS_CURTAILMENT_LIMIT, GPF_OBS_CURRENT_STEP, GPF_OBS_GEN_P_BEFORE_CURTAIL, GPF_OBS_GEN_P_DELTA})
+                   GPF_OBS_CURTAILMENT_LIMIT, GPF_OBS_CURRENT_STEP, GPF_OBS_GEN_P_BEFORE_CURTAIL, GPF_OBS_GEN_P_DELTA,
+                   GPF_OBS_ACTIVE_ALERT, GPF_OBS_TIME_SINCE_LAST_ALERT, GPF_OBS_ALERT_DURATION, GPF_OBS_TOTAL_NUMBER_OF_ALERT,
+                   GPF_OBS_TIME_SINCE_LAST_ATTACK, GPF_OBS_ATTACK_UNDER_ALERT, GPF_OBS_WAS_ALERT_USED_AFTER_ATTACK})
     if (spec_uses(e, kind))
       return fail(GPF_E_INVALID, std::string("gpf_obs_vector_trajectory: ") + kKindName[kind] + " has no per-step copy in the trajectory buffers: "
                                  "take it out of the spec for this mode");

@@ -113,6 +113,7 @@ int gpf_set_opponent(gpf_handle e, const gpf_opponent_desc* d) {
     e->opp_host_kind = GPF_OPP_NONE;
     e->opp_host_lines.clear();
     opponent_areas_off(e);
+    alerts_off(e);                            // (the alertable lines were this opponent's)
     return GPF_OK;
   }
   const std::string at = "gpf_set_opponent: ";
@@ -156,6 +157,7 @@ int gpf_set_opponent(gpf_handle e, const gpf_opponent_desc* d) {
   e->opp_host_kind = d->kind;
   e->opp_host_lines.assign(d->line_ids, d->line_ids + d->n_lines);
   if (e->dry) {
+    alerts_off(e);
     e->opp_desc = *d;
     e->opp_desc.line_ids = nullptr; e->opp_desc.rho_normalization = nullptr;
     e->opp_n_area = 0; e->opp_area_lines_host.clear(); e->opp_area_off.clear();
@@ -165,6 +167,7 @@ int gpf_set_opponent(gpf_handle e, const gpf_opponent_desc* d) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->opp_kind = GPF_OPP_NONE;
   opponent_areas_off(e);
+  alerts_off(e);                              // a new opponent: a new alertable list (gpf_set_alerts comes after it)
   std::vector<double> norm(d->n_lines, 1.0);
   if (d->kind == GPF_OPP_WEIGHTED_RANDOM && d->rho_normalization) std::copy(d->rho_normalization, d->rho_normalization + d->n_lines, norm.begin());
   HIP_TRY(e->opp_lines.upload(d->line_ids, (size_t)d->n_lines));
@@ -294,12 +297,14 @@ int gpf_set_opponent_areas(gpf_handle e, int32_t n_area, const int32_t* area_of_
     for (int i = 0; i < n_lines; ++i) grouped[fill[area_of_line[i]]++] = e->opp_host_lines[i];     // descriptor order inside an area: it decides the cdf
   }
   if (e->dry) {                              // (kept, so that the state setters can refuse on a header-only handle too)
+    alerts_off(e);
     e->opp_n_area = n_area; e->opp_area_lines_host = grouped; e->opp_area_off = off;
     return fail(GPF_E_DEVICE, "gpf_set_opponent_areas: header-only handle: no HIP device");
   }
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   opponent_areas_off(e);
+  alerts_off(e);                             // areas regroup the alertable list
   int rc = opponent_clear_lanes(e);          // every lane's opponent starts reset, with or without areas
   if (rc != GPF_OK || n_area == 0) return rc;
   std::vector<int> tab(2 * (size_t)n_area);

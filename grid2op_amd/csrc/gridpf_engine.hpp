@@ -247,6 +247,15 @@ struct gpf_engine {
   int opp_host_kind = 0, opp_n_area = 0;
   std::vector<int> opp_host_lines, opp_area_lines_host, opp_area_off;   // opp_area_off: [n_area + 1]
   DevArr<int> opp_area_lines, opp_area_tab, opp_area_state, opp_area_sched;   // opp_area_tab: [2][n_area] offsets, counts
+  // alerts and AlertReward (gridpf_alert.hpp, gridpf_capi_alert.hip): the descriptor, the number of alertable lines (= the opponent's list
+  // when gpf_set_alerts was called; al_host_A is kept on a header-only handle too, so that the masks can be refused there), the lanes'
+  // observation block [cap_lanes][6 A + 1], words [cap_lanes][3 + 2 R], alert masks of the next launch and rewards of the last one
+  bool al_on = false, al_host = false, al_dev = false;   // al_host / al_dev: the next launch carries masks set by the host / written on the device
+  int al_A = 0, al_host_A = 0;
+  gpf_alert_desc al_desc{};
+  DevArr<int> al_obs, al_area_of;
+  DevArr<unsigned long long> al_aux, al_act;
+  DevArr<float> al_reward;
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
@@ -377,6 +386,13 @@ struct gpf_engine {
 // gridpf_capi_opp.hip: the opponent's pre-step of a one-step launch (queued on the engine's stream) and its share of gpf_copy_lanes
 int opponent_prestep(gpf_engine* e);
 hipError_t opponent_copy_lanes(gpf_engine* e, int src, int dst, int n);
+// gridpf_capi_alert.hip: the two side kernels of a one-step launch with alerts on (queued on the engine's stream), the alerts' share of
+// gpf_copy_lanes / gpf_reset_lanes, and "off" (a new opponent or new areas change the alertable list)
+int alert_prestep(gpf_engine* e);
+int alert_poststep(gpf_engine* e);
+hipError_t alert_copy_lanes(gpf_engine* e, int src, int dst, int n);
+int alert_reset_lanes(gpf_engine* e, int lane0, int n);
+void alerts_off(gpf_engine* e);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

@@ -49,6 +49,8 @@ struct ObsSrc {
   const int* maint_next;            // [n_tables][T][n_line] or null: -1
   const int* maint_durn;            // [n_tables][T][n_line] or null: 0
   const float* thermal_limit;       // [n_line]
+  const int* alert;                 // [lanes][6 alert_A + 1] the alert block (gpf_set_alerts), or null (its kinds are then refused by the host)     (no per-step copy)
+  int alert_A;
   int T, t, step_minutes, max_step; // chronics rows per table (0: none uploaded), time index of step 0 of the rows
   int n_out, n_line, dim_topo, n_shunt, n_sub, n_gen, n_sto, gen_p_off, n_inj, inj_gen_p_off;
   long long lane_stride;            // trajectory mode: rows per step (the lane capacity)
@@ -209,6 +211,21 @@ __global__ __launch_bounds__(64 * OBS_WPB) void obs_gather_kernel(ObsSrc S, cons
           break;
         }
         case GPF_OBS_THERMAL_LIMIT: { const auto sp = gptr(S.thermal_limit) + so; emit([&](int i) { return sp[i]; }); break; }
+        case GPF_OBS_ACTIVE_ALERT:
+        case GPF_OBS_TIME_SINCE_LAST_ALERT:
+        case GPF_OBS_ALERT_DURATION:
+        case GPF_OBS_TOTAL_NUMBER_OF_ALERT:
+        case GPF_OBS_TIME_SINCE_LAST_ATTACK:
+        case GPF_OBS_ATTACK_UNDER_ALERT:
+        case GPF_OBS_WAS_ALERT_USED_AFTER_ATTACK: {
+          const int sec = kind == GPF_OBS_ACTIVE_ALERT ? GPF_ALERT_OBS_ACTIVE : kind == GPF_OBS_TIME_SINCE_LAST_ALERT ? GPF_ALERT_OBS_SINCE_ALERT
+                        : kind == GPF_OBS_ALERT_DURATION ? GPF_ALERT_OBS_DURATION : kind == GPF_OBS_TOTAL_NUMBER_OF_ALERT ? GPF_ALERT_OBS_TOTAL
+                        : kind == GPF_OBS_TIME_SINCE_LAST_ATTACK ? GPF_ALERT_OBS_SINCE_ATTACK : kind == GPF_OBS_ATTACK_UNDER_ALERT ? GPF_ALERT_OBS_UNDER_ALERT
+                        : GPF_ALERT_OBS_USED;
+          const auto sp = gptr(S.alert) + (size_t)lane * (6 * S.alert_A + 1) + sec * S.alert_A + so;
+          emit([&](int i) { return (float)sp[i]; });
+          break;
+        }
         default: break;                     // (kinds are validated on the host)
       }
     }

@@ -28,6 +28,9 @@ Sources (``PowerFlowEngine.observation_vector``):
 * ``gen_p_before_curtail`` (renewables: the generator set-point the last launch left in the injection row, others 0) and ``gen_p_delta``
   (``gen_p`` minus that set-point: what the slack absorbed) -- the reference's values while no curtailment limit acts on the lane;
   under an acting limit ``gen_p_before_curtail`` shows the CURTAILED set-point: a caller who curtails covers it with a ``const`` entry;
+* with ``dim_alerts=A``: ``active_alert``, ``time_since_last_alert``, ``alert_duration``, ``time_since_last_attack``, ``attack_under_alert``,
+  ``was_alert_used_after_attack`` (A elements each) and ``total_number_of_alert`` (ONE element): the lanes' alert state
+  (`PowerFlowEngine.set_alerts`, which must be on when the spec is set); without the keyword these names are refused as before;
 * ``thermal_limit`` (not part of the reference vector; ``BoxGymObsSpace`` keeps it);
 * ``("const", size, value)``: a fill -- how a caller covers attributes of features the engine does not model.
 
@@ -45,7 +48,8 @@ __all__ = ["ObsSpec", "ATTR_TABLE", "KIND", "out_offsets"]
 KIND = dict(const=0, out=1, rho=2, line_status=3, topo_vect=4, shunt_bus=5, overflow=6, cooldown_line=7, cooldown_sub=8, target_dispatch=9,
             actual_dispatch=10, storage_charge=11, curtailment_limit=12, margin_up=13, margin_down=14, calendar=15, current_step=16,
             max_step=17, delta_time=18, time_next_maintenance=19, duration_next_maintenance=20, thermal_limit=21, gen_p_before_curtail=22,
-            gen_p_delta=23)
+            gen_p_delta=23, active_alert=24, time_since_last_alert=25, alert_duration=26, total_number_of_alert=27, time_since_last_attack=28,
+            attack_under_alert=29, was_alert_used_after_attack=30)
 GO_ZERO, GO_KEEP, GO_MINUS1, GO_ONE = 0, 1, 2, 3       # what a game-over lane writes (BaseObservation.set_game_over, baseObservation.py:1551-1700)
 MAX_SEGMENTS = 64
 
@@ -104,9 +108,26 @@ _DIRECT = {"rho": ("rho", GO_ZERO), "line_status": ("line_status", GO_ZERO), "to
            "gen_p_delta": ("gen_p_delta", GO_ZERO), "timestep_protection_engaged": ("overflow", GO_ZERO)}
 
 
-def _sizes(model) -> Dict[str, int]:
+# the alert attributes (``ObsSpec(..., dim_alerts=A)``, `PowerFlowEngine.set_alerts`): attribute -> (source kind, game-over value); a
+# game-over observation keeps the environment's attack_under_alert / was_alert_used_after_attack (baseObservation.py:1681-1687).
+# ``total_number_of_alert`` has ONE element (baseObservation.py:5142-5143), whatever `ATTR_TABLE`'s size rule for the alert-free layout says.
+_ALERT = {"active_alert": ("active_alert", GO_ZERO), "time_since_last_alert": ("time_since_last_alert", GO_ZERO),
+          "alert_duration": ("alert_duration", GO_ZERO), "total_number_of_alert": ("total_number_of_alert", GO_ZERO),
+          "time_since_last_attack": ("time_since_last_attack", GO_MINUS1), "attack_under_alert": ("attack_under_alert", GO_KEEP),
+          "was_alert_used_after_attack": ("was_alert_used_after_attack", GO_KEEP)}
+MAX_ALERTS = 64
+
+
+def _check_dim_alerts(dim_alerts) -> int:
+    a = int(dim_alerts)
+    if not 0 <= a <= MAX_ALERTS:
+        raise ValueError(f"dim_alerts {a} is outside [0, {MAX_ALERTS}]")
+    return a
+
+
+def _sizes(model, dim_alerts: int = 0) -> Dict[str, int]:
     return dict(one=1, n_gen=model.n_gen, n_load=model.n_load, n_line=model.n_line, n_sub=model.n_sub, dim_topo=model.dim_topo,
-                n_storage=model.n_storage, n_shunt=model.n_shunt, dim_alarms=0, dim_alerts=0, detach_n_load=0, detach_n_gen=0,
+                n_storage=model.n_storage, n_shunt=model.n_shunt, dim_alarms=0, dim_alerts=dim_alerts, detach_n_load=0, detach_n_gen=0,
                 detach_n_storage=0)
 
 
@@ -128,10 +149,11 @@ class ObsSpec:
     array (a const entry is addressed as ``"const<k>"``, k counting the const entries from 0); the value written is
     ``(x - subtract) / divide`` in float32, a plain cast where both are the defaults 0 and 1."""
 
-    def __init__(self, model, attrs: Sequence, subtract: Optional[dict] = None, divide: Optional[dict] = None):
-        sizes = _sizes(model)
+    def __init__(self, model, attrs: Sequence, subtract: Optional[dict] = None, divide: Optional[dict] = None, dim_alerts: int = 0):
+        self.dim_alerts = _check_dim_alerts(dim_alerts)
+        sizes = _sizes(model, self.dim_alerts)
         known = {name: rule for name, rule, _, _ in ATTR_TABLE + _EXTRA}
-        filled = {name for name, _, _, fill in ATTR_TABLE if fill is not None}
+        filled = {name for name, _, _, fill in ATTR_TABLE if fill is not None and not (self.dim_alerts > 0 and name in _ALERT)}
         oo = out_offsets(model)
         self.model = model
         self.attrs: List = []
@@ -157,13 +179,15 @@ class ObsSpec:
                                      + ": cover it with a ('const', size, value) entry")
                 if name in self.offsets:
                     raise ValueError(f"observation attribute {name!r} is listed twice")
-                size = sizes[known[name]]
+                size = 1 if name == "total_number_of_alert" and self.dim_alerts > 0 else sizes[known[name]]
                 if size == 0:
                     raise ValueError(f"observation attribute {name!r} has no element on this grid")
                 if name in _OUT_ATTR:
                     kind, src, go = KIND["out"], oo[_OUT_ATTR[name]], GO_ZERO
                 elif name in _CALENDAR:
                     kind, src, go = KIND["calendar"], _CALENDAR.index(name), GO_KEEP
+                elif name in _ALERT:
+                    kind, src, go = KIND[_ALERT[name][0]], 0, _ALERT[name][1]
                 else:
                     kind, src, go = KIND[_DIRECT[name][0]], 0, _DIRECT[name][1]
             self.attrs.append(a if not isinstance(a, list) else tuple(a))
@@ -199,22 +223,25 @@ class ObsSpec:
         return out
 
     @classmethod
-    def complete(cls, model, fill: bool = False, subtract=None, divide=None) -> "ObsSpec":
+    def complete(cls, model, fill: bool = False, subtract=None, divide=None, dim_alerts: int = 0) -> "ObsSpec":
         """The reference's ``CompleteObservation.attr_list_vect`` order.  ``fill=False``: the attributes the engine assembles;
-        ``fill=True``: the reference's full layout, the others as ``const`` entries at the reference's values (`ATTR_TABLE`)."""
-        sizes = _sizes(model)
+        ``fill=True``: the reference's full layout, the others as ``const`` entries at the reference's values (`ATTR_TABLE`).
+        ``dim_alerts=A`` (an environment with A alertable lines, `PowerFlowEngine.set_alerts`): the seven alert attributes at their
+        positions, assembled by the engine."""
+        dim_alerts = _check_dim_alerts(dim_alerts)
+        sizes = _sizes(model, dim_alerts)
         attrs = []
         for name, rule, _, fillv in ATTR_TABLE:
             if sizes[rule] == 0:
                 continue
-            if fillv is None:
+            if fillv is None or (dim_alerts > 0 and name in _ALERT):
                 attrs.append(name)
             elif fill:
                 if attrs and isinstance(attrs[-1], tuple) and attrs[-1][2] == fillv:      # neighbours with one value: one segment
                     attrs[-1] = ("const", attrs[-1][1] + sizes[rule], fillv)
                 else:
                     attrs.append(("const", sizes[rule], fillv))
-        return cls(model, attrs, subtract, divide)
+        return cls(model, attrs, subtract, divide, dim_alerts=dim_alerts)
 
 
 def check_segments(segments, dim):

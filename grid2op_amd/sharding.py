@@ -489,6 +489,35 @@ class ShardedEngine:
     def opponent_attack_lines(self, lane0: int = 0, n=None):
         return np.concatenate([eng.opponent_attack_lines(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
 
+    # ---- alerts and AlertReward (PowerFlowEngine.set_alerts): the same configuration on every device, per-lane data by blocks ----
+    def set_alerts(self, time_window=12, **constants):
+        for eng in self.engines:
+            eng.set_alerts(time_window, **constants)
+
+    def set_lane_alerts(self, alerts):
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.set_lane_alerts(None if alerts is None else np.asarray(alerts)[b0:b0 + bn])
+
+    def alerts_on_device(self, on: bool = True):
+        """every device's ``act_alert`` buffer holds the next launch's masks of its own lanes"""
+        for eng in self.engines:
+            eng.alerts_on_device(on)
+
+    def alert_state(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.alert_state(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
+    def set_alert_state(self, rows, lane0: int = 0):
+        r = np.asarray(rows)
+        r = r.reshape(-1, r.shape[-1])
+        for eng, l0, k, off in self._parts(lane0, r.shape[0]):
+            eng.set_alert_state(r[off:off + k], lane0=l0)
+
+    def alert_state_fields(self, rows) -> dict:
+        return self.engines[0].alert_state_fields(rows)
+
+    def alert_reward(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.alert_reward(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

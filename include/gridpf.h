@@ -640,6 +640,74 @@ int gpf_get_opponent_area_state(gpf_handle h, int32_t lane0, int32_t n, int32_t*
 int gpf_set_opponent_area_state(gpf_handle h, int32_t lane0, int32_t n, const int32_t* state);
 int gpf_get_opponent_attack_lines(gpf_handle h, int32_t lane0, int32_t n, uint8_t* attacked);
 
+/* ---- alerts and AlertReward of the batched acting path (grid2op_amd/csrc/gridpf_alert.hpp): the bookkeeping of an environment whose
+ * alerts_info.json says {"by_line": "opponent"} (l2rpn_idf_2023), for every lane of a one-step launch, in two side kernels -- one queued
+ * after the opponent's kernel and before the step, one after the step; the step, power-flow, topology and opponent kernels are not
+ * involved, and with alerts off gpf_step_n launches nothing for them.  The A alertable lines are the current opponent's attackable lines in
+ * its order (with areas: grouped by area, descriptor order inside an area -- the reference's flattened lines_attacked).
+ *   - BaseEnv._update_alert_properties (Environment/baseEnv.py:3295-3329) runs in every step that reaches the backend, after the opponent
+ *     and before the power flow: last_alert, time_since_last_alert, alert_duration, total_number_of_alert, then with an attack
+ *     (info["opponent_attack_line"] is not None: here a non-zero row of gpf_get_opponent_attack_lines; an attack refused for budget is none)
+ *     time_since_last_attack = 0 on the lines attacked for the first time, +1 on the others that are not -1, is_already_attacked set on the
+ *     attacked lines and NOT cleared on a line that leaves a continuing attack; without an attack +1 and is_already_attacked cleared; then
+ *     attack_under_alert = 2 last_alert - 1 where time_since_last_attack == 0 and 0 where it exceeds time_window.
+ *   - BaseEnv._reset_alert (:1677-1685) on the lane's env.reset() launch (no completed step in its episode) and gpf_reset_lanes.
+ *   - AlertReward (Reward/alertReward.py:105-207): two boolean rings of time_window + 2 rows; per step the ring index advances, the newly
+ *     attacked lines are noted, the alerts are noted, was_alert_used_after_attack is cleared; a step that fails (the engine's done: the
+ *     reference's blackout, done and has_error) gives every line attacked in the last time_window + 1 rows the alert of the FIRST row where
+ *     it was noted: was_alert_used_after_attack = 2 alert - 1, reward = mean(alert) (max_blackout - min_blackout) + min_blackout (0 without
+ *     such a line); any other step scores the row time_window steps back: was_alert_used_after_attack = 1 - 2 alert, reward =
+ *     (min_no_blackout - max_no_blackout) mean(alert) + max_no_blackout, the row is cleared.  The mean is a count ratio in float64, the
+ *     result float32.  OUT OF SCOPE: reward_end_episode_bonus applies when done comes without an error; the engine has no such done (its
+ *     chronics cursor keeps running), so the bonus stays with the caller that truncates episodes.  Alarms, the alert budget and
+ *     _is_alert_illegal (always False in the reference) are not modelled; the agent's alert survives an illegal or ambiguous topology action
+ *     (baseEnv.py:3716-3766), so alerts are booked whatever gpf_get_topo_flags says.
+ *   gpf_set_alerts      : NULL turns alerts off, as gpf_set_opponent and gpf_set_opponent_areas do.  Refused before the device is touched
+ *                         (on a header-only handle too): no opponent, more than GPF_ALERT_MAX_LINES attackable lines, time_window outside
+ *                         [1, GPF_ALERT_MAX_WINDOW], a constant that is not finite.  Every lane starts reset.
+ *   gpf_set_lane_alerts : mask[n_lanes] for the NEXT launch, bit i = an alert on alertable line i (NULL: none); a bit at or above A is
+ *                         GPF_E_INVALID.  gpf_alerts_on_device(h, 1): the next launch takes the masks the caller wrote into the device buffer
+ *                         (gpf_alert_device_pointers entry 0); there the kernel drops the bits at or above A, which are outside the feature's
+ *                         domain.  Both are consumed by the launch, like the topology actions.
+ *   gpf_get_alert_state / gpf_set_alert_state : state[n][gpf_alert_state_ints] int32 rows, A = number of alertable lines, R = time_window + 2:
+ *                         [0, 7 A) seven arrays of A: last_alert, is_already_attacked, time_since_last_alert, alert_duration,
+ *                         time_since_last_attack, attack_under_alert, was_alert_used_after_attack; [7 A] total_number_of_alert; [7 A + 1]
+ *                         AlertReward._current_id; [7 A + 2] 1: the lane's bookkeeping ran in the last launch (its post-step scores it);
+ *                         [7 A + 3, 8 A + 3) _lines_currently_attacked; then _ts_attack [R][A] and _alert_launched [R][A].  The row length is
+ *                         8 A + 3 + 2 R A (gpf_alert_state_ints(h, &n) returns it).  The setter refuses booleans outside {0, 1}, a
+ *                         _current_id outside [0, R), counters below -1 / 0.
+ *   gpf_get_alert_reward: reward[n] of the last launch (0 on a lane that was reset or left alone).
+ *   gpf_alert_device_pointers : out[0] the alert masks uint64 [lane capacity], out[1] the rewards float32 [lane capacity], out[2] the
+ *                         observation block int32 [lane capacity][6 A + 1]: sections of A at GPF_ALERT_OBS_* x A, total_number_of_alert at
+ *                         6 A.  n must be GPF_N_ALERT_POINTERS.  (A call of its own: the length of gpf_device_pointers' table is fixed.)
+ * gpf_copy_lanes copies the alert state, gpf_reset_lanes resets it; gpf_fanout_n1 and gpf_simulate_batch leave it alone (AlertReward
+ * returns 0 inside simulate); gpf_step_n with alerts on keeps the opponent's two refusals. */
+#define GPF_ALERT_MAX_LINES 64
+#define GPF_ALERT_MAX_WINDOW 62
+#define GPF_N_ALERT_POINTERS 3
+#define GPF_ALERT_OBS_ACTIVE 0
+#define GPF_ALERT_OBS_SINCE_ALERT 1
+#define GPF_ALERT_OBS_DURATION 2
+#define GPF_ALERT_OBS_SINCE_ATTACK 3
+#define GPF_ALERT_OBS_UNDER_ALERT 4
+#define GPF_ALERT_OBS_USED 5
+#define GPF_ALERT_OBS_TOTAL 6
+typedef struct gpf_alert_desc {
+  int32_t time_window;             /* Parameters.ALERT_TIME_WINDOW (12) */
+  float reward_min_no_blackout;    /* -1 */
+  float reward_min_blackout;       /* -10 */
+  float reward_max_no_blackout;    /* 1 */
+  float reward_max_blackout;       /* 2 */
+} gpf_alert_desc;
+int gpf_set_alerts(gpf_handle h, const gpf_alert_desc* desc);
+int gpf_set_lane_alerts(gpf_handle h, const uint64_t* mask);
+int gpf_alerts_on_device(gpf_handle h, int32_t on);
+int gpf_alert_state_ints(gpf_handle h, int32_t* n_ints);
+int gpf_get_alert_state(gpf_handle h, int32_t lane0, int32_t n, int32_t* state);
+int gpf_set_alert_state(gpf_handle h, int32_t lane0, int32_t n, const int32_t* state);
+int gpf_get_alert_reward(gpf_handle h, int32_t lane0, int32_t n, float* reward);
+int gpf_alert_device_pointers(gpf_handle h, void** out, int32_t n);
+
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
  * Observation/baseObservation.py:4464-4540; with subtract / divide what gym_compat.BoxGymObsSpace(attr_to_keep, subtract, divide) puts on
@@ -702,7 +770,18 @@ int gpf_get_opponent_attack_lines(gpf_handle h, int32_t lane0, int32_t n, uint8_
 #define GPF_OBS_THERMAL_LIMIT 21
 #define GPF_OBS_GEN_P_BEFORE_CURTAIL 22   /* renewables: the generator set-point the last launch left in the injection row, others 0 */
 #define GPF_OBS_GEN_P_DELTA 23            /* gen_p of the power flow minus that set-point (what the slack absorbed), float32 */
-#define GPF_OBS_N_KINDS 24
+/* the alert attributes (Observation/baseObservation.py:4630-4636, 5142-5143): the lane's alert block (gpf_set_alerts), A elements each and
+ * ONE for the total; refused by gpf_set_obs_spec while alerts are off and, by name, in trajectory mode (no per-step copy).  A game-over
+ * lane (:1681-1687) writes 0 / 0 / 0 / 0 and -1 for the first five below and KEEPS the environment's values of the last two: the flags
+ * of their segments say so (0, 0, 0, 0, 2, 1, 1). */
+#define GPF_OBS_ACTIVE_ALERT 24
+#define GPF_OBS_TIME_SINCE_LAST_ALERT 25
+#define GPF_OBS_ALERT_DURATION 26
+#define GPF_OBS_TOTAL_NUMBER_OF_ALERT 27
+#define GPF_OBS_TIME_SINCE_LAST_ATTACK 28
+#define GPF_OBS_ATTACK_UNDER_ALERT 29
+#define GPF_OBS_WAS_ALERT_USED_AFTER_ATTACK 30
+#define GPF_OBS_N_KINDS 31
 #define GPF_OBS_MAX_SEGMENTS 64
 int gpf_set_obs_clock(gpf_handle h, int32_t n_tables, const int64_t* start_minutes, int32_t step_minutes, int32_t max_step);
 int gpf_set_obs_spec(gpf_handle h, int32_t n_seg, const int32_t* segments, int32_t dim, const float* subtract, const float* divide,
