@@ -165,7 +165,17 @@ __global__ __launch_bounds__(WAVE) void redispatch_kernel(RedispDev R, int n, co
           s = wave_sum_f64(s);
           if (s < r) a = mid; else b = mid;
         }
-        const double alpha = 0.5 * (a + b);
+        double alpha = 0.5 * (a + b);
+        // the bisection resolves alpha to 2^-64 of its bracket, an ABSOLUTE error: where nothing is left to share (r = 0, the common balanced
+        // action) it would hand ~1e-19 MW to every free generator.  With the active set at alpha known, alpha is the root of a linear equation.
+        double s_fix = 0.0, s_inv = 0.0;
+#pragma unroll
+        for (int q = 0; q < RD_PER_LANE; ++q) if (part[q] && !mod[q]) {
+          const double u = alpha / w[q];
+          if (u <= lo[q]) s_fix += lo[q]; else if (u >= hi[q]) s_fix += hi[q]; else s_inv += 1.0 / w[q];
+        }
+        s_fix = wave_sum_f64(s_fix); s_inv = wave_sum_f64(s_inv);
+        if (s_inv > 0.0) alpha = (r - s_fix) / s_inv;
 #pragma unroll
         for (int q = 0; q < RD_PER_LANE; ++q) if (part[q] && !mod[q]) x[q] = fmin(fmax(alpha / w[q], lo[q]), hi[q]);
       }

@@ -3,8 +3,9 @@
 CPU: the oracle restatement (oracle/redispatch_oracle.py, scipy SLSQP like the reference) reproduces the calls recorded inside
 unmodified reference environments (tests/golden/redispatch_cases.npz).  GPU: the device kernel behind ``gpf_redispatch`` solves the
 same quadratic program exactly (the program is separable: one multiplier); it must satisfy the constraints, reach the optimum
-of the objective (never worse than SLSQP's approximate minimiser) and land on the recorded dispatch wherever the minimiser is
-unique."""
+of the objective (never worse than SLSQP's approximate minimiser), land on the recorded dispatch wherever the minimiser is
+unique, and equal the closed-form reference (tests/redispatch_ref.py) to one float32 spacing.  What `apply=True` installs is
+checked in tests/test_gpu_redispatch.py."""
 import numpy as np
 import pytest
 
@@ -43,6 +44,7 @@ def test_oracle_reproduces_the_reference_automaton(env):
 def test_device_redispatch_solves_the_same_program(env, load_model):
     from grid2op_amd.engine import PowerFlowEngine
     from oracle.redispatch_oracle import objective_mw, qp_terms
+    from redispatch_ref import dispatch_ref, spacing32
     m = load_model(env)
     c, lim = _cases(env)
     n = len(c["ok"])
@@ -53,8 +55,14 @@ def test_device_redispatch_solves_the_same_program(env, load_model):
     ok, after = eng.redispatch(c["new_p"], prev, c["actual"], c["target"], c["modified"], rhs)
     assert np.array_equal(ok, c["ok"])
     n_unique = 0
-    worst = gap = 0.0
+    worst = gap = dev = 0.0
     for k in range(n):
+        # the exact reference on the recorded inputs: the final cast to float32 is the only rounding that counts (one spacing, no more)
+        ok_ref, after_ref = dispatch_ref(c["new_p"][k], prev[k], c["actual"][k], c["target"][k], c["modified"][k], rhs[k], lim)
+        assert ok_ref == bool(ok[k]), k
+        d = np.abs(after[k].astype(np.float64) - np.float32(after_ref).astype(np.float64)) / spacing32(after_ref)
+        assert (d <= 1.0).all(), (k, float(d.max()), int(d.argmax()), after[k][d.argmax()], after_ref[d.argmax()])
+        dev = max(dev, float(d.max()))
         q = qp_terms(c["new_p"][k], c["prev_p"][k], c["actual"][k], c["target"][k], c["modified"][k], float(c["storage"][k]),
                      float(c["curtail"][k]), float(c["detached"][k]), lim, first=bool(c["first"][k]))
         part = q["part"]
@@ -74,7 +82,5 @@ def test_device_redispatch_solves_the_same_program(env, load_model):
         worst = max(worst, float(np.abs(x - x_ref)[q["mod"]].max()))
     assert n_unique >= 5
     print(f"{env}: {n} programs, worst |x - x_SLSQP| on the modified generators {worst:.3f} MW, SLSQP objective above the exact "
-          f"optimum by up to {gap:.2e} MW^2")
-    # apply=True installs the dispatch as the lanes' redispatch delta: the next step's generator set-points move by it
-    eng.redispatch(c["new_p"], prev, c["actual"], c["target"], c["modified"], rhs, apply=True)
+          f"optimum by up to {gap:.2e} MW^2; worst distance to the closed-form reference {dev:.2f} float32 spacings")
     eng.close()
