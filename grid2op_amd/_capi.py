@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "library_path", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
@@ -37,8 +37,10 @@ EXPORTED_SYMBOLS = [
     "gpf_get_opponent_attack_lines",
     "gpf_set_alerts", "gpf_set_lane_alerts", "gpf_alerts_on_device", "gpf_alert_state_ints", "gpf_get_alert_state", "gpf_set_alert_state",
     "gpf_get_alert_reward", "gpf_alert_device_pointers",
+    "gpf_set_rewards", "gpf_get_rewards", "gpf_rewards_eval", "gpf_reward_device_pointers",
 ]
 N_ALERT_POINTERS = 3       # include/gridpf.h GPF_N_ALERT_POINTERS
+N_REWARD_POINTERS = 1      # include/gridpf.h GPF_N_REWARD_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
 
@@ -82,6 +84,11 @@ class GpfOpponentDesc(C.Structure):
         ("attack_duration", C.c_int32), ("attack_cooldown", C.c_int32), ("draw_source", C.c_int32), ("seed_lo", C.c_uint32),
         ("seed_hi", C.c_uint32), ("lane_base", C.c_int32), ("schedule_cap", C.c_int32),
     ]
+
+
+class GpfRewardSlot(C.Structure):
+    """include/gridpf.h gpf_reward_slot"""
+    _fields_ = [("kind", C.c_int32), ("p", C.c_double * 6)]
 
 
 class GpfAlertDesc(C.Structure):
@@ -235,6 +242,10 @@ def lib() -> C.CDLL:
     L.gpf_set_alert_state.argtypes = [h, i32, i32, _ip]
     L.gpf_get_alert_reward.argtypes = [h, i32, i32, _fp]
     L.gpf_alert_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
+    L.gpf_set_rewards.argtypes = [h, i32, C.POINTER(GpfRewardSlot), _fp]
+    L.gpf_get_rewards.argtypes = [h, i32, i32, _fp]
+    L.gpf_rewards_eval.argtypes = [h, i32, i32, C.c_void_p, C.c_void_p, C.c_int64]
+    L.gpf_reward_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

@@ -665,6 +665,7 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   if (e->env_on) { int rc_e = reset_env_state(e, lane0, n); if (rc_e != GPF_OK) return rc_e; }
   if (e->ta_on) { int rc_t = reset_topo_state(e, lane0, n); if (rc_t != GPF_OK) return rc_t; }
   if (e->al_on) { int rc_a = alert_reset_lanes(e, lane0, n); if (rc_a != GPF_OK) return rc_a; }
+  if (e->rw_on) { int rc_r = reward_reset_lanes(e, lane0, n); if (rc_r != GPF_OK) return rc_r; }
   topo_unmoved(e, lane0, n);
   HIP_TRY(hipStreamSynchronize(e->stream));
   const int init_class = topo_class_of(e, e->h_init_topo.data(), g.n_shunt ? e->h_init_shunt_bus.data() : nullptr);
@@ -1760,6 +1761,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = alert_prestep(e);
     if (rc != GPF_OK) return rc;
   }
+  if (e->rw_on && e->env_on && n_steps == 1) {   // the cancelled-redispatch counters before the step: their change is the step's flag
+    rc = reward_prestep(e);
+    if (rc != GPF_OK) return rc;
+  }
   rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
   if (rc != GPF_OK) return rc;
   if (e->ta_on) {
@@ -1773,6 +1778,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   }
   if (e->al_on) {                           // the reward of the step, on its done flag
     rc = alert_poststep(e);
+    if (rc != GPF_OK) return rc;
+  }
+  if (e->rw_on && n_steps == 1) {           // the rewards of the step, last: on its results, done flag and flags
+    rc = reward_poststep(e, acts);
     if (rc != GPF_OK) return rc;
   }
   e->traj_valid = e->traj_cap ? n_steps : 0;

@@ -256,6 +256,14 @@ struct gpf_engine {
   DevArr<int> al_obs, al_area_of;
   DevArr<unsigned long long> al_aux, al_act;
   DevArr<float> al_reward;
+  // the environment's rewards (gridpf_reward.hpp, gridpf_capi_reward.hip): the slot table and the cost table on the device, the
+  // engine-owned rewards [cap_lanes][rw_n_slot] of the last one-step launch and the snapshot of env_illegal queued before its step
+  bool rw_on = false;
+  int rw_n_slot = 0;
+  bool rw_cost_on = false;              // a slot reads the cost table
+  DevArr<unsigned char> rw_slots;       // [rw_n_slot] gpf_reward_slot
+  DevArr<float> rw_cost, rw_out;
+  DevArr<int> rw_ill_snap;              // [cap_lanes]
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
@@ -393,6 +401,12 @@ int alert_poststep(gpf_engine* e);
 hipError_t alert_copy_lanes(gpf_engine* e, int src, int dst, int n);
 int alert_reset_lanes(gpf_engine* e, int lane0, int n);
 void alerts_off(gpf_engine* e);
+
+// gridpf_capi_reward.hip: the rewards' share of a one-step launch (the snapshot before the step, reward_kernel after it; topo_flags:
+// the launch carried topology actions) and of gpf_reset_lanes
+int reward_prestep(gpf_engine* e);
+int reward_poststep(gpf_engine* e, bool topo_flags);
+int reward_reset_lanes(gpf_engine* e, int lane0, int n);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import GpfAlertDesc, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
+from ._capi import GpfAlertDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
 from .grid_model import GridModel
 
 __all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT", "MASK_TOO_MANY_LINES", "MASK_TOO_MANY_SUBS",
@@ -154,6 +154,63 @@ def opponent_config(model, opponent_class, kwargs_opponent=None, opponent_init_b
         out.update(attack_hazard_rate=hazard, recovery_rate=1.0 / (ts_per_hour * (avg - mini)),
                    recovery_minimum_duration=int(mini * ts_per_hour), pmax_pmin_ratio=float(kw.get("pmax_pmin_ratio", 4)),
                    episode_max_time=int(max_episode_duration), schedule_cap=int(schedule_cap))
+    return out
+
+
+RW_REDISP, RW_L2RPN, RW_LINES_CAPACITY, RW_ECONOMIC, RW_GAMEPLAY = 1, 2, 3, 4, 5      # include/gridpf.h GPF_RW_*
+REWARD_MAX_SLOTS = 8
+REWARD_KINDS = {"RedispReward": RW_REDISP, "L2RPNReward": RW_L2RPN, "LinesCapacityReward": RW_LINES_CAPACITY, "EconomicReward": RW_ECONOMIC,
+                "GameplayReward": RW_GAMEPLAY}
+
+
+def reward_config(kind, gen_cost_per_MW=None, gen_pmax=None, delta_time_seconds=300.0, **meta) -> dict:
+    """One slot of `PowerFlowEngine.set_rewards` from a reference-style configuration: ``kind`` is a ``RW_*`` constant or the reference
+    class's name (``"RedispReward"`` ...); ``meta`` are the class's meta-parameters with the reference's defaults.  ``max_regret`` of
+    ``RedispReward`` and ``worst_cost`` of ``EconomicReward`` are derived as the two ``initialize`` methods derive them
+    (Reward/redispReward.py:141-167, Reward/economicReward.py:49-55), float32 where the reference uses ``dt_float``.  Returns
+    ``dict(kind=..., p=[...])`` plus the derived values by name (``reward_max`` of ``RedispReward`` among them)."""
+    f32 = np.float32
+    k = REWARD_KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+    dts = float(delta_time_seconds) / 3600.0
+
+    def take(name, default):
+        return meta.pop(name, default)
+    out = dict(kind=k)
+    if k == RW_REDISP:
+        if gen_cost_per_MW is None or gen_pmax is None:
+            raise ValueError("reward_config: RedispReward needs gen_cost_per_MW and gen_pmax")
+        cost, pmax = np.asarray(gen_cost_per_MW, f32), np.asarray(gen_pmax, f32)
+        alpha, min_load_ratio = f32(take("alpha_redisph", 5.0)), f32(take("min_load_ratio", 0.1))
+        worst_losses_ratio, min_reward = f32(take("worst_losses_ratio", 0.05)), f32(take("min_reward", -10.0))
+        least_losses_ratio, ria = f32(take("least_losses_ratio", 0.015)), f32(take("reward_illegal_ambiguous", 0.0))
+        worst_marginal_cost = np.max(cost)
+        worst_load = pmax.sum(dtype=f32)
+        worst_losses = f32(worst_losses_ratio) * worst_load
+        worst_redisp = alpha * pmax.sum()
+        max_regret = (worst_losses + worst_redisp) * worst_marginal_cost * float(delta_time_seconds) / 3600.0
+        least_loads = f32(worst_load * min_load_ratio)
+        least_losses = f32(least_losses_ratio * least_loads * float(delta_time_seconds) / 3600.0)
+        base_marginal_cost = np.min(cost[cost > 0.0])
+        min_regret = (least_losses + f32(0.0)) * base_marginal_cost
+        reward_max = f32((max_regret - min_regret) / least_loads)
+        out.update(p=[float(alpha), float(max_regret), float(min_reward), float(ria), dts], max_regret=float(max_regret),
+                   reward_min=float(min_reward), reward_max=float(reward_max))
+    elif k == RW_ECONOMIC:
+        if gen_cost_per_MW is None or gen_pmax is None:
+            raise ValueError("reward_config: EconomicReward needs gen_cost_per_MW and gen_pmax")
+        cost, pmax = np.asarray(gen_cost_per_MW, f32), np.asarray(gen_pmax, f32)
+        worst_cost = f32((cost * pmax).sum() * float(delta_time_seconds) / 3600.0)
+        rmin, rmax = f32(take("reward_min", 0.0)), f32(take("reward_max", 1.0))
+        out.update(p=[float(worst_cost), float(rmin), float(rmax), dts], worst_cost=float(worst_cost), reward_min=float(rmin), reward_max=float(rmax))
+    elif k == RW_GAMEPLAY:
+        rmin, rmax = f32(take("reward_min", -1.0)), f32(take("reward_max", 1.0))
+        out.update(p=[float(rmin), float(rmax)], reward_min=float(rmin), reward_max=float(rmax))
+    elif k in (RW_L2RPN, RW_LINES_CAPACITY):
+        out.update(p=[])
+    else:
+        raise ValueError(f"reward_config: unknown reward kind {kind!r}")
+    if meta:
+        raise ValueError(f"reward_config: unknown meta-parameters {sorted(meta)}")
     return out
 
 
@@ -1105,6 +1162,91 @@ class PowerFlowEngine:
         sr = np.empty((n, 2), dtype=np.int32)
         check(self._lib.gpf_get_episode(self._h, lane0, n, ptr(done, C.c_uint8), ptr(sr, C.c_int32)), "gpf_get_episode")
         return done.astype(bool), sr[:, 0].copy(), sr[:, 1].copy()
+
+    # ---- the environment's rewards (include/gridpf.h gpf_set_rewards; grid2op_amd/csrc/gridpf_reward.hpp) ----
+    def set_rewards(self, slots, gen_cost_per_MW=None):
+        """The rewards of ``env.step`` on every lane of the one-step launches: ``slots`` is a list of up to 8 slots, each a `reward_config`
+        result, a ``(kind, p)`` pair or a bare ``RW_*`` kind (the reference's ``reward_class`` first, then its ``other_rewards``);
+        ``gen_cost_per_MW`` ``[n_gen]`` is needed by `RW_REDISP` / `RW_ECONOMIC`.  None or an empty list: off."""
+        self._rw_view = None
+        if not slots:
+            check(self._lib.gpf_set_rewards(self._h, 0, None, None), "gpf_set_rewards")
+            self._n_reward_slot = 0
+            return
+        arr = (GpfRewardSlot * len(slots))()
+        for i, s_ in enumerate(slots):
+            if isinstance(s_, dict):
+                kind, p = s_["kind"], s_.get("p", ())
+            elif isinstance(s_, (tuple, list)):
+                kind, p = s_
+            else:
+                kind, p = s_, ()
+            p = [float(x) for x in p]
+            if len(p) > 6:
+                raise ValueError("set_rewards: a slot has at most 6 parameters")
+            arr[i].kind = int(kind)
+            for j, x in enumerate(p):
+                arr[i].p[j] = x
+        cost = None
+        if gen_cost_per_MW is not None:
+            cost = np.ascontiguousarray(gen_cost_per_MW, dtype=np.float32).reshape(self.model.n_gen)
+        self._n_reward_slot = 0
+        check(self._lib.gpf_set_rewards(self._h, len(slots), arr, ptr(cost, C.c_float)), "gpf_set_rewards")
+        self._n_reward_slot = len(slots)
+
+    def _reward_slots(self, what):
+        n = int(getattr(self, "_n_reward_slot", 0))
+        if n == 0:
+            raise GridPFError(f"{what}: rewards are off (set_rewards)")
+        return n
+
+    def rewards(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """float32 ``[n, n_slot]``: the rewards of the last one-step launch (0 on a lane that was reset since); synchronous.  Refused after
+        a multi-step launch, which computes none."""
+        ns = self._reward_slots("rewards")
+        lane0, n = self._range(lane0, n)
+        out = np.zeros((n, ns), dtype=np.float32)
+        check(self._lib.gpf_get_rewards(self._h, lane0, n, ptr(out, C.c_float)), "gpf_get_rewards")
+        return out
+
+    def reward_views(self) -> dict:
+        """``{"rewards": float32 torch tensor [n_lanes, n_slot]}`` ALIASING the engine-owned rewards (what a device-resident learner reads,
+        no copy; order the reader on ``device_views()["stream"]``)."""
+        import torch
+        ns = self._reward_slots("reward_views")
+        rp = (C.c_void_p * _capi.N_REWARD_POINTERS)()
+        check(self._lib.gpf_reward_device_pointers(self._h, rp, _capi.N_REWARD_POINTERS), "gpf_reward_device_pointers")
+        cap = self._lib.gpf_lane_capacity(self._h)
+        iface = {"shape": (cap, ns), "typestr": "<f4", "data": (int(rp[0]), False), "version": 2, "strides": None}
+        holder = type("_Arr", (), {"__cuda_array_interface__": iface})()
+        return {"rewards": torch.as_tensor(holder, device=torch.device("cuda", self.device))[:self.n_lanes]}
+
+    def rewards_eval(self, lane0: int = 0, n: Optional[int] = None, flags=None, out=None):
+        """The rewards of lanes ``[lane0, lane0 + n)`` on their CURRENT state (results row, rho, line status, done / status, dispatch, storage
+        set-points), one read-only kernel queued on the engine's stream: for a state restored or copied into a lane.  ``flags``: a uint8
+        CUDA tensor ``[n, 2]`` {illegal, ambiguous} (None: none).  Without ``out`` the result ALIASES the lanes' rows of the engine-owned
+        rewards; ``out`` may be a float32 CUDA tensor ``[n, >= n_slot]`` with unit column stride."""
+        import torch
+        ns = self._reward_slots("rewards_eval")
+        lane0, n = self._range(lane0, n)
+        fp = None
+        if flags is not None:
+            if not (isinstance(flags, torch.Tensor) and flags.is_cuda and flags.dtype == torch.uint8 and tuple(flags.shape) == (n, 2)
+                    and flags.is_contiguous() and flags.device.index == self.device):
+                raise ValueError(f"rewards_eval: flags must be a contiguous uint8 CUDA tensor [{n}, 2] on cuda:{self.device}")
+            fp = C.c_void_p(flags.data_ptr())
+        if out is None:
+            check(self._lib.gpf_rewards_eval(self._h, lane0, n, fp, None, 0), "gpf_rewards_eval")
+            if getattr(self, "_rw_view", None) is None:
+                self._rw_view = self.reward_views()["rewards"]
+            return self._rw_view[lane0:lane0 + n]
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2):
+            raise ValueError("rewards_eval: out must be a 2-d float32 CUDA tensor")
+        if out.device.index != self.device or out.shape[0] != n or out.stride(1) != 1:
+            raise ValueError(f"rewards_eval: out must live on cuda:{self.device} and have {n} rows with unit column stride")
+        stride = int(out.stride(0)) if n > 1 and out.shape[1] >= ns else int(out.shape[1])
+        check(self._lib.gpf_rewards_eval(self._h, lane0, n, fp, C.c_void_p(out.data_ptr()), stride), "gpf_rewards_eval")
+        return out[:, :ns]
 
     # ---- zero-copy device views ------------------------------------------------------------------------------------------
     def device_views(self):

@@ -518,6 +518,28 @@ class ShardedEngine:
     def alert_reward(self, lane0: int = 0, n=None):
         return np.concatenate([eng.alert_reward(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
 
+    # ---- the environment's rewards (PowerFlowEngine.set_rewards): the same slots on every device, rows by blocks ----
+    def set_rewards(self, slots, gen_cost_per_MW=None):
+        for eng in self.engines:
+            eng.set_rewards(slots, gen_cost_per_MW)
+
+    def rewards(self, lane0: int = 0, n=None):
+        return np.concatenate([eng.rewards(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
+
+    def rewards_eval(self, lane0: int = 0, n=None, flags=None, out=None):
+        """One tensor per shard that intersects the range (each on its own device and stream); ``flags`` / ``out``: a list with one tensor
+        per such shard (the rows of its lanes)."""
+        parts = self._parts(lane0, n)
+        fl = [None] * len(parts) if flags is None else list(flags)
+        outs = [None] * len(parts) if out is None else list(out)
+        if len(outs) != len(parts) or len(fl) != len(parts):
+            raise ValueError(f"ShardedEngine.rewards_eval: {len(parts)} shards intersect the range, {len(fl)} flag / {len(outs)} output tensors given")
+        return [eng.rewards_eval(l0, k, flags=f, out=o) for (eng, l0, k, _), f, o in zip(parts, fl, outs)]
+
+    def reward_views(self):
+        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
+        return [eng.reward_views() for eng in self.engines]
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

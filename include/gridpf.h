@@ -708,6 +708,60 @@ int gpf_set_alert_state(gpf_handle h, int32_t lane0, int32_t n, const int32_t* s
 int gpf_get_alert_reward(gpf_handle h, int32_t lane0, int32_t n, float* reward);
 int gpf_alert_device_pointers(gpf_handle h, void** out, int32_t n);
 
+/* ---- the environment's rewards of the batched acting path (grid2op_amd/csrc/gridpf_reward.hpp): what env.step returns as `reward` and
+ * info["rewards"], for every lane of a ONE-STEP launch, in one side kernel queued last (after the alert post-step); the step, power-flow,
+ * topology, opponent and alert kernels are not involved, and with rewards off gpf_step_n launches nothing for them.  A lane has up to
+ * GPF_REWARD_MAX_SLOTS slots (the reference's reward_class + other_rewards); a slot is a kind and its parameters p[]:
+ *   GPF_RW_REDISP (Reward/redispReward.py:169-211)  p = alpha_redisp, max_regret, min_reward, reward_illegal_ambiguous, dts
+ *       failed: min_reward; illegal or ambiguous: reward_illegal_ambiguous; else
+ *       (max_regret - mc dts (sum gen_p - sum load_p + alpha sum|actual_dispatch| + sum|storage_power|)) / sum load_p, mc the largest
+ *       gen_cost_per_mw over the generators whose gen_p of this step is > 0.  dts: hours per step (delta_time_seconds / 3600).
+ *   GPF_RW_L2RPN (Reward/l2RPNReward.py:56-77)      no p.  failed: 0; else sum over the lines of
+ *       max(1 - min(|a_or| / (|thermal_limit| + float32(0.1)), 1)^2, 0); the flags play no part.
+ *   GPF_RW_LINES_CAPACITY (Reward/linesCapacityReward.py:49-62)  no p.  failed, illegal or ambiguous: 0; else with n connected lines and
+ *       u = clip(sum rho[connected], 0, n): (n - u) / n.
+ *   GPF_RW_ECONOMIC (Reward/economicReward.py:57-71) p = worst_cost, reward_min, reward_max, dts.  failed, illegal or ambiguous: reward_min;
+ *       else with c = sum(gen_p cost) dts: reward_min + (reward_max - reward_min) clip(worst_cost - c, 0, worst_cost) / worst_cost.
+ *   GPF_RW_GAMEPLAY (Reward/gameplayReward.py:44-52) p = reward_min, reward_max.  failed: reward_min; illegal or ambiguous: reward_min / 2
+ *       (a float32 division); else reward_max.
+ * failed is the lane's episode-ending step, the engine's done (it has no done without an error: the reference's is_done and has_error
+ * coincide; with auto-reset the done byte still says that the step failed).  illegal = the topology flag of THIS launch (a launch without
+ * topology actions has none, whatever gpf_get_topo_flags still holds) OR "a redispatch action was cancelled in this step" (the change of
+ * gpf_get_env_illegal over the step, from a device-side snapshot queued before it when rewards and dynamics are both on); ambiguous = the
+ * topology flag.  The reference's is_illegal_reco cannot occur (generator switch-off is not modelled).
+ * Inputs: gen_p / load_p / a_or of the float32 results row, rho, line_status, the thermal limits; actual_dispatch = the dynamics' actual
+ * dispatch with gpf_set_env_dynamics on, else the lanes' gpf_set_lane_redispatch delta, else zero; storage_power = the storage set-points
+ * of the lane's injection row as float32 (with the dynamics on the step wrote them: the power AFTER _compute_storage's clamps).
+ * Arithmetic: every sum, product and maximum in float64 from the float32 inputs, share t of 64 takes elements t, t + 64, ... in order,
+ * the shares are combined by a fixed butterfly, the slot is rounded ONCE to float32: the same bits in every run and at every place in
+ * the batch.  Out of the reference's domain: GPF_RW_REDISP with no generator at gen_p > 0 (the reference raises) writes a quiet NaN; a
+ * zero load sum gives the IEEE quotient; GPF_RW_LINES_CAPACITY with no line connected gives 1, what numpy.interp returns for xp = [0, 0].
+ *   gpf_set_rewards   : n_slot = 0 or slots = NULL turns rewards off.  Refused before the device is touched (on a header-only handle too):
+ *                       more than GPF_REWARD_MAX_SLOTS slots, an unknown kind, a parameter that is not finite, dts <= 0, GPF_RW_REDISP /
+ *                       GPF_RW_ECONOMIC without gen_cost_per_mw [n_gen] or with a cost that is negative or not finite.  Rewards start at 0.
+ *   gpf_get_rewards   : reward[n][n_slot] of the last launch (0 on a lane that was reset since).  GPF_E_INVALID while rewards are off and
+ *                       when the last gpf_step_n was a multi-step launch (it queues nothing for rewards).
+ *   gpf_rewards_eval  : the same rules on the lanes' CURRENT state (a state restored or copied into a lane), read-only, queued on the
+ *                       engine's stream.  failed here is done or a non-zero status; flags_dev is a DEVICE array [n][2] {illegal, ambiguous}
+ *                       (NULL: none).  out_dev = NULL writes the engine-owned rows of the lanes; else rows of row_stride >= n_slot floats.
+ *   gpf_reward_device_pointers : out[0] the engine-owned rewards, float32 [lane capacity][n_slot].  n must be GPF_N_REWARD_POINTERS.
+ * gpf_reset_lanes zeroes the lanes' rewards; gpf_copy_lanes, gpf_fanout_n1 and gpf_simulate_batch leave them alone. */
+#define GPF_REWARD_MAX_SLOTS 8
+#define GPF_N_REWARD_POINTERS 1
+#define GPF_RW_REDISP 1
+#define GPF_RW_L2RPN 2
+#define GPF_RW_LINES_CAPACITY 3
+#define GPF_RW_ECONOMIC 4
+#define GPF_RW_GAMEPLAY 5
+typedef struct gpf_reward_slot {
+  int32_t kind;                    /* GPF_RW_* */
+  double p[6];                     /* the kind's parameters, in the order above; the rest is ignored */
+} gpf_reward_slot;
+int gpf_set_rewards(gpf_handle h, int32_t n_slot, const gpf_reward_slot* slots, const float* gen_cost_per_mw);
+int gpf_get_rewards(gpf_handle h, int32_t lane0, int32_t n, float* reward);
+int gpf_rewards_eval(gpf_handle h, int32_t lane0, int32_t n, const uint8_t* flags_dev, float* out_dev, int64_t row_stride);
+int gpf_reward_device_pointers(gpf_handle h, void** out, int32_t n);
+
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
  * Observation/baseObservation.py:4464-4540; with subtract / divide what gym_compat.BoxGymObsSpace(attr_to_keep, subtract, divide) puts on
