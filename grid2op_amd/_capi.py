@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "library_path", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
@@ -38,9 +38,11 @@ EXPORTED_SYMBOLS = [
     "gpf_set_alerts", "gpf_set_lane_alerts", "gpf_alerts_on_device", "gpf_alert_state_ints", "gpf_get_alert_state", "gpf_set_alert_state",
     "gpf_get_alert_reward", "gpf_alert_device_pointers",
     "gpf_set_rewards", "gpf_get_rewards", "gpf_rewards_eval", "gpf_reward_device_pointers",
+    "gpf_set_episode_limit", "gpf_get_episode_ends", "gpf_get_episode_stats", "gpf_episode_device_pointers",
 ]
 N_ALERT_POINTERS = 3       # include/gridpf.h GPF_N_ALERT_POINTERS
 N_REWARD_POINTERS = 1      # include/gridpf.h GPF_N_REWARD_POINTERS
+N_EPISODE_POINTERS = 8     # include/gridpf.h GPF_N_EPISODE_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
 
@@ -89,6 +91,11 @@ class GpfOpponentDesc(C.Structure):
 class GpfRewardSlot(C.Structure):
     """include/gridpf.h gpf_reward_slot"""
     _fields_ = [("kind", C.c_int32), ("p", C.c_double * 6)]
+
+
+class GpfEpisodeDesc(C.Structure):
+    """include/gridpf.h gpf_episode_desc"""
+    _fields_ = [("max_steps", C.c_int32), ("lane_max_steps", _ip), ("per_timestep", C.c_float), ("alert_end_bonus", C.c_float)]
 
 
 class GpfAlertDesc(C.Structure):
@@ -246,6 +253,10 @@ def lib() -> C.CDLL:
     L.gpf_get_rewards.argtypes = [h, i32, i32, _fp]
     L.gpf_rewards_eval.argtypes = [h, i32, i32, C.c_void_p, C.c_void_p, C.c_int64]
     L.gpf_reward_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
+    L.gpf_set_episode_limit.argtypes = [h, C.POINTER(GpfEpisodeDesc)]
+    L.gpf_get_episode_ends.argtypes = [h, i32, i32, _bp, _bp, _ip, _fp]
+    L.gpf_get_episode_stats.argtypes = [h, i32, i32, _dp, _dp, _ip, _ip]
+    L.gpf_episode_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

@@ -21,6 +21,8 @@
 
 #include <stdint.h>
 
+#include "gridpf_episode.hpp"
+
 namespace gpf {
 
 // the lane's block the observation reads: int32 [6 A + 1], sections of A elements at k * A (= GPF_ALERT_OBS_* of include/gridpf.h)
@@ -38,6 +40,12 @@ constexpr int AX_CURRENT = 1;         // AlertReward._lines_currently_attacked
 constexpr int AX_ID = 2;              // bits 0-31 AlertReward._current_id, bit 32: the lane's pre-step ran in this launch
 constexpr int AX_RINGS = 3;           // _ts_attack [R], then _alert_launched [R]
 constexpr uint64_t AX_RAN = (uint64_t)1 << 32;
+// bit 33: this step may be the lane's truncated one (it reaches the episode limit unless it fails), so the pre-step left
+// _was_alert_used_after_attack as the previous step's reward had set it: on a done without an error AlertReward returns its bonus BEFORE
+// _update_state clears that array (alertReward.py:179-183), and the final observation shows the previous step's values.  The post-step
+// clears it after all when the step was not truncated.
+constexpr uint64_t AX_KEPT = (uint64_t)1 << 33;
+GPF_ALERT_HD inline bool alert_may_truncate(int steps_before, int limit) { return limit > 0 && steps_before + 1 >= limit; }
 GPF_ALERT_HD inline int alert_aux_words(int W) { return 3 + 2 * (W + 2); }
 
 struct AlertCfg {
@@ -138,7 +146,7 @@ GPF_ALERT_HD inline int alert_used_no_blackout(bool alerted) { return alerted ? 
 // ---- one lane with plain loops (the host emulator; the kernels below run the same rules with one thread per line) -----------------------
 // ob: the lane's observation block, ax: its words.  steps_survived / done: the lane's episode[0] and done flag BEFORE the step.
 // Returns 1 when the lane's bookkeeping ran (neither reset nor left alone).
-inline int alert_prestep_serial(const AlertCfg& c, int* ob, uint64_t* ax, int steps_survived, int done, uint64_t raise, uint64_t att) {
+inline int alert_prestep_serial(const AlertCfg& c, int* ob, uint64_t* ax, int steps_survived, int done, uint64_t raise, uint64_t att, int limit = 0) {
   const int A = c.A;
   if (steps_survived == 0) {
     for (int t = 0; t < A; ++t) {
@@ -154,24 +162,30 @@ inline int alert_prestep_serial(const AlertCfg& c, int* ob, uint64_t* ax, int st
   if (done) { ax[AX_ID] &= ~AX_RAN; return 0; }
   raise &= alert_valid_bits(A); att &= alert_valid_bits(A);
   uint64_t already = 0;
+  const bool kept = alert_may_truncate(steps_survived, limit);
   for (int t = 0; t < A; ++t) {
     AlertLine s{ob[AO_ACTIVE * A + t], ob[AO_SINCE_ALERT * A + t], ob[AO_DURATION * A + t], ob[AO_SINCE_ATTACK * A + t], ob[AO_UNDER_ALERT * A + t]};
     const bool b = alert_update_line(c.W, (raise >> t) & 1, (att >> t) & 1, att != 0, (ax[AX_ALREADY] >> t) & 1, s);
     already |= (uint64_t)(b ? 1 : 0) << t;
     ob[AO_ACTIVE * A + t] = s.last; ob[AO_SINCE_ALERT * A + t] = s.since_alert; ob[AO_DURATION * A + t] = s.duration;
     ob[AO_SINCE_ATTACK * A + t] = s.since_attack; ob[AO_UNDER_ALERT * A + t] = s.under_alert;
-    ob[AO_USED * A + t] = 0;                                           // (alertReward.py:156)
+    if (!kept) ob[AO_USED * A + t] = 0;                                // (alertReward.py:156)
   }
   ob[AO_TOTAL * A] += alert_popcount(raise);
   ax[AX_ALREADY] = already;
   alert_ring_update(c.W, ax, att, raise);
+  if (kept) ax[AX_ID] |= AX_KEPT;
   return 1;
 }
 
-// ... and its post-step: blackout = the lane's done flag AFTER the step (in the engine done = the step failed = has_error).  Returns the reward.
-inline float alert_poststep_serial(const AlertCfg& c, int* ob, uint64_t* ax, int blackout) {
+// ... and its post-step: blackout = the lane's done flag AFTER the step (in the engine done = the step failed = has_error).  truncated:
+// the step reached the lane's episode limit without failing: the reward is AlertReward's end-of-episode bonus and nothing is scored
+// (alertReward.py:179-181).  Returns the reward.
+inline float alert_poststep_serial(const AlertCfg& c, int* ob, uint64_t* ax, int blackout, bool truncated = false, float end_bonus = 0.f) {
   if (!(ax[AX_ID] & AX_RAN)) return 0.f;
+  if (truncated) return end_bonus;
   const int A = c.A, W = c.W, id = (int)(uint32_t)ax[AX_ID];
+  if (ax[AX_ID] & AX_KEPT) for (int t = 0; t < A; ++t) ob[AO_USED * A + t] = 0;
   uint64_t* ts = ax + AX_RINGS;
   const uint64_t* al = ts + (W + 2);
   if (blackout) {
@@ -200,6 +214,8 @@ struct AlertDev {
   int info_lane, info_area;
   const int* lines;                  // [A] the alertable line ids (the opponent's list; grouped by area with areas)
   const int* area_of;                // [A] area of every alertable line (zeros without areas)
+  const int* ep_limit;               // [lanes] episode limits (gpf_set_episode_limit), or null: off
+  float end_bonus;                   // AlertReward.reward_end_episode_bonus
 };
 
 constexpr int ALERT_WPB = 4;         // lanes (wavefronts) per block
@@ -233,18 +249,20 @@ __global__ __launch_bounds__(64 * ALERT_WPB) void alert_prestep_kernel(AlertCfg 
   const bool att_t = mine && d.info[(size_t)lane * d.info_lane + (size_t)d.area_of[tid] * d.info_area] == d.lines[tid];
   const uint64_t att = __ballot(att_t);
   bool already = false;
+  const bool kept = d.ep_limit && alert_may_truncate(d.episode[(size_t)lane * 2], d.ep_limit[lane]);
   if (mine) {
     AlertLine s{ob[AO_ACTIVE * A + tid], ob[AO_SINCE_ALERT * A + tid], ob[AO_DURATION * A + tid], ob[AO_SINCE_ATTACK * A + tid], ob[AO_UNDER_ALERT * A + tid]};
     already = alert_update_line(c.W, (raise >> tid) & 1, att_t, att != 0, (ax[AX_ALREADY] >> tid) & 1, s);
     ob[AO_ACTIVE * A + tid] = s.last; ob[AO_SINCE_ALERT * A + tid] = s.since_alert; ob[AO_DURATION * A + tid] = s.duration;
     ob[AO_SINCE_ATTACK * A + tid] = s.since_attack; ob[AO_UNDER_ALERT * A + tid] = s.under_alert;
-    ob[AO_USED * A + tid] = 0;                                         // (alertReward.py:156)
+    if (!kept) ob[AO_USED * A + tid] = 0;                              // (alertReward.py:156)
   }
   const uint64_t already_all = __ballot(already);
   if (tid == 0) {
     ob[AO_TOTAL * A] += alert_popcount(raise);
     ax[AX_ALREADY] = already_all;
     alert_ring_update(c.W, ax, att, raise);
+    if (kept) ax[AX_ID] |= AX_KEPT;
   }
 }
 
@@ -260,6 +278,11 @@ __global__ __launch_bounds__(64 * ALERT_WPB) void alert_poststep_kernel(AlertCfg
   uint64_t* ax = (uint64_t*)d.aux + (size_t)lane * alert_aux_words(W);
   const uint64_t idw = ax[AX_ID];
   if (!(idw & AX_RAN)) { if (tid == 0) d.reward[lane] = 0.f; return; }
+  if (d.ep_limit && episode_truncated(d.episode[(size_t)lane * 2], d.ep_limit[lane], d.done[lane] != 0)) {
+    if (tid == 0) d.reward[lane] = d.end_bonus;                        // (alertReward.py:179-181: before _update_state, nothing is scored)
+    return;
+  }
+  if ((idw & AX_KEPT) && tid < A) ob[AO_USED * A + tid] = 0;
   const int id = (int)(uint32_t)idw;
   uint64_t* ts = ax + AX_RINGS;
   const uint64_t* al = ts + (W + 2);

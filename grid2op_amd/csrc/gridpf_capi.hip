@@ -666,6 +666,7 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   if (e->ta_on) { int rc_t = reset_topo_state(e, lane0, n); if (rc_t != GPF_OK) return rc_t; }
   if (e->al_on) { int rc_a = alert_reset_lanes(e, lane0, n); if (rc_a != GPF_OK) return rc_a; }
   if (e->rw_on) { int rc_r = reward_reset_lanes(e, lane0, n); if (rc_r != GPF_OK) return rc_r; }
+  if (e->ep_on) { int rc_p = episode_reset_lanes(e, lane0, n); if (rc_p != GPF_OK) return rc_p; }
   topo_unmoved(e, lane0, n);
   HIP_TRY(hipStreamSynchronize(e->stream));
   const int init_class = topo_class_of(e, e->h_init_topo.data(), g.n_shunt ? e->h_init_shunt_bus.data() : nullptr);
@@ -1229,6 +1230,7 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
   }
   if (e->opp_kind && err == hipSuccess) err = opponent_copy_lanes(e, src, dst, n);
   if (e->al_on && err == hipSuccess) err = alert_copy_lanes(e, src, dst, n);
+  if (e->ep_on && err == hipSuccess) err = episode_copy_lanes(e, src, dst, n);
   HIP_TRY(err);
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
@@ -1723,6 +1725,9 @@ extern "C" {
 int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o) {
   if (!e || !o) return fail(GPF_E_INVALID, "gpf_step_n: null");
   if (n_steps <= 0) return fail(GPF_E_INVALID, "gpf_step_n: n_steps must be positive");
+  if ((e->ep_on || e->ep_host_on) && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: with an episode limit set (gpf_set_episode_limit) a launch must be a one-step launch (an episode "
+                               "ends, and a truncated lane restarts, between two steps): use n_steps = 1");
   if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_step_n: no chronics uploaded");
   if (e->traj_cap && n_steps > e->traj_cap)
     return fail(GPF_E_INVALID, "gpf_step_n: n_steps exceeds the trajectory buffer (gpf_set_trajectory sizes it; 0 releases it)");
@@ -1767,14 +1772,15 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   }
   rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
   if (rc != GPF_OK) return rc;
+  // lanes an action moved to another class than their reset topology's: an auto-reset puts them back, the host re-keys them (with an
+  // episode limit set the truncated lanes join the list, and it is read back once, behind episode_kernel)
+  const bool list_resets = e->ta_on && o->auto_reset && e->ta_n_moved > 0;
   if (e->ta_on) {
-    // lanes an action moved to another class than their reset topology's: an auto-reset puts them back, the host re-keys them
-    const bool list_resets = o->auto_reset && e->ta_n_moved > 0;
     if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
     hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), *e->ta_rules,
                        e->n_lanes, acts ? 1 : 0, n_steps, list_resets ? 1 : 0);
     HIP_TRY(hipGetLastError());
-    if (list_resets) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
+    if (list_resets && !e->ep_on) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
   }
   if (e->al_on) {                           // the reward of the step, on its done flag
     rc = alert_poststep(e);
@@ -1783,6 +1789,11 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if (e->rw_on && n_steps == 1) {           // the rewards of the step, last: on its results, done flag and flags
     rc = reward_poststep(e, acts);
     if (rc != GPF_OK) return rc;
+  }
+  if (e->ep_on) {                           // the episode's end, behind everything that reads the final step's state
+    rc = episode_poststep(e, o->auto_reset != 0, o->track_cooldown != 0, list_resets);
+    if (rc != GPF_OK) return rc;
+    if (list_resets) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
   }
   e->traj_valid = e->traj_cap ? n_steps : 0;
   e->last_t0 = t0; e->last_n_steps = n_steps; e->last_track_cooldown = o->track_cooldown != 0;

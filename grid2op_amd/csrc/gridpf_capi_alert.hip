@@ -29,6 +29,7 @@ gpf::AlertDev alert_dev(const gpf_engine* e, bool with_act) {
     d.lines = e->opp_lines.p;
   }
   d.area_of = e->al_area_of.p;
+  if (e->ep_on) { d.ep_limit = e->ep_limit.p; d.end_bonus = e->ep_alert_bonus; }
   return d;
 }
 

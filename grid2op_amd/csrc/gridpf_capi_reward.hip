@@ -63,6 +63,7 @@ int reward_poststep(gpf_engine* e, bool topo_flags) {
   gpf::RewardDev d = reward_dev(e);
   d.topo_flags = topo_flags ? e->ta_flags.p : nullptr;
   if (e->env_on) { d.ill_now = e->env_illegal.p; d.ill_snap = e->rw_ill_snap.p; }
+  if (e->ep_on) { d.ep_limit = e->ep_limit.p; d.episode = e->episode.p; }     // a step at the lane's limit is the reference's is_done
   d.reward = e->rw_out.p; d.row_stride = e->rw_n_slot;
   return reward_launch(e, d, 0, e->n_lanes);
 }
@@ -79,6 +80,7 @@ int gpf_set_rewards(gpf_handle e, int32_t n_slot, const gpf_reward_slot* slots, 
   if (n_slot == 0 || !slots) {
     if (e->rw_on) { HIP_TRY(hipSetDevice(e->device)); HIP_TRY(hipStreamSynchronize(e->stream)); }
     rewards_off(e);
+    if (e->ep_on) return episode_rewards_changed(e);
     return GPF_OK;
   }
   const std::string at = "gpf_set_rewards: ";
@@ -115,6 +117,7 @@ int gpf_set_rewards(gpf_handle e, int32_t n_slot, const gpf_reward_slot* slots, 
   if (err == hipSuccess) err = hipMemset(e->rw_ill_snap.p, 0, cap * sizeof(int));
   if (err != hipSuccess) { rewards_off(e); HIP_TRY(err); }
   e->rw_n_slot = n_slot; e->rw_cost_on = need_cost; e->rw_on = true;
+  if (e->ep_on) return episode_rewards_changed(e);    // the returns of another slot table mean nothing for this one
   return GPF_OK;
 }
 

@@ -264,6 +264,15 @@ struct gpf_engine {
   DevArr<unsigned char> rw_slots;       // [rw_n_slot] gpf_reward_slot
   DevArr<float> rw_cost, rw_out;
   DevArr<int> rw_ill_snap;              // [cap_lanes]
+  // episode time limits (gridpf_episode.hpp, gridpf_capi_episode.hip): the lanes' limits, the flags / length / duration reward of the last
+  // one-step launch, episode[lane][0] as that launch left it, and the statistics across launches (returns: [cap_lanes][8] float64).
+  // ep_host_on: a header-only handle was given a valid limit (gpf_step_n refuses multi-step launches there too)
+  bool ep_on = false, ep_host_on = false;
+  float ep_per_timestep = 1.f, ep_alert_bonus = 0.f;
+  DevArr<int> ep_limit, ep_length, ep_steps_prev, ep_length_last, ep_n_episodes;
+  DevArr<unsigned char> ep_flags;
+  DevArr<float> ep_duration;
+  DevArr<double> ep_ret_run, ep_ret_last;
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
@@ -407,6 +416,14 @@ void alerts_off(gpf_engine* e);
 int reward_prestep(gpf_engine* e);
 int reward_poststep(gpf_engine* e, bool topo_flags);
 int reward_reset_lanes(gpf_engine* e, int lane0, int n);
+
+// gridpf_capi_episode.hip: episode_kernel, queued last in a one-step launch with a limit set (list_resets: truncated lanes are appended to
+// ta_list / ta_list_rows for the host's re-keying), the feature's share of gpf_reset_lanes / gpf_copy_lanes, and what gpf_set_rewards
+// does to the returns (a new slot table starts them at 0)
+int episode_poststep(gpf_engine* e, bool auto_reset, bool track_cooldown, bool list_resets);
+int episode_reset_lanes(gpf_engine* e, int lane0, int n);
+hipError_t episode_copy_lanes(gpf_engine* e, int src, int dst, int n);
+int episode_rewards_changed(gpf_engine* e);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

@@ -22,6 +22,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "gridpf_episode.hpp"
+
 namespace gpf {
 
 // kinds (= GPF_RW_* of include/gridpf.h) and the parameters p[] of each
@@ -80,16 +82,20 @@ constexpr double RW_LINES_CAPACITY_NONE = 1.0;
 
 // One slot of one lane.  failed: the lane's episode-ending step (the engine's done = the reference's is_done and has_error);
 // illegal / ambiguous: the reference's is_illegal / is_ambiguous of the step.  Out of the reference's domain: RW_REDISP without a
-// generator that produces (the reference raises) is a quiet NaN; a zero load sum gives the IEEE quotient.
+// generator that produces (the reference raises) is a quiet NaN; a zero load sum gives the IEEE quotient.  truncated: the step reached the
+// lane's episode limit without failing (episode_truncated): the reference's is_done is failed || truncated, and two kinds read it --
+// L2RPNReward returns 0 when is_done (l2RPNReward.py:57), RedispReward gives an illegal or ambiguous FINAL step reward_min
+// (redispReward.py:171-176).
 template <typename X>
-GPF_RW_HD inline float reward_value(const X& x, const RewardSlot& s, const RewardRow& r, bool failed, bool illegal, bool ambiguous) {
+GPF_RW_HD inline float reward_value(const X& x, const RewardSlot& s, const RewardRow& r, bool failed, bool illegal, bool ambiguous,
+                                    bool truncated = false) {
   GPF_RW_NO_FMA
   const bool bad = illegal || ambiguous;
   const double* p = s.p;
   switch (s.kind) {
     case RW_REDISP: {
       if (failed) return (float)p[2];
-      if (bad) return (float)p[3];
+      if (bad) return (float)(truncated ? p[2] : p[3]);
       const double sg = x.reduce(r.n_gen, 0.0, [&](int i) { return (double)r.gen_p[i]; }, RwAdd{});
       const double sl = x.reduce(r.n_load, 0.0, [&](int i) { return (double)r.load_p[i]; }, RwAdd{});
       const double sd = r.dispatch ? x.reduce(r.n_gen, 0.0, [&](int i) { return fabs((double)r.dispatch[i]); }, RwAdd{}) : 0.0;
@@ -101,7 +107,7 @@ GPF_RW_HD inline float reward_value(const X& x, const RewardSlot& s, const Rewar
       return (float)((p[1] - regret) / sl);
     }
     case RW_L2RPN: {
-      if (failed) return 0.f;
+      if (failed || truncated) return 0.f;
       const double v = x.reduce(r.n_line, 0.0, [&](int i) {
         const double rel = fmin(fabs((double)r.a_or[i]) / (fabs((double)r.thermal[i]) + (double)0.1f), 1.0);
         return fmax(1.0 - rel * rel, 0.0);
@@ -159,6 +165,8 @@ struct RewardDev {
   const int* ill_now;                // [lanes] cancelled redispatch actions since the reset, after the step ...
   const int* ill_snap;               // ... and before it; both null: no dynamics
   const unsigned char* eval_flags;   // [n][2] the caller's flags (gpf_rewards_eval), indexed from the range's first lane, or null
+  const int* ep_limit;               // [lanes] episode limits (gpf_set_episode_limit), or null: off, or gpf_rewards_eval ...
+  const int* episode;                // ... and the lanes' {steps survived, resets} after the step
   float* reward;                     // row of the range's first lane
   long long row_stride;
   int n_out, n_inj, off_gen_p, off_load_p, off_a_or, off_sto, n_gen, n_load, n_line, n_sto;
@@ -180,6 +188,7 @@ __global__ __launch_bounds__(64 * RW_WPB) void reward_kernel(RewardDev d, const 
   if (d.topo_flags) { illegal = d.topo_flags[lane * 2] != 0; ambiguous = d.topo_flags[lane * 2 + 1] != 0; }
   if (d.ill_now) illegal = illegal || d.ill_now[lane] != d.ill_snap[lane];
   if (d.eval_flags) { illegal = illegal || d.eval_flags[(size_t)k * 2] != 0; ambiguous = ambiguous || d.eval_flags[(size_t)k * 2 + 1] != 0; }
+  const bool truncated = d.ep_limit && episode_truncated(d.episode[lane * 2], d.ep_limit[lane], failed);
   const float* row = d.out + lane * d.n_out;
   RewardRow r;
   r.gen_p = row + d.off_gen_p; r.load_p = row + d.off_load_p; r.a_or = row + d.off_a_or;
@@ -190,7 +199,7 @@ __global__ __launch_bounds__(64 * RW_WPB) void reward_kernel(RewardDev d, const 
   float* o = d.reward + (size_t)k * d.row_stride;
   const RewardWave x{tid};
   for (int s = 0; s < n_slot; ++s) {
-    const float v = reward_value(x, slots[s], r, failed, illegal, ambiguous);
+    const float v = reward_value(x, slots[s], r, failed, illegal, ambiguous, truncated);
     if (tid == 0) o[s] = v;
   }
 }

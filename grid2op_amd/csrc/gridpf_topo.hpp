@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "gridpf_episode.hpp"
 #include "gridpf_topo_mask.hpp"
 
 namespace gpf {
@@ -300,8 +301,7 @@ __global__ __launch_bounds__(64) void topo_poststep_kernel(TopoDev g, TopoLanes 
   int* lb = s.last_bus + (size_t)lane * D;
   const int* topo = g.topo + (size_t)lane * D;
   if (g.episode[(size_t)lane * 2 + 1] != s.ep_snap[lane]) {     // auto-reset in this launch: env.reset() starts from scratch
-    for (int i = tid; i < S; i += nth) scd[i] = 0;
-    for (int i = tid; i < D; i += nth) { const int v = g.topo0[(size_t)lane * D + i]; lb[i] = v >= 1 ? v : 1; }
+    topo_reset_acting(scd, lb, g.topo0 + (size_t)lane * D, S, D, tid, nth);
     if (list_resets) {
       __shared__ int slot;
       if (tid == 0) { slot = atomicAdd(&s.list[0], 1); s.list[1 + slot] = lane; }

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import GpfAlertDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
+from ._capi import GpfAlertDesc, GpfEpisodeDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
 from .grid_model import GridModel
 
 __all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT", "MASK_TOO_MANY_LINES", "MASK_TOO_MANY_SUBS",
@@ -214,10 +214,19 @@ def reward_config(kind, gen_cost_per_MW=None, gen_pmax=None, delta_time_seconds=
     return out
 
 
+def alert_end_bonus(alert_reward=None) -> float:
+    """``reward_end_episode_bonus`` of an ``AlertReward`` instance (anything with that attribute), or the class's default 1.0
+    (Reward/alertReward.py:75-91): the ``alert_end_bonus`` of `PowerFlowEngine.set_episode_limit`."""
+    if alert_reward is None:
+        return 1.0
+    return float(alert_reward.reward_end_episode_bonus)
+
+
 def alert_config(parameters=None, reward_min_no_blackout=-1.0, reward_min_blackout=-10.0, reward_max_no_blackout=1.0, reward_max_blackout=2.0) -> dict:
     """Keyword arguments of `PowerFlowEngine.set_alerts` from a reference-style configuration: ``parameters`` is a ``grid2op.Parameters``
     (or anything with ``ALERT_TIME_WINDOW``, or a dict, or None for the default 12); the four constants are ``AlertReward``'s
-    (Reward/alertReward.py:75-91).  ``reward_end_episode_bonus`` has no counterpart: the caller that truncates episodes adds it."""
+    (Reward/alertReward.py:75-91).  ``reward_end_episode_bonus`` belongs to the episode limit: `alert_end_bonus` returns it for
+    `PowerFlowEngine.set_episode_limit`."""
     if parameters is None:
         w = 12
     elif isinstance(parameters, dict):
@@ -999,7 +1008,7 @@ class PowerFlowEngine:
         """The alert bookkeeping of ``BaseEnv.step`` and ``AlertReward`` on every lane of the one-step launches (`alert_config` builds the
         arguments from the reference's ``Parameters``).  The alertable lines are the current opponent's ``lines`` (with areas: grouped by
         area), so call it after `set_opponent` / `set_opponent_areas`, which turn alerts off.  ``time_window`` None: off.  Every lane
-        starts reset.  The end-of-episode bonus of ``AlertReward`` is NOT applied (the engine has no ``done`` without an error)."""
+        starts reset.  The end-of-episode bonus of ``AlertReward`` is paid on a step truncated by `set_episode_limit`, which carries it."""
         if time_window is None:
             check(self._lib.gpf_set_alerts(self._h, None), "gpf_set_alerts")
             self._alert = None
@@ -1247,6 +1256,77 @@ class PowerFlowEngine:
         stride = int(out.stride(0)) if n > 1 and out.shape[1] >= ns else int(out.shape[1])
         check(self._lib.gpf_rewards_eval(self._h, lane0, n, fp, C.c_void_p(out.data_ptr()), stride), "gpf_rewards_eval")
         return out[:, :ns]
+
+    # ---- episode time limits (include/gridpf.h gpf_set_episode_limit; grid2op_amd/csrc/gridpf_episode.hpp) ----
+    def set_episode_limit(self, max_steps, per_timestep: float = 1.0, alert_end_bonus: float = 0.0):
+        """The reference's ``done`` without an error on every lane of the one-step launches: ``max_steps`` is one step count for all lanes
+        or an array ``[n_lanes]`` (0: no limit for that lane; after `reset` the N-th launch of a lane with limit N is the truncated one,
+        as after ``env.reset(options={"max step": N})``); None, or 0, turns the feature off.  ``per_timestep`` is
+        ``EpisodeDurationReward``'s, ``alert_end_bonus`` ``AlertReward.reward_end_episode_bonus`` (`alert_end_bonus` reads it).  Under
+        ``auto_reset`` a truncated lane restarts as a failed one does; while a limit is set multi-step launches are refused."""
+        self._ep_on = False
+        if max_steps is None:
+            check(self._lib.gpf_set_episode_limit(self._h, None), "gpf_set_episode_limit")
+            return
+        d = GpfEpisodeDesc(0, None, float(per_timestep), float(alert_end_bonus))
+        lim = None
+        if np.ndim(max_steps) > 0:
+            lim = np.ascontiguousarray(max_steps, dtype=np.int32).reshape(self.n_lanes)
+            d.lane_max_steps = ptr(lim, C.c_int32)
+            on = True
+        else:
+            d.max_steps = int(max_steps)
+            on = d.max_steps > 0
+        check(self._lib.gpf_set_episode_limit(self._h, C.byref(d)), "gpf_set_episode_limit")
+        self._ep_on = on
+
+    def _episode_on(self, what):
+        if not getattr(self, "_ep_on", False):
+            raise GridPFError(f"{what}: episode limits are off (set_episode_limit)")
+
+    def episode_ends(self, lane0: int = 0, n: Optional[int] = None) -> dict:
+        """``terminated`` / ``truncated`` bool ``[n]``, ``length`` int32 ``[n]`` (``nb_time_step`` of the episode that ended in the last
+        launch, else 0), ``duration_reward`` float32 ``[n]`` (``EpisodeDurationReward``); synchronous."""
+        self._episode_on("episode_ends")
+        lane0, n = self._range(lane0, n)
+        te, tr = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        ln, du = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        check(self._lib.gpf_get_episode_ends(self._h, lane0, n, ptr(te, C.c_uint8), ptr(tr, C.c_uint8), ptr(ln, C.c_int32), ptr(du, C.c_float)),
+              "gpf_get_episode_ends")
+        return dict(terminated=te.astype(bool), truncated=tr.astype(bool), length=ln, duration_reward=du)
+
+    def episode_stats(self, lane0: int = 0, n: Optional[int] = None) -> dict:
+        """``return_running`` / ``return_last`` float64 ``[n, n_slot]`` (sequential sums of the launches' float32 rewards; the episode under
+        way / the last one that ended), ``length_last`` / ``n_episodes`` int32 ``[n]``; synchronous."""
+        self._episode_on("episode_stats")
+        lane0, n = self._range(lane0, n)
+        ns = int(getattr(self, "_n_reward_slot", 0))
+        run, last = np.zeros((n, REWARD_MAX_SLOTS), np.float64), np.zeros((n, REWARD_MAX_SLOTS), np.float64)
+        ll, ne = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        check(self._lib.gpf_get_episode_stats(self._h, lane0, n, ptr(run, C.c_double), ptr(last, C.c_double), ptr(ll, C.c_int32), ptr(ne, C.c_int32)),
+              "gpf_get_episode_stats")
+        return dict(return_running=run[:, :ns].copy(), return_last=last[:, :ns].copy(), length_last=ll, n_episodes=ne)
+
+    def episode_views(self) -> dict:
+        """Zero-copy torch tensors ALIASING the episode buffers (order the reader on ``device_views()["stream"]``): ``limit`` int32
+        ``[n_lanes]`` (writable: the next launch reads it), ``terminated`` / ``truncated`` uint8 ``[n_lanes]``, ``length``,
+        ``duration_reward``, ``return_running`` / ``return_last`` float64 ``[n_lanes, n_slot]``, ``length_last``, ``n_episodes``."""
+        import torch
+        self._episode_on("episode_views")
+        ep = (C.c_void_p * _capi.N_EPISODE_POINTERS)()
+        check(self._lib.gpf_episode_device_pointers(self._h, ep, _capi.N_EPISODE_POINTERS), "gpf_episode_device_pointers")
+        cap = self._lib.gpf_lane_capacity(self._h)
+        dev = torch.device("cuda", self.device)
+        ns = int(getattr(self, "_n_reward_slot", 0))
+
+        def view(p, shape, typestr):
+            iface = {"shape": shape, "typestr": typestr, "data": (int(p), False), "version": 2, "strides": None}
+            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=dev)[:self.n_lanes]
+        flags = view(ep[1], (cap, 2), "|u1")
+        return {"limit": view(ep[0], (cap,), "<i4"), "terminated": flags[:, 0], "truncated": flags[:, 1], "length": view(ep[2], (cap,), "<i4"),
+                "duration_reward": view(ep[3], (cap,), "<f4"), "return_running": view(ep[4], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns],
+                "return_last": view(ep[5], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns], "length_last": view(ep[6], (cap,), "<i4"),
+                "n_episodes": view(ep[7], (cap,), "<i4")}
 
     # ---- zero-copy device views ------------------------------------------------------------------------------------------
     def device_views(self):

@@ -540,6 +540,26 @@ class ShardedEngine:
         """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
         return [eng.reward_views() for eng in self.engines]
 
+    # ---- episode time limits (PowerFlowEngine.set_episode_limit): one limit everywhere, or per-lane limits cut by blocks ----
+    def set_episode_limit(self, max_steps, per_timestep: float = 1.0, alert_end_bonus: float = 0.0):
+        per_lane = max_steps is not None and np.ndim(max_steps) > 0
+        if per_lane:
+            max_steps = np.asarray(max_steps).reshape(self.n_lanes)
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.set_episode_limit(max_steps[b0:b0 + bn] if per_lane else max_steps, per_timestep, alert_end_bonus)
+
+    def episode_ends(self, lane0: int = 0, n=None) -> dict:
+        parts = [eng.episode_ends(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
+        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+
+    def episode_stats(self, lane0: int = 0, n=None) -> dict:
+        parts = [eng.episode_stats(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
+        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
+
+    def episode_views(self):
+        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
+        return [eng.episode_views() for eng in self.engines]
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

@@ -658,8 +658,8 @@ int gpf_get_opponent_attack_lines(gpf_handle h, int32_t lane0, int32_t n, uint8_
  *     it was noted: was_alert_used_after_attack = 2 alert - 1, reward = mean(alert) (max_blackout - min_blackout) + min_blackout (0 without
  *     such a line); any other step scores the row time_window steps back: was_alert_used_after_attack = 1 - 2 alert, reward =
  *     (min_no_blackout - max_no_blackout) mean(alert) + max_no_blackout, the row is cleared.  The mean is a count ratio in float64, the
- *     result float32.  OUT OF SCOPE: reward_end_episode_bonus applies when done comes without an error; the engine has no such done (its
- *     chronics cursor keeps running), so the bonus stays with the caller that truncates episodes.  Alarms, the alert budget and
+ *     result float32.  reward_end_episode_bonus applies when done comes without an error (alertReward.py:179-181): that is a step
+ *     truncated by gpf_set_episode_limit, which carries the bonus; without a limit the engine has no such done.  Alarms, the alert budget and
  *     _is_alert_illegal (always False in the reference) are not modelled; the agent's alert survives an illegal or ambiguous topology action
  *     (baseEnv.py:3716-3766), so alerts are booked whatever gpf_get_topo_flags says.
  *   gpf_set_alerts      : NULL turns alerts off, as gpf_set_opponent and gpf_set_opponent_areas do.  Refused before the device is touched
@@ -724,8 +724,10 @@ int gpf_alert_device_pointers(gpf_handle h, void** out, int32_t n);
  *       else with c = sum(gen_p cost) dts: reward_min + (reward_max - reward_min) clip(worst_cost - c, 0, worst_cost) / worst_cost.
  *   GPF_RW_GAMEPLAY (Reward/gameplayReward.py:44-52) p = reward_min, reward_max.  failed: reward_min; illegal or ambiguous: reward_min / 2
  *       (a float32 division); else reward_max.
- * failed is the lane's episode-ending step, the engine's done (it has no done without an error: the reference's is_done and has_error
- * coincide; with auto-reset the done byte still says that the step failed).  illegal = the topology flag of THIS launch (a launch without
+ * failed is the lane's failed step, the engine's done (with auto-reset the done byte still says that the step failed).  Without an episode
+ * limit the reference's is_done and has_error coincide; with one (gpf_set_episode_limit) is_done is failed OR truncated, and the two kinds
+ * that read it follow: GPF_RW_L2RPN is 0 on a truncated step, GPF_RW_REDISP gives an illegal or ambiguous truncated step min_reward
+ * (redispReward.py:171-176; a legal truncated step gets the formula).  gpf_rewards_eval never sees a truncated step.  illegal = the topology flag of THIS launch (a launch without
  * topology actions has none, whatever gpf_get_topo_flags still holds) OR "a redispatch action was cancelled in this step" (the change of
  * gpf_get_env_illegal over the step, from a device-side snapshot queued before it when rewards and dynamics are both on); ambiguous = the
  * topology flag.  The reference's is_illegal_reco cannot occur (generator switch-off is not modelled).
@@ -761,6 +763,63 @@ int gpf_set_rewards(gpf_handle h, int32_t n_slot, const gpf_reward_slot* slots, 
 int gpf_get_rewards(gpf_handle h, int32_t lane0, int32_t n, float* reward);
 int gpf_rewards_eval(gpf_handle h, int32_t lane0, int32_t n, const uint8_t* flags_dev, float* out_dev, int64_t row_stride);
 int gpf_reward_device_pointers(gpf_handle h, void** out, int32_t n);
+
+/* ---- episode time limits of the batched acting path (grid2op_amd/csrc/gridpf_episode.hpp): the reference's done WITHOUT an error -- the
+ * episode ends at max_episode_duration() (chronics_handler.done(), or env.reset(options={"max step": N})) -- for every lane of a ONE-STEP
+ * launch, in one side kernel queued last (after the reward kernel: the rewards and the alert reward of a truncated step see the step's
+ * state before the reset); the step, power-flow and topology kernels are not involved, and with the feature off gpf_step_n launches
+ * nothing for it.  gpf_get_episode and the done byte keep their meaning: the step failed.
+ *   limit[lane]     int32 steps, 0: none.  The lane's steps are counted as gpf_get_episode counts them (episode[lane][0], every launch since
+ *                   the lane's last reset counts): after gpf_reset_lanes the N-th launch of a lane with limit N is the truncated one, as the
+ *                   N-th env.step after env.reset(options={"max step": N}).  (A loop that spends a launch on the reset observation, as the
+ *                   opponent and the alerts expect, counts that launch too.)
+ *   terminated      the lane's done byte.  truncated = !terminated && limit > 0 && steps survived >= limit, on the state after the step; a
+ *                   step that fails at the limit is terminated (the reference's has_error case).
+ *   length          env.nb_time_step of the episode that ended in this launch (the limit on truncation; steps survived + 1 on failure: the
+ *                   reference counts the failing step), 0 while the episode goes on.
+ *   duration_reward EpisodeDurationReward (Reward/episodeDurationReward.py:64-71): length / (limit x per_timestep) when terminated or
+ *                   truncated (the length itself with limit 0), else 0; float32, the product in float32 as dt_float keeps total_time_steps.
+ *   rewards         see gpf_set_rewards: the reference's is_done is failed || truncated.
+ *   alert reward    a truncated lane whose alert pre-step ran gets alert_end_bonus (AlertReward.reward_end_episode_bonus) instead of the
+ *                   window scoring (alertReward.py:179-181).  The reference returns it BEFORE _update_state runs, so the final observation's
+ *                   was_alert_used_after_attack is what the PREVIOUS step's reward left (it is not cleared, :156); the other six alert
+ *                   attributes are the environment's and do not differ.  The engine reproduces that.
+ *   returns         with rewards on: return_running[lane][slot] float64 takes every launch's float32 reward, widened, ONE add per slot and
+ *                   launch in launch order (bit-reproducible); when an episode ends the total with the final step's reward moves to
+ *                   return_last, length_last takes the length, n_episodes goes up by one and the running total restarts at 0, with or
+ *                   without auto_reset.  Rows are GPF_REWARD_MAX_SLOTS wide, the slots beyond n_slot stay 0; gpf_set_rewards zeroes them.
+ *   auto_reset      a truncated lane leaves the launch as a failed lane does: topology row = its topo0 row, overflow counters and (when the
+ *                   launch tracks them) line cooldowns 0, the dynamics' target / actual / previous / already-modified dispatch, curtailment
+ *                   limit and scalars, fresh flag and illegal count cleared, storage charge = charge0, sub_cooldown 0, last_bus from topo0,
+ *                   episode = {0, resets + 1} -- the opponent and the alerts then reset themselves at the next launch; the chronics cursor
+ *                   keeps running.  The results row, rho, rewards and flags stay those of the final step: the terminal observation.  The host
+ *                   re-keys a lane an action had moved to another topology class exactly as for a failure.  Without auto_reset a truncated
+ *                   lane is left alone: it reports truncated again at every later launch, its statistics roll over once.
+ *   gpf_set_episode_limit : lane_max_steps [n_lanes] (NULL: max_steps for every lane).  NULL, or max_steps 0 without a table, turns the
+ *                   feature off.  Refused before the device is touched (on a header-only handle too): a negative limit, a per_timestep that
+ *                   is not finite or not positive, a bonus that is not finite.  A new limit on a running feature keeps the statistics.
+ *                   While a limit is set gpf_step_n refuses n_steps != 1.
+ *   gpf_get_episode_ends  : terminated [n], truncated [n], length [n], duration_reward [n] of the last launch; any pointer may be NULL.
+ *   gpf_get_episode_stats : return_running / return_last [n][GPF_REWARD_MAX_SLOTS], length_last [n], n_episodes [n]; any may be NULL.
+ *   gpf_episode_device_pointers : out[0] limits int32 [lanes], out[1] flags uint8 [lanes][2] {terminated, truncated}, out[2] length int32,
+ *                   out[3] duration_reward float32, out[4] return_running, out[5] return_last float64 [lanes][GPF_REWARD_MAX_SLOTS],
+ *                   out[6] length_last, out[7] n_episodes int32 [lanes] (lanes = gpf_lane_capacity).  n must be GPF_N_EPISODE_POINTERS.
+ *   The getters fail with "episode limits are off" while the feature is off.
+ * gpf_reset_lanes zeroes every episode buffer of the lanes (not their limits); gpf_copy_lanes copies them with the limits; gpf_fanout_n1
+ * and gpf_simulate_batch leave them alone.  OUT OF SCOPE: truncation inside multi-step launches, a chronics cursor that jumps to a new
+ * scenario at the reset, CombinedReward, N1Reward. */
+#define GPF_N_EPISODE_POINTERS 8
+typedef struct gpf_episode_desc {
+  int32_t max_steps;               /* the limit of every lane (0: none) ... */
+  const int32_t* lane_max_steps;   /* ... or one per lane [n_lanes] (NULL: max_steps) */
+  float per_timestep;              /* EpisodeDurationReward.per_timestep (1) */
+  float alert_end_bonus;           /* AlertReward.reward_end_episode_bonus (1) */
+} gpf_episode_desc;
+int gpf_set_episode_limit(gpf_handle h, const gpf_episode_desc* desc);
+int gpf_get_episode_ends(gpf_handle h, int32_t lane0, int32_t n, uint8_t* terminated, uint8_t* truncated, int32_t* length, float* duration_reward);
+int gpf_get_episode_stats(gpf_handle h, int32_t lane0, int32_t n, double* return_running, double* return_last, int32_t* length_last,
+                          int32_t* n_episodes);
+int gpf_episode_device_pointers(gpf_handle h, void** out, int32_t n);
 
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
