@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "GpfCursorDesc", "library_path", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
@@ -39,10 +39,12 @@ EXPORTED_SYMBOLS = [
     "gpf_get_alert_reward", "gpf_alert_device_pointers",
     "gpf_set_rewards", "gpf_get_rewards", "gpf_rewards_eval", "gpf_reward_device_pointers",
     "gpf_set_episode_limit", "gpf_get_episode_ends", "gpf_get_episode_stats", "gpf_episode_device_pointers",
+    "gpf_set_chronics_cursor", "gpf_upload_cursor_draws", "gpf_get_cursor_state", "gpf_set_cursor_state", "gpf_cursor_device_pointers",
 ]
 N_ALERT_POINTERS = 3       # include/gridpf.h GPF_N_ALERT_POINTERS
 N_REWARD_POINTERS = 1      # include/gridpf.h GPF_N_REWARD_POINTERS
 N_EPISODE_POINTERS = 8     # include/gridpf.h GPF_N_EPISODE_POINTERS
+N_CURSOR_POINTERS = 3      # include/gridpf.h GPF_N_CURSOR_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
 
@@ -96,6 +98,13 @@ class GpfRewardSlot(C.Structure):
 class GpfEpisodeDesc(C.Structure):
     """include/gridpf.h gpf_episode_desc"""
     _fields_ = [("max_steps", C.c_int32), ("lane_max_steps", _ip), ("per_timestep", C.c_float), ("alert_end_bonus", C.c_float)]
+
+
+class GpfCursorDesc(C.Structure):
+    """include/gridpf.h gpf_cursor_desc"""
+    _fields_ = [("n_order", C.c_int32), ("order", _ip), ("policy", C.c_int32), ("cdf", _dp), ("first_row", C.c_int32), ("lane_first_row", _ip),
+                ("next_pos", C.c_int32), ("lane_next_pos", _ip), ("draw_source", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
+                ("lane_base", C.c_int32)]
 
 
 class GpfAlertDesc(C.Structure):
@@ -257,6 +266,11 @@ def lib() -> C.CDLL:
     L.gpf_get_episode_ends.argtypes = [h, i32, i32, _bp, _bp, _ip, _fp]
     L.gpf_get_episode_stats.argtypes = [h, i32, i32, _dp, _dp, _ip, _ip]
     L.gpf_episode_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
+    L.gpf_set_chronics_cursor.argtypes = [h, C.POINTER(GpfCursorDesc)]
+    L.gpf_upload_cursor_draws.argtypes = [h, i32, _dp]
+    L.gpf_get_cursor_state.argtypes = [h, i32, i32, _ip]
+    L.gpf_set_cursor_state.argtypes = [h, i32, i32, _ip]
+    L.gpf_cursor_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

@@ -879,6 +879,7 @@ int gpf_create(const gpf_grid_desc* d, int32_t n_lanes, int32_t device, gpf_hand
   e->h_lane_table.assign(e->cap_lanes, 0);
   e->h_lane_offset.assign(e->cap_lanes, 0);
   e->h_lane_forecast.assign(e->cap_lanes, 0);
+  e->h_lane_n1.assign(e->cap_lanes, 0);
   e->h_lane_topo.assign((size_t)e->cap_lanes * g.dim_topo, INT_MIN);
   e->h_lane_sb.assign((size_t)e->cap_lanes * std::max(g.n_shunt, 1), INT_MIN);
   {
@@ -1231,6 +1232,7 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
   if (e->opp_kind && err == hipSuccess) err = opponent_copy_lanes(e, src, dst, n);
   if (e->al_on && err == hipSuccess) err = alert_copy_lanes(e, src, dst, n);
   if (e->ep_on && err == hipSuccess) err = episode_copy_lanes(e, src, dst, n);
+  if (e->cur_on && err == hipSuccess) err = cursor_copy_lanes(e, src, dst, n);
   HIP_TRY(err);
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
@@ -1261,6 +1263,8 @@ int gpf_fanout_n1(gpf_handle e, int32_t src, int32_t dst0, int32_t n_out, const 
     hipLaunchKernelGGL(gpf::topo_fanout_kernel, dim3((unsigned)n_out), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), src, dst0, n_out);
     HIP_TRY(hipGetLastError());
   }
+  if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, dst0, n_out, 1));     // contingency lanes start no scenario of their own
+  std::fill_n(e->h_lane_n1.begin() + dst0, n_out, 1);
   HIP_TRY(hipStreamSynchronize(e->stream));   // out_lines may be reused by the caller
   for (int k = 0; k < n_out; ++k) { e->lane_nb[dst0 + k] = e->lane_nb[src]; e->lane_nj[dst0 + k] = e->lane_nj[src]; e->lane_mb[dst0 + k] = e->lane_mb[src]; e->lane_class[dst0 + k] = e->lane_class[src];
     e->h_lane_topo[(size_t)(dst0 + k) * e->g.dim_topo] = INT_MIN; }     // a line was forced off on the device: mirror unknown
@@ -1443,6 +1447,10 @@ int gpf_get_results_pinned(gpf_handle e, int32_t lane0, int32_t n, int32_t what,
 
 int gpf_upload_chronics(gpf_handle e, int32_t n_tables, int32_t T, const float* data) {
   if (!e || n_tables <= 0 || T <= 0 || !data) return fail(GPF_E_INVALID, "gpf_upload_chronics: bad arguments");
+  if (e->cur_on && (n_tables <= e->cur_max_table || T <= e->cur_max_first_row))
+    return fail(GPF_E_INVALID, "gpf_upload_chronics: the chronics cursor is on (gpf_set_chronics_cursor) and its order names table " +
+                               std::to_string(e->cur_max_table) + ", its first_row row " + std::to_string(e->cur_max_first_row) +
+                               ": upload at least that many tables and rows, or turn the cursor off first");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->maint.release();                       // belongs to the previous tables
@@ -1545,6 +1553,8 @@ int gpf_set_lane_chronics(gpf_handle e, const int32_t* lane_table, const int32_t
     HIP_TRY(hipMemcpyAsync(e->lane_offset.p, lane_offset, B * sizeof(int), hipMemcpyHostToDevice, e->stream));
     std::copy(lane_offset, lane_offset + B, e->h_lane_offset.begin());
     std::fill(e->h_lane_forecast.begin(), e->h_lane_forecast.end(), 0);       // every lane is back on the chronics tables
+    std::fill(e->h_lane_n1.begin(), e->h_lane_n1.end(), 0);
+    if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, 0, e->cap_lanes, 0));
   }
   if (lane_scale) {
     if (!e->lane_scale.p) {
@@ -1728,6 +1738,9 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if ((e->ep_on || e->ep_host_on) && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with an episode limit set (gpf_set_episode_limit) a launch must be a one-step launch (an episode "
                                "ends, and a truncated lane restarts, between two steps): use n_steps = 1");
+  if ((e->cur_on || e->cur_host_on) && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: with the chronics cursor on (gpf_set_chronics_cursor) a launch must be a one-step launch (a lane "
+                               "that restarts inside a launch would start a scenario there): use n_steps = 1");
   if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_step_n: no chronics uploaded");
   if (e->traj_cap && n_steps > e->traj_cap)
     return fail(GPF_E_INVALID, "gpf_step_n: n_steps exceeds the trajectory buffer (gpf_set_trajectory sizes it; 0 releases it)");
@@ -1753,6 +1766,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
                                "only counted down by a launch that maintains the line cooldowns)");
   HIP_TRY(hipSetDevice(e->device));
   int rc = GPF_OK;
+  if (e->cur_on) {                          // first: every kernel behind it reads the scenario of a lane that starts an episode
+    rc = cursor_prestep(e, t0);
+    if (rc != GPF_OK) return rc;
+  }
   if (e->ta_on) {
     if (acts) { e->ta_host = e->ta_dev = false; e->dev_topo_dirty = true; }   // consumed by this launch, whatever happens below
     rc = topo_prestep(e, acts);
@@ -2335,6 +2352,7 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
   }
   int* const rows = e->sim_pin.p;
   HIP_TRY(hipMemcpyAsync(rows, e->sim_rows.p, n_rows * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (e->cur_on) HIP_TRY(cursor_fetch_mirrors(e));     // the device moved the lanes' cursors: the mirrors below are read back, not remembered
   HIP_TRY(hipStreamSynchronize(e->stream));
   const double tm1 = sim_timing ? now_us() : 0.0;
   // 2. candidate topologies on the host (the launch planner needs them anyway: busbars per substation, topology classes)
@@ -2394,6 +2412,7 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
     e->h_lane_offset[dst_lane0 + q] = time_step == 0 ? idx : (fc ? e->fc_h : 1) * idx + (time_step - 1);
     e->h_lane_forecast[dst_lane0 + q] = 1;          // its cursor is an ABSOLUTE row (of the forecast tables when time_step > 0), not an offset to t
   }
+  if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, dst_lane0, (int)n_dst, 1));
   // with the injection dynamics on, the scratch lanes start from their source's dispatch / storage / curtailment state and take
   // ONE do-nothing step of the dynamics on the forecast (the candidates are topology actions: no redispatch / storage part)
   struct ActGuard {

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstring>
 
+#define GPF_OPPONENT_KERNEL
 #include "gridpf_engine.hpp"
 #include "gridpf_opponent.hpp"
 

@@ -273,6 +273,16 @@ struct gpf_engine {
   DevArr<unsigned char> ep_flags;
   DevArr<float> ep_duration;
   DevArr<double> ep_ret_run, ep_ret_last;
+  // the chronics cursor (gridpf_cursor.hpp, gridpf_capi_cursor.hip): the validated configuration (host), the order and the cdf on the
+  // device, the lanes' words, the byte that keeps the kernel off scratch and contingency lanes and the draws table.  cur_host_on: a
+  // header-only handle was given a valid descriptor (gpf_step_n refuses multi-step launches there too)
+  bool cur_on = false, cur_host_on = false;
+  gpf_cursor_desc cur_desc{};           // as validated (its pointers are not kept)
+  int cur_n_draw = 0, cur_max_table = 0, cur_max_first_row = 0;
+  DevArr<int> cur_order, cur_pos, cur_next_pos, cur_n_started, cur_draws_used, cur_flags, cur_first_row;
+  DevArr<unsigned char> cur_skip;
+  DevArr<double> cur_cdf, cur_draws;
+  std::vector<char> h_lane_n1;          // 1: the lane is a contingency lane of gpf_fanout_n1 (until gpf_set_lane_chronics)
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
@@ -424,6 +434,14 @@ int episode_poststep(gpf_engine* e, bool auto_reset, bool track_cooldown, bool l
 int episode_reset_lanes(gpf_engine* e, int lane0, int n);
 hipError_t episode_copy_lanes(gpf_engine* e, int src, int dst, int n);
 int episode_rewards_changed(gpf_engine* e);
+
+// gridpf_capi_cursor.hip: cursor_prestep_kernel, queued first in a one-step launch with the cursor on, the feature's share of
+// gpf_copy_lanes, the skip byte of lanes [lane0, lane0 + n) (gpf_fanout_n1, gpf_simulate_batch: 1; gpf_set_lane_chronics: 0) and the
+// read-back of lane_table / lane_offset into the host mirrors (queued; the caller synchronises)
+int cursor_prestep(gpf_engine* e, int t);
+hipError_t cursor_copy_lanes(gpf_engine* e, int src, int dst, int n);
+hipError_t cursor_mark_lanes(gpf_engine* e, int lane0, int n, int skip);
+hipError_t cursor_fetch_mirrors(gpf_engine* e);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

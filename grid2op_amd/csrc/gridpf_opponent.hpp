@@ -20,7 +20,8 @@
 // areas draw from the lane's ONE stream, in area order (opp_area_*, opponent_area_prestep_kernel).
 // Three parts: the scalar rules (plain C++, the ONE statement of each rule, run by the kernel on one thread per lane and by the host
 // emulator of tests/native/), the line choice (opp_weight + the threshold rule, summed by a wavefront scan on the device and by a plain
-// loop in the emulator), and the kernel.  Without hipcc only the first two exist: the header then needs no HIP header.
+// loop in the emulator), and the kernels, for the one unit that defines GPF_OPPONENT_KERNEL (gridpf_capi_opp.hip; gridpf_cursor.hpp
+// includes this header for Philox alone).  Without hipcc only the first two exist: the header then needs no HIP header.
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -433,7 +434,7 @@ inline int opp_area_prestep_serial(const OppCfg& c, const OppLane& L, const OppA
 }
 
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && defined(GPF_OPPONENT_KERNEL)      // (the one unit that launches the kernels: gridpf_capi_opp.hip)
 // the lanes' rows the kernel touches
 struct OppDev {
   double* budget; int* state; const double* draws; int* sched;
@@ -560,6 +561,6 @@ __global__ __launch_bounds__(64 * OPP_WPB) void opponent_area_prestep_kernel(Opp
     opp_area_apply(A, R, d.topo + (size_t)lane * d.dim_topo, d.cooldown + (size_t)lane * d.n_line, d.or_pos, d.ex_pos);
   }
 }
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && GPF_OPPONENT_KERNEL
 
 }  // namespace gpf

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import GpfAlertDesc, GpfEpisodeDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
+from ._capi import GpfAlertDesc, GpfCursorDesc, GpfEpisodeDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
 from .grid_model import GridModel
 
 __all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT", "MASK_TOO_MANY_LINES", "MASK_TOO_MANY_SUBS",
@@ -44,6 +44,10 @@ OPP_STATE_INTS = 14
 OPP_TIME_NONE = -2 ** 31
 OPP_FLAG_DRAWS_EXHAUSTED, OPP_FLAG_SCHEDULE_CAPPED = 1, 2
 OPP_MAX_AREAS, OPP_AREA_STATE_INTS = 16, 8
+# the chronics cursor of `PowerFlowEngine.set_chronics_cursor` (include/gridpf.h GPF_CURSOR_*)
+CURSOR_SEQUENTIAL, CURSOR_SAMPLED = 0, 1
+CURSOR_FLAG_DRAWS_EXHAUSTED, CURSOR_FLAG_NEXT_POS_WRAPPED = 1, 2
+CURSOR_STATE_INTS = 7
 ALERT_MAX_LINES, ALERT_MAX_WINDOW = 64, 62
 ALERT_OBS_SECTIONS = ("active_alert", "time_since_last_alert", "alert_duration", "time_since_last_attack", "attack_under_alert",
                       "was_alert_used_after_attack")      # sections of A of the lane's alert block; total_number_of_alert is its element 6 A
@@ -82,6 +86,46 @@ class OpponentState:
         for k, name in enumerate(self._COLS):
             out[:, k] = getattr(self, name)
         return out
+
+
+@dataclass
+class CursorState:
+    """Per-lane state of the chronics cursor (`PowerFlowEngine.chronics_cursor_state`): the chronics table and offset the lane reads
+    (``lane_table`` / ``lane_offset``), the position in the order of the episode under way (-1: none yet), the position the next episode
+    takes (-1: none given), the episodes started, the draws consumed and the sticky `CURSOR_FLAG_DRAWS_EXHAUSTED` /
+    `CURSOR_FLAG_NEXT_POS_WRAPPED` bits."""
+    table: np.ndarray
+    offset: np.ndarray
+    pos: np.ndarray
+    next_pos: np.ndarray
+    n_started: np.ndarray
+    draws_used: np.ndarray
+    flags: np.ndarray
+
+    _COLS = ("table", "offset", "pos", "next_pos", "n_started", "draws_used", "flags")
+
+    @classmethod
+    def from_rows(cls, rows):
+        return cls(*(rows[:, k].copy() for k in range(len(cls._COLS))))
+
+    def rows(self) -> np.ndarray:
+        out = np.zeros((len(self.table), CURSOR_STATE_INTS), dtype=np.int32)
+        for k, name in enumerate(self._COLS):
+            out[:, k] = getattr(self, name)
+        return out
+
+
+def cursor_cdf(probabilities) -> np.ndarray:
+    """The cumulative distribution ``Multifolder.sample_next_chronics`` and ``RandomState.choice`` search (Chronics/multiFolder.py:345-356):
+    the probabilities as float32 over their float32 sum, then a float64 cumulative sum over its last entry."""
+    p = np.array(probabilities, dtype=np.float32)
+    tot = p.sum()
+    if p.ndim != 1 or p.size == 0 or (p < 0).any() or not np.isfinite(tot) or abs(tot) <= 1e-5:
+        raise ValueError("probabilities: a non-empty vector of non-negative numbers that does not sum to 0")
+    p /= tot
+    cdf = p.astype(np.float64).cumsum()
+    cdf /= cdf[-1]
+    return cdf
 
 
 @dataclass
@@ -631,6 +675,7 @@ class PowerFlowEngine:
         check(self._lib.gpf_upload_chronics(self._h, tables.shape[0], tables.shape[1], ptr(tables, C.c_float)),
               "gpf_upload_chronics")
         self.chron_T = tables.shape[1]
+        self.chron_tables = tables.shape[0]
 
     def upload_maintenance(self, maintenance):
         """Scheduled maintenance of the uploaded tables: ``[n_tables, T, n_line]`` (or ``[T, n_line]``) 0/1; None removes it."""
@@ -1327,6 +1372,84 @@ class PowerFlowEngine:
                 "duration_reward": view(ep[3], (cap,), "<f4"), "return_running": view(ep[4], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns],
                 "return_last": view(ep[5], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns], "length_last": view(ep[6], (cap,), "<i4"),
                 "n_episodes": view(ep[7], (cap,), "<i4")}
+
+    # ---- the chronics cursor (include/gridpf.h gpf_set_chronics_cursor; grid2op_amd/csrc/gridpf_cursor.hpp) ----
+    def set_chronics_cursor(self, order=None, policy="sequential", probabilities=None, first_row=0, next_pos=None, seed=None, lane_base: int = 0):
+        """Every lane that starts an episode in a one-step launch starts a scenario, as ``env.reset()`` does (``next_chronics``).
+        ``order``: table indices (``Multifolder._order``; None: every uploaded table in order), or False to turn the feature off.
+        ``policy`` "sequential" walks the order; "sampled" draws a position with ``probabilities`` (None: uniform) as
+        ``sample_next_chronics`` does.  ``first_row``: the row the first launch of an episode reads, one value or ``[n_lanes]`` (0 for a
+        loop that spends a launch on the reset observation, 1 for one that does not, ``k`` / ``k + 1`` for ``options={"init ts": k}``).
+        ``next_pos``: the position the first episode takes, one value or ``[n_lanes]`` (None: 0 when sequential, a draw when sampled);
+        later ones are written through `cursor_views` (``env.set_id``).  ``seed`` None: the uniforms come from `upload_cursor_draws`;
+        an integer: Philox on (episodes started, lane + ``lane_base``).  While it is on multi-step launches are refused."""
+        self._cur_on = False
+        if order is False:
+            check(self._lib.gpf_set_chronics_cursor(self._h, None), "gpf_set_chronics_cursor")
+            return
+        if order is None:
+            order = np.arange(int(getattr(self, "chron_tables", 1)))
+        order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        pol = {"sequential": CURSOR_SEQUENTIAL, "sampled": CURSOR_SAMPLED}.get(policy, policy)
+        d = GpfCursorDesc(n_order=len(order), order=ptr(order, C.c_int32), policy=int(pol), lane_base=int(lane_base))
+        cdf = None
+        if pol == CURSOR_SAMPLED:
+            cdf = cursor_cdf(np.ones(len(order)) if probabilities is None else probabilities)
+            if len(cdf) != len(order):
+                raise ValueError("probabilities: one per position of the order")
+            d.cdf = ptr(cdf, C.c_double)
+        keep = []
+        for name, val, default in (("first_row", first_row, 0), ("next_pos", next_pos, 0 if pol == CURSOR_SEQUENTIAL else -1)):
+            val = default if val is None else val
+            if np.ndim(val) > 0:
+                arr = np.ascontiguousarray(val, dtype=np.int32).reshape(self.n_lanes)
+                keep.append(arr)
+                setattr(d, "lane_" + name, ptr(arr, C.c_int32))
+            else:
+                setattr(d, name, int(val))
+        if seed is None:
+            d.draw_source = OPP_DRAWS_TABLE
+        else:
+            d.draw_source, d.seed_lo, d.seed_hi = OPP_DRAWS_PHILOX, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+        check(self._lib.gpf_set_chronics_cursor(self._h, C.byref(d)), "gpf_set_chronics_cursor")
+        self._cur_on = True
+
+    def _cursor_on(self, what):
+        if not getattr(self, "_cur_on", False):
+            raise GridPFError(f"{what}: the chronics cursor is off (set_chronics_cursor)")
+
+    def upload_cursor_draws(self, draws):
+        """``[n_lanes, n_draw]`` float64 uniforms in [0, 1) of the sampled policy, one per episode start and lane, consumed in order."""
+        self._cursor_on("upload_cursor_draws")
+        u = np.ascontiguousarray(draws, dtype=np.float64).reshape(self.n_lanes, -1)
+        check(self._lib.gpf_upload_cursor_draws(self._h, u.shape[1], ptr(u, C.c_double)), "gpf_upload_cursor_draws")
+
+    def chronics_cursor_state(self, lane0: int = 0, n: Optional[int] = None) -> "CursorState":
+        self._cursor_on("chronics_cursor_state")
+        lane0, n = self._range(lane0, n)
+        rows = np.zeros((n, CURSOR_STATE_INTS), np.int32)
+        check(self._lib.gpf_get_cursor_state(self._h, lane0, n, ptr(rows, C.c_int32)), "gpf_get_cursor_state")
+        return CursorState.from_rows(rows)
+
+    def set_chronics_cursor_state(self, state: "CursorState", lane0: int = 0):
+        self._cursor_on("set_chronics_cursor_state")
+        rows = np.ascontiguousarray(state.rows(), dtype=np.int32)
+        check(self._lib.gpf_set_cursor_state(self._h, lane0, rows.shape[0], ptr(rows, C.c_int32)), "gpf_set_cursor_state")
+
+    def cursor_views(self) -> dict:
+        """Zero-copy torch tensors ALIASING the cursor's buffers (order the reader on ``device_views()["stream"]``), int32 ``[n_lanes]``:
+        ``next_pos`` (writable: ``env.set_id`` on the device), ``pos``, ``n_started``."""
+        import torch
+        self._cursor_on("cursor_views")
+        cp = (C.c_void_p * _capi.N_CURSOR_POINTERS)()
+        check(self._lib.gpf_cursor_device_pointers(self._h, cp, _capi.N_CURSOR_POINTERS), "gpf_cursor_device_pointers")
+        cap = self._lib.gpf_lane_capacity(self._h)
+        dev = torch.device("cuda", self.device)
+
+        def view(p):
+            iface = {"shape": (cap,), "typestr": "<i4", "data": (int(p), False), "version": 2, "strides": None}
+            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=dev)[:self.n_lanes]
+        return {"next_pos": view(cp[0]), "pos": view(cp[1]), "n_started": view(cp[2])}
 
     # ---- zero-copy device views ------------------------------------------------------------------------------------------
     def device_views(self):

@@ -560,6 +560,36 @@ class ShardedEngine:
         """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
         return [eng.episode_views() for eng in self.engines]
 
+    # ---- the chronics cursor (PowerFlowEngine.set_chronics_cursor): the configuration goes to every device with the shard's lane_base,
+    # per-lane first rows / positions, the draws and the state are cut by block ----
+    def set_chronics_cursor(self, order=None, policy="sequential", probabilities=None, first_row=0, next_pos=None, seed=None, lane_base: int = 0):
+        def cut(v, b0, bn):
+            return v if v is None or np.ndim(v) == 0 else np.asarray(v).reshape(self.n_lanes)[b0:b0 + bn]
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            if order is False:
+                eng.set_chronics_cursor(False)
+            else:
+                eng.set_chronics_cursor(order, policy, probabilities, cut(first_row, b0, bn), cut(next_pos, b0, bn), seed, lane_base=int(lane_base) + b0)
+
+    def upload_cursor_draws(self, draws):
+        u = np.asarray(draws).reshape(self.n_lanes, -1)
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            eng.upload_cursor_draws(u[b0:b0 + bn])
+
+    def chronics_cursor_state(self, lane0: int = 0, n=None):
+        from .engine import CursorState
+        return CursorState.from_rows(np.concatenate([eng.chronics_cursor_state(l0, k).rows() for eng, l0, k, _ in self._parts(lane0, n)]))
+
+    def set_chronics_cursor_state(self, state, lane0: int = 0):
+        from .engine import CursorState
+        rows = state.rows()
+        for eng, l0, k, off in self._parts(lane0, rows.shape[0]):
+            eng.set_chronics_cursor_state(CursorState.from_rows(rows[off:off + k]), lane0=l0)
+
+    def cursor_views(self):
+        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
+        return [eng.cursor_views() for eng in self.engines]
+
     def set_gen_renewable(self, renewable):
         for eng in self.engines:
             eng.set_gen_renewable(renewable)

@@ -237,7 +237,8 @@ typedef struct gpf_step_opts {
   int32_t auto_reset;    /* != 0: a lane whose step fails (game over: BaseEnv.step sets done when the backend diverges,
                             Environment/baseEnv.py:3847-3931) restarts at the next step from the topology the host sent last
                             (gpf_set_topology / gpf_reset_lanes), overflow counters cleared -- what env.reset() does to the
-                            backend (Environment/environment.py:1418 reset_grid); the chronics cursor keeps running */
+                            backend (Environment/environment.py:1418 reset_grid); the chronics cursor runs on, unless
+                            gpf_set_chronics_cursor is on: then the lane's next launch starts a scenario */
   int32_t warm_start;    /* != 0 (OPT-IN, NOT what PandaPowerBackend does): steps 2..n of a launch start Newton from the previous
                             step's voltages while the lane's topology stands, instead of the DC initialisation pandapower
                             performs on every runpf (pandaPowerBackend.py:1086 _pf_init = "dc"; LightSimBackend-style warm start).
@@ -791,8 +792,8 @@ int gpf_reward_device_pointers(gpf_handle h, void** out, int32_t n);
  *   auto_reset      a truncated lane leaves the launch as a failed lane does: topology row = its topo0 row, overflow counters and (when the
  *                   launch tracks them) line cooldowns 0, the dynamics' target / actual / previous / already-modified dispatch, curtailment
  *                   limit and scalars, fresh flag and illegal count cleared, storage charge = charge0, sub_cooldown 0, last_bus from topo0,
- *                   episode = {0, resets + 1} -- the opponent and the alerts then reset themselves at the next launch; the chronics cursor
- *                   keeps running.  The results row, rho, rewards and flags stay those of the final step: the terminal observation.  The host
+ *                   episode = {0, resets + 1} -- the opponent and the alerts then reset themselves at the next launch, and with
+ *                   gpf_set_chronics_cursor on the lane then starts a scenario (off: the chronics cursor runs on).  The results row, rho, rewards and flags stay those of the final step: the terminal observation.  The host
  *                   re-keys a lane an action had moved to another topology class exactly as for a failure.  Without auto_reset a truncated
  *                   lane is left alone: it reports truncated again at every later launch, its statistics roll over once.
  *   gpf_set_episode_limit : lane_max_steps [n_lanes] (NULL: max_steps for every lane).  NULL, or max_steps 0 without a table, turns the
@@ -806,8 +807,8 @@ int gpf_reward_device_pointers(gpf_handle h, void** out, int32_t n);
  *                   out[6] length_last, out[7] n_episodes int32 [lanes] (lanes = gpf_lane_capacity).  n must be GPF_N_EPISODE_POINTERS.
  *   The getters fail with "episode limits are off" while the feature is off.
  * gpf_reset_lanes zeroes every episode buffer of the lanes (not their limits); gpf_copy_lanes copies them with the limits; gpf_fanout_n1
- * and gpf_simulate_batch leave them alone.  OUT OF SCOPE: truncation inside multi-step launches, a chronics cursor that jumps to a new
- * scenario at the reset, CombinedReward, N1Reward. */
+ * and gpf_simulate_batch leave them alone.  OUT OF SCOPE: truncation inside multi-step launches, CombinedReward, N1Reward (the scenario
+ * of the next episode: gpf_set_chronics_cursor below). */
 #define GPF_N_EPISODE_POINTERS 8
 typedef struct gpf_episode_desc {
   int32_t max_steps;               /* the limit of every lane (0: none) ... */
@@ -820,6 +821,81 @@ int gpf_get_episode_ends(gpf_handle h, int32_t lane0, int32_t n, uint8_t* termin
 int gpf_get_episode_stats(gpf_handle h, int32_t lane0, int32_t n, double* return_running, double* return_last, int32_t* length_last,
                           int32_t* n_episodes);
 int gpf_episode_device_pointers(gpf_handle h, void** out, int32_t n);
+
+/* ---- the chronics cursor: each new episode starts a scenario, on the device (grid2op_amd/csrc/gridpf_cursor.hpp) ----------------------
+ * What Environment.reset does to the time series (Environment/environment.py reset: chronics_handler.next_chronics(), then row 0 of the
+ * new scenario is the reset observation), for every lane of a one-step launch (gpf_step_n with n_steps = 1).  ONE side kernel,
+ * cursor_prestep_kernel, is queued FIRST in the launch, before the opponent's, the topology actions' and the alerts' pre-steps and before
+ * the step kernel; with the feature off nothing is launched and no other kernel changes.
+ *   episode start   a lane starts an episode in a launch when its episode[lane][0] (gpf_get_episode: steps survived) is 0 before the step:
+ *                   its first launch, the launch after gpf_reset_lanes, the launch after the one in which it failed or was truncated under
+ *                   auto_reset.  It is the test the opponent and the alerts use for their own reset.  The lane then takes a position p of
+ *                   `order`, sets lane_table = order[p] and lane_offset so that the row gpf_step_n reads at this launch's time index,
+ *                   (t + lane_offset) mod T, is first_row, sets pos = p and counts n_started up.
+ *   when it moves   at the START of the new episode, not at the end of the old one: after the launch that ended an episode lane_table /
+ *                   lane_offset still describe the step that ended it, so the terminal gpf_obs_vector (calendar, time / duration of the
+ *                   next maintenance), the rewards and a gpf_simulate_batch from that lane belong to the OLD scenario; after the next
+ *                   launch they belong to the new one.
+ *   sequential      Multifolder.next_chronics (Chronics/multiFolder.py:290-295): p = next_pos, then next_pos = (p + 1) mod n_order.
+ *   sampled         Multifolder.sample_next_chronics (multiFolder.py:341-359) + RandomState.choice: ONE uniform u in [0, 1) per episode
+ *                   start, p = the first index with cdf[p] > u (searchsorted side="right").  cdf [n_order] is built by the caller as the
+ *                   reference and numpy build it: the probabilities as float32 over their float32 sum, a float64 cumulative sum over its
+ *                   last entry.  The device samples POSITIONS of `order`; the reference indexes positions by scenario id on a filtered or
+ *                   shuffled order (multiFolder.py:356-358), the same thing whenever order is 0 .. n - 1.
+ *   next_pos        int32 [lanes] on the device, writable between launches (gpf_cursor_device_pointers): env.set_id(k) /
+ *                   env.reset(options={"time serie id": k}) (Environment/environment.py set_id: chronics_handler.tell_id).  A value >= 0 is
+ *                   taken under both policies; the sequential policy leaves the position after it, the sampled policy leaves -1 and draws
+ *                   only when it finds a negative value (the sequential policy then follows pos).  The first episode after
+ *                   gpf_set_chronics_cursor takes the next_pos of the descriptor as it is.  A value >= n_order written on the device is
+ *                   taken modulo n_order and sets GPF_CURSOR_FLAG_NEXT_POS_WRAPPED.
+ *   first_row       0 for a loop that spends a launch on the reset observation (the opponent's and the alerts' loops), 1 for one that does
+ *                   not, k or k + 1 for env.reset(options={"init ts": k}); one value, or one per lane.
+ *   draws           GPF_OPP_DRAWS_TABLE: gpf_upload_cursor_draws gives every lane n_draw float64 uniforms, consumed in order; a used-up
+ *                   table sets the sticky GPF_CURSOR_FLAG_DRAWS_EXHAUSTED and the lane restarts its current scenario at first_row.
+ *                   GPF_OPP_DRAWS_PHILOX: Philox4x32-10 keyed by the seed on the counter {n_started, 0, lane + lane_base, "curs"}: the
+ *                   stream depends on the global lane alone (shards with their lane_base equal one engine) and differs from the
+ *                   opponent's under the same seed.
+ *   gpf_set_chronics_cursor : NULL turns the feature off.  Refused with GPF_E_INVALID and a message: an empty order, a cdf that is not
+ *                   non-decreasing to 1 (sampled), a negative first_row, a next_pos >= n_order, an unknown policy or draw source (these
+ *                   on a header-only handle too); no chronics uploaded, an order entry >= n_tables, a first_row >= T.  Every call starts
+ *                   the lanes' cursor state afresh (pos -1, n_started 0, no draws); lane_table / lane_offset stay until a lane starts an
+ *                   episode.  While it is on: gpf_step_n refuses n_steps != 1 (a restart inside a launch cannot be followed);
+ *                   gpf_upload_chronics refuses fewer tables than an order entry needs or fewer rows than a first_row;
+ *                   gpf_set_lane_chronics stays legal and positions a lane until its next episode start; gpf_reset_lanes needs nothing
+ *                   (it zeroes episode, so the next launch starts a scenario, as env.reset() does); gpf_copy_lanes copies the cursor
+ *                   state with lane_table / lane_offset; the contingency lanes of gpf_fanout_n1 and the scratch lanes of
+ *                   gpf_simulate_batch are left alone by the kernel until gpf_set_lane_chronics puts them back on the tables;
+ *                   gpf_simulate_batch reads its source lanes' two words back before it looks for the maintenance ahead of them.
+ *   gpf_upload_cursor_draws : draws [n_lanes][n_draw] in [0, 1); the lanes' draw counters restart at 0.
+ *   gpf_get_cursor_state / gpf_set_cursor_state : rows [n][GPF_CURSOR_STATE_INTS] = {table, offset, pos, next_pos, n_started, draws
+ *                   used, flags} (a learner's checkpoint; the setter validates table, pos and next_pos).
+ *   gpf_cursor_device_pointers : out[0] next_pos (writable), out[1] pos, out[2] n_started, int32 [lanes] (lanes = gpf_lane_capacity).
+ * OUT OF SCOPE: scenarios of different lengths (the loader truncates them to one T; the episode's length is the caller's:
+ * gpf_set_episode_limit), chunked or generated chronics, anything inside multi-step launches. */
+#define GPF_CURSOR_SEQUENTIAL 0
+#define GPF_CURSOR_SAMPLED 1
+#define GPF_CURSOR_FLAG_DRAWS_EXHAUSTED 1
+#define GPF_CURSOR_FLAG_NEXT_POS_WRAPPED 2
+#define GPF_CURSOR_STATE_INTS 7
+#define GPF_N_CURSOR_POINTERS 3
+typedef struct gpf_cursor_desc {
+  int32_t n_order;                 /* positions of the order (> 0) */
+  const int32_t* order;            /* [n_order] table indices: Multifolder._order after filter and shuffle */
+  int32_t policy;                  /* GPF_CURSOR_SEQUENTIAL / GPF_CURSOR_SAMPLED */
+  const double* cdf;               /* [n_order], sampled only */
+  int32_t first_row;               /* the row the first launch of an episode reads ... */
+  const int32_t* lane_first_row;   /* ... or one per lane [n_lanes] (NULL: first_row) */
+  int32_t next_pos;                /* the position the first episode takes (< 0: none) ... */
+  const int32_t* lane_next_pos;    /* ... or one per lane [n_lanes] (NULL: next_pos) */
+  int32_t draw_source;             /* GPF_OPP_DRAWS_TABLE / GPF_OPP_DRAWS_PHILOX */
+  uint32_t seed_lo, seed_hi;       /* Philox key */
+  int32_t lane_base;               /* global index of lane 0 (sharding) */
+} gpf_cursor_desc;
+int gpf_set_chronics_cursor(gpf_handle h, const gpf_cursor_desc* desc);
+int gpf_upload_cursor_draws(gpf_handle h, int32_t n_draw, const double* draws);
+int gpf_get_cursor_state(gpf_handle h, int32_t lane0, int32_t n, int32_t* state);
+int gpf_set_cursor_state(gpf_handle h, int32_t lane0, int32_t n, const int32_t* state);
+int gpf_cursor_device_pointers(gpf_handle h, void** out, int32_t n);
 
 /* ---- observation vectors assembled on the device (what an agent reads: obs.to_vect(), Space/GridObjects.py to_vect over
  * CompleteObservation.attr_list_vect, Observation/completeObservation.py:140-212, filled by BaseObservation._update_obs_complete,
