@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = [
     "gpf_set_storage_params", "gpf_set_env_dynamics", "gpf_set_lane_actions", "gpf_lane_actions_on_device", "gpf_get_env_state", "gpf_get_env_illegal", "gpf_set_env_illegal", "gpf_set_env_state", "gpf_set_gen_renewable", "gpf_set_lane_curtailment", "gpf_get_episode", "gpf_lane_capacity", "gpf_get_step_outputs", "gpf_sync",
     "gpf_get_results_pinned", "gpf_set_profiling", "gpf_get_kernel_time", "gpf_get_plan", "gpf_device_pointers", "gpf_device_pointers_n",
     "gpf_get_counters", "gpf_upload_outage_durations", "gpf_get_cooldown", "gpf_set_cooldown", "gpf_get_trajectory_cooldown", "gpf_ptdf_build", "gpf_ptdf_build_batch", "gpf_ptdf_batch_info", "gpf_ptdf_batch_get", "gpf_ptdf_get", "gpf_ptdf_flows", "gpf_get_ptdf_flows", "gpf_ptdf_flows_rows", "gpf_get_ptdf_flows_rows", "gpf_lodf_screen",
-    "gpf_jit_enable", "gpf_jit_disable", "gpf_jit_info", "gpf_jit_source",
+    "gpf_jit_enable", "gpf_jit_disable", "gpf_jit_info", "gpf_jit_source", "gpf_jit_features", "gpf_jit_feature_word",
     "gpf_set_topo_rules", "gpf_upload_topo_actions", "gpf_set_lane_topo_actions", "gpf_topo_actions_on_device", "gpf_get_sub_cooldown",
     "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags", "gpf_topo_action_mask", "gpf_get_topo_action_mask",
     "gpf_set_topo_areas", "gpf_set_topo_slots", "gpf_get_topo_action_areas",
@@ -286,6 +286,8 @@ def lib() -> C.CDLL:
     L.gpf_jit_disable.argtypes = [h]
     L.gpf_jit_info.argtypes = [h, C.POINTER(C.c_int64), _dp, C.c_char_p, C.c_size_t]
     L.gpf_jit_source.argtypes = [h, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.gpf_jit_features.argtypes = [h, C.c_int32]
+    L.gpf_jit_feature_word.argtypes = [h, C.c_int32, C.POINTER(GpfStepOpts), C.c_uint32, C.POINTER(C.c_uint32)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("gpf_last_error",):

@@ -31,8 +31,16 @@ def _model(path):
     return load_grid_model(path)
 
 
-def header_and_variants(model, lanes, n_busbar: int = 2, env_dynamics: bool = False):
-    """(generated header, [[kind, variant], ...]) for batches of the given lane counts -- no device needed."""
+# the launches whose FEATURE kernels are built ahead of time (--features NAME): arguments of PowerFlowEngine.feature_word
+FEATURE_LAUNCHES = {
+    # bench.py's headline: multi-step launches with the observation trajectory on, load jitter, generation rebalanced to 1.02 x load
+    "headline": dict(n_steps=16, lane_scale=True, trajectory_obs=True, rebalance=1.02),
+}
+
+
+def header_and_variants(model, lanes, n_busbar: int = 2, env_dynamics: bool = False, features=()):
+    """(generated header, [[kind, variant], ...]) for batches of the given lane counts -- no device needed.  ``features``: names of
+    FEATURE_LAUNCHES whose step variant is added with the launch-feature word the library computes for it."""
     from .engine import PowerFlowEngine
     hdr, variants = None, []
     for n in lanes:
@@ -42,11 +50,13 @@ def header_and_variants(model, lanes, n_busbar: int = 2, env_dynamics: bool = Fa
             assert hdr is None or h == hdr, "the header of a grid does not depend on the batch size"
             hdr = h
             p = eng.plan()
+            words = [eng.feature_word(**FEATURE_LAUNCHES[f]) for f in features]
         finally:
             eng.close()
         b = lambda x: "true" if x else "false"  # noqa: E731
         nb, st, ipw, wpi, yr = p["busbars_per_block"], p["staging_tier"], p["instances_per_wavefront"], p["wavefronts_per_instance"], p["ybus_in_registers"]
         cand = [["step", f"{nb},{st},{ipw},2,{wpi},false,{b(yr)},false"], ["runpf", f"{nb},{st},{ipw},2,{wpi},false,{b(yr)}"]]
+        cand += [["step", f"{cand[0][1]},{w}"] for w in words if w]
         if env_dynamics:                                  # the ENV step kernels: tables in global memory unless instance groups (gridpf_capi.hip plan_launch)
             st_e = st if ipw > 1 else 0
             cand.append(["step", f"{nb},{st_e},{ipw},2,{wpi},false,{b(yr and st_e == 0)},true"])
@@ -106,11 +116,16 @@ def main(argv=None):
     ap.add_argument("--lanes", type=int, action="append", help="batch size(s) the engine will be created with (default: 1 and 4096)")
     ap.add_argument("--n-busbar", type=int, default=2)
     ap.add_argument("--env-dynamics", action="store_true", help="also the step kernel with the environment's injection dynamics on")
+    ap.add_argument("--features", action="append", choices=sorted(FEATURE_LAUNCHES), default=[],
+                    help="also the step kernel compiled for the launch features of this launch (its word comes from the library)")
+    ap.add_argument("--only-features", action="store_true", help="add the --features variants alone (a grid whose other variants are listed already)")
     ap.add_argument("--out", default=os.path.join(HERE, "aot"))
     ap.add_argument("--label", default=None)
     a = ap.parse_args(argv)
     m = _model(a.grid)
-    hdr, variants = header_and_variants(m, a.lanes or [1, 4096], a.n_busbar, a.env_dynamics)
+    hdr, variants = header_and_variants(m, a.lanes or [1, 4096], a.n_busbar, a.env_dynamics, a.features)
+    if a.only_features:
+        variants = [v for v in variants if v[0] == "step" and len(v[1].split(",")) == 9]
     label = a.label or os.path.basename(os.path.dirname(os.path.abspath(a.grid))) or os.path.basename(a.grid)
     hid = add_to_manifest(a.out, label, hdr, variants)
     print(f"{a.out}/{hid}.h + manifest.json: {label}: {' '.join(k + '<' + v + '>' for k, v in variants)}")

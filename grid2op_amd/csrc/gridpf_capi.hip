@@ -726,6 +726,12 @@ int gpf_jit_disable(gpf_handle e) {
   return GPF_OK;
 }
 
+int gpf_jit_features(gpf_handle e, int32_t on) {
+  if (!e) return fail(GPF_E_INVALID, "gpf_jit_features: null handle");
+  e->jit.features = on != 0;
+  return GPF_OK;
+}
+
 int gpf_jit_info(gpf_handle e, int64_t* counts, double* seconds, char* text, size_t cap) {
   if (!e) return fail(GPF_E_INVALID, "gpf_jit_info: null handle");
   if (counts) { counts[0] = e->jit.on ? 1 : 0; counts[1] = e->jit.n_compiled; counts[2] = e->jit.n_cached; counts[3] = e->jit.n_failed; counts[4] = e->jit.n_launches; counts[5] = e->jit.n_aot; }
@@ -1580,6 +1586,17 @@ int gpf_set_thermal_limits(gpf_handle e, const float* limit_a) {
 
 }  // extern "C"
 namespace {
+// the kernel's launch arguments of a step launch with these options (kept state: filled in by step_range)
+gpf::StepArgs make_step_args(const gpf_step_opts* o, int lane0, int t0, int T, int n_steps) {
+  gpf::StepArgs sa{};
+  sa.t = t0; sa.T = T; sa.rebalance_on = o->rebalance > 0.0 ? 1 : 0; sa.rebalance = o->rebalance; sa.cascade = o->cascade;
+  sa.is_dc = o->is_dc ? 1 : 0; sa.n_steps = n_steps; sa.auto_reset = o->auto_reset ? 1 : 0; sa.warm_start = o->warm_start ? 1 : 0;
+  sa.nb_ts_allowed = o->nb_ts_allowed; sa.max_rounds = o->max_rounds; sa.hard_overflow = o->hard_overflow; sa.soft_overflow = o->soft_overflow;
+  sa.nb_ts_reco = o->track_cooldown ? std::max(o->nb_ts_reco, 0) : -1;      // (kernel side: < 0 = the counters are not maintained)
+  sa.lane0 = lane0;
+  return sa;
+}
+
 // n_steps env steps of lanes [lane0, lane0 + n) from time index t0 (T rows per chronics table in `b.chron`)
 int step_range(gpf_engine* e, const gpf::Bufs& b_in, int lane0, int n, int t0, int T, int n_steps, const gpf_step_opts* o, const char* who,
                bool keep_state = false) {
@@ -1598,12 +1615,7 @@ int step_range(gpf_engine* e, const gpf::Bufs& b_in, int lane0, int n, int t0, i
     return fail(GPF_E_INVALID, std::string(who) + ": multi-step launches need a batch that runs as ONE launch (mixed split / unsplit lanes "
                                "without topology classes run as two): use n_steps = 1");
   if (o->cascade != 0 || b.maint != nullptr) e->dev_topo_dirty = true;     // (lines tripped / taken out by the kernel: see gpf_ptdf_build_batch)
-  gpf::StepArgs sa{};
-  sa.t = t0; sa.T = T; sa.rebalance_on = o->rebalance > 0.0 ? 1 : 0; sa.rebalance = o->rebalance; sa.cascade = o->cascade;
-  sa.is_dc = o->is_dc ? 1 : 0; sa.n_steps = n_steps; sa.auto_reset = o->auto_reset ? 1 : 0; sa.warm_start = o->warm_start ? 1 : 0;
-  sa.nb_ts_allowed = o->nb_ts_allowed; sa.max_rounds = o->max_rounds; sa.hard_overflow = o->hard_overflow; sa.soft_overflow = o->soft_overflow;
-  sa.nb_ts_reco = o->track_cooldown ? std::max(o->nb_ts_reco, 0) : -1;      // (kernel side: < 0 = the counters are not maintained)
-  sa.lane0 = lane0;
+  gpf::StepArgs sa = make_step_args(o, lane0, t0, T, n_steps);
   // one-step launches of the engine's own lanes share the topology-derived state of the reference topology (gpf::KeepArgs): single-busbar
   // kernels only (the split lanes of a mixed batch -- topology classes, NB = 2 -- rebuild theirs).  The key is the pristine (ghost) lane's rows.
   if (keep_state && e->keep_enabled && n_steps == 1 && p.sparse_nb == 1 && !p.tc && !o->is_dc) {        // (a DC step builds no Ybus blocks)
@@ -1641,8 +1653,8 @@ int step_range(gpf_engine* e, const gpf::Bufs& b_in, int lane0, int n, int t0, i
   p.env = pb.env = e->env_on;
   p.jit = pb.jit = jit_for_launch(e);
   int n_disp = 0;
-  HIP_TRY(gpf_launch_step_sparse(p, e->device, e->d_params_s.p, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
-  if (pb.sparse_nb) HIP_TRY(gpf_launch_step_sparse(pb, e->device, e->d_params_s.p, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
+  HIP_TRY(gpf_launch_step_sparse(p, e->device, e->d_params_s.p, e->h_params_s, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
+  if (pb.sparse_nb) HIP_TRY(gpf_launch_step_sparse(pb, e->device, e->d_params_s.p, e->h_params_s, e->stream, n, o->max_iter, tol_pu, sa, &n_disp));
   e->n_step_calls += 1; e->n_step_dispatches += n_disp;
   HIP_TRY(hipGetLastError());
   if (e->profiling) HIP_TRY(hipEventRecord(eb, e->stream));
@@ -1731,6 +1743,32 @@ int topo_readback(gpf_engine* e, bool moved) {
 }
 }  // namespace
 extern "C" {
+
+// The launch-feature word (gridpf_host.hpp: gpf_step_features) of a DESCRIBED gpf_step_n launch over all lanes of the engine: the engine's
+// own state, plus the optional inputs `have` says the launch will have (a header-only handle has none of its own).  No device needed.
+int gpf_jit_feature_word(gpf_handle e, int32_t n_steps, const gpf_step_opts* o, uint32_t have, uint32_t* word) {
+  if (!e || !o || !word || n_steps <= 0) return fail(GPF_E_INVALID, "gpf_jit_feature_word: null / n_steps must be positive");
+  LaunchPlan p, pb;
+  int rc = plan_launch(e, 0, e->n_lanes, p, pb);
+  if (rc != GPF_OK) return rc;
+  gpf::DevParamsS hp{};
+  hp.b = e->bufs();
+  hp.dcf = p.dcf;
+  gpf::Bufs& b = hp.b;
+  auto some = [](auto*& q) { if (!q) q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(uintptr_t(64)); };   // (never dereferenced: only null or not)
+  if (have & GPF_HAVE_LANE_SCALE) some(b.lane_scale);
+  if (have & GPF_HAVE_OUTAGES) { some(b.maint); some(b.maint_dur); }
+  if (have & GPF_HAVE_GEN_DELTA) some(b.lane_gen_delta);
+  if (have & GPF_HAVE_TRAJ_OBS) {
+    some(b.traj_out); some(b.traj_topo); some(b.traj_shb); some(b.traj_lstat); some(b.traj_rho); some(b.traj_status);
+    b.traj_cap = std::max(b.traj_cap, (int)n_steps);
+  }
+  gpf::StepArgs sa = make_step_args(o, 0, 0, std::max(e->chron_T, 1), n_steps);
+  // (the kept state of the reference topology: what step_range decides for gpf_step_n)
+  if (e->keep_enabled && n_steps == 1 && p.sparse_nb == 1 && !p.tc && !o->is_dc && e->cap_lanes > e->n_lanes) some(sa.keep.p);
+  *word = gpf_step_features(sa, hp, p.n_list ? p.list : nullptr, p.n_list ? p.n_list : e->n_lanes, std::max(p.ipw, 1));
+  return GPF_OK;
+}
 
 int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o) {
   if (!e || !o) return fail(GPF_E_INVALID, "gpf_step_n: null");

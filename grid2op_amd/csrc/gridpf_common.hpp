@@ -162,6 +162,29 @@ struct StepArgs {
   KeepArgs keep;     // (gpf_step_n, n_steps = 1, single-busbar kernels without topology classes)
 };
 
+// Launch features of the step kernel (its last template argument, FEAT): each bit is ONE assumption about a launch that the host guarantees
+// (gridpf_host.hpp: gpf_step_features is the only place that computes the word, and a code object compiled for a word is only ever launched
+// with that word).  The grid-specialised kernel then carries the literal instead of asking the parameter block at every step.  FEAT = 0
+// assumes nothing: the kernels libgridpf.so itself contains.
+enum : unsigned {
+  FEAT_NO_CASCADE = 1u << 0,     // StepArgs::cascade == 0
+  FEAT_NO_AUTO_RESET = 1u << 1,  // StepArgs::auto_reset == 0
+  FEAT_COLD_START = 1u << 2,     // StepArgs::warm_start == 0
+  FEAT_AC = 1u << 3,             // StepArgs::is_dc == 0
+  FEAT_NO_COOLDOWN = 1u << 4,    // StepArgs::nb_ts_reco < 0 (line cooldowns not maintained: Bufs::maint_dur / traj_cool are not read)
+  FEAT_REBALANCE = 1u << 5,      // StepArgs::rebalance_on == 1
+  FEAT_NO_KEEP = 1u << 6,        // StepArgs::keep.p == nullptr (no kept state of the reference topology)
+  FEAT_CONTIGUOUS = 1u << 7,     // no lane list: the launch covers lanes lane0, lane0 + 1, ...
+  FEAT_NO_MAINT = 1u << 8,       // Bufs::maint == nullptr and Bufs::maint_dur == nullptr (no outage tables)
+  FEAT_NO_GEN_DELTA = 1u << 9,   // Bufs::lane_gen_delta == nullptr
+  FEAT_LANE_SCALE = 1u << 10,    // Bufs::lane_scale != nullptr (per-lane load jitter)
+  FEAT_TRAJ_OBS = 1u << 11,      // the observation trajectory takes every step: traj_out / traj_topo / traj_shb / traj_lstat / traj_rho / traj_status
+                                 // are set and n_steps <= traj_cap
+  FEAT_DCF = 1u << 12,           // DevParamsS::dcf != 0 (the LDS layout holds the factored DC matrix)
+  FEAT_NO_GHOST = 1u << 13,      // every lane of the launch is a real lane (index < Bufs::n_real_lanes)
+  FEAT_ALL = (1u << 14) - 1
+};
+
 // K9: the chronics row a lane reads at time index t -- (t + lane_offset) mod T, non-negative (gpf_step_n; the observation clock of
 // gridpf_obs.hpp dates the lane's last step with the same row)
 __host__ __device__ __forceinline__ int chron_row_index(int t, int off, int T) {

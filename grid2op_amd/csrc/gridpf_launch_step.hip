@@ -37,7 +37,7 @@ int dispatches_for(int n_vb, int slots, bool tc) {
 }
 
 template <int NB, int ST, int IPW, int WP, bool TC, bool YR = false, bool ENV = false>
-hipError_t launch(const LaunchPlan& p, int device, const gpf::DevParamsS* d_params, hipStream_t stream, int n_l, const int* list,
+hipError_t launch(const LaunchPlan& p, int device, const gpf::DevParamsS* d_params, const gpf::DevParamsS& h_params, hipStream_t stream, int n_l, const int* list,
                   int max_iter, double tol_pu, const gpf::StepArgs& sa_in, int* n_dispatched) {
   static size_t lds_set[64] = {0};
   static const size_t pad = getenv("GRIDPF_LDS_PAD") ? (size_t)atoi(getenv("GRIDPF_LDS_PAD")) : 0;   // occupancy experiments only
@@ -45,7 +45,15 @@ hipError_t launch(const LaunchPlan& p, int device, const gpf::DevParamsS* d_para
   const size_t lds = p.lds + pad;
   const int n_vb = (n_l + IPW - 1) / IPW;
   hipFunction_t f = nullptr;
-  if (p.jit && p.jit->on) f = gpf_jit_get(*p.jit, NB, ST, IPW, WP, TC, YR, ENV, false, lds);   // grid-specialised kernel (gridpf_jit.hip), compiled on first use
+  if (p.jit && p.jit->on) {
+    // 1. the code object of this launch's features (ahead-of-time object, disk cache, compiler), 2. the grid-only specialised kernel
+    //    (gridpf_jit.hip, compiled on first use), 3. the shipped kernel.  An object is only ever launched with the word it was compiled for.
+    if (p.jit->features) {
+      const unsigned feat = gpf_step_features(sa_in, h_params, list, n_l, IPW);
+      if (feat) f = gpf_jit_get(*p.jit, NB, ST, IPW, WP, TC, YR, ENV, false, lds, feat);
+    }
+    if (!f) f = gpf_jit_get(*p.jit, NB, ST, IPW, WP, TC, YR, ENV, false, lds);
+  }
   if (!f && lds > lds_set[device & 63]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -77,11 +85,11 @@ hipError_t launch(const LaunchPlan& p, int device, const gpf::DevParamsS* d_para
 }  // namespace
 
 // one launch for all the lanes of the engine, or for the lanes of a device index list
-hipError_t gpf_launch_step_sparse(const LaunchPlan& p, int device, const gpf::DevParamsS* d_params, hipStream_t stream, int n_lanes,
-                                  int max_iter, double tol_pu, const gpf::StepArgs& sa, int* n_dispatched) {
+hipError_t gpf_launch_step_sparse(const LaunchPlan& p, int device, const gpf::DevParamsS* d_params, const gpf::DevParamsS& h_params, hipStream_t stream,
+                                  int n_lanes, int max_iter, double tol_pu, const gpf::StepArgs& sa, int* n_dispatched) {
   const int n_l = p.n_list ? p.n_list : n_lanes;
   const int* list = p.n_list ? p.list : nullptr;
-#define LAUNCH_ARGS p, device, d_params, stream, n_l, list, max_iter, tol_pu, sa, n_dispatched
+#define LAUNCH_ARGS p, device, d_params, h_params, stream, n_l, list, max_iter, tol_pu, sa, n_dispatched
 #define GO(NB, ST, IPW, WP, TC) return launch<NB, ST, IPW, WP, TC>(LAUNCH_ARGS)
 #define GOE(ST, IPW, WP, TC) return launch<1, ST, IPW, WP, TC, false, true>(LAUNCH_ARGS)
   if (p.env) {          // environment injection dynamics: single-busbar kernels, tables in LDS only with instance groups (plan_launch)

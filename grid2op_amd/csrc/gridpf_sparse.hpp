@@ -2158,7 +2158,7 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
 #define GPF_GRID_SYM P->sym
 #define GPF_GRID_SYM_DECL
 #endif
-#define GPF_CARVE_AND_VIEW(G_)                                                                                                   \
+#define GPF_CARVE_AND_VIEW(G_, DCF_)                                                                                                  \
   GPF_GRID_SYM_DECL                                                                                                              \
   SymDev S_loc = GPF_GRID_SYM;                                                                                                   \
   if (TC) { S_loc = P->classes[gptr(lane_class)[blockIdx.x * IPW]].sym; GPF_SPEC_SO(S_loc.so); }                                 \
@@ -2168,7 +2168,7 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
   const SymDev& S = S_loc;                                                                                                       \
   const int lds_rows = TC ? P->tc_rows : -1, lds_nslot = TC ? P->tc_nslot : (NB == 1 ? GPF_GRID_SYM.nslot : GPF_GRID_SYM.nslot_lu),                                        \
             lds_nslot_y = YR ? 0 : TC ? P->tc_nslot_y : GPF_GRID_SYM.nslot_y;      /* YR: the Ybus blocks live in registers */          \
-  const bool lds_dcf = P->dcf != 0;                                                                                              \
+  const bool lds_dcf = (DCF_);                                                                                                      \
   const size_t per_inst = lds_bytes_instance<NB>(G_, lds_nslot, lds_nslot_y, STAGE != 0, lds_rows, lds_dcf);                     \
   carve_sparse<NB>(c, smem + (size_t)grp * per_inst, G_, lds_nslot, lds_nslot_y, STAGE != 0, lds_rows, lds_dcf);                 \
   constexpr int GWI = gw_index(Grp<IPW, WPI>::GW);                                                                               \
@@ -2208,7 +2208,7 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void runpf_sparse_kerne
 #else
   const GridDev& g = P->g;
 #endif
-  GPF_CARVE_AND_VIEW(g);
+  GPF_CARVE_AND_VIEW(g, P->dcf != 0);
   double2 yreg[2 * YR_PASSES + 1];
   unsigned rcreg[2 * YR_PASSES];
   int n_iter, nb;
@@ -2470,7 +2470,11 @@ __device__ inline bool env_dynamics_step(const EnvDyn& E, int k, int n_gen, int 
 // depends on the topology (element -> bus maps, bus types, connectivity verdict, Ybus blocks, the factored DC matrix).
 // ENV: the kernel also evaluates the environment's injection dynamics (EnvDyn) at every step -- a separate instantiation, so that
 // the plain DoNothing kernels do not carry its registers and code (measured: -2.5 % on the 14-substation headline otherwise).
-template <int NB, int STAGE, int IPW, int MINW, int WPI, bool TC = false, bool YR = false, bool ENV = false>
+// FEAT: the launch features the kernel may assume (gridpf_common.hpp: FEAT_*; 0 = none, the kernels of the library).  A grid-specialised code
+// object compiled for a word has the literal of every assumption in its local copies of the launch arguments, so the per-step plumbing
+// written for every feature of the engine (outage tables, cascade rounds, auto-reset, cooldowns, kept state, lane lists, trajectory on or
+// off ...) folds down to what the launch uses, and the answers are no longer re-read from the parameter block step after step.
+template <int NB, int STAGE, int IPW, int MINW, int WPI, bool TC = false, bool YR = false, bool ENV = false, unsigned FEAT = 0>
 __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel(const DevParamsS* __restrict__ P, const int* __restrict__ lane_list,
                                                            const int* __restrict__ lane_class, int max_iter, double tol_pu,
                                                            StepArgs sa) {
@@ -2488,13 +2492,35 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
   const GridDev& g = P->g;
   const OutOff& oo = P->oo;
 #endif
-  const Bufs& b = P->b;
+  const Bufs* b_p = &P->b;
+  Bufs b_k;
+  if constexpr (FEAT != 0) {                                   // (same pattern as GPF_SPEC_G: a local copy that gets the literals)
+    b_k = P->b;
+    if (FEAT & FEAT_NO_CASCADE) sa.cascade = 0;
+    if (FEAT & FEAT_NO_AUTO_RESET) sa.auto_reset = 0;
+    if (FEAT & FEAT_COLD_START) sa.warm_start = 0;
+    if (FEAT & FEAT_AC) sa.is_dc = 0;
+    if (FEAT & FEAT_NO_COOLDOWN) sa.nb_ts_reco = -1;
+    if (FEAT & FEAT_REBALANCE) sa.rebalance_on = 1;
+    if (FEAT & FEAT_NO_KEEP) sa.keep.p = nullptr;
+    if (FEAT & FEAT_CONTIGUOUS) lane_list = nullptr;
+    if (FEAT & FEAT_NO_MAINT) { b_k.maint = nullptr; b_k.maint_dur = nullptr; }
+    if (FEAT & FEAT_NO_GEN_DELTA) b_k.lane_gen_delta = nullptr;
+    if (FEAT & FEAT_LANE_SCALE) __builtin_assume(b_k.lane_scale != nullptr);
+    if (FEAT & FEAT_TRAJ_OBS) {                                // every step of the launch has its trajectory row
+      __builtin_assume(b_k.traj_out != nullptr); __builtin_assume(b_k.traj_rho != nullptr); __builtin_assume(b_k.traj_status != nullptr);
+      b_k.traj_cap = 0x7fffffff;
+    }
+    b_p = &b_k;
+  }
+  const Bufs& b = *b_p;
+#define GPF_DCF_ON ((FEAT & FEAT_DCF) ? true : P->dcf != 0)
   const int grp0 = threadIdx.x / GW, tid0 = threadIdx.x % GW;
   const int inst0 = lane_list ? gptr(lane_list)[blockIdx.x * IPW + grp0] : sa.lane0 + blockIdx.x * IPW + grp0;   // ghost-padded by the host
   int grp = grp0, tid = tid0, inst = inst0;
-  const bool ghost = inst >= (int)b.n_real_lanes;               // padding lane of an instance group: computes, never mutates state
+  const bool ghost = (FEAT & FEAT_NO_GHOST) ? false : inst >= (int)b.n_real_lanes;               // padding lane of an instance group: computes, never mutates state
   CarveP<NB> c;
-  GPF_CARVE_AND_VIEW(g);
+  GPF_CARVE_AND_VIEW(g, GPF_DCF_ON);
   double2 yreg[2 * YR_PASSES + 1];
   unsigned rcreg[2 * YR_PASSES];
   if (STAGE) GPF_SYNC();                                       // the static tables are read from here on
@@ -2508,7 +2534,7 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
   typedef double v2d_ __attribute__((ext_vector_type(2)));
   constexpr bool KEEP = NB == 1 && !TC;
   const bool keep_on = KEEP && sa.keep.p != nullptr;            // kernel-uniform
-  const bool keep_dcf = P->dcf != 0;
+  const bool keep_dcf = GPF_DCF_ON;
   constexpr int KT = 2, KC = 2, KY = 4, KA = 8;                 // unrolled trips of the key / image / Ybus / DC-factor loads (longer rows: loops in the second half)
   int k_h0 = 0, k_h1 = 0, k_h2 = 0;                             // header words (KEEP_HDR_INTS)
   int kk[KT] = {}, tn[KT] = {};
@@ -2875,7 +2901,7 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
       // a group whose cascade has ended re-solves its unchanged state along with the others (same results)
       int it_k = 0, nb_k = 0;
       SolveCtl ctl;
-      ctl.inj_staged = true; ctl.topo_staged = first; ctl.reuse = first && reuse; ctl.dcf = P->dcf != 0 && (sa.n_steps > 1 || keep_on); ctl.write_bus = last; ctl.warm = sa.warm_start != 0 && !(keep_hit && step == 0); ctl.sums_done = first && sums_in_k9;   // (kept state holds no voltages to start from)
+      ctl.inj_staged = true; ctl.topo_staged = first; ctl.reuse = first && reuse; ctl.dcf = GPF_DCF_ON && (sa.n_steps > 1 || keep_on); ctl.write_bus = last; ctl.warm = sa.warm_start != 0 && !(keep_hit && step == 0); ctl.sums_done = first && sums_in_k9;   // (kept state holds no voltages to start from)
       orow = otraj ? step * (int)b.lane_stride + inst : inst;          // (re-derived: see GPF_REDERIVE)
       ctl.otraj = otraj; ctl.orow = orow; ctl.write_topo = otraj || (keep_hit && step == 0);   // (kept state: the lane's topology outputs may be another launch's)
       ctl.tc_rebuild = keep_hit && step == 0;
@@ -3001,6 +3027,7 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
     if (!last) GPF_SYNC_IF(G::block_any_u(failed && sa.auto_reset != 0));   // auto-reset rewrote topology rows with another lane mapping
   }
 #undef GPF_REDERIVE
+#undef GPF_DCF_ON
   grp = grp0; tid = tid0; inst = inst0;
   if (keep_on) {
     // The blob has a key but no state yet, this instance is on the key, rebuilt the state in this launch and nothing tripped or failed since

@@ -1728,7 +1728,7 @@ class PowerFlowEngine:
         check(self._lib.gpf_get_kernel_time(self._h, C.byref(ms), C.byref(n)), "gpf_get_kernel_time")
         return ms.value, n.value
 
-    def specialize(self, enable: bool = True, cache_dir: str = None, verify: bool = True) -> dict:
+    def specialize(self, enable: bool = True, cache_dir: str = None, verify: bool = True, features: bool = True) -> dict:
         """Switch the engine's solver launches (`step`, `simulate_batch`, `runpf`, `solve_lane`) to kernels compiled AT RUN TIME FOR THIS GRID
         (gpf_jit_enable): every size and table offset of the grid is a literal in them instead of a value read from the
         launch parameter block.  The first launch of each kernel variant compiles it (hipcc, about a second; cached on disk per
@@ -1737,7 +1737,13 @@ class PowerFlowEngine:
         (synthetic chronics around the grid's own injections, load jitter, generation rebalancing) and an AC + a DC `runpf` with the
         shipped and with the specialised kernels, and every result must agree bit for bit -- a specialised kernel is a new binary, and a binary
         is only trusted after it reproduced the validated one; on a mismatch the engine keeps the shipped kernels and
-        `GridPFError` is raised.  Raises `GridPFError` too when no hipcc is available (shipped kernels stay)."""
+        `GridPFError` is raised.  Raises `GridPFError` too when no hipcc is available (shipped kernels stay).
+        ``features`` (default on): a step launch first looks for a kernel compiled for its LAUNCH FEATURES as well -- which of cascade,
+        auto-reset, cooldowns, outage tables, kept state, lane lists, trajectory ... the launch uses at all (`feature_word`) -- then for the
+        grid-only kernel.  At most 4 feature words per kernel variant and engine are compiled at run time (further words run on the grid-only
+        kernel; kernels built ahead of time do not count); without a compiler a missing feature kernel is silently the grid-only one.
+        ``features=False``: grid-only kernels.  The self-test runs its launches both ways."""
+        check(self._lib.gpf_jit_features(self._h, int(bool(features))), "gpf_jit_features")
         if not enable:
             check(self._lib.gpf_jit_disable(self._h), "gpf_jit_disable")
             return self.specialization()
@@ -1780,8 +1786,12 @@ class PowerFlowEngine:
 
             ref = run()
             src = (os.environ.get("GRIDPF_JIT_SRC") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")).encode()
+            check(twin._lib.gpf_jit_features(twin._h, 0), "gpf_jit_features")            # the grid-only kernels ...
             check(twin._lib.gpf_jit_enable(twin._h, src, cache_dir.encode() if cache_dir else None), "gpf_jit_enable")
             got = run()
+            check(twin._lib.gpf_jit_features(twin._h, 1), "gpf_jit_features")            # ... and the same launches under their feature kernels
+            got += run()
+            ref = ref + ref
             info = twin.specialization()
             if info["launches"] == 0:
                 raise GridPFError(f"specialised kernels could not be built for this grid ({info['variants']}): the shipped kernels stay")
@@ -1801,6 +1811,25 @@ class PowerFlowEngine:
         check(self._lib.gpf_jit_info(self._h, counts, C.byref(sec), text, len(text)), "gpf_jit_info")
         return {"enabled": bool(counts[0]), "compiled": int(counts[1]), "cached": int(counts[2]), "failed": int(counts[3]),
                 "launches": int(counts[4]), "aot": int(counts[5]), "seconds": float(sec.value), "variants": text.value.decode()}
+
+    def feature_word(self, n_steps: int = 1, lane_scale: bool = False, outages: bool = False, gen_delta: bool = False,
+                     trajectory_obs: bool = False, **step_kw) -> int:
+        """The launch-feature word (gpf_jit_feature_word) of ``step(t, n_steps=n_steps, **step_kw)`` on this engine as it stands, plus the
+        optional inputs the flags say the launch will have (a header-only engine has none of its own): what names the feature kernel of that
+        launch in `specialization()["variants"]` and in ``grid2op_amd/aot/manifest.json``.  Needs no device."""
+        kw = dict(max_iter=10, tol_mva=1e-8, rebalance=0.0, cascade=False, hard_overflow=2.0, soft_overflow=1.0, nb_ts_allowed=2, max_rounds=16,
+                  is_dc=False, auto_reset=False, warm_start=False, nb_ts_reco=None)
+        kw.update(step_kw)
+        reco = kw["nb_ts_reco"]
+        if reco is None:
+            reco = 10 if (kw["cascade"] or outages or getattr(self, "_has_outages", False)) else -1
+        o = GpfStepOpts(int(kw["max_iter"]), float(kw["tol_mva"]), float(kw["rebalance"]), int(bool(kw["cascade"])), float(kw["hard_overflow"]),
+                        float(kw["soft_overflow"]), int(kw["nb_ts_allowed"]), int(kw["max_rounds"]), int(bool(kw["is_dc"])), int(bool(kw["auto_reset"])),
+                        int(bool(kw["warm_start"])), int(reco >= 0), max(int(reco), 0))
+        have = (1 if lane_scale else 0) | (4 if outages else 0) | (8 if gen_delta else 0) | (16 if trajectory_obs else 0)     # GPF_HAVE_*
+        word = C.c_uint32(0)
+        check(self._lib.gpf_jit_feature_word(self._h, int(n_steps), C.byref(o), have, C.byref(word)), "gpf_jit_feature_word")
+        return int(word.value)
 
     def specialization_header(self) -> str:
         """The generated header the specialised kernels are compiled with (gpf_jit_source): this grid's numbers as C literals."""

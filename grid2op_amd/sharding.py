@@ -638,12 +638,13 @@ class ShardedEngine:
     def plan(self):
         return [eng.plan() for eng in self.engines]
 
-    def specialize(self, enable: bool = True, cache_dir=None, verify: bool = True):
+    def specialize(self, enable: bool = True, cache_dir=None, verify: bool = True, features: bool = True):
         """`PowerFlowEngine.specialize` on every device's engine (same grid: the self-test runs once, the code objects are shared
-        through the on-disk cache); returns one `specialization()` dict per device."""
+        through the on-disk cache); returns one `specialization()` dict per device.  ``features=False``: grid-only kernels."""
         out = []
+        kw = {} if features else {"features": False}
         for k, eng in enumerate(self.engines):
-            out.append(eng.specialize(enable, cache_dir=cache_dir, verify=verify and k == 0) if hasattr(eng, "specialize") else None)
+            out.append(eng.specialize(enable, cache_dir=cache_dir, verify=verify and k == 0, **kw) if hasattr(eng, "specialize") else None)
         return out
 
     def specialization(self):

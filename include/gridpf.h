@@ -1122,6 +1122,23 @@ int gpf_jit_disable(gpf_handle h);
  * variants loaded from the ahead-of-time directory ("_aot" next to the library)};
  * seconds = time spent compiling / loading; text = the variants loaded so far (+ the last error).  Any pointer may be NULL. */
 int gpf_jit_info(gpf_handle h, int64_t* counts, double* seconds, char* text, size_t cap);
+/* Launch features.  Beyond the grid, a step launch fixes which facilities of the engine it uses at all: cascade, auto-reset, warm start,
+ * DC, line cooldowns, rebalancing, kept state, lane lists, outage tables, redispatch deltas, load jitter, the
+ * observation trajectory, the DC factors' place in LDS, padding lanes.  With features on (the default of gpf_jit_enable) a step launch
+ * first looks for a code object compiled for exactly its set of those answers (one 32-bit word, computed by the library for every launch;
+ * it shows as the last template argument in gpf_jit_info's text), then for the grid-only object, then takes the shipped kernel.  A
+ * missing feature object is no failure and is not reported.  At run time at most 4 words per kernel variant and engine are compiled or
+ * taken from the disk cache; further words run on the grid-only object.  Ahead-of-time objects do not count.  Results are bit-identical
+ * on every path.  on = 0: grid-only objects as before.
+ * gpf_jit_feature_word: the word of a gpf_step_n launch of n_steps over all lanes with the options `opts`, on the engine as it stands plus
+ * the optional inputs `have` (GPF_HAVE_*) says the launch will have; works on a header-only handle (how grid2op_amd/aot.py names the
+ * ahead-of-time feature variants of a grid). */
+#define GPF_HAVE_LANE_SCALE 1u  /* gpf_set_lane_chronics with lane_scale */
+#define GPF_HAVE_OUTAGES 4u     /* gpf_upload_maintenance / gpf_upload_hazards */
+#define GPF_HAVE_GEN_DELTA 8u   /* gpf_set_lane_redispatch */
+#define GPF_HAVE_TRAJ_OBS 16u   /* gpf_set_trajectory(h, cap >= n_steps, GPF_TRAJ_OBS) */
+int gpf_jit_features(gpf_handle h, int32_t on);
+int gpf_jit_feature_word(gpf_handle h, int32_t n_steps, const gpf_step_opts* opts, uint32_t have, uint32_t* word);
 /* the header the specialised kernels are compiled with (one grid's numbers as C literals); *need = bytes incl. the terminator */
 int gpf_jit_source(gpf_handle h, char* text, size_t cap, size_t* need);
 

@@ -3,6 +3,7 @@
 
     python -c "import __graft_entry__ as g; g.build_timing_lib()"      # -> grid2op_amd/libgridpf_timing.so
     GRIDPF_LIB=grid2op_amd/libgridpf_timing.so python tools/phase_timing.py [batch]
+    GRIDPF_LIB=... GRIDPF_JIT_FLAGS=-DGPF_TIMING PT_JIT=1 [PT_HEADLINE=1] [PT_FEATURES=0] NSTEPS=20 python tools/phase_timing.py 4096     # specialised kernels
 """
 import ctypes as C
 import os
@@ -23,13 +24,21 @@ m = GridModel.load_npz(os.path.join(gold, f"{env}.grid.npz"))
 ch = dict(np.load(os.path.join(gold, f"{env}.chronics.npz")))
 eng = PowerFlowEngine(m, n_lanes=B)
 eng.upload_chronics(eng.pack_chronics(ch["load_p"], ch["load_q"], ch["prod_p"], ch.get("prod_v", np.tile((m.gen_vm0 * m.sub_vn_kv[m.gen_sub]).astype(np.float32), (ch["prod_p"].shape[0], 1)))))
-eng.set_lane_chronics(lane_offset=(7 * np.arange(B)) % ch["load_p"].shape[0])
-if os.environ.get("PT_JIT"):      # the grid-specialised kernels with the stamps: GRIDPF_JIT_FLAGS=-DGPF_TIMING PT_JIT=1 (the library must be the timing build too)
-    print("specialised:", eng.specialize(verify=False))
 NS = int(os.environ.get("NSTEPS", "1"))
+if os.environ.get("PT_HEADLINE"):  # the launch of bench.py's headline: load jitter and the observation trajectory on (its launch-feature word)
+    eng.set_lane_chronics(lane_offset=(7 * np.arange(B)) % ch["load_p"].shape[0],
+                          lane_scale=(1 + 0.05 * np.random.default_rng(0).standard_normal((B, 2 * m.n_load))).astype(np.float32))
+    eng.set_trajectory(NS, eng.TRAJ_OBS)
+else:
+    eng.set_lane_chronics(lane_offset=(7 * np.arange(B)) % ch["load_p"].shape[0])
+if os.environ.get("PT_JIT"):      # the grid-specialised kernels with the stamps: GRIDPF_JIT_FLAGS=-DGPF_TIMING PT_JIT=1 (the library must be the timing build too)
+    # PT_FEATURES=0: the grid-only object (what every launch ran on before the launch features); default: the launch's feature object
+    print("specialised:", eng.specialize(verify=False, features=os.environ.get("PT_FEATURES", "1") != "0"))
 for t in range(5):
     eng.step(t * NS, rebalance=1.02, n_steps=NS)
 eng.sync()
+if os.environ.get("PT_JIT"):
+    print("launched:", eng.specialization()["variants"])
 L = _capi.lib()
 ROW = 88
 buf = np.zeros((B, ROW))
