@@ -6,6 +6,8 @@ box, gloo in the CPU tests) is only used for the barrier and the max-over-ranks 
 """
 from __future__ import annotations
 
+from dataclasses import fields, is_dataclass
+from operator import attrgetter
 from typing import Tuple
 
 import numpy as np
@@ -69,10 +71,16 @@ class ShardedEngine:
     call is forwarded to the engines that own the addressed lanes (asynchronous calls stay asynchronous, i.e. one host
     thread keeps all the devices busy) and results are concatenated in global lane order.
 
+    Most of the batched API is forwarded by one of the routing rules below the class: `ROUTES` names the rule of every
+    such method and one loop installs them, so a new batched engine method is one name in one table.  The methods written
+    out here are the ones that fit no rule; `NOT_SHARDED` lists the engine methods that are not forwarded at all.
+
     Counterpart in the reference: its only parallelism is one process per environment -- ``Runner._run_parrallel``
     (grid2op/Runner/runner.py:1071-1253, a ``multiprocessing.Pool`` over episodes) and ``BaseMultiProcessEnvironment``
     (grid2op/Environment/baseMultiProcessEnv.py:22, 293, one worker process per environment copy).  ``bench.py``
     uses the other form (one PROCESS per GPU, `lane_range` of the global batch per rank)."""
+
+    TRAJ_RHO, TRAJ_OBS = 1, 2
 
     def __init__(self, model, n_lanes: int, devices=None, n_busbar: int = 2, engine_factory=None):
         if devices is None:
@@ -113,49 +121,6 @@ class ShardedEngine:
         (eng, l0, _, _), = self._parts(lane, 1)
         return eng, l0
 
-    # ---- state ----------------------------------------------------------------------------------------------------------
-    def pack_injections(self, n: int = 1, **fields):
-        return self.engines[0].pack_injections(n, **fields)
-
-    def pack_chronics(self, *a):
-        return self.engines[0].pack_chronics(*a)
-
-    def set_injections(self, inj, lane0: int = 0):
-        inj = np.asarray(inj).reshape(-1, self.n_inj)
-        for eng, l0, n, off in self._parts(lane0, inj.shape[0]):
-            eng.set_injections(inj[off:off + n], lane0=l0)
-
-    def get_injections(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.get_injections(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def set_topology(self, topo, shunt_bus=None, lane0: int = 0):
-        topo = np.asarray(topo).reshape(-1, self.model.dim_topo)
-        sb = None if shunt_bus is None or not self.model.n_shunt else np.asarray(shunt_bus).reshape(-1, self.model.n_shunt)
-        for eng, l0, n, off in self._parts(lane0, topo.shape[0]):
-            eng.set_topology(topo[off:off + n], None if sb is None else sb[off:off + n], lane0=l0)
-
-    def reset(self, lane0: int = 0, n=None):
-        for eng, l0, k, _ in self._parts(lane0, n):
-            eng.reset(l0, k)
-
-    def disconnect_line(self, lane: int, line_id: int):
-        eng, l0 = self.owner(lane)
-        eng.disconnect_line(l0, line_id)
-
-    def upload_chronics(self, tables):
-        for eng in self.engines:                     # every device holds its own copy of the (small) tables
-            eng.upload_chronics(tables)
-        self.chron_T = self.engines[0].chron_T
-
-    def set_lane_chronics(self, lane_table=None, lane_offset=None, lane_scale=None):
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            cut = lambda a: None if a is None else np.asarray(a)[b0:b0 + bn]  # noqa: E731
-            eng.set_lane_chronics(cut(lane_table), cut(lane_offset), cut(lane_scale))
-
-    def set_thermal_limits(self, limit_a):
-        for eng in self.engines:
-            eng.set_thermal_limits(limit_a)
-
     # ---- solve (asynchronous: queued on every device's stream) ----------------------------------------------------------------
     # One host thread per device: a launch call is planning + parameter upload + the launch itself (~10 us of host time on an
     # MI355X box) and the ctypes call releases the GIL, so the launches of the devices are issued CONCURRENTLY -- issued from one
@@ -179,85 +144,32 @@ class ShardedEngine:
     def step(self, t: int, **kw):
         self._fan([(lambda e=eng: e.step(t, **kw)) for eng in self.engines])
 
-    def set_lane_redispatch(self, delta_mw):
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.set_lane_redispatch(None if delta_mw is None else np.asarray(delta_mw)[b0:b0 + bn])
+    # ---- what fits no rule -----------------------------------------------------------------------------------------------
+    def upload_chronics(self, tables):                   # no rule: records the tables' length
+        for eng in self.engines:                     # every device holds its own copy of the (small) tables
+            eng.upload_chronics(tables)
+        self.chron_T = self.engines[0].chron_T
 
-    def episode(self, lane0: int = 0, n=None):
-        parts = [eng.episode(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+    def upload_topo_actions(self, actions):              # no rule: every device gets the table, the first one's answer comes back
+        return [eng.upload_topo_actions(actions) for eng in self.engines][0]
 
-    def sync(self):
-        for eng in self.engines:
-            eng.sync()
+    def disconnect_line(self, lane: int, line_id: int):  # no rule: one lane of one device
+        eng, l0 = self.owner(lane)
+        eng.disconnect_line(l0, line_id)
 
     def results(self, lane0: int = 0, n=None, with_bus: bool = True, pinned: bool = False):
         """(``pinned``: every device's rows come over by DMA into its engine's pinned block; the concatenation below is the one host copy)"""
-        from .engine import LaneResults
-        rs = [eng.results(l0, k, with_bus=with_bus, **({"pinned": True} if pinned else {})) for eng, l0, k, _ in self._parts(lane0, n)]
-        cat = lambda f: None if getattr(rs[0], f) is None else np.concatenate([getattr(r, f) for r in rs])  # noqa: E731
-        return LaneResults(out=cat("out"), topo_vect=cat("topo_vect"), shunt_bus=cat("shunt_bus"), line_status=cat("line_status"),
-                           status=cat("status"), bus_vm=cat("bus_vm"), bus_va=cat("bus_va"), _slices=rs[0]._slices)
+        # no rule: ``pinned`` is forwarded only when set (the engine of the launcher test has no such keyword)
+        return _cat([eng.results(l0, k, with_bus=with_bus, **({"pinned": True} if pinned else {})) for eng, l0, k, _ in self._parts(lane0, n)])
 
-    def cooldown(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.cooldown(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def set_cooldown(self, line_cooldown, lane0: int = 0):
-        c = np.asarray(line_cooldown).reshape(-1, self.model.n_line)
-        for eng, l0, k, off in self._parts(lane0, c.shape[0]):
-            eng.set_cooldown(c[off:off + k], lane0=l0)
-
-    # ---- observation vectors (PowerFlowEngine.set_obs_spec ...): per-shard tensors on each device, host copies concatenated ----------
-    def set_obs_clock(self, *a, **kw):
-        for eng in self.engines:
-            eng.set_obs_clock(*a, **kw)
-
-    def set_obs_spec(self, spec, game_over_fill: bool = True):
-        for eng in self.engines:
-            eng.set_obs_spec(spec, game_over_fill)
-
-    def observation_vector(self, lane0: int = 0, n=None, out=None):
-        """One tensor per shard that intersects the range (each on its own device and stream); ``out``: a list with one tensor per such shard."""
-        parts = self._parts(lane0, n)
-        outs = [None] * len(parts) if out is None else list(out)
-        if len(outs) != len(parts):
-            raise ValueError(f"ShardedEngine.observation_vector: {len(parts)} shards intersect the range, {len(outs)} output tensors given")
-        return [eng.observation_vector(l0, k, out=o) for (eng, l0, k, _), o in zip(parts, outs)]
-
-    def observation_trajectory(self, n_steps: int, step0: int = 0, lane0: int = 0, n=None):
-        return [eng.observation_trajectory(n_steps, step0, l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-
-    def observation_vector_host(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.observation_vector_host(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def step_outputs(self, lane0: int = 0, n=None):
-        parts = [eng.step_outputs(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
-
-    # ---- the rest of the batched API: per-table calls go to every device, per-lane calls are cut by block ---------------------
-    TRAJ_RHO, TRAJ_OBS = 1, 2
-
-    def upload_maintenance(self, maintenance):
-        for eng in self.engines:
-            eng.upload_maintenance(maintenance)
-
-    def upload_outage_durations(self, durations):
-        for e in self.engines:
-            e.upload_outage_durations(durations)
-
-    def upload_hazards(self, hazards):
-        for eng in self.engines:
-            eng.upload_hazards(hazards)
-
-    def set_deterministic(self, flag: bool = True):
-        for eng in self.engines:
-            eng.set_deterministic(flag)
-
-    def set_gen_limits(self, *a, **kw):
-        for eng in self.engines:
-            eng.set_gen_limits(*a, **kw)
+    def set_topology(self, topo, shunt_bus=None, lane0: int = 0):        # no rule: two row arrays, the second optional and absent without shunts
+        topo = np.asarray(topo).reshape(-1, self.model.dim_topo)
+        sb = None if shunt_bus is None or not self.model.n_shunt else np.asarray(shunt_bus).reshape(-1, self.model.n_shunt)
+        for eng, l0, n, off in self._parts(lane0, topo.shape[0]):
+            eng.set_topology(topo[off:off + n], None if sb is None else sb[off:off + n], lane0=l0)
 
     def redispatch(self, new_p, prev_p, actual, target, modified, rhs, lane0: int = 0, apply: bool = False):
+        # no rule: five row arrays and one value per lane go out, two arrays come back
         ng = self.model.n_gen
         rows = [np.asarray(a).reshape(-1, ng) for a in (new_p, prev_p, actual, target, modified)]
         n = rows[0].shape[0]
@@ -269,32 +181,38 @@ class ShardedEngine:
             afters.append(after)
         return np.concatenate(oks), np.concatenate(afters)
 
-    def set_trajectory(self, n_steps_cap: int, what: int = 1):
-        for eng in self.engines:
-            eng.set_trajectory(n_steps_cap, what)
-
-    def trajectory(self, n_steps: int, step0: int = 0, lane0: int = 0, n=None):
-        parts = [eng.trajectory(n_steps, step0, l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return np.concatenate([p[0] for p in parts], axis=1), np.concatenate([p[1] for p in parts], axis=1)
-
-    def trajectory_obs(self, n_steps: int, step0: int = 0, lane0: int = 0, n=None):
-        from .engine import LaneResults
-        parts = [eng.trajectory_obs(n_steps, step0, l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        out = []
-        for s in range(n_steps):
-            rs = [p[s] for p in parts]
-            cat = lambda f: np.concatenate([getattr(r, f) for r in rs])  # noqa: E731
-            out.append(LaneResults(out=cat("out"), topo_vect=cat("topo_vect"), shunt_bus=cat("shunt_bus"), line_status=cat("line_status"),
-                                   status=cat("status"), bus_vm=None, bus_va=None, _slices=rs[0]._slices))
-        return out
-
-    def trajectory_cooldown(self, n_steps: int, step0: int = 0, lane0: int = 0, n=None):
-        return np.concatenate([eng.trajectory_cooldown(n_steps, step0, l0, k) for eng, l0, k, _ in self._parts(lane0, n)], axis=1)
+    def set_env_state(self, lane0: int = 0, **fields):                   # no rule: the rows are whatever keywords are given
+        """`PowerFlowEngine.set_env_state` on the global lane range starting at ``lane0``: every array is cut by device block."""
+        arrs = {k: np.asarray(v) for k, v in fields.items() if v is not None}
+        if not arrs:
+            return
+        n = next(iter(arrs.values())).shape[0]
+        for eng, l0, k, off in self._parts(lane0, n):
+            eng.set_env_state(l0, **{key: a[off:off + k] for key, a in arrs.items()})
 
     def counters(self) -> dict:
         """Step launches / kernel dispatches summed over the devices."""
         cs = [eng.counters() for eng in self.engines]
         return {k: sum(c[k] for c in cs) for k in cs[0]}
+
+    # the opponent and the chronics cursor: the configuration goes to every device with the shard's lane_base (which makes the Philox
+    # streams of the shards those of one engine) and has an "off" form
+    def set_opponent(self, kind=0, lines=(), **kw):
+        base = int(kw.pop("lane_base", 0))
+        for eng, (b0, _) in zip(self.engines, self.blocks):
+            if kind is None or int(kind) == 0:
+                eng.set_opponent(None)
+            else:
+                eng.set_opponent(kind, lines, lane_base=base + b0, **kw)
+
+    def set_chronics_cursor(self, order=None, policy="sequential", probabilities=None, first_row=0, next_pos=None, seed=None, lane_base: int = 0):
+        def cut(v, b0, bn):
+            return v if v is None or np.ndim(v) == 0 else np.asarray(v).reshape(self.n_lanes)[b0:b0 + bn]
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            if order is False:
+                eng.set_chronics_cursor(False)
+            else:
+                eng.set_chronics_cursor(order, policy, probabilities, cut(first_row, b0, bn), cut(next_pos, b0, bn), seed, lane_base=int(lane_base) + b0)
 
     # DC sensitivities of per-lane topologies: every device builds the tables of the topologies ITS lanes hold; class ids are per shard
     # (a class of shard s is reported as ``class_offset[s] + local id``), so that `ptdf_class` finds the owner again
@@ -333,10 +251,7 @@ class ShardedEngine:
         if all(getattr(e, "env_dynamics_on", False) for e in self.engines):
             self.set_env_state(dst, **self.env_state(src, n))
 
-    def get_topology(self, lane0: int = 0, n=None):
-        parts = [eng.get_topology(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
-
+    # the same-device calls: the source lanes and the lanes they are copied to must be on one device
     def fanout_n1(self, src_lane: int, dst_lane0: int, out_lines):
         """N-1 fan-out of one source lane; source and destinations must live on the same device (the contingencies of an
         environment sit next to it: SURVEY.md 8(e))."""
@@ -355,271 +270,6 @@ class ShardedEngine:
             raise ValueError("ShardedEngine.simulate_candidates: the source lane and its candidate lanes must be on the same device")
         return es.simulate_candidates(ls, pd[0][1], actions=actions, topologies=topologies, **kw)
 
-    def set_storage_params(self, *a, **kw):
-        for eng in self.engines:
-            eng.set_storage_params(*a, **kw)
-
-    def set_env_dynamics(self, *a, **kw):
-        for eng in self.engines:
-            eng.set_env_dynamics(*a, **kw)
-
-    def set_lane_actions(self, redispatch=None, storage_power=None, hold_storage: bool = False):
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            cut = lambda a: None if a is None else np.asarray(a)[b0:b0 + bn]  # noqa: E731
-            eng.set_lane_actions(cut(redispatch), cut(storage_power), hold_storage)
-
-    def lane_actions_on_device(self, *a, **kw):
-        """every device's action buffers (`device_views()[k]["act_*"]`) hold the next launch's actions of its own lanes"""
-        for eng in self.engines:
-            eng.lane_actions_on_device(*a, **kw)
-
-    # topology actions: the table and the rules go to every device, indices / per-lane state are cut by block
-    def set_topo_rules(self, *a, **kw):
-        for eng in self.engines:
-            eng.set_topo_rules(*a, **kw)
-
-    def set_topo_areas(self, areas=None):
-        for eng in self.engines:
-            eng.set_topo_areas(areas)
-
-    def set_topo_slots(self, n_slot: int = 1):
-        for eng in self.engines:
-            eng.set_topo_slots(n_slot)
-
-    def topo_action_areas(self):
-        return self.engines[0].topo_action_areas()
-
-    def upload_topo_actions(self, actions):
-        return [eng.upload_topo_actions(actions) for eng in self.engines][0]
-
-    def set_lane_topo_actions(self, index):
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.set_lane_topo_actions(None if index is None else np.asarray(index)[b0:b0 + bn])
-
-    def topo_actions_on_device(self, on: bool = True):
-        """every device's ``act_topo`` buffer holds the next launch's indices of its own lanes"""
-        for eng in self.engines:
-            eng.topo_actions_on_device(on)
-
-    def sub_cooldown(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.sub_cooldown(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def set_sub_cooldown(self, sub_cooldown, lane0: int = 0):
-        c = np.asarray(sub_cooldown).reshape(-1, self.model.n_sub)
-        for eng, l0, k, off in self._parts(lane0, c.shape[0]):
-            eng.set_sub_cooldown(c[off:off + k], lane0=l0)
-
-    def last_bus(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.last_bus(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def set_last_bus(self, last_bus, lane0: int = 0):
-        c = np.asarray(last_bus).reshape(-1, self.model.dim_topo)
-        for eng, l0, k, off in self._parts(lane0, c.shape[0]):
-            eng.set_last_bus(c[off:off + k], lane0=l0)
-
-    def topo_action_flags(self, lane0: int = 0, n=None):
-        parts = [eng.topo_action_flags(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(2))
-
-    def topo_action_mask(self, lane0: int = 0, n=None, out=None):
-        """One tensor per shard that intersects the range (each on its own device and stream); ``out``: a list with one tensor per such shard."""
-        parts = self._parts(lane0, n)
-        outs = [None] * len(parts) if out is None else list(out)
-        if len(outs) != len(parts):
-            raise ValueError(f"ShardedEngine.topo_action_mask: {len(parts)} shards intersect the range, {len(outs)} output tensors given")
-        return [eng.topo_action_mask(l0, k, out=o) for (eng, l0, k, _), o in zip(parts, outs)]
-
-    def topo_action_mask_host(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.topo_action_mask_host(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    # the opponent: the configuration goes to every device with the shard's lane_base, tables and per-lane state are cut by block
-    def set_opponent(self, kind=0, lines=(), **kw):
-        base = int(kw.pop("lane_base", 0))
-        for eng, (b0, _) in zip(self.engines, self.blocks):
-            if kind is None or int(kind) == 0:
-                eng.set_opponent(None)
-            else:
-                eng.set_opponent(kind, lines, lane_base=base + b0, **kw)
-
-    def upload_opponent_draws(self, draws):
-        u = np.asarray(draws).reshape(self.n_lanes, -1)
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.upload_opponent_draws(u[b0:b0 + bn])
-
-    def upload_opponent_schedule(self, schedule, count):
-        sch = np.asarray(schedule).reshape(self.n_lanes, -1, 2)
-        cnt = np.broadcast_to(np.asarray(count), (self.n_lanes,))
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.upload_opponent_schedule(sch[b0:b0 + bn], cnt[b0:b0 + bn])
-
-    def opponent_state(self, lane0: int = 0, n=None):
-        from .engine import OpponentState
-        parts = [eng.opponent_state(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return OpponentState.from_rows(np.concatenate([p.budget for p in parts]), np.concatenate([p.rows() for p in parts]))
-
-    def set_opponent_state(self, state, lane0: int = 0):
-        from .engine import OpponentState
-        bud, rows = np.asarray(state.budget), state.rows()
-        for eng, l0, k, off in self._parts(lane0, len(bud)):
-            eng.set_opponent_state(OpponentState.from_rows(bud[off:off + k], rows[off:off + k]), lane0=l0)
-
-    # the multi-area opponent: the areas go to every device, area schedules and area state are cut by block
-    def set_opponent_areas(self, area_of_line):
-        for eng in self.engines:
-            eng.set_opponent_areas(area_of_line)
-
-    def upload_opponent_area_schedule(self, schedule, count):
-        sch, cnt = np.asarray(schedule), np.asarray(count)
-        if sch.ndim == 3:
-            sch = np.broadcast_to(sch, (self.n_lanes,) + sch.shape)
-        cnt = np.broadcast_to(cnt, (self.n_lanes, sch.shape[1]))
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.upload_opponent_area_schedule(sch[b0:b0 + bn], cnt[b0:b0 + bn])
-
-    def opponent_area_state(self, lane0: int = 0, n=None):
-        from .engine import OpponentAreaState
-        return OpponentAreaState.from_rows(np.concatenate([eng.opponent_area_state(l0, k).rows() for eng, l0, k, _ in self._parts(lane0, n)]))
-
-    def set_opponent_area_state(self, state, lane0: int = 0):
-        from .engine import OpponentAreaState
-        rows = state.rows()
-        for eng, l0, k, off in self._parts(lane0, rows.shape[0]):
-            eng.set_opponent_area_state(OpponentAreaState.from_rows(rows[off:off + k]), lane0=l0)
-
-    def opponent_attack_lines(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.opponent_attack_lines(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    # ---- alerts and AlertReward (PowerFlowEngine.set_alerts): the same configuration on every device, per-lane data by blocks ----
-    def set_alerts(self, time_window=12, **constants):
-        for eng in self.engines:
-            eng.set_alerts(time_window, **constants)
-
-    def set_lane_alerts(self, alerts):
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.set_lane_alerts(None if alerts is None else np.asarray(alerts)[b0:b0 + bn])
-
-    def alerts_on_device(self, on: bool = True):
-        """every device's ``act_alert`` buffer holds the next launch's masks of its own lanes"""
-        for eng in self.engines:
-            eng.alerts_on_device(on)
-
-    def alert_state(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.alert_state(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def set_alert_state(self, rows, lane0: int = 0):
-        r = np.asarray(rows)
-        r = r.reshape(-1, r.shape[-1])
-        for eng, l0, k, off in self._parts(lane0, r.shape[0]):
-            eng.set_alert_state(r[off:off + k], lane0=l0)
-
-    def alert_state_fields(self, rows) -> dict:
-        return self.engines[0].alert_state_fields(rows)
-
-    def alert_reward(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.alert_reward(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    # ---- the environment's rewards (PowerFlowEngine.set_rewards): the same slots on every device, rows by blocks ----
-    def set_rewards(self, slots, gen_cost_per_MW=None):
-        for eng in self.engines:
-            eng.set_rewards(slots, gen_cost_per_MW)
-
-    def rewards(self, lane0: int = 0, n=None):
-        return np.concatenate([eng.rewards(l0, k) for eng, l0, k, _ in self._parts(lane0, n)])
-
-    def rewards_eval(self, lane0: int = 0, n=None, flags=None, out=None):
-        """One tensor per shard that intersects the range (each on its own device and stream); ``flags`` / ``out``: a list with one tensor
-        per such shard (the rows of its lanes)."""
-        parts = self._parts(lane0, n)
-        fl = [None] * len(parts) if flags is None else list(flags)
-        outs = [None] * len(parts) if out is None else list(out)
-        if len(outs) != len(parts) or len(fl) != len(parts):
-            raise ValueError(f"ShardedEngine.rewards_eval: {len(parts)} shards intersect the range, {len(fl)} flag / {len(outs)} output tensors given")
-        return [eng.rewards_eval(l0, k, flags=f, out=o) for (eng, l0, k, _), f, o in zip(parts, fl, outs)]
-
-    def reward_views(self):
-        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
-        return [eng.reward_views() for eng in self.engines]
-
-    # ---- episode time limits (PowerFlowEngine.set_episode_limit): one limit everywhere, or per-lane limits cut by blocks ----
-    def set_episode_limit(self, max_steps, per_timestep: float = 1.0, alert_end_bonus: float = 0.0):
-        per_lane = max_steps is not None and np.ndim(max_steps) > 0
-        if per_lane:
-            max_steps = np.asarray(max_steps).reshape(self.n_lanes)
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.set_episode_limit(max_steps[b0:b0 + bn] if per_lane else max_steps, per_timestep, alert_end_bonus)
-
-    def episode_ends(self, lane0: int = 0, n=None) -> dict:
-        parts = [eng.episode_ends(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
-
-    def episode_stats(self, lane0: int = 0, n=None) -> dict:
-        parts = [eng.episode_stats(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
-
-    def episode_views(self):
-        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
-        return [eng.episode_views() for eng in self.engines]
-
-    # ---- the chronics cursor (PowerFlowEngine.set_chronics_cursor): the configuration goes to every device with the shard's lane_base,
-    # per-lane first rows / positions, the draws and the state are cut by block ----
-    def set_chronics_cursor(self, order=None, policy="sequential", probabilities=None, first_row=0, next_pos=None, seed=None, lane_base: int = 0):
-        def cut(v, b0, bn):
-            return v if v is None or np.ndim(v) == 0 else np.asarray(v).reshape(self.n_lanes)[b0:b0 + bn]
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            if order is False:
-                eng.set_chronics_cursor(False)
-            else:
-                eng.set_chronics_cursor(order, policy, probabilities, cut(first_row, b0, bn), cut(next_pos, b0, bn), seed, lane_base=int(lane_base) + b0)
-
-    def upload_cursor_draws(self, draws):
-        u = np.asarray(draws).reshape(self.n_lanes, -1)
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.upload_cursor_draws(u[b0:b0 + bn])
-
-    def chronics_cursor_state(self, lane0: int = 0, n=None):
-        from .engine import CursorState
-        return CursorState.from_rows(np.concatenate([eng.chronics_cursor_state(l0, k).rows() for eng, l0, k, _ in self._parts(lane0, n)]))
-
-    def set_chronics_cursor_state(self, state, lane0: int = 0):
-        from .engine import CursorState
-        rows = state.rows()
-        for eng, l0, k, off in self._parts(lane0, rows.shape[0]):
-            eng.set_chronics_cursor_state(CursorState.from_rows(rows[off:off + k]), lane0=l0)
-
-    def cursor_views(self):
-        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
-        return [eng.cursor_views() for eng in self.engines]
-
-    def set_gen_renewable(self, renewable):
-        for eng in self.engines:
-            eng.set_gen_renewable(renewable)
-
-    def set_lane_curtailment(self, limit):
-        for eng, (b0, bn) in zip(self.engines, self.blocks):
-            eng.set_lane_curtailment(None if limit is None else np.asarray(limit)[b0:b0 + bn])
-
-    def env_state(self, lane0: int = 0, n=None) -> dict:
-        parts = [eng.env_state(l0, k) for eng, l0, k, _ in self._parts(lane0, n)]
-        return {key: np.concatenate([p[key] for p in parts]) for key in parts[0]}
-
-    def set_env_state(self, lane0: int = 0, **fields):
-        """`PowerFlowEngine.set_env_state` on the global lane range starting at ``lane0``: every array is cut by device block."""
-        arrs = {k: np.asarray(v) for k, v in fields.items() if v is not None}
-        if not arrs:
-            return
-        n = next(iter(arrs.values())).shape[0]
-        for eng, l0, k, off in self._parts(lane0, n):
-            eng.set_env_state(l0, **{key: a[off:off + k] for key, a in arrs.items()})
-
-    def set_overflow_count(self, counts, lane0: int = 0):
-        c = np.asarray(counts).reshape(-1, self.model.n_line)
-        for eng, l0, n, off in self._parts(lane0, c.shape[0]):
-            eng.set_overflow_count(c[off:off + n], lane0=l0)
-
-    def upload_forecasts(self, tables):
-        for eng in self.engines:
-            eng.upload_forecasts(tables)
-
     def simulate_batch(self, t_obs: int, src_lanes, actions, dst_lane0: int, **kw):
         """`PowerFlowEngine.simulate_batch`; the source lanes and their candidate lanes must live on ONE device."""
         src = np.asarray(src_lanes, dtype=np.int64).reshape(-1)
@@ -630,13 +280,6 @@ class ShardedEngine:
         eng = pd[0][0]
         b0 = self.blocks[self.engines.index(eng)][0]
         return eng.simulate_batch(t_obs, src - b0, actions, pd[0][1], **kw)
-
-    def device_views(self):
-        """One dict of zero-copy torch views per device (global lane order = concatenation over the list)."""
-        return [eng.device_views() for eng in self.engines]
-
-    def plan(self):
-        return [eng.plan() for eng in self.engines]
 
     def specialize(self, enable: bool = True, cache_dir=None, verify: bool = True, features: bool = True):
         """`PowerFlowEngine.specialize` on every device's engine (same grid: the self-test runs once, the code objects are shared
@@ -657,3 +300,195 @@ class ShardedEngine:
         for eng in self.engines:
             eng.close()
         self.engines = []
+
+
+# ---- the routing rules: each takes the name of an engine method and returns the method that forwards it ------------------------------
+def _cat(parts, axis=0):
+    """What the shards returned, joined in global lane order by the type of the first part: arrays are concatenated, tuples, lists and
+    dicts element by element, dataclasses (`LaneResults`, the state classes) field by field with the underscore fields of the first."""
+    p = parts[0] if parts else None
+    if p is None:
+        return None
+    if isinstance(p, np.ndarray):
+        return np.concatenate(parts, axis)
+    if isinstance(p, (tuple, list)):
+        return type(p)(_cat([q[i] for q in parts], axis) for i in range(len(p)))
+    if isinstance(p, dict):
+        return {key: _cat([q[key] for q in parts], axis) for key in p}
+    if is_dataclass(p):
+        names = [f.name for f in fields(p)]
+        return type(p)(**{f: getattr(p, f) if f.startswith("_") else _cat([getattr(q, f) for q in parts], axis) for f in names})
+    return np.concatenate(parts, axis)
+
+
+def every(name):
+    def method(self, *args, **kw):
+        for eng in self.engines:
+            getattr(eng, name)(*args, **kw)
+    return method
+
+
+def first(name):
+    def method(self, *args, **kw):
+        return getattr(self.engines[0], name)(*args, **kw)
+    return method
+
+
+def per_device(name):
+    def method(self, *args, **kw):
+        return [getattr(eng, name)(*args, **kw) for eng in self.engines]
+    return method
+
+
+def cut(name, by_lane=None):
+    """Whole-batch arguments: every positional or keyword argument that is not None and not a scalar is cut ``[b0:b0+bn]`` by device
+    block.  ``by_lane(n_lanes, *args, **kw) -> (args, kw)`` first brings arguments that may come flat or shared to ``[n_lanes, ...]``."""
+    def block(a, b0, bn):
+        return a if a is None or np.ndim(a) == 0 else np.asarray(a)[b0:b0 + bn]
+
+    def method(self, *args, **kw):
+        if by_lane is not None:
+            args, kw = by_lane(self.n_lanes, *args, **kw)
+        for eng, (b0, bn) in zip(self.engines, self.blocks):
+            getattr(eng, name)(*[block(a, b0, bn) for a in args], **{key: block(v, b0, bn) for key, v in kw.items()})
+    return method
+
+
+def _draws_by_lane(n_lanes, draws):
+    return (np.asarray(draws).reshape(n_lanes, -1),), {}
+
+
+def _schedule_by_lane(n_lanes, schedule, count):
+    return (np.asarray(schedule).reshape(n_lanes, -1, 2), np.broadcast_to(np.asarray(count), (n_lanes,))), {}
+
+
+def _area_schedule_by_lane(n_lanes, schedule, count):
+    sch = np.asarray(schedule)
+    if sch.ndim == 3:
+        sch = np.broadcast_to(sch, (n_lanes,) + sch.shape)
+    return (sch, np.broadcast_to(np.asarray(count), (n_lanes, sch.shape[1]))), {}
+
+
+def _episode_limit_by_lane(n_lanes, max_steps, *args, **kw):
+    if max_steps is not None and np.ndim(max_steps) > 0:
+        max_steps = np.asarray(max_steps).reshape(n_lanes)
+    return (max_steps,) + args, kw
+
+
+def _ranged(core, steps):
+    """The method ``([n_steps, step0=0,] lane0=0, n=None, *args, **kw)`` around ``core(self, head, lane0, n, args, kw)``."""
+    if steps:
+        return lambda self, n_steps, step0=0, lane0=0, n=None, *args, **kw: core(self, (n_steps, step0), lane0, n, args, kw)
+    return lambda self, lane0=0, n=None, *args, **kw: core(self, (), lane0, n, args, kw)
+
+
+def gather(name, steps=False, axis=0):
+    """A getter of the global lane range ``(lane0, n)``, after ``(n_steps, step0)`` if ``steps``: what the shards of `_parts` return
+    goes through `_cat` on ``axis``."""
+    def core(self, head, lane0, n, args, kw):
+        return _cat([getattr(eng, name)(*head, l0, k, *args, **kw) for eng, l0, k, _ in self._parts(lane0, n)], axis)
+    return _ranged(core, steps)
+
+
+def per_shard_tensor(name, keys, steps=False):
+    """A getter of the global lane range that leaves one tensor per intersecting shard on its device and returns them as a list; every
+    argument of ``keys`` (after the range, or by keyword) is None or a list with one tensor per such shard (the rows of its lanes)."""
+    label = {"out": "output", "flags": "flag"}
+
+    def core(self, head, lane0, n, args, kw):
+        if args:
+            if len(args) > len(keys) or any(key in kw for key in keys[:len(args)]):
+                raise TypeError(f"ShardedEngine.{name}: after the lane range, {' and '.join(keys)} once each")
+            kw.update(zip(keys, args))
+        parts = self._parts(lane0, n)
+        lists = {key: list(kw.pop(key)) for key in keys if kw.get(key) is not None}
+        if not lists:
+            return [getattr(eng, name)(*head, l0, k, **kw) for eng, l0, k, _ in parts]
+        if any(len(given) != len(parts) for given in lists.values()):
+            given = " / ".join(f"{len(lists.get(key, parts))} {label.get(key, key)}" for key in keys)
+            raise ValueError(f"ShardedEngine.{name}: {len(parts)} shards intersect the range, {given} tensors given")
+        return [getattr(eng, name)(*head, l0, k, **kw, **{key: given[i] for key, given in lists.items()}) for i, (eng, l0, k, _) in enumerate(parts)]
+    return _ranged(core, steps)
+
+
+def scatter(name, rows, width=None):
+    """A setter ``(rows, lane0=0)`` of the rows that start at global lane ``lane0``; ``rows`` is the engine's name of that argument.  The
+    rows are reshaped ``[-1, width]``, ``width`` being an attribute path from the sharded engine, or keep their last axis (None)."""
+    key, get_width = rows, attrgetter(width) if width else None
+
+    def method(self, rows=None, lane0=0, **kw):
+        rows = np.asarray(kw.pop(key) if rows is None else rows)
+        rows = rows.reshape(-1, get_width(self) if get_width else rows.shape[-1])
+        for eng, l0, k, off in self._parts(lane0, rows.shape[0]):
+            getattr(eng, name)(rows[off:off + k], lane0=l0, **kw)
+    return method
+
+
+def scatter_state(name):
+    """A setter ``(state, lane0=0)`` of one of the state dataclasses: every engine gets the lanes' slice of each field."""
+    def method(self, state, lane0=0, **kw):
+        names = [f.name for f in fields(state)]
+        for eng, l0, k, off in self._parts(lane0, len(getattr(state, names[0]))):
+            getattr(eng, name)(type(state)(*(getattr(state, f)[off:off + k] for f in names)), lane0=l0, **kw)
+    return method
+
+
+# ---- the table: the rule of every forwarded method (name -> the rule's parameters) ------------------------------------------------
+ROUTES = {
+    # the same call on every device: tables, rules and switches (every device holds its own copy)
+    every: dict.fromkeys((
+        "sync", "set_deterministic", "set_thermal_limits", "upload_maintenance", "upload_outage_durations", "upload_hazards", "upload_forecasts",
+        "set_gen_limits", "set_gen_renewable", "set_storage_params", "set_env_dynamics", "set_trajectory", "set_obs_clock", "set_obs_spec",
+        "lane_actions_on_device", "topo_actions_on_device", "alerts_on_device",        # each device's act_* buffers hold its own lanes
+        "set_topo_rules", "set_topo_areas", "set_topo_slots", "set_opponent_areas", "set_alerts", "set_rewards"), {}),
+    # host-side helpers that depend on the grid alone
+    first: dict.fromkeys(("pack_injections", "pack_chronics", "topo_action_areas", "alert_state_fields"), {}),
+    # one entry per device; the views are zero-copy torch tensors (global lane order = concatenation over the list)
+    per_device: dict.fromkeys(("device_views", "reward_views", "episode_views", "cursor_views", "plan"), {}),
+    # whole-batch per-lane arrays, cut by device block
+    cut: {**dict.fromkeys(("set_lane_chronics", "set_lane_redispatch", "set_lane_actions", "set_lane_curtailment", "set_lane_topo_actions",
+                           "set_lane_alerts"), {}),
+          "upload_opponent_draws": dict(by_lane=_draws_by_lane), "upload_cursor_draws": dict(by_lane=_draws_by_lane),
+          "upload_opponent_schedule": dict(by_lane=_schedule_by_lane), "upload_opponent_area_schedule": dict(by_lane=_area_schedule_by_lane),
+          "set_episode_limit": dict(by_lane=_episode_limit_by_lane)},
+    # getters of a lane range
+    gather: {**dict.fromkeys((
+        "reset", "get_injections", "get_topology", "step_outputs", "episode", "cooldown", "sub_cooldown", "last_bus", "env_state",
+        "observation_vector_host", "topo_action_flags", "topo_action_mask_host", "opponent_state", "opponent_area_state",
+        "opponent_attack_lines", "alert_state", "alert_reward", "rewards", "episode_ends", "episode_stats", "chronics_cursor_state"), {}),
+        "trajectory": dict(steps=True, axis=1), "trajectory_cooldown": dict(steps=True, axis=1), "trajectory_obs": dict(steps=True)},
+    # getters that leave their result on the devices: one tensor per shard, each on its own device and stream
+    per_shard_tensor: {"observation_vector": dict(keys=("out",)), "topo_action_mask": dict(keys=("out",)),
+                       "rewards_eval": dict(keys=("flags", "out")), "observation_trajectory": dict(keys=("out",), steps=True)},
+    # setters of the rows that start at a lane
+    scatter: {"set_injections": dict(rows="inj", width="n_inj"), "set_cooldown": dict(rows="line_cooldown", width="model.n_line"),
+              "set_overflow_count": dict(rows="counts", width="model.n_line"), "set_sub_cooldown": dict(rows="sub_cooldown", width="model.n_sub"),
+              "set_last_bus": dict(rows="last_bus", width="model.dim_topo"), "set_alert_state": dict(rows="rows")},
+    scatter_state: dict.fromkeys(("set_opponent_state", "set_opponent_area_state", "set_chronics_cursor_state"), {}),
+}
+
+# engine methods that `ShardedEngine` does not forward (calling one raises AttributeError), and why
+NOT_SHARDED = (
+    ("solve_lane", "one lane at a time: use `owner(lane)`"),
+    ("candidate_topologies", "host-side helper of `simulate_candidates`: any engine answers"),
+    ("pack_actions", "host-side helper of `simulate_batch`: any engine answers"),
+    ("ptdf_build", "one lane's table: `ptdf_build_batch` is the sharded form"),
+    ("ptdf", "reads the table of `ptdf_build`"),
+    ("ptdf_batch_info", "`ptdf_build_batch` returns the info with the shards' class offsets applied"),
+    ("ptdf_flows", "not forwarded yet: a `gather` over each device's own tables"),
+    ("ptdf_flows_rows", "not forwarded yet: its lane range comes after four other arguments"),
+    ("lodf_screen", "not forwarded yet: a `gather` whose ``cap_mw`` goes to every device"),
+    ("set_profiling", "timing is per device: use `engines[k]`"),
+    ("kernel_time", "timing is per device: use `engines[k]`"),
+    ("feature_word", "describes one engine's launch: use `engines[k]`"),
+    ("specialization_header", "describes one engine's kernels: use `engines[k]`"),
+    ("algorithmic_bytes_per_step", "a per-engine figure of the benchmark, which runs one engine per process"),
+)
+
+for _rule, _names in ROUTES.items():
+    for _name, _params in _names.items():
+        assert _name not in vars(ShardedEngine), _name
+        _method = _rule(_name, **_params)
+        _method.__name__, _method.__qualname__ = _name, f"ShardedEngine.{_name}"
+        _method.__doc__ = f"`PowerFlowEngine.{_name}` on the lanes of every device, forwarded by the rule `{_rule.__name__}`."
+        setattr(ShardedEngine, _name, _method)
