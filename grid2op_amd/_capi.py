@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "GpfCursorDesc", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "GpfCursorDesc", "GpfCombinedDesc", "library_path", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
@@ -40,11 +40,13 @@ EXPORTED_SYMBOLS = [
     "gpf_set_rewards", "gpf_get_rewards", "gpf_rewards_eval", "gpf_reward_device_pointers",
     "gpf_set_episode_limit", "gpf_get_episode_ends", "gpf_get_episode_stats", "gpf_episode_device_pointers",
     "gpf_set_chronics_cursor", "gpf_upload_cursor_draws", "gpf_get_cursor_state", "gpf_set_cursor_state", "gpf_cursor_device_pointers",
+    "gpf_set_combined_actions", "gpf_get_action_flags", "gpf_combined_device_pointers",
 ]
 N_ALERT_POINTERS = 3       # include/gridpf.h GPF_N_ALERT_POINTERS
 N_REWARD_POINTERS = 1      # include/gridpf.h GPF_N_REWARD_POINTERS
 N_EPISODE_POINTERS = 8     # include/gridpf.h GPF_N_EPISODE_POINTERS
 N_CURSOR_POINTERS = 3      # include/gridpf.h GPF_N_CURSOR_POINTERS
+N_COMBINED_POINTERS = 1    # include/gridpf.h GPF_N_COMBINED_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
 
 
@@ -105,6 +107,11 @@ class GpfCursorDesc(C.Structure):
     _fields_ = [("n_order", C.c_int32), ("order", _ip), ("policy", C.c_int32), ("cdf", _dp), ("first_row", C.c_int32), ("lane_first_row", _ip),
                 ("next_pos", C.c_int32), ("lane_next_pos", _ip), ("draw_source", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
                 ("lane_base", C.c_int32)]
+
+
+class GpfCombinedDesc(C.Structure):
+    """include/gridpf.h gpf_combined_desc"""
+    _fields_ = [("on", C.c_int32), ("check_values", C.c_int32), ("storage_max_p_prod", _fp), ("storage_max_p_absorb", _fp)]
 
 
 class GpfAlertDesc(C.Structure):
@@ -271,6 +278,9 @@ def lib() -> C.CDLL:
     L.gpf_get_cursor_state.argtypes = [h, i32, i32, _ip]
     L.gpf_set_cursor_state.argtypes = [h, i32, i32, _ip]
     L.gpf_cursor_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
+    L.gpf_set_combined_actions.argtypes = [h, C.POINTER(GpfCombinedDesc)]
+    L.gpf_get_action_flags.argtypes = [h, i32, i32, _bp]
+    L.gpf_combined_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
     L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
     L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
     L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]

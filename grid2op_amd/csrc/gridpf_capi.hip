@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "gridpf_engine.hpp"
+#include "gridpf_combined.hpp"
 #include "gridpf_redispatch.hpp"
 #include "gridpf_topo.hpp"
 #include "gridpf_topo_mask.hpp"
@@ -667,6 +668,7 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   if (e->al_on) { int rc_a = alert_reset_lanes(e, lane0, n); if (rc_a != GPF_OK) return rc_a; }
   if (e->rw_on) { int rc_r = reward_reset_lanes(e, lane0, n); if (rc_r != GPF_OK) return rc_r; }
   if (e->ep_on) { int rc_p = episode_reset_lanes(e, lane0, n); if (rc_p != GPF_OK) return rc_p; }
+  if (e->cb_on) { int rc_c = combined_reset_lanes(e, lane0, n); if (rc_c != GPF_OK) return rc_c; }
   topo_unmoved(e, lane0, n);
   HIP_TRY(hipStreamSynchronize(e->stream));
   const int init_class = topo_class_of(e, e->h_init_topo.data(), g.n_shunt ? e->h_init_shunt_bus.data() : nullptr);
@@ -1239,6 +1241,7 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
   if (e->al_on && err == hipSuccess) err = alert_copy_lanes(e, src, dst, n);
   if (e->ep_on && err == hipSuccess) err = episode_copy_lanes(e, src, dst, n);
   if (e->cur_on && err == hipSuccess) err = cursor_copy_lanes(e, src, dst, n);
+  if (e->cb_on && err == hipSuccess) err = combined_copy_lanes(e, src, dst, n);
   HIP_TRY(err);
   for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
     std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
@@ -1793,9 +1796,18 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     return fail(GPF_E_INVALID, "gpf_step_n: auto-reset in a multi-step launch while topology actions keep lanes on another topology class than "
                                "their reset topology (the launch plan cannot follow a reset inside the launch): use n_steps = 1, or send the "
                                "lanes' rows with gpf_set_topology / gpf_reset_lanes");
-  if (acts && e->env_on && (e->env_act_r || e->env_act_s || e->env_act_c))
+  const bool inj = e->env_on && (e->env_act_r || e->env_act_s || e->env_act_c);
+  const bool comb = e->cb_on && e->env_on && e->ta_on && n_steps == 1;      // combined mode (gpf_set_combined_actions): gridpf_combined.hpp
+  if (acts && inj && !e->cb_on)
     return fail(GPF_E_INVALID, "gpf_step_n: topology actions and injection actions (redispatch / storage / curtailment) are pending for the same "
-                               "launch: combined actions are not supported (in the reference the illegality of either part cancels both)");
+                               "launch: combined actions are not supported (in the reference the illegality of either part cancels both) unless "
+                               "gpf_set_combined_actions turned them on");
+  if (acts && inj && e->env_hold && e->env_act_s)
+    return fail(GPF_E_INVALID, "gpf_step_n: a held storage action (hold_storage) and topology actions are pending for the same launch: a combined "
+                               "action cannot suppress one step of a held action; send the storage power at every step");
+  if (e->cb_on && inj && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: in combined mode (gpf_set_combined_actions) a launch that carries injection actions must be a one-step "
+                               "launch (the actions are screened once, in front of the step): use n_steps = 1");
   if (e->opp_kind && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with an opponent set (gpf_set_opponent) a launch must be a one-step launch (the opponent's choice "
                                "needs the previous step's rho and line status): use n_steps = 1");
@@ -1808,9 +1820,17 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = cursor_prestep(e, t0);
     if (rc != GPF_OK) return rc;
   }
+  if (comb && inj) {                        // in front of the pre-step: the storage units' busbars before the action
+    rc = combined_screen(e, acts, e->ta_rules->on);
+    if (rc != GPF_OK) return rc;
+  }
   if (e->ta_on) {
     if (acts) { e->ta_host = e->ta_dev = false; e->dev_topo_dirty = true; }   // consumed by this launch, whatever happens below
     rc = topo_prestep(e, acts);
+    if (rc != GPF_OK) return rc;
+  }
+  if (comb && inj && acts) {                // a verdict of either part leaves no injection action (without topology actions the screen did it)
+    rc = combined_cancel(e, acts);
     if (rc != GPF_OK) return rc;
   }
   if (e->opp_kind) {                        // after the agent's action, before the step: the attack wins
@@ -1830,6 +1850,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   // lanes an action moved to another class than their reset topology's: an auto-reset puts them back, the host re-keys them (with an
   // episode limit set the truncated lanes join the list, and it is read back once, behind episode_kernel)
   const bool list_resets = e->ta_on && o->auto_reset && e->ta_n_moved > 0;
+  if (comb) {                               // a redispatch the step cancelled books nothing for the action; the step's flags
+    rc = combined_settle(e, acts, inj);
+    if (rc != GPF_OK) return rc;
+  }
   if (e->ta_on) {
     if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
     hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), *e->ta_rules,
@@ -1842,7 +1866,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     if (rc != GPF_OK) return rc;
   }
   if (e->rw_on && n_steps == 1) {           // the rewards of the step, last: on its results, done flag and flags
-    rc = reward_poststep(e, acts);
+    rc = reward_poststep(e, acts, comb);
     if (rc != GPF_OK) return rc;
   }
   if (e->ep_on) {                           // the episode's end, behind everything that reads the final step's state
@@ -1960,13 +1984,16 @@ int gpf_upload_topo_actions(gpf_handle e, int32_t n_act, const int32_t* act_off,
   int rc = topo_enable(e);
   if (rc != GPF_OK) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));                 // (a launch in flight may read the old table)
-  e->ta_off.release(); e->ta_items.release(); e->ta_amb.release();
+  e->ta_off.release(); e->ta_items.release(); e->ta_amb.release(); e->ta_sto_word.release();
   e->ta_m_off.release(); e->ta_m_line.release(); e->ta_m_sub.release(); e->ta_m_end.release(); e->ta_mask.release();
   e->ta_n_act = 0;
   if (n_act) {
     HIP_TRY(e->ta_off.upload(act_off, (size_t)n_act + 1));
     if (n_items_total) HIP_TRY(e->ta_items.upload(act_items, 3 * (size_t)n_items_total));
     HIP_TRY(e->ta_amb.upload(amb.data(), amb.size()));
+    std::vector<unsigned long long> sto_word((size_t)n_act, 0);      // the storage units every entry reconnects or moves (gridpf_combined.hpp)
+    gpf::combined_entry_words(n_act, act_off, act_items, g.n_sto, e->h_sto_pos.data(), sto_word.data());
+    HIP_TRY(e->ta_sto_word.upload(sto_word.data(), sto_word.size()));
     HIP_TRY(e->ta_m_off.upload(ms.off.data(), ms.off.size())); HIP_TRY(e->ta_m_line.upload(ms.line.data(), ms.line.size()));
     HIP_TRY(e->ta_m_sub.upload(ms.sub.data(), ms.sub.size())); HIP_TRY(e->ta_m_end.upload(ms.end.data(), ms.end.size()));
     HIP_TRY(e->ta_mask.alloc((size_t)e->cap_lanes * n_act));

@@ -59,9 +59,10 @@ int reward_prestep(gpf_engine* e) {
   return GPF_OK;
 }
 
-int reward_poststep(gpf_engine* e, bool topo_flags) {
+int reward_poststep(gpf_engine* e, bool topo_flags, bool combined) {
   gpf::RewardDev d = reward_dev(e);
-  d.topo_flags = topo_flags ? e->ta_flags.p : nullptr;
+  d.topo_flags = (topo_flags && !combined) ? e->ta_flags.p : nullptr;
+  d.step_flags = combined ? e->cb_flags.p : nullptr;        // combined mode: the flags of the whole step (gridpf_combined.hpp)
   if (e->env_on) { d.ill_now = e->env_illegal.p; d.ill_snap = e->rw_ill_snap.p; }
   if (e->ep_on) { d.ep_limit = e->ep_limit.p; d.episode = e->episode.p; }     // a step at the lane's limit is the reference's is_done
   d.reward = e->rw_out.p; d.row_stride = e->rw_n_slot;

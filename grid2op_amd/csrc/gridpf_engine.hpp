@@ -282,6 +282,14 @@ struct gpf_engine {
   DevArr<int> cur_order, cur_pos, cur_next_pos, cur_n_started, cur_draws_used, cur_flags, cur_first_row;
   DevArr<unsigned char> cur_skip;
   DevArr<double> cur_cdf, cur_draws;
+  // combined topology + injection actions (gridpf_combined.hpp, gridpf_capi_combined.hip): the step's flags [cap_lanes][4] of the last
+  // one-step launch, the screen's verdict byte and the snapshot of env_illegal between its kernels, the storage units' power limits (empty:
+  // not checked) and, uploaded with every action table, one word per entry: the storage units it reconnects or moves
+  bool cb_on = false, cb_check = false;
+  DevArr<unsigned char> cb_flags, cb_screen;
+  DevArr<int> cb_ill_snap;
+  DevArr<float> cb_max_prod, cb_max_absorb;
+  DevArr<unsigned long long> ta_sto_word;
   std::vector<char> h_lane_n1;          // 1: the lane is a contingency lane of gpf_fanout_n1 (until gpf_set_lane_chronics)
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
@@ -424,7 +432,7 @@ void alerts_off(gpf_engine* e);
 // gridpf_capi_reward.hip: the rewards' share of a one-step launch (the snapshot before the step, reward_kernel after it; topo_flags:
 // the launch carried topology actions) and of gpf_reset_lanes
 int reward_prestep(gpf_engine* e);
-int reward_poststep(gpf_engine* e, bool topo_flags);
+int reward_poststep(gpf_engine* e, bool topo_flags, bool combined = false);
 int reward_reset_lanes(gpf_engine* e, int lane0, int n);
 
 // gridpf_capi_episode.hip: episode_kernel, queued last in a one-step launch with a limit set (list_resets: truncated lanes are appended to
@@ -442,6 +450,14 @@ int cursor_prestep(gpf_engine* e, int t);
 hipError_t cursor_copy_lanes(gpf_engine* e, int src, int dst, int n);
 hipError_t cursor_mark_lanes(gpf_engine* e, int lane0, int n, int skip);
 hipError_t cursor_fetch_mirrors(gpf_engine* e);
+
+// gridpf_capi_combined.hip: the three side kernels of a one-step launch in combined mode (acts: it carries topology actions; rules_on:
+// the storage rule applies; screened: combined_screen ran in this launch) and the feature's share of gpf_reset_lanes / gpf_copy_lanes
+int combined_screen(gpf_engine* e, bool acts, int rules_on);
+int combined_cancel(gpf_engine* e, bool acts);
+int combined_settle(gpf_engine* e, bool acts, bool screened);
+int combined_reset_lanes(gpf_engine* e, int lane0, int n);
+hipError_t combined_copy_lanes(gpf_engine* e, int src, int dst, int n);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

@@ -165,6 +165,7 @@ struct RewardDev {
   const int* ill_now;                // [lanes] cancelled redispatch actions since the reset, after the step ...
   const int* ill_snap;               // ... and before it; both null: no dynamics
   const unsigned char* eval_flags;   // [n][2] the caller's flags (gpf_rewards_eval), indexed from the range's first lane, or null
+  const unsigned char* step_flags;   // [lanes][4] {illegal, ambiguous, illegal redispatch, reason} of the whole step (combined mode), or null
   const int* ep_limit;               // [lanes] episode limits (gpf_set_episode_limit), or null: off, or gpf_rewards_eval ...
   const int* episode;                // ... and the lanes' {steps survived, resets} after the step
   float* reward;                     // row of the range's first lane
@@ -187,6 +188,7 @@ __global__ __launch_bounds__(64 * RW_WPB) void reward_kernel(RewardDev d, const 
   bool illegal = false, ambiguous = false;
   if (d.topo_flags) { illegal = d.topo_flags[lane * 2] != 0; ambiguous = d.topo_flags[lane * 2 + 1] != 0; }
   if (d.ill_now) illegal = illegal || d.ill_now[lane] != d.ill_snap[lane];
+  if (d.step_flags) { illegal = illegal || d.step_flags[lane * 4] != 0 || d.step_flags[lane * 4 + 2] != 0; ambiguous = ambiguous || d.step_flags[lane * 4 + 1] != 0; }
   if (d.eval_flags) { illegal = illegal || d.eval_flags[(size_t)k * 2] != 0; ambiguous = ambiguous || d.eval_flags[(size_t)k * 2 + 1] != 0; }
   const bool truncated = d.ep_limit && episode_truncated(d.episode[lane * 2], d.ep_limit[lane], failed);
   const float* row = d.out + lane * d.n_out;

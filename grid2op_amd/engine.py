@@ -17,7 +17,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _capi
-from ._capi import GpfAlertDesc, GpfCursorDesc, GpfEpisodeDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
+from ._capi import GpfAlertDesc, GpfCombinedDesc, GpfCursorDesc, GpfEpisodeDesc, GpfRewardSlot, GpfGridDesc, GpfLayout, GpfOpponentDesc, GpfStepOpts, GridPFError, check, ptr
 from .grid_model import GridModel
 
 __all__ = ["PowerFlowEngine", "LaneResults", "GridPFError", "ST_CONVERGED", "STATUS_TEXT", "MASK_TOO_MANY_LINES", "MASK_TOO_MANY_SUBS",
@@ -1372,6 +1372,50 @@ class PowerFlowEngine:
                 "duration_reward": view(ep[3], (cap,), "<f4"), "return_running": view(ep[4], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns],
                 "return_last": view(ep[5], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns], "length_last": view(ep[6], (cap,), "<i4"),
                 "n_episodes": view(ep[7], (cap,), "<i4")}
+
+    # ---- combined topology + injection actions (include/gridpf.h gpf_set_combined_actions; grid2op_amd/csrc/gridpf_combined.hpp) ----
+    def set_combined_actions(self, on: bool = True, check_values: bool = True, storage_max_p_prod=None, storage_max_p_absorb=None):
+        """One-step launches take topology actions and injection actions (redispatch / storage / curtailment) together, lane by lane, as
+        ``BaseEnv.step`` does: a verdict on either part voids both, ``PreventDiscoStorageModif`` joins the rules, a redispatch the step
+        cancels books no cooldown.  ``check_values``: the reference's value rules on every lane of the launch (``storage_max_p_prod`` /
+        ``storage_max_p_absorb`` ``[n_storage]``: the storage range; None: not checked).  Needs `set_env_dynamics` and the acting path;
+        ``on=False`` brings the refusal of combined launches back."""
+        self._cb_on = False
+        if not on:
+            check(self._lib.gpf_set_combined_actions(self._h, None), "gpf_set_combined_actions")
+            return
+        d = GpfCombinedDesc(1, 1 if check_values else 0, None, None)
+        keep = []
+        for name, v in (("storage_max_p_prod", storage_max_p_prod), ("storage_max_p_absorb", storage_max_p_absorb)):
+            if v is not None:
+                a = np.ascontiguousarray(v, dtype=np.float32).reshape(self.model.n_storage)
+                keep.append(a)
+                setattr(d, name, ptr(a, C.c_float))
+        check(self._lib.gpf_set_combined_actions(self._h, C.byref(d)), "gpf_set_combined_actions")
+        self._cb_on = True
+
+    def action_flags(self, lane0: int = 0, n: Optional[int] = None) -> dict:
+        """``is_illegal`` / ``is_ambiguous`` / ``is_illegal_redisp`` bool ``[n]`` and ``reason`` uint8 ``[n]`` (``GPF_CB_*``) of the whole
+        step of the last one-step launch in combined mode; synchronous."""
+        if not getattr(self, "_cb_on", False):
+            raise GridPFError("action_flags: combined actions are off (set_combined_actions)")
+        lane0, n = self._range(lane0, n)
+        f = np.zeros((n, 4), np.uint8)
+        check(self._lib.gpf_get_action_flags(self._h, lane0, n, ptr(f, C.c_uint8)), "gpf_get_action_flags")
+        return dict(is_illegal=f[:, 0].astype(bool), is_ambiguous=f[:, 1].astype(bool), is_illegal_redisp=f[:, 2].astype(bool), reason=f[:, 3].copy())
+
+    def combined_views(self) -> dict:
+        """``{"flags": uint8 torch tensor [n_lanes, 4]}`` {is_illegal, is_ambiguous, is_illegal_redisp, reason} ALIASING the engine-owned
+        flags of the last one-step launch (no copy; order the reader on ``device_views()["stream"]``)."""
+        import torch
+        if not getattr(self, "_cb_on", False):
+            raise GridPFError("combined_views: combined actions are off (set_combined_actions)")
+        cp = (C.c_void_p * _capi.N_COMBINED_POINTERS)()
+        check(self._lib.gpf_combined_device_pointers(self._h, cp, _capi.N_COMBINED_POINTERS), "gpf_combined_device_pointers")
+        cap = self._lib.gpf_lane_capacity(self._h)
+        iface = {"shape": (cap, 4), "typestr": "|u1", "data": (int(cp[0]), False), "version": 2, "strides": None}
+        holder = type("_Arr", (), {"__cuda_array_interface__": iface})()
+        return {"flags": torch.as_tensor(holder, device=torch.device("cuda", self.device))[:self.n_lanes]}
 
     # ---- the chronics cursor (include/gridpf.h gpf_set_chronics_cursor; grid2op_amd/csrc/gridpf_cursor.hpp) ----
     def set_chronics_cursor(self, order=None, policy="sequential", probabilities=None, first_row=0, next_pos=None, seed=None, lane_base: int = 0):

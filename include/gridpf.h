@@ -396,8 +396,8 @@ int gpf_simulate_batch(gpf_handle h, int32_t t_obs, int32_t time_step, int32_t n
  *   - a launch that carries topology actions must be a one-step launch (GPF_E_INVALID otherwise: the line-cooldown rule needs the
  *     action step's trips and outages);
  *   - topology actions and injection actions (gpf_set_lane_actions / gpf_lane_actions_on_device / gpf_set_lane_curtailment, a held
- *     storage action included) pending for the same launch: GPF_E_INVALID.  Combined actions are out of scope: in the reference the
- *     illegality of either part cancels both, a coupling that reaches into the dynamics of the step kernel;
+ *     storage action included) pending for the same launch: GPF_E_INVALID, unless gpf_set_combined_actions (below) turned combined
+ *     actions on: in the reference the illegality of either part cancels both;
  *   - cooldown_line > 0 needs gpf_step_opts::track_cooldown on the action launch (GPF_E_INVALID otherwise): the agents' line cooldowns
  *     are counted down by the launches that maintain the line cooldowns, never by the acting path itself;
  *   - an auto-reset puts a lane an action moved to another topology class back on its reset topology: after such a one-step launch the
@@ -405,8 +405,8 @@ int gpf_simulate_batch(gpf_handle h, int32_t t_obs, int32_t time_step, int32_t n
  *     auto_reset while any lane is on a moved class is refused (GPF_E_INVALID: the plan of a launch cannot follow a reset inside it);
  *   - the pending indices are consumed by the launch that takes them, also when it fails after the pre-step (the rows may already be
  *     rewritten: reset or re-send the lanes after a failed launch);
- *   - also out of scope: the opponent, PreventDiscoStorageModif (it cannot fire on a pure topology action) and combined topology +
- *     injection actions.  RulesByArea (l2rpn_idf_2023) is covered by gpf_set_topo_areas / gpf_set_topo_slots below.
+ *   - PreventDiscoStorageModif cannot fire on a pure topology action; it is part of the combined actions of gpf_set_combined_actions.
+ *     RulesByArea (l2rpn_idf_2023) is covered by gpf_set_topo_areas / gpf_set_topo_slots below.
  * The launch planner needs every lane's topology class: the pre-step kernel lists the lanes whose class key or busbar count changed
  * and the host reads that one compact list back (skipped when no entry of the table can change a class).  The auto-reset target
  * (the rows last sent with gpf_set_topology) is not changed by an action.
@@ -821,6 +821,71 @@ int gpf_get_episode_ends(gpf_handle h, int32_t lane0, int32_t n, uint8_t* termin
 int gpf_get_episode_stats(gpf_handle h, int32_t lane0, int32_t n, double* return_running, double* return_last, int32_t* length_last,
                           int32_t* n_episodes);
 int gpf_episode_device_pointers(gpf_handle h, void** out, int32_t n);
+
+/* ---- combined topology + injection actions of the batched acting path (grid2op_amd/csrc/gridpf_combined.hpp): one action with a
+ * topology part (the table indices above) and an injection part (redispatch / storage / curtailment rows), lane by lane, in a one-step
+ * launch.  OFF by default: without this call gpf_step_n refuses such a launch and queues exactly what it queued before.  Paths relative
+ * to the reference checkout (Environment/baseEnv.py step):
+ *   1. ambiguity is tested on the whole action (Action/baseAction.py:3621-3668, _is_storage_ambiguous :3889-3927,
+ *      _is_curtailment_ambiguous :3929-3968): an ambiguous action does nothing in ALL its parts, is_ambiguous and not is_illegal.  The
+ *      injection-side rules are value rules, compared in float32 (check_values): a redispatch with |x| >= 1e-7 on a generator that is
+ *      not redispatchable, above gen_max_ramp_up, below -gen_max_ramp_down; a storage power outside [-storage_max_p_prod,
+ *      storage_max_p_absorb]; a curtailment < 0 (other than -1, "no change") or > 1, or on a generator that is not renewable;
+ *   2. the rules run in the order LookParam, PreventDiscoStorageModif, PreventReconnection (baseEnv.py:3754-3767,
+ *      Rules/DefaultRules.py:36-44); an illegal action does nothing in all its parts, is_illegal.  PreventDiscoStorageModif
+ *      (Rules/PreventDiscoStorageModif.py:39-46) fires on a storage unit whose topo_vect entry before the action is < 0 when the action
+ *      gives it a finite power with |p| >= 1e-7 and neither sets it to a busbar > 0 nor changes its bus (with gpf_set_topo_rules on = 0,
+ *      AlwaysLegal, it does not exist);
+ *   3. the surviving topology reaches the backend action (baseEnv.py:3798) before the redispatch is prepared (:3806): a redispatch the
+ *      step cancels as illegal (the case gpf_get_env_illegal counts) leaves the topology applied and books NOTHING for the action -- no
+ *      line cooldown, no substation cooldown (:3193-3201, :3373) --, is_illegal_redisp.
+ * Three side kernels (one wavefront per lane, no LDS, no atomics) around kernels that stay as they are; queue order of a one-step launch:
+ * cursor, SCREEN, topology pre-step, CANCEL, opponent, alert pre-step, reward pre-step, step, SETTLE, topology post-step, alert
+ * post-step, rewards, episode.  The screen is queued only when injection actions are pending, the cancel only when topology actions are
+ * pending too (else the screen cancels), settle in every one-step launch: three, two or one more dispatch.
+ * With check_values on the value rules hold for EVERY lane of the launch, pure injection lanes included (what makes device-written float
+ * actions safe), and so does PreventDiscoStorageModif.  A verdict rewrites the lane's rows of the pending action buffers to 0 / 0 / -1
+ * and, unless the topology part is ambiguous by its table entry, the lane's slots of act_topo to -1: both are consumed by the launch.
+ * gpf_step_n with the mode on:
+ *   - topology and injection actions pending for the same launch are accepted;
+ *   - a held storage action (hold_storage != 0) pending together with topology actions: GPF_E_INVALID (a combined action cannot suppress
+ *     one step of a held action); without topology actions a held storage action stays outside the screen;
+ *   - a launch that carries actions of either kind must be a one-step launch.
+ * The rewards (gpf_set_rewards) read the flags of the whole step.  Composite actions (gpf_set_topo_slots > 1): the screen tells a
+ * topology part that is ambiguous by ONE of its entries; a composite that is ambiguous only between its entries, on a lane where
+ * PreventDiscoStorageModif also fires, reports is_illegal where the reference reports is_ambiguous (the action is void either way).
+ * OUT OF SCOPE: held storage actions combined with topology, LIMIT_INFEASIBLE_CURTAILMENT_STORAGE_ACTION, minimum up / down times
+ * (is_illegal_reco), the value rules against prod_p injections (baseAction.py:3648-3661), anything inside multi-step launches.
+ *   gpf_set_combined_actions : needs gpf_set_env_dynamics on and the acting path enabled (GPF_E_INVALID otherwise).  NULL or on = 0: off,
+ *                   the refusal of combined launches is back.  storage_max_p_prod / storage_max_p_absorb [n_storage]: may both be NULL
+ *                   without storage units or with check_values = 0 (then the storage range is not checked).
+ *   gpf_get_action_flags : flags[n][4] {is_illegal, is_ambiguous, is_illegal_redisp, reason} of the last one-step launch in combined mode,
+ *                   merged as the reference merges them (an ambiguous action is not also illegal); reason: GPF_CB_*, the screen's rule
+ *                   before the topology part's.  gpf_get_topo_flags keeps its meaning, the topology part's own verdict (of the slots
+ *                   the screen left).  gpf_reset_lanes clears the flags, gpf_copy_lanes copies them; a lane that auto-resets keeps the
+ *                   flags of its final step, as it keeps its topology flags.
+ *   gpf_combined_device_pointers : out[0] flags uint8 [lanes][4] (lanes = gpf_lane_capacity).  n must be GPF_N_COMBINED_POINTERS.
+ * gpf_simulate_batch and gpf_fanout_n1 leave these buffers alone. */
+#define GPF_N_COMBINED_POINTERS 1
+#define GPF_CB_NONE 0
+#define GPF_CB_REDISP_FIXED_GEN 1      /* redispatch on a generator that is not redispatchable */
+#define GPF_CB_REDISP_RAMP_UP 2
+#define GPF_CB_REDISP_RAMP_DOWN 3
+#define GPF_CB_STORAGE_POWER 4         /* storage power outside the unit's range */
+#define GPF_CB_CURTAIL_RANGE 5         /* curtailment < 0 (not -1) or > 1 */
+#define GPF_CB_CURTAIL_FIXED_GEN 6     /* curtailment on a generator that is not renewable */
+#define GPF_CB_DISCO_STORAGE 7         /* PreventDiscoStorageModif */
+#define GPF_CB_TOPO_RULES 8            /* LookParam / PreventReconnection on the topology part */
+#define GPF_CB_TOPO_AMBIGUOUS 9        /* the topology part is ambiguous */
+typedef struct gpf_combined_desc {
+  int32_t on;
+  int32_t check_values;
+  const float* storage_max_p_prod;
+  const float* storage_max_p_absorb;
+} gpf_combined_desc;
+int gpf_set_combined_actions(gpf_handle h, const gpf_combined_desc* desc);
+int gpf_get_action_flags(gpf_handle h, int32_t lane0, int32_t n, uint8_t* flags);
+int gpf_combined_device_pointers(gpf_handle h, void** out, int32_t n);
 
 /* ---- the chronics cursor: each new episode starts a scenario, on the device (grid2op_amd/csrc/gridpf_cursor.hpp) ----------------------
  * What Environment.reset does to the time series (Environment/environment.py reset: chronics_handler.next_chronics(), then row 0 of the
