@@ -1,6 +1,7 @@
-// gridpf_capi.hip -- host side of libgridpf.so: the C ABI declared in include/gridpf.h (its DC sensitivity part: gridpf_capi_ptdf.hip) on
-// the engine of gridpf_engine.hpp; launches the kernels of gridpf_sparse.hpp, gridpf_topo.hpp and gridpf_redispatch.hpp.  gfx950 only; no
-// fallback path: if HIP is unavailable every entry point fails with GPF_E_DEVICE.
+// gridpf_capi.hip -- host side of libgridpf.so: the C ABI declared in include/gridpf.h on the engine of gridpf_engine.hpp: creation, the
+// lanes' lifecycle, launch planning and the launches of the kernels of gridpf_sparse.hpp and gridpf_redispatch.hpp.  The DC sensitivity
+// part and every feature of the acting step have units of their own (gridpf_capi_<feature>.hip), called here through the hooks declared
+// in gridpf_engine.hpp.  gfx950 only; no fallback path: if HIP is unavailable every entry point fails with GPF_E_DEVICE.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,10 +17,8 @@
 #include <vector>
 
 #include "gridpf_engine.hpp"
-#include "gridpf_combined.hpp"
 #include "gridpf_redispatch.hpp"
 #include "gridpf_topo.hpp"
-#include "gridpf_topo_mask.hpp"
 
 namespace gpf {
 // device-side lane utilities ------------------------------------------------------------------------------------------
@@ -115,42 +114,7 @@ __global__ void simulate_prepare_kernel(GridDev g, Bufs b, const int* __restrict
   }
 }
 
-// the environment-dynamics state of the source lane -> the scratch lane (simulate: _ObsEnv starts from the environment's own
-// _target_dispatch / _actual_dispatch / _gen_activeprod_t_redisp / storage charge / curtailment limits, Environment/_obsEnv.py)
-__global__ void simulate_env_copy_kernel(EnvDyn E, int n_gen, int n_sto, const int* __restrict__ src_lanes, int n_act, int n_dst, int dst0) {
-  const int q = blockIdx.x;
-  if (q >= n_dst) return;
-  const int src = src_lanes[q / n_act], dst = dst0 + q, tid = threadIdx.x;
-  for (int i = tid; i < n_gen; i += blockDim.x) {
-    const size_t s_ = (size_t)src * n_gen + i, d_ = (size_t)dst * n_gen + i;
-    E.target[d_] = E.target[s_]; E.actual[d_] = E.actual[s_]; E.prev_p[d_] = E.prev_p[s_]; E.already[d_] = E.already[s_]; E.limit[d_] = E.limit[s_];
-  }
-  for (int i = tid; i < n_sto; i += blockDim.x) E.charge[(size_t)dst * n_sto + i] = E.charge[(size_t)src * n_sto + i];
-  if (tid == 0) { E.amount_prev[dst] = E.amount_prev[src]; E.curt_prev[dst] = E.curt_prev[src]; E.fresh[dst] = E.fresh[src]; E.illegal[dst] = E.illegal[src]; }
-}
-
 }  // namespace gpf
-
-namespace {
-
-// Rows [lane0, lane0 + n) of a lane-major device array with `stride` elements per lane, copied on the engine's stream (asynchronous:
-// the caller synchronises).  No-op when the host pointer is null or the stride is 0.
-template <typename T>
-hipError_t rows_to_host(const gpf_engine* e, T* host, const DevArr<T>& arr, size_t stride, int lane0, int n) {
-  if (!host || stride == 0) return hipSuccess;
-  return hipMemcpyAsync(host, arr.p + (size_t)lane0 * stride, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToHost, e->stream);
-}
-template <typename T>
-hipError_t rows_to_device(const gpf_engine* e, const DevArr<T>& arr, const T* host, size_t stride, int lane0, int n) {
-  if (!host || stride == 0) return hipSuccess;
-  return hipMemcpyAsync(arr.p + (size_t)lane0 * stride, host, (size_t)n * stride * sizeof(T), hipMemcpyHostToDevice, e->stream);
-}
-// ... and rows [src, src + n) -> [dst, dst + n) of the same array
-template <typename T>
-hipError_t rows_copy(const gpf_engine* e, const DevArr<T>& arr, size_t stride, int src, int dst, int n) {
-  if (stride == 0) return hipSuccess;
-  return hipMemcpyAsync(arr.p + (size_t)dst * stride, arr.p + (size_t)src * stride, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToDevice, e->stream);
-}
 
 // the lanes' rows were sent by the host (their reset topology is their topology again)
 void topo_unmoved(gpf_engine* e, int lane0, int n) {
@@ -158,22 +122,7 @@ void topo_unmoved(gpf_engine* e, int lane0, int n) {
   for (int k = lane0; k < lane0 + n; ++k) if (e->ta_moved[k]) { e->ta_moved[k] = 0; --e->ta_n_moved; }
 }
 
-gpf::TopoDev topo_dev(const gpf_engine* e) {
-  const gpf::GridDev& g = e->g;
-  gpf::TopoDev d{};
-  d.dim_topo = g.dim_topo; d.n_line = g.n_line; d.n_sub = g.n_sub; d.n_shunt = g.n_shunt; d.n_busbar = g.n_busbar;
-  d.line_or_pos = g.line_or_pos; d.line_ex_pos = g.line_ex_pos; d.shunt_sub = g.shunt_sub;
-  d.topo = e->topo.p; d.shunt_bus = e->shunt_bus.p; d.cooldown = e->cooldown.p; d.topo0 = e->topo0.p; d.episode = e->episode.p; d.done = e->done.p;
-  return d;
-}
-
-gpf::TopoLanes topo_lanes(const gpf_engine* e) {
-  gpf::TopoLanes t{};
-  t.act = e->ta_act.p; t.sub_cd = e->ta_sub_cd.p; t.last_bus = e->ta_last_bus.p; t.flags = e->ta_flags.p; t.aff = e->ta_aff.p;
-  t.ep_snap = e->ta_ep_snap.p; t.list = e->ta_list.p; t.list_rows = e->ta_list_rows.p; t.pos_sub = e->ta_pos_sub.p; t.pos_other = e->ta_pos_other.p;
-  t.n_slot = e->ta_n_slot;
-  return t;
-}
+namespace {
 
 // number of active buses and Newton unknowns of one lane (host mirror of K1's counting)
 void count_lane(const gpf_engine* e, const int* topo, const int* shunt_bus, int& nb, int& nj, int& mb) {
@@ -543,15 +492,9 @@ int upload_params_s(gpf_engine* e, const gpf::Bufs& b, const LaunchPlan* tc, int
   hp.dcf = dcf;
   if (e->env_on) {
     gpf::EnvDyn& E = hp.env;
-    E.on = 1; E.hold_storage = e->env_hold ? 1 : 0; E.loss_on = e->env_loss_on; E.coeff = e->env_coeff; E.eps_poly = e->rd_eps; E.tol_poly = e->env_tol;
-    E.target = e->env_target.p; E.actual = e->env_actual.p; E.prev_p = e->env_prev.p; E.already = e->env_already.p; E.charge = e->env_charge.p;
-    E.amount_prev = e->env_amount_prev.p; E.fresh = e->env_fresh.p;
+    E = env_dyn(e);                          // ... and the actions this launch carries
     E.act_redisp = e->env_act_r ? e->env_act_redisp.p : nullptr; E.act_storage = e->env_act_s ? e->env_act_storage : nullptr;
-    E.limit = e->env_limit.p; E.curt_prev = e->env_curt_prev.p; E.act_curtail = e->env_act_c ? e->env_act_curtail.p : nullptr;
-    E.illegal = e->env_illegal.p;
-    E.renewable = e->env_has_ren ? e->env_renewable.p : nullptr;
-    E.pmin = e->rd_pmin.p; E.pmax = e->rd_pmax.p; E.ramp_up = e->rd_ru.p; E.ramp_down = e->rd_rd.p; E.redispatchable = e->rd_redisp.p;
-    E.Emax = e->sto_emax.p; E.Emin = e->sto_emin.p; E.loss = e->sto_loss.p; E.eff_c = e->sto_effc.p; E.eff_d = e->sto_effd.p; E.charge0 = e->sto_charge0.p;
+    E.act_curtail = e->env_act_c ? e->env_act_curtail.p : nullptr;
   }
   if (!e->d_params_s.p) HIP_TRY(e->d_params_s.alloc(1));
   if (!e->params_s_valid || std::memcmp(&hp, &e->h_params_s, sizeof(hp)) != 0) {
@@ -602,46 +545,6 @@ int drain_events(gpf_engine* e) {
   return GPF_OK;
 }
 
-// env dynamics of lanes [lane0, lane0 + n) back to the state after env.reset(): no dispatch, initial state of charge
-int reset_env_state(gpf_engine* e, int lane0, int n) {
-  const size_t ng = e->g.n_gen, ns = e->g.n_sto;
-  HIP_TRY(hipMemsetAsync(e->env_target.p + lane0 * ng, 0, n * ng * sizeof(float), e->stream));
-  HIP_TRY(hipMemsetAsync(e->env_actual.p + lane0 * ng, 0, n * ng * sizeof(float), e->stream));
-  HIP_TRY(hipMemsetAsync(e->env_prev.p + lane0 * ng, 0, n * ng * sizeof(float), e->stream));
-  HIP_TRY(hipMemsetAsync(e->env_already.p + lane0 * ng, 0, n * ng, e->stream));
-  HIP_TRY(hipMemsetAsync(e->env_amount_prev.p + lane0, 0, (size_t)n * sizeof(float), e->stream));
-  HIP_TRY(hipMemsetAsync(e->env_curt_prev.p + lane0, 0, (size_t)n * sizeof(float), e->stream));
-  HIP_TRY(hipMemsetAsync(e->env_illegal.p + lane0, 0, (size_t)n * sizeof(int), e->stream));
-  {
-    std::vector<float> ones((size_t)n * ng, 1.0f);
-    HIP_TRY(hipMemcpyAsync(e->env_limit.p + lane0 * ng, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  HIP_TRY(hipMemsetAsync(e->env_fresh.p + lane0, 1, (size_t)n, e->stream));
-  if (ns) {
-    std::vector<float> c((size_t)n * ns);
-    for (int k = 0; k < n; ++k) std::copy(e->h_charge0.begin(), e->h_charge0.end(), c.begin() + (size_t)k * ns);
-    HIP_TRY(hipMemcpyAsync(e->env_charge.p + lane0 * ns, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  return GPF_OK;
-}
-
-// acting-path state of lanes [lane0, lane0 + n) back to env.reset(): no cooldown, no pending action, last known busbar = the lanes'
-// reset topology (busbar 1 where it has an open end)
-int reset_topo_state(gpf_engine* e, int lane0, int n) {
-  const gpf::GridDev& g = e->g;
-  std::vector<int> lb((size_t)n * g.dim_topo), act((size_t)n * e->ta_n_slot, -1);
-  for (int k = 0; k < n; ++k)
-    for (int i = 0; i < g.dim_topo; ++i) lb[(size_t)k * g.dim_topo + i] = std::max(e->h_init_topo[i], 1);
-  HIP_TRY(hipMemcpyAsync(e->ta_last_bus.p + (size_t)lane0 * g.dim_topo, lb.data(), lb.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->ta_act.p + (size_t)lane0 * e->ta_n_slot, act.data(), act.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemsetAsync(e->ta_sub_cd.p + (size_t)lane0 * g.n_sub, 0, (size_t)n * g.n_sub * sizeof(int), e->stream));
-  HIP_TRY(hipMemsetAsync(e->ta_flags.p + (size_t)lane0 * 2, 0, (size_t)n * 2, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));                 // (the host vectors go out of scope)
-  return GPF_OK;
-}
-
 int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   HIP_TRY(hipSetDevice(e->device));
   const gpf::GridDev& g = e->g;
@@ -663,8 +566,8 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
   HIP_TRY(hipMemsetAsync(e->done.p + lane0, 0, (size_t)n, e->stream));
   HIP_TRY(hipMemsetAsync(e->episode.p + (size_t)lane0 * 2, 0, (size_t)n * 2 * sizeof(int), e->stream));
   HIP_TRY(hipMemsetAsync(e->status.p + (size_t)lane0 * 4, 0xFF, (size_t)n * 4 * sizeof(int), e->stream));
-  if (e->env_on) { int rc_e = reset_env_state(e, lane0, n); if (rc_e != GPF_OK) return rc_e; }
-  if (e->ta_on) { int rc_t = reset_topo_state(e, lane0, n); if (rc_t != GPF_OK) return rc_t; }
+  if (e->env_on) { int rc_e = env_reset_lanes(e, lane0, n); if (rc_e != GPF_OK) return rc_e; }
+  if (e->ta_on) { int rc_t = topo_reset_lanes(e, lane0, n); if (rc_t != GPF_OK) return rc_t; }
   if (e->al_on) { int rc_a = alert_reset_lanes(e, lane0, n); if (rc_a != GPF_OK) return rc_a; }
   if (e->rw_on) { int rc_r = reward_reset_lanes(e, lane0, n); if (rc_r != GPF_OK) return rc_r; }
   if (e->ep_on) { int rc_p = episode_reset_lanes(e, lane0, n); if (rc_p != GPF_OK) return rc_p; }
@@ -1113,10 +1016,6 @@ int gpf_set_injections(gpf_handle e, int32_t lane0, int32_t n, const double* inj
 }
 
 }  // extern "C"
-namespace {
-// gpf_set_topology.  `engine_rows`: the rows were built by the library itself in its own PINNED block (gpf_simulate_batch: validated
-// action items applied to rows that came from the device) -- no validation pass, the uploads are true asynchronous DMA and nothing is
-// waited for (the block stays untouched until the stream has drained: the next user of it synchronises first).
 // the host's bookkeeping of one lane whose topology row is now `t` / `sb` (busbar / unknown counts, topology class, mirror of the
 // sent rows); true: it changed.  gpf_set_topology and the read-back of the device-side topology actions (gpf_step_n) both use it.
 bool note_lane_row(gpf_engine* e, int lane, const int* t, const int* sb) {
@@ -1134,6 +1033,10 @@ bool note_lane_row(gpf_engine* e, int lane, const int* t, const int* sb) {
   return true;
 }
 
+namespace {
+// gpf_set_topology.  `engine_rows`: the rows were built by the library itself in its own PINNED block (gpf_simulate_batch: validated
+// action items applied to rows that came from the device) -- no validation pass, the uploads are true asynchronous DMA and nothing is
+// waited for (the block stays untouched until the stream has drained: the next user of it synchronises first).
 int set_topology_rows(gpf_engine* e, int32_t lane0, int32_t n, const int32_t* topo, const int32_t* shunt_bus, bool engine_rows) {
   const gpf::GridDev& g = e->g;
   if (!engine_rows) {
@@ -1228,15 +1131,8 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
   cp(e->shunt_bus_out, g.n_shunt); cp(e->line_status, g.n_line); cp(e->status, 4); cp(e->bus_vm, g.nb_tot); cp(e->bus_va, g.nb_tot);
   cp(e->overflow_count, g.n_line); cp(e->cooldown, g.n_line); cp(e->disc_round, g.n_line); cp(e->rho, g.n_line); cp(e->topo0, g.dim_topo);
   cp(e->done, 1); cp(e->episode, 2);
-  if (e->env_on) {          // the environment's injection dynamics are part of the lane's state (Backend.copy / env.copy keep them)
-    cp(e->env_target, g.n_gen); cp(e->env_actual, g.n_gen); cp(e->env_prev, g.n_gen); cp(e->env_already, g.n_gen); cp(e->env_limit, g.n_gen);
-    cp(e->env_charge, g.n_sto); cp(e->env_amount_prev, 1); cp(e->env_curt_prev, 1); cp(e->env_fresh, 1); cp(e->env_illegal, 1);
-  }
-  if (e->ta_on) {                           // the acting path's state
-    cp(e->ta_sub_cd, g.n_sub); cp(e->ta_last_bus, g.dim_topo); cp(e->ta_flags, 2); cp(e->ta_act, e->ta_n_slot);
-    HIP_TRY(err);
-    for (int k = 0; k < n; ++k) { e->ta_n_moved += e->ta_moved[src + k] - e->ta_moved[dst + k]; e->ta_moved[dst + k] = e->ta_moved[src + k]; }
-  }
+  if (e->env_on && err == hipSuccess) err = env_copy_lanes(e, src, dst, n);
+  if (e->ta_on && err == hipSuccess) err = topo_copy_lanes(e, src, dst, n);
   if (e->opp_kind && err == hipSuccess) err = opponent_copy_lanes(e, src, dst, n);
   if (e->al_on && err == hipSuccess) err = alert_copy_lanes(e, src, dst, n);
   if (e->ep_on && err == hipSuccess) err = episode_copy_lanes(e, src, dst, n);
@@ -1262,16 +1158,9 @@ int gpf_fanout_n1(gpf_handle e, int32_t src, int32_t dst0, int32_t n_out, const 
   if (e->env_on) {                          // the contingency lanes start from the source's injection dynamics
     if (e->sim_src.n < 1) HIP_TRY(e->sim_src.alloc(1));
     HIP_TRY(hipMemcpyAsync(e->sim_src.p, &src, sizeof(int), hipMemcpyHostToDevice, e->stream));
-    gpf::EnvDyn E{};
-    E.target = e->env_target.p; E.actual = e->env_actual.p; E.prev_p = e->env_prev.p; E.already = e->env_already.p; E.charge = e->env_charge.p;
-    E.amount_prev = e->env_amount_prev.p; E.fresh = e->env_fresh.p; E.limit = e->env_limit.p; E.curt_prev = e->env_curt_prev.p; E.illegal = e->env_illegal.p;
-    hipLaunchKernelGGL(gpf::simulate_env_copy_kernel, dim3((unsigned)n_out), dim3(64), 0, e->stream, E, e->g.n_gen, e->g.n_sto, e->sim_src.p, n_out, n_out, dst0);
-    HIP_TRY(hipGetLastError());
+    int rc_e = env_copy_from(e, e->sim_src.p, n_out, n_out, dst0); if (rc_e != GPF_OK) return rc_e;
   }
-  if (e->ta_on) {                           // ... and its acting-path state (cooldowns, last known busbars)
-    hipLaunchKernelGGL(gpf::topo_fanout_kernel, dim3((unsigned)n_out), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), src, dst0, n_out);
-    HIP_TRY(hipGetLastError());
-  }
+  if (e->ta_on) { int rc_t = topo_fanout_lanes(e, src, dst0, n_out); if (rc_t != GPF_OK) return rc_t; }   // ... and its acting-path state
   if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, dst0, n_out, 1));     // contingency lanes start no scenario of their own
   std::fill_n(e->h_lane_n1.begin() + dst0, n_out, 1);
   HIP_TRY(hipStreamSynchronize(e->stream));   // out_lines may be reused by the caller
@@ -1672,78 +1561,6 @@ void apply_topo_action(const gpf_engine* e, int* row, int* sb, const int* last, 
   const gpf::TopoMaps m{e->h_line_or_pos.data(), e->h_line_ex_pos.data(), e->g.n_line};
   gpf::apply_topo_action(m, row, sb, last, items, n_items, or_before.data(), ex_before.data(), 0, 1, gpf::NoSync{});
 }
-
-int topo_readback(gpf_engine* e, bool moved);
-
-// composite actions (more than one slot) or limits per area: the pre-step runs its GEN instantiation
-bool topo_general(const gpf_engine* e) { return e->ta_n_slot > 1 || e->ta_n_area > 0; }
-
-// dynamic LDS of the pre-step kernel for a setting of slots / areas / gathered items
-size_t topo_prestep_lds_bytes(const gpf_engine* e, int n_slot, int n_area, int max_items) {
-  const gpf::GridDev& g = e->g;
-  return gpf::topo_prestep_lds_ints(g.dim_topo, g.n_line, g.n_sub, g.n_shunt, g.n_busbar, (n_slot > 1 || n_area > 0) ? max_items : -1) * sizeof(int);
-}
-
-// items of the longest composite of a table: n_slot times its longest entry (one index may sit in several slots of a lane)
-int topo_max_items(int n_act, const int* act_off, int n_slot) {
-  int longest = 0;
-  for (int k = 0; k < n_act; ++k) longest = std::max(longest, act_off[k + 1] - act_off[k]);
-  return n_slot * longest;
-}
-
-// Steps 1-4 of the acting path on the device (topo_prestep_kernel), then the host's planning bookkeeping of the lanes it moved to another
-// topology class or busbar count: ONE compact read-back (count, lane ids, rows), skipped when the table cannot move a lane.
-int topo_prestep(gpf_engine* e, bool acts) {
-  const gpf::GridDev& g = e->g;
-  const bool readback = acts && g.n_busbar >= 2 && (e->ta_bus_items || e->ta_may_split);
-  if (acts) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
-  const gpf::TopoTab tab{e->ta_off.p, e->ta_items.p, e->ta_amb.p, e->ta_n_act};
-  const bool gen = topo_general(e);          // composite actions or areas: the GEN instantiation; else the kernel of one entry per lane
-  const gpf::TopoComp comp{e->ta_n_area ? e->ta_sub_area.p : nullptr, e->ta_n_area, e->ta_max_items};
-  const size_t lds = acts ? topo_prestep_lds_bytes(e, e->ta_n_slot, e->ta_n_area, e->ta_max_items) : 0;
-  hipLaunchKernelGGL(gen ? gpf::topo_prestep_kernel<true> : gpf::topo_prestep_kernel<false>, dim3((unsigned)e->n_lanes), dim3(64), lds, e->stream,
-                     topo_dev(e), tab, topo_lanes(e), *e->ta_rules, comp, e->n_lanes, acts ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  if (!readback) return GPF_OK;
-  return topo_readback(e, true);
-}
-
-// The compact list the topology kernels left in ta_list / ta_list_rows (count, lane ids, rows) -> the host's per-lane planning bookkeeping
-// (note_lane_row: what gpf_set_topology does).  moved: the rows are action results (the lane's class may differ from its reset
-// topology's); else they are reset topologies (the lane is back on the class of the rows last sent).
-int topo_readback(gpf_engine* e, bool moved) {
-  const gpf::GridDev& g = e->g;
-  const size_t w = (size_t)g.dim_topo + g.n_shunt;
-  const size_t need = 1 + (size_t)e->n_lanes + (size_t)e->n_lanes * w;
-  if (e->ta_pin.n < need) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(e->ta_pin.reserve(need));
-  }
-  HIP_TRY(hipMemcpyAsync(e->ta_pin.p, e->ta_list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int cnt = e->ta_pin.p[0];
-  if (cnt <= 0) return GPF_OK;
-  if (cnt > e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back count)");
-  int* ids = e->ta_pin.p + 1;
-  int* rows = ids + e->n_lanes;
-  HIP_TRY(hipMemcpyAsync(ids, e->ta_list.p + 1, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(rows, e->ta_list_rows.p, (size_t)cnt * w * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  std::vector<int> order(cnt);                           // lane order: classes are created in the order gpf_set_topology would create them
-  for (int i = 0; i < cnt; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [ids](int a, int b) { return ids[a] < ids[b]; });
-  bool changed = false;
-  for (int i : order) {
-    const int lane = ids[i];
-    if (lane < 0 || lane >= e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back lane)");
-    const int* t = rows + (size_t)i * w;
-    changed |= note_lane_row(e, lane, t, g.n_shunt ? t + g.dim_topo : nullptr);
-    if (moved && !e->ta_moved[lane]) { e->ta_moved[lane] = 1; ++e->ta_n_moved; }
-    if (!moved && e->ta_moved[lane]) { e->ta_moved[lane] = 0; --e->ta_n_moved; }
-  }
-  if (changed) e->plan_valid = false;
-  return GPF_OK;
-}
 }  // namespace
 extern "C" {
 
@@ -1789,7 +1606,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if (acts && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: a launch that carries topology actions must be a one-step launch (the line-cooldown rule needs the "
                                "action step's trips and outages): use n_steps = 1");
-  if (acts && e->ta_rules->cd_line > 0 && !o->track_cooldown)
+  if (acts && e->ta_rules.cd_line > 0 && !o->track_cooldown)
     return fail(GPF_E_INVALID, "gpf_step_n: topology actions with cooldown_line > 0 need gpf_step_opts::track_cooldown (the agents' line "
                                "cooldowns are only counted down by a launch that maintains the line cooldowns)");
   if (e->ta_on && e->ta_n_moved > 0 && o->auto_reset && n_steps != 1)
@@ -1821,7 +1638,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     if (rc != GPF_OK) return rc;
   }
   if (comb && inj) {                        // in front of the pre-step: the storage units' busbars before the action
-    rc = combined_screen(e, acts, e->ta_rules->on);
+    rc = combined_screen(e, acts, e->ta_rules.on);
     if (rc != GPF_OK) return rc;
   }
   if (e->ta_on) {
@@ -1854,11 +1671,9 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = combined_settle(e, acts, inj);
     if (rc != GPF_OK) return rc;
   }
-  if (e->ta_on) {
-    if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
-    hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), *e->ta_rules,
-                       e->n_lanes, acts ? 1 : 0, n_steps, list_resets ? 1 : 0);
-    HIP_TRY(hipGetLastError());
+  if (e->ta_on) {                           // the cooldowns and last known busbars the step leaves
+    rc = topo_poststep(e, acts, n_steps, list_resets);
+    if (rc != GPF_OK) return rc;
     if (list_resets && !e->ep_on) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
   }
   if (e->al_on) {                           // the reward of the step, on its done flag
@@ -1883,474 +1698,6 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     if (!e->env_hold) e->env_act_s = false;
     e->env_act_c = false;                   // (the curtailment limits live on in the lanes' state)
   }
-  return GPF_OK;
-}
-
-}  // extern "C"
-namespace {
-constexpr size_t TOPO_LDS_LIMIT = 64 * 1024;      // LDS of one workgroup
-
-// substation of every topo_vect position (host; a header-only handle needs no more)
-void topo_host_maps(gpf_engine* e) {
-  const gpf::GridDev& g = e->g;
-  if (!e->h_ta_pos_sub.empty()) return;
-  std::vector<int> pos_sub(g.dim_topo, 0);
-  for (int l = 0; l < g.n_line; ++l) { pos_sub[e->h_line_or_pos[l]] = e->h_line_or_sub[l]; pos_sub[e->h_line_ex_pos[l]] = e->h_line_ex_sub[l]; }
-  for (int i = 0; i < g.n_gen; ++i) pos_sub[e->h_gen_pos[i]] = e->h_gen_sub[i];
-  for (int i = 0; i < g.n_load; ++i) pos_sub[e->h_load_pos[i]] = e->h_load_sub[i];
-  for (int i = 0; i < g.n_sto; ++i) pos_sub[e->h_sto_pos[i]] = e->h_sto_sub[i];
-  e->h_ta_pos_sub = pos_sub;
-}
-
-gpf::TopoMaskGrid topo_mask_grid(const gpf_engine* e) {
-  return gpf::TopoMaskGrid{e->g.dim_topo, e->g.n_line, e->g.n_sub, e->h_line_or_pos.data(), e->h_line_ex_pos.data(), e->h_ta_pos_sub.data()};
-}
-
-// the acting path's buffers + static maps, once per engine (lanes start as after gpf_reset_lanes)
-int topo_enable(gpf_engine* e) {
-  if (e->ta_on) return GPF_OK;
-  const gpf::GridDev& g = e->g;
-  const size_t lds = gpf::topo_prestep_lds_ints(g.dim_topo, g.n_line, g.n_sub, g.n_shunt, g.n_busbar) * sizeof(int);
-  if (lds > TOPO_LDS_LIMIT) return fail(GPF_E_CAPACITY, "topology actions: the grid's rows do not fit the 64 KiB of LDS of the pre-step kernel");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t cap = (size_t)e->cap_lanes;
-  std::vector<int> pos_other(g.dim_topo, -1);
-  for (int l = 0; l < g.n_line; ++l) { pos_other[e->h_line_or_pos[l]] = e->h_line_ex_pos[l]; pos_other[e->h_line_ex_pos[l]] = e->h_line_or_pos[l]; }
-  topo_host_maps(e);
-  HIP_TRY(e->ta_pos_sub.upload(e->h_ta_pos_sub.data(), e->h_ta_pos_sub.size()));
-  HIP_TRY(e->ta_pos_other.upload(pos_other.data(), pos_other.size()));
-  if (e->ta_n_area) HIP_TRY(e->ta_sub_area.upload(e->h_ta_sub_area.data(), e->h_ta_sub_area.size()));
-  HIP_TRY(e->ta_act.alloc(cap * e->ta_n_slot)); HIP_TRY(e->ta_sub_cd.alloc(cap * g.n_sub)); HIP_TRY(e->ta_last_bus.alloc(cap * g.dim_topo));
-  HIP_TRY(e->ta_ep_snap.alloc(cap)); HIP_TRY(e->ta_list.alloc(cap + 1)); HIP_TRY(e->ta_list_rows.alloc(cap * ((size_t)g.dim_topo + g.n_shunt)));
-  HIP_TRY(e->ta_flags.alloc(cap * 2)); HIP_TRY(e->ta_aff.alloc(cap * ((size_t)g.n_line + g.n_sub)));
-  HIP_TRY(hipMemsetAsync(e->ta_aff.p, 0, cap * ((size_t)g.n_line + g.n_sub), e->stream));
-  e->ta_moved.assign(cap, 0);
-  e->ta_n_moved = 0;
-  e->ta_rules = std::make_unique<gpf::TopoRules>();
-  e->ta_on = true;
-  for (int v : e->h_init_topo) e->ta_may_split |= v >= 2;
-  return reset_topo_state(e, 0, (int)cap);
-}
-}  // namespace
-extern "C" {
-
-int gpf_set_topo_rules(gpf_handle e, int32_t on, int32_t max_sub_changed, int32_t max_line_status_changed, int32_t cooldown_sub,
-                       int32_t cooldown_line) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_topo_rules: null");
-  if (max_sub_changed < 0 || max_line_status_changed < 0 || cooldown_sub < 0 || cooldown_line < 0)
-    return fail(GPF_E_INVALID, "gpf_set_topo_rules: negative parameter");
-  if (e->ta_n_area && on && (max_sub_changed > gpf::TM_AREA_MAX_LIMIT || max_line_status_changed > gpf::TM_AREA_MAX_LIMIT))
-    return fail(GPF_E_INVALID, "gpf_set_topo_rules: with areas set (gpf_set_topo_areas) the two limits must not exceed 254 (8-bit per-area counters)");
-  int rc = topo_enable(e);
-  if (rc != GPF_OK) return rc;
-  *e->ta_rules = gpf::TopoRules{on ? 1 : 0, max_sub_changed, max_line_status_changed, cooldown_sub, cooldown_line};
-  return GPF_OK;
-}
-
-int gpf_upload_topo_actions(gpf_handle e, int32_t n_act, const int32_t* act_off, const int32_t* act_items, uint8_t* ambiguous) {
-  if (!e || n_act < 0 || (n_act > 0 && !act_off)) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad arguments");
-  const gpf::GridDev& g = e->g;
-  const int n_items_total = n_act ? act_off[n_act] : 0;
-  if (n_act && (act_off[0] != 0 || (n_items_total > 0 && !act_items))) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action offsets");
-  for (int k = 0; k < n_act; ++k) if (act_off[k + 1] < act_off[k]) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action offsets");
-  bool bus_items = false;
-  for (int q = 0; q < n_items_total; ++q) {                  // (the validation of gpf_simulate_batch)
-    const int kind = act_items[3 * q], id = act_items[3 * q + 1], v = act_items[3 * q + 2];
-    const bool pos_kind = kind == GPF_ACT_SET_BUS || kind == GPF_ACT_CHANGE_BUS, line_kind = kind == GPF_ACT_SET_LINE_STATUS || kind == GPF_ACT_CHANGE_LINE_STATUS;
-    if (!(pos_kind || line_kind || kind == GPF_ACT_SET_SHUNT_BUS) || id < 0 || (pos_kind && id >= g.dim_topo) || (line_kind && id >= g.n_line) ||
-        (kind == GPF_ACT_SET_SHUNT_BUS && id >= g.n_shunt) || ((kind == GPF_ACT_SET_BUS || kind == GPF_ACT_SET_SHUNT_BUS) && (v < -1 || v > g.n_busbar)) ||
-        (kind == GPF_ACT_CHANGE_BUS && g.n_busbar != 2))
-      return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action item (kind, id or bus; change_bus needs exactly 2 busbars per substation)");
-    bus_items |= kind == GPF_ACT_CHANGE_BUS || kind == GPF_ACT_SET_SHUNT_BUS || (kind == GPF_ACT_SET_BUS && v != 0);
-  }
-  const int max_items = topo_max_items(n_act, act_off, e->ta_n_slot);
-  if (topo_prestep_lds_bytes(e, e->ta_n_slot, e->ta_n_area, max_items) > TOPO_LDS_LIMIT)
-    return fail(GPF_E_INVALID, "gpf_upload_topo_actions: the gathered item list (gpf_set_topo_slots times the table's longest entry) does not fit "
-                               "the 64 KiB of LDS of the pre-step kernel");
-  topo_host_maps(e);
-  // static ambiguity of every entry and the static summary the legality masks are evaluated from (gridpf_topo_mask.hpp)
-  std::vector<unsigned char> amb((size_t)n_act, 0);
-  const gpf::TopoMaskGrid mg = topo_mask_grid(e);
-  gpf::topo_static_ambiguity(mg, n_act, act_off, act_items, amb.data());
-  gpf::TopoMaskSummary ms;
-  if (!gpf::build_topo_mask_summary(mg, n_act, act_off, act_items, amb.data(), ms, e->ta_n_area ? e->h_ta_sub_area.data() : nullptr))
-    return fail(GPF_E_CAPACITY, "gpf_upload_topo_actions: more than 2^20 - 1 lines or substations (the summary words of the legality masks)");
-  if (e->dry) {                                             // header-only handle: the table on the host (gpf_get_topo_action_areas)
-    e->h_ta_off.assign(act_off, act_off + (n_act ? n_act + 1 : 0)); e->h_ta_items.assign(act_items, act_items + 3 * (size_t)n_items_total);
-    e->h_ta_amb = amb; e->ta_n_act = n_act; e->ta_max_items = max_items;
-    if (ambiguous) std::memcpy(ambiguous, amb.data(), amb.size());
-    return GPF_OK;
-  }
-  int rc = topo_enable(e);
-  if (rc != GPF_OK) return rc;
-  HIP_TRY(hipStreamSynchronize(e->stream));                 // (a launch in flight may read the old table)
-  e->ta_off.release(); e->ta_items.release(); e->ta_amb.release(); e->ta_sto_word.release();
-  e->ta_m_off.release(); e->ta_m_line.release(); e->ta_m_sub.release(); e->ta_m_end.release(); e->ta_mask.release();
-  e->ta_n_act = 0;
-  if (n_act) {
-    HIP_TRY(e->ta_off.upload(act_off, (size_t)n_act + 1));
-    if (n_items_total) HIP_TRY(e->ta_items.upload(act_items, 3 * (size_t)n_items_total));
-    HIP_TRY(e->ta_amb.upload(amb.data(), amb.size()));
-    std::vector<unsigned long long> sto_word((size_t)n_act, 0);      // the storage units every entry reconnects or moves (gridpf_combined.hpp)
-    gpf::combined_entry_words(n_act, act_off, act_items, g.n_sto, e->h_sto_pos.data(), sto_word.data());
-    HIP_TRY(e->ta_sto_word.upload(sto_word.data(), sto_word.size()));
-    HIP_TRY(e->ta_m_off.upload(ms.off.data(), ms.off.size())); HIP_TRY(e->ta_m_line.upload(ms.line.data(), ms.line.size()));
-    HIP_TRY(e->ta_m_sub.upload(ms.sub.data(), ms.sub.size())); HIP_TRY(e->ta_m_end.upload(ms.end.data(), ms.end.size()));
-    HIP_TRY(e->ta_mask.alloc((size_t)e->cap_lanes * n_act));
-    HIP_TRY(hipMemset(e->ta_mask.p, 0, (size_t)e->cap_lanes * n_act));
-    e->ta_n_act = n_act;
-  }
-  e->h_ta_off.assign(act_off, act_off + (n_act ? n_act + 1 : 0)); e->h_ta_items.assign(act_items, act_items + 3 * (size_t)n_items_total);
-  e->h_ta_amb = amb; e->ta_max_items = max_items;
-  e->ta_bus_items = bus_items;
-  for (int q = 0; q < n_items_total; ++q)
-    e->ta_may_split |= (act_items[3 * q] == GPF_ACT_SET_BUS && act_items[3 * q + 2] >= 2) || act_items[3 * q] == GPF_ACT_CHANGE_BUS;
-  if (ambiguous) std::memcpy(ambiguous, amb.data(), amb.size());
-  return GPF_OK;
-}
-
-int gpf_set_lane_topo_actions(gpf_handle e, const int32_t* index) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_lane_topo_actions: null");
-  if (!index) { e->ta_host = false; return GPF_OK; }
-  int rc = topo_enable(e);
-  if (rc != GPF_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->ta_act.p, index, (size_t)e->n_lanes * e->ta_n_slot * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));                 // (the caller may reuse `index`)
-  e->ta_host = true;
-  return GPF_OK;
-}
-
-int gpf_topo_actions_on_device(gpf_handle e, int32_t on) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_topo_actions_on_device: null");
-  int rc = topo_enable(e);
-  if (rc != GPF_OK) return rc;
-  e->ta_dev = on != 0;
-  return GPF_OK;
-}
-
-int gpf_set_topo_areas(gpf_handle e, int32_t n_area, const int32_t* sub_area) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_topo_areas: null");
-  const gpf::GridDev& g = e->g;
-  if (n_area < 0) return fail(GPF_E_INVALID, "gpf_set_topo_areas: negative number of areas");
-  if (n_area == 0 || !sub_area) n_area = 0;
-  if (n_area > gpf::TM_MAX_AREAS) return fail(GPF_E_INVALID, "gpf_set_topo_areas: at most 16 areas");
-  std::vector<int> area, seen((size_t)n_area, 0);
-  if (n_area) {
-    area.assign(sub_area, sub_area + g.n_sub);
-    for (int v : area) {
-      if (v < 0 || v >= n_area) return fail(GPF_E_INVALID, "gpf_set_topo_areas: a substation's area is outside [0, n_area)");
-      seen[v] = 1;
-    }
-    for (int k = 0; k < n_area; ++k) if (!seen[k]) return fail(GPF_E_INVALID, "gpf_set_topo_areas: an area holds no substation");
-    if (e->ta_rules && e->ta_rules->on && (e->ta_rules->max_sub > gpf::TM_AREA_MAX_LIMIT || e->ta_rules->max_line > gpf::TM_AREA_MAX_LIMIT))
-      return fail(GPF_E_INVALID, "gpf_set_topo_areas: the limits of gpf_set_topo_rules exceed 254 (8-bit per-area counters)");
-    if (topo_prestep_lds_bytes(e, e->ta_n_slot, n_area, e->ta_max_items) > TOPO_LDS_LIMIT)
-      return fail(GPF_E_INVALID, "gpf_set_topo_areas: the pre-step kernel's rows do not fit the 64 KiB of LDS of a workgroup");
-  }
-  topo_host_maps(e);
-  // the static areas in the summary of an uploaded table are re-derived
-  gpf::TopoMaskSummary ms;
-  const bool table = e->ta_n_act > 0;
-  if (table && !gpf::build_topo_mask_summary(topo_mask_grid(e), e->ta_n_act, e->h_ta_off.data(), e->h_ta_items.data(), e->h_ta_amb.data(), ms,
-                                             n_area ? area.data() : nullptr))
-    return fail(GPF_E_CAPACITY, "gpf_set_topo_areas: internal (summary)");
-  if (!e->dry) {
-    int rc = topo_enable(e);
-    if (rc != GPF_OK) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));               // (a launch in flight may read the old areas)
-    if (n_area) HIP_TRY(e->ta_sub_area.upload(area.data(), area.size())); else e->ta_sub_area.release();
-    if (table) { HIP_TRY(e->ta_m_line.upload(ms.line.data(), ms.line.size())); HIP_TRY(e->ta_m_sub.upload(ms.sub.data(), ms.sub.size())); }
-  }
-  e->h_ta_sub_area = area;
-  e->ta_n_area = n_area;
-  return GPF_OK;
-}
-
-int gpf_set_topo_slots(gpf_handle e, int32_t n_slot) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_topo_slots: null");
-  if (n_slot < 1 || n_slot > 8) return fail(GPF_E_INVALID, "gpf_set_topo_slots: n_slot must be 1..8");
-  const int max_items = e->ta_n_act ? topo_max_items(e->ta_n_act, e->h_ta_off.data(), n_slot) : 0;
-  if (topo_prestep_lds_bytes(e, n_slot, e->ta_n_area, max_items) > TOPO_LDS_LIMIT)
-    return fail(GPF_E_INVALID, "gpf_set_topo_slots: the gathered item list (n_slot times the table's longest entry) does not fit the 64 KiB of LDS "
-                               "of the pre-step kernel");
-  if (!e->dry) {
-    int rc = topo_enable(e);
-    if (rc != GPF_OK) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (n_slot != e->ta_n_slot) {                           // a buffer of the new shape, all slots empty: pending indices are dropped
-      std::vector<int> none((size_t)e->cap_lanes * n_slot, -1);
-      HIP_TRY(e->ta_act.upload(none.data(), none.size()));
-      e->ta_host = e->ta_dev = false;
-    }
-  }
-  e->ta_n_slot = n_slot;
-  e->ta_max_items = max_items;
-  return GPF_OK;
-}
-
-int gpf_get_topo_action_areas(gpf_handle e, uint32_t* areas) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_get_topo_action_areas: null");
-  if (e->ta_n_act == 0) return fail(GPF_E_INVALID, "gpf_get_topo_action_areas: no action table (gpf_upload_topo_actions)");
-  if (!areas) return fail(GPF_E_INVALID, "gpf_get_topo_action_areas: null output");
-  gpf::topo_action_areas(topo_mask_grid(e), e->ta_n_act, e->h_ta_off.data(), e->h_ta_items.data(), e->ta_n_area ? e->h_ta_sub_area.data() : nullptr,
-                         e->g.n_shunt ? e->h_shunt_sub.data() : nullptr, areas);
-  return GPF_OK;
-}
-}  // extern "C"
-namespace {
-// the acting path's row accessors below: argument checks (the first call allocates the acting path's buffers), one row range, a
-// synchronisation (the caller may reuse its array at once)
-template <typename T>
-int topo_rows(gpf_engine* e, DevArr<T>& arr, size_t stride, int lane0, int n, T* get, const T* set, const char* who) {
-  if (!check_range(e, lane0, n) || (!get && !set && n)) return fail(GPF_E_INVALID, std::string(who) + ": bad range");
-  int rc = topo_enable(e);
-  if (rc != GPF_OK || n == 0) return rc;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(rows_to_host(e, get, arr, stride, lane0, n));
-  HIP_TRY(rows_to_device(e, arr, set, stride, lane0, n));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-}  // namespace
-extern "C" {
-
-int gpf_get_sub_cooldown(gpf_handle e, int32_t lane0, int32_t n, int32_t* sub_cooldown) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_get_sub_cooldown: null");
-  return topo_rows<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, sub_cooldown, nullptr, "gpf_get_sub_cooldown");
-}
-int gpf_set_sub_cooldown(gpf_handle e, int32_t lane0, int32_t n, const int32_t* sub_cooldown) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_sub_cooldown: null");
-  if (sub_cooldown) for (size_t i = 0; i < (size_t)std::max(n, 0) * e->g.n_sub; ++i)
-    if (sub_cooldown[i] < 0) return fail(GPF_E_INVALID, "gpf_set_sub_cooldown: negative cooldown");
-  return topo_rows<int>(e, e->ta_sub_cd, e->g.n_sub, lane0, n, nullptr, sub_cooldown, "gpf_set_sub_cooldown");
-}
-int gpf_get_last_bus(gpf_handle e, int32_t lane0, int32_t n, int32_t* last_bus) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_get_last_bus: null");
-  return topo_rows<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, last_bus, nullptr, "gpf_get_last_bus");
-}
-int gpf_set_last_bus(gpf_handle e, int32_t lane0, int32_t n, const int32_t* last_bus) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_last_bus: null");
-  if (last_bus) for (size_t i = 0; i < (size_t)std::max(n, 0) * e->g.dim_topo; ++i) {
-    if (last_bus[i] < 1 || last_bus[i] > e->g.n_busbar) return fail(GPF_E_INVALID, "gpf_set_last_bus: busbars must be 1..n_busbar");
-    e->ta_may_split |= last_bus[i] >= 2;
-  }
-  return topo_rows<int>(e, e->ta_last_bus, e->g.dim_topo, lane0, n, nullptr, last_bus, "gpf_set_last_bus");
-}
-int gpf_get_topo_flags(gpf_handle e, int32_t lane0, int32_t n, uint8_t* flags) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_get_topo_flags: null");
-  return topo_rows<unsigned char>(e, e->ta_flags, 2, lane0, n, flags, nullptr, "gpf_get_topo_flags");
-}
-
-int gpf_topo_action_mask(gpf_handle e, int32_t lane0, int32_t n, uint8_t* out_dev, int64_t row_stride) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_topo_action_mask: null");
-  if (e->dry) return fail(GPF_E_INVALID, "gpf_topo_action_mask: header-only handle");
-  if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_topo_action_mask: bad lane range");
-  if (!e->ta_on || e->ta_n_act == 0) return fail(GPF_E_INVALID, "gpf_topo_action_mask: no action table (gpf_upload_topo_actions)");
-  if (out_dev && row_stride < e->ta_n_act) return fail(GPF_E_INVALID, "gpf_topo_action_mask: row_stride is smaller than the table's number of entries");
-  if (n == 0) return GPF_OK;
-  const gpf::GridDev& g = e->g;
-  const size_t lds = (2 * (size_t)gpf::tm_words(g.n_line) + gpf::tm_words(g.n_sub)) * sizeof(unsigned long long);
-  if (lds > 64 * 1024) return fail(GPF_E_CAPACITY, "gpf_topo_action_mask: the grid's line and substation bit sets do not fit 64 KiB of LDS");
-  HIP_TRY(hipSetDevice(e->device));
-  const gpf::TopoMaskTab tab{e->ta_m_off.p, e->ta_m_line.p, e->ta_m_sub.p, e->ta_m_end.p, e->ta_amb.p, e->ta_n_act};
-  const gpf::TopoMaskLanes s{e->topo.p, e->cooldown.p, e->ta_sub_cd.p, e->line_or_pos.p, e->line_ex_pos.p, g.dim_topo, g.n_line, g.n_sub};
-  const gpf::TopoRules& r = *e->ta_rules;
-  unsigned char* dst = out_dev ? out_dev : e->ta_mask.p + (size_t)lane0 * e->ta_n_act;
-  const unsigned chunks = (unsigned)std::min((e->ta_n_act + gpf::TM_CHUNK - 1) / gpf::TM_CHUNK, 65535);
-  hipLaunchKernelGGL(gpf::topo_mask_kernel, dim3((unsigned)n, chunks), dim3(64), lds, e->stream, tab, s, r.on, r.max_line, r.max_sub, lane0, n, dst,
-                     out_dev ? (long long)row_stride : (long long)e->ta_n_act, (r.on && e->ta_n_area) ? 1 : 0);
-  HIP_TRY(hipGetLastError());
-  return GPF_OK;
-}
-
-int gpf_get_topo_action_mask(gpf_handle e, int32_t lane0, int32_t n, uint8_t* host_out) {
-  int rc = gpf_topo_action_mask(e, lane0, n, nullptr, 0);      // (its refusals first: they say what is missing)
-  if (rc != GPF_OK) return rc;
-  if (n > 0 && !host_out) return fail(GPF_E_INVALID, "gpf_get_topo_action_mask: null output");
-  if (n > 0)
-    HIP_TRY(hipMemcpyAsync(host_out, e->ta_mask.p + (size_t)lane0 * e->ta_n_act, (size_t)n * e->ta_n_act, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
-int gpf_set_storage_params(gpf_handle e, const double* emax, const double* emin, const double* loss, const double* eff_charge,
-                           const double* eff_discharge, const float* charge0, double delta_time_seconds, int32_t activate_loss) {
-  if (!e || delta_time_seconds <= 0.0) return fail(GPF_E_INVALID, "gpf_set_storage_params: bad arguments");
-  const size_t ns = e->g.n_sto;
-  if (ns && (!emax || !emin || !loss || !eff_charge || !eff_discharge || !charge0)) return fail(GPF_E_INVALID, "gpf_set_storage_params: null");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(e->sto_emax.upload(emax, ns)); HIP_TRY(e->sto_emin.upload(emin, ns)); HIP_TRY(e->sto_loss.upload(loss, ns));
-  HIP_TRY(e->sto_effc.upload(eff_charge, ns)); HIP_TRY(e->sto_effd.upload(eff_discharge, ns)); HIP_TRY(e->sto_charge0.upload(charge0, ns));
-  e->h_charge0.assign(charge0, charge0 + ns);
-  e->env_coeff = delta_time_seconds / 3600.0;
-  e->env_loss_on = activate_loss ? 1 : 0;
-  e->sto_ready = true;
-  e->params_s_valid = false;
-  return GPF_OK;
-}
-
-int gpf_set_env_dynamics(gpf_handle e, int32_t on, double tol_poly) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_env_dynamics: null");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->plan_valid = false;
-  if (!on) { e->env_on = false; e->params_s_valid = false; return GPF_OK; }
-  if (!e->rd_ready) return fail(GPF_E_INVALID, "gpf_set_env_dynamics: call gpf_set_gen_limits first");
-  if (e->g.n_sto && !e->sto_ready) return fail(GPF_E_INVALID, "gpf_set_env_dynamics: call gpf_set_storage_params first (the grid has storage units)");
-  if (e->g.n_gen > 64 || e->g.n_sto > 64) return fail(GPF_E_CAPACITY, "gpf_set_env_dynamics: more than 64 generators or storage units");
-  const size_t B = e->cap_lanes, ng = e->g.n_gen, ns = std::max(e->g.n_sto, 1);
-  if (!e->env_target.p) {
-    HIP_TRY(e->env_target.alloc(B * ng)); HIP_TRY(e->env_actual.alloc(B * ng)); HIP_TRY(e->env_prev.alloc(B * ng)); HIP_TRY(e->env_already.alloc(B * ng));
-    HIP_TRY(e->env_charge.alloc(B * ns)); HIP_TRY(e->env_amount_prev.alloc(B)); HIP_TRY(e->env_fresh.alloc(B));
-    // the redispatch and storage action rows of all lanes are ONE allocation ([B][n_gen] | [B][n_storage]): a host agent's two uploads per step are one DMA
-    HIP_TRY(e->env_act_redisp.alloc(B * ng + B * ns)); e->env_act_storage = e->env_act_redisp.p + B * ng;
-    HIP_TRY(e->env_limit.alloc(B * ng)); HIP_TRY(e->env_curt_prev.alloc(B)); HIP_TRY(e->env_act_curtail.alloc(B * ng)); HIP_TRY(e->env_illegal.alloc(B));
-    HIP_TRY(hipMemset(e->env_act_redisp.p, 0, B * ng * sizeof(float))); HIP_TRY(hipMemset(e->env_act_storage, 0, B * ns * sizeof(float)));
-    HIP_TRY(hipMemset(e->env_charge.p, 0, B * ns * sizeof(float)));
-  }
-  e->env_on = true;
-  e->env_tol = tol_poly > 0.0 ? tol_poly : 1e-2;
-  e->env_act_r = e->env_act_s = e->env_act_c = false; e->env_hold = false;
-  e->params_s_valid = false;
-  return reset_env_state(e, 0, e->cap_lanes);
-}
-
-}  // extern "C"
-namespace {
-// The agents' per-launch actions go through a pinned block of the engine: the caller's (pageable) arrays are copied into it, the
-// uploads are true asynchronous DMA behind whatever the stream is doing, and NOTHING is waited for -- a host agent that acts at every
-// step paid a staged pageable copy plus a stream synchronisation per step before.  The block is rewritten by the next call, which
-// first waits for the event recorded behind this call's uploads (reached long before: they sit in front of the step launch).
-// Layout: redispatch [B][n_gen] | storage [B][n_sto] | curtailment [B][n_gen].
-int act_pin_begin(gpf_engine* e) {
-  const size_t B = e->cap_lanes, ng = e->g.n_gen, ns = std::max(e->g.n_sto, 1), need = B * (2 * ng + ns);     // (the device layout: padded lane count)
-  if (e->act_up) HIP_TRY(hipEventSynchronize(e->act_up));
-  if (e->act_pin.n < need) {
-    HIP_TRY(e->act_pin.reserve(need));
-    std::memset(e->act_pin.p, 0, need * sizeof(float));         // (the padding lanes' rows travel with the others)
-  }
-  if (!e->act_up) HIP_TRY(e->act_up.create(hipEventDisableTiming));
-  return GPF_OK;
-}
-}  // namespace
-extern "C" {
-
-int gpf_set_lane_actions(gpf_handle e, const float* redispatch, const float* storage_power, int32_t hold_storage) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_lane_actions: null");
-  if (!e->env_on) return fail(GPF_E_INVALID, "gpf_set_lane_actions: the environment dynamics are off (gpf_set_env_dynamics)");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t B = e->n_lanes, ng = e->g.n_gen, ns = e->g.n_sto;
-  if (redispatch || (storage_power && ns)) {
-    const int rc = act_pin_begin(e);
-    if (rc != GPF_OK) return rc;
-  }
-  const size_t Bc = e->cap_lanes, so = Bc * ng;                  // storage rows: behind the (padded) redispatch rows, on the host block as on the device
-  if (redispatch) std::memcpy(e->act_pin.p, redispatch, B * ng * sizeof(float));
-  if (storage_power && ns) std::memcpy(e->act_pin.p + so, storage_power, B * ns * sizeof(float));
-  if (redispatch && storage_power && ns) {
-    HIP_TRY(hipMemcpyAsync(e->env_act_redisp.p, e->act_pin.p, (so + B * ns) * sizeof(float), hipMemcpyHostToDevice, e->stream));     // one DMA for both
-  } else if (redispatch) {
-    HIP_TRY(hipMemcpyAsync(e->env_act_redisp.p, e->act_pin.p, B * ng * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  } else if (storage_power && ns) {
-    HIP_TRY(hipMemcpyAsync(e->env_act_storage, e->act_pin.p + so, B * ns * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  }
-  e->env_act_r = redispatch != nullptr;
-  e->env_act_s = storage_power != nullptr && ns > 0;
-  e->env_hold = hold_storage != 0;
-  if (redispatch || (storage_power && ns)) HIP_TRY(hipEventRecord(e->act_up, e->stream));
-  return GPF_OK;
-}
-
-int gpf_lane_actions_on_device(gpf_handle e, int32_t redispatch, int32_t storage_power, int32_t curtailment, int32_t hold_storage) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_lane_actions_on_device: null");
-  if (!e->env_on) return fail(GPF_E_INVALID, "gpf_lane_actions_on_device: the environment dynamics are off (gpf_set_env_dynamics)");
-  if (curtailment && !e->env_has_ren) return fail(GPF_E_INVALID, "gpf_lane_actions_on_device: curtailment needs gpf_set_gen_renewable");
-  HIP_TRY(hipSetDevice(e->device));
-  e->env_act_r = redispatch != 0;
-  e->env_act_s = storage_power != 0 && e->g.n_sto > 0;
-  e->env_act_c = curtailment != 0;
-  e->env_hold = hold_storage != 0;
-  return GPF_OK;
-}
-
-int gpf_set_gen_renewable(gpf_handle e, const uint8_t* renewable) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_gen_renewable: null");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  e->env_renewable.release();
-  e->env_has_ren = false;
-  if (renewable) { HIP_TRY(e->env_renewable.upload(renewable, (size_t)e->g.n_gen)); e->env_has_ren = true; }
-  e->params_s_valid = false;
-  return GPF_OK;
-}
-
-int gpf_set_lane_curtailment(gpf_handle e, const float* limit) {
-  if (!e) return fail(GPF_E_INVALID, "gpf_set_lane_curtailment: null");
-  if (!e->env_on || !e->env_has_ren) return fail(GPF_E_INVALID, "gpf_set_lane_curtailment: needs gpf_set_env_dynamics and gpf_set_gen_renewable");
-  HIP_TRY(hipSetDevice(e->device));
-  if (!limit) { e->env_act_c = false; return GPF_OK; }
-  const size_t n = (size_t)e->n_lanes * e->g.n_gen;
-  for (size_t i = 0; i < n; ++i) if (!(limit[i] == -1.0f || (limit[i] >= 0.0f && limit[i] <= 1.0f))) return fail(GPF_E_INVALID, "gpf_set_lane_curtailment: limits are ratios in [0, 1], -1 = no change");
-  {
-    const int rc = act_pin_begin(e);
-    if (rc != GPF_OK) return rc;
-  }
-  float* stage = e->act_pin.p + (size_t)e->cap_lanes * (e->g.n_gen + std::max(e->g.n_sto, 1));       // (behind the redispatch | storage rows: act_pin_begin)
-  std::memcpy(stage, limit, n * sizeof(float));
-  HIP_TRY(hipMemcpyAsync(e->env_act_curtail.p, stage, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipEventRecord(e->act_up, e->stream));
-  e->env_act_c = true;
-  return GPF_OK;
-}
-
-int gpf_get_env_state(gpf_handle e, int32_t lane0, int32_t n, float* target, float* actual, float* prev_p, uint8_t* already_modified,
-                      float* charge, float* amount_prev, float* curtail_limit, float* curtail_prev) {
-  if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_get_env_state: bad range");
-  if (!e->env_on) return fail(GPF_E_INVALID, "gpf_get_env_state: the environment dynamics are off");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t ng = e->g.n_gen, ns = e->g.n_sto;
-  HIP_TRY(rows_to_host(e, target, e->env_target, ng, lane0, n)); HIP_TRY(rows_to_host(e, actual, e->env_actual, ng, lane0, n));
-  HIP_TRY(rows_to_host(e, prev_p, e->env_prev, ng, lane0, n)); HIP_TRY(rows_to_host(e, already_modified, e->env_already, ng, lane0, n));
-  HIP_TRY(rows_to_host(e, charge, e->env_charge, ns, lane0, n)); HIP_TRY(rows_to_host(e, amount_prev, e->env_amount_prev, 1, lane0, n));
-  HIP_TRY(rows_to_host(e, curtail_limit, e->env_limit, ng, lane0, n)); HIP_TRY(rows_to_host(e, curtail_prev, e->env_curt_prev, 1, lane0, n));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
-int gpf_get_env_illegal(gpf_handle e, int32_t lane0, int32_t n, int32_t* count) {
-  if (!check_range(e, lane0, n) || !count) return fail(GPF_E_INVALID, "gpf_get_env_illegal: bad range / null");
-  if (!e->env_on) return fail(GPF_E_INVALID, "gpf_get_env_illegal: the environment dynamics are off");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(rows_to_host(e, count, e->env_illegal, 1, lane0, n));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
-int gpf_set_env_illegal(gpf_handle e, int32_t lane0, int32_t n, const int32_t* count) {
-  if (!check_range(e, lane0, n) || !count) return fail(GPF_E_INVALID, "gpf_set_env_illegal: bad range / null");
-  if (!e->env_on) return fail(GPF_E_INVALID, "gpf_set_env_illegal: the environment dynamics are off");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(rows_to_device(e, e->env_illegal, count, 1, lane0, n));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return GPF_OK;
-}
-
-int gpf_set_env_state(gpf_handle e, int32_t lane0, int32_t n, const float* target, const float* actual, const float* prev_p,
-                      const uint8_t* already_modified, const float* charge, const float* amount_prev, const float* curtail_limit,
-                      const float* curtail_prev) {
-  if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_set_env_state: bad range");
-  if (!e->env_on) return fail(GPF_E_INVALID, "gpf_set_env_state: the environment dynamics are off");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t ng = e->g.n_gen, ns = e->g.n_sto;
-  HIP_TRY(rows_to_device(e, e->env_target, target, ng, lane0, n)); HIP_TRY(rows_to_device(e, e->env_actual, actual, ng, lane0, n));
-  HIP_TRY(rows_to_device(e, e->env_prev, prev_p, ng, lane0, n)); HIP_TRY(rows_to_device(e, e->env_already, already_modified, ng, lane0, n));
-  HIP_TRY(rows_to_device(e, e->env_charge, charge, ns, lane0, n)); HIP_TRY(rows_to_device(e, e->env_amount_prev, amount_prev, 1, lane0, n));
-  HIP_TRY(rows_to_device(e, e->env_limit, curtail_limit, ng, lane0, n)); HIP_TRY(rows_to_device(e, e->env_curt_prev, curtail_prev, 1, lane0, n));
-  if (prev_p) HIP_TRY(hipMemsetAsync(e->env_fresh.p + lane0, 0, (size_t)n, e->stream));     // previous set-points given: not a fresh episode
-  HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
 
@@ -2485,14 +1832,7 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
     explicit ActGuard(gpf_engine* e_) : e(e_), r(e_->env_act_r), s(e_->env_act_s), c(e_->env_act_c) { e->env_act_r = e->env_act_s = e->env_act_c = false; }
     ~ActGuard() { e->env_act_r = r; e->env_act_s = s; e->env_act_c = c; }
   } act_guard(e);
-  if (e->env_on) {
-    gpf::EnvDyn E{};
-    E.target = e->env_target.p; E.actual = e->env_actual.p; E.prev_p = e->env_prev.p; E.already = e->env_already.p; E.charge = e->env_charge.p;
-    E.amount_prev = e->env_amount_prev.p; E.fresh = e->env_fresh.p; E.limit = e->env_limit.p; E.curt_prev = e->env_curt_prev.p; E.illegal = e->env_illegal.p;
-    hipLaunchKernelGGL(gpf::simulate_env_copy_kernel, dim3((unsigned)n_dst), dim3(64), 0, e->stream, E, g.n_gen, g.n_sto, e->sim_src.p, n_act,
-                       (int)n_dst, dst_lane0);
-    HIP_TRY(hipGetLastError());
-  }
+  if (e->env_on) { rc = env_copy_from(e, e->sim_src.p, n_act, (int)n_dst, dst_lane0); if (rc != GPF_OK) return rc; }
   // 4. ONE step of the destination range on the forecast tables (no trajectory rows: these are scratch lanes)
   gpf::Bufs b = e->bufs();
   if (fc) b.chron = e->forecast.p;

@@ -1,5 +1,6 @@
 // gridpf_engine.hpp -- what the C ABI units (gridpf_capi*.hip) share: the engine behind a gpf_handle, the owners of its device memory, pinned
-// blocks, stream and events, the error plumbing.  Host-only: no header that defines a non-template kernel (each has exactly one unit).
+// blocks, stream and events, the error plumbing, the row copies of lane-major arrays and the hooks each feature's unit offers the shared
+// lifecycle code of gridpf_capi.hip.  Host-only: no header that defines a non-template kernel outside its unit's guard (each has one unit).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,8 +16,7 @@
 #include "gridpf_common.hpp"
 #include "gridpf_host.hpp"
 #include "gridpf_symbolic.hpp"
-
-namespace gpf { struct TopoRules; }        // gridpf_topo.hpp (next to the topology kernels: gridpf_capi.hip only)
+#include "gridpf_topo.hpp"                  // (TopoRules; its kernels exist in gridpf_capi_topo.hip only)
 
 #pragma GCC visibility push(hidden)         // internal to libgridpf.so: only the gpf_* entry points are its interface
 
@@ -152,9 +152,10 @@ struct gpf_engine {
   DevArr<double> inj, bus_vm, bus_va, work;
   DevArr<int> topo, shunt_bus, topo_out, shunt_bus_out, status, overflow_count, disc_round, lane_table, lane_offset, tmp_lines;
   DevArr<int> cooldown;                 // [B][n_line] line cooldowns of the environment (gpf::Bufs::cooldown)
-  // topology actions of the batched acting path (gridpf_topo.hpp): allocated by the first gpf_set_topo_rules / gpf_upload_topo_actions
+  // topology actions of the batched acting path (gridpf_topo.hpp, gridpf_capi_topo.hip): allocated by the first gpf_set_topo_rules /
+  // gpf_upload_topo_actions
   bool ta_on = false;
-  std::unique_ptr<gpf::TopoRules> ta_rules;   // (allocated with the buffers: the type is complete in gridpf_capi.hip only)
+  gpf::TopoRules ta_rules{};            // (on = 0 until gpf_set_topo_rules)
   DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_list, ta_list_rows, ta_off, ta_items, ta_pos_sub, ta_pos_other;
   DevArr<unsigned char> ta_flags, ta_aff, ta_amb;
   int ta_n_act = 0;
@@ -193,7 +194,7 @@ struct gpf_engine {
   std::vector<unsigned short> h_outage_dur;       // gpf_upload_outage_durations: remaining durations given by the caller (else derived from the tables)
   std::vector<int> h_lane_table, h_lane_offset;   // host mirror of lane_table / lane_offset (gpf_simulate_batch: maintenance ahead of a source lane)
   std::vector<char> h_lane_forecast;              // 1: the lane is a scratch lane of gpf_simulate_batch (its offset is an absolute row, of the forecast tables for time_step > 0)
-  // injection dynamics of the environment (gpf::EnvDyn)
+  // injection dynamics of the environment (gpf::EnvDyn, gridpf_capi_env.hip)
   bool env_on = false, env_hold = false, env_act_r = false, env_act_s = false, sto_ready = false;
   int env_loss_on = 1;
   double env_coeff = 300.0 / 3600.0, env_tol = 1e-2;
@@ -417,6 +418,49 @@ struct gpf_engine {
     return b;
   }
 };
+
+// Rows [lane0, lane0 + n) of a lane-major device array with `stride` elements per lane, copied on the engine's stream (asynchronous:
+// the caller synchronises).  No-op when the host pointer is null or the stride is 0.
+template <typename T>
+hipError_t rows_to_host(const gpf_engine* e, T* host, const DevArr<T>& arr, size_t stride, int lane0, int n) {
+  if (!host || stride == 0) return hipSuccess;
+  return hipMemcpyAsync(host, arr.p + (size_t)lane0 * stride, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToHost, e->stream);
+}
+template <typename T>
+hipError_t rows_to_device(const gpf_engine* e, const DevArr<T>& arr, const T* host, size_t stride, int lane0, int n) {
+  if (!host || stride == 0) return hipSuccess;
+  return hipMemcpyAsync(arr.p + (size_t)lane0 * stride, host, (size_t)n * stride * sizeof(T), hipMemcpyHostToDevice, e->stream);
+}
+// ... and rows [src, src + n) -> [dst, dst + n) of the same array
+template <typename T>
+hipError_t rows_copy(const gpf_engine* e, const DevArr<T>& arr, size_t stride, int src, int dst, int n) {
+  if (stride == 0) return hipSuccess;
+  return hipMemcpyAsync(arr.p + (size_t)dst * stride, arr.p + (size_t)src * stride, (size_t)n * stride * sizeof(T), hipMemcpyDeviceToDevice, e->stream);
+}
+
+// gridpf_capi.hip, the planner's bookkeeping: the host's record of one lane whose topology row is now `t` / `sb` (true: it changed), and
+// "the lanes' rows were sent by the host" (their reset topology is their topology again)
+bool note_lane_row(gpf_engine* e, int lane, const int* t, const int* sb);
+void topo_unmoved(gpf_engine* e, int lane0, int n);
+
+// gridpf_capi_env.hip: the state pointers of the injection dynamics (no action pointers: upload_params_s adds its launch's), the
+// feature's share of gpf_reset_lanes / gpf_copy_lanes, and simulate_env_copy_kernel: lanes dst0 + q, q < n_dst, take the state of lane
+// src_lanes_dev[q / n_act] (gpf_fanout_n1, gpf_simulate_batch)
+gpf::EnvDyn env_dyn(const gpf_engine* e);
+int env_reset_lanes(gpf_engine* e, int lane0, int n);
+hipError_t env_copy_lanes(gpf_engine* e, int src, int dst, int n);
+int env_copy_from(gpf_engine* e, const int* src_lanes_dev, int n_act, int n_dst, int dst0);
+
+// gridpf_capi_topo.hip: topo_prestep_kernel in front of a launch (acts: it carries topology actions) with the read-back of the lanes it
+// moved to another topology class, topo_poststep_kernel behind it (list_resets: lanes that auto-reset are listed), the read-back of that
+// list into the planner's bookkeeping (moved: the rows are action results, else reset topologies) and the feature's share of
+// gpf_reset_lanes / gpf_copy_lanes / gpf_fanout_n1
+int topo_prestep(gpf_engine* e, bool acts);
+int topo_poststep(gpf_engine* e, bool acts, int n_steps, bool list_resets);
+int topo_readback(gpf_engine* e, bool moved);
+int topo_reset_lanes(gpf_engine* e, int lane0, int n);
+hipError_t topo_copy_lanes(gpf_engine* e, int src, int dst, int n);
+int topo_fanout_lanes(gpf_engine* e, int src, int dst0, int n_out);
 
 // gridpf_capi_opp.hip: the opponent's pre-step of a one-step launch (queued on the engine's stream) and its share of gpf_copy_lanes
 int opponent_prestep(gpf_engine* e);

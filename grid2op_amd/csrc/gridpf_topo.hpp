@@ -15,6 +15,10 @@
 // concatenation, in slot order, of the item lists of its non-empty slots as ONE action -- dense arrays, run-time ambiguity
 // (topo_dense_ambiguity, gridpf_topo_mask.hpp), impact, legality with the limits held per area, ONE call of apply_topo_action.  That is the
 // GEN instantiation of topo_prestep_kernel; with one slot and no areas the engine launches the other one, which is the kernel as it was.
+//
+// Two parts: what the host shares (apply_topo_action, the argument blocks, the LDS size of the pre-step: gridpf_capi.hip's
+// gpf_simulate_batch and the engine of gridpf_engine.hpp include the header for these) and, for the one unit that defines GPF_TOPO_KERNEL
+// (gridpf_capi_topo.hip), the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -110,6 +114,7 @@ __host__ __device__ inline size_t topo_prestep_lds_ints(int dim_topo, int n_line
   return max_items < 0 ? base : base + 3 * (size_t)max_items + (size_t)dim_topo + 2 * (size_t)n_line + 2 * TM_MAX_AREAS;
 }
 
+#if defined(__HIPCC__) && defined(GPF_TOPO_KERNEL)
 // Steps 1-4 for one lane per 64-thread block (one wavefront), its rows staged in LDS.  act_on = 0: only the auto-reset snapshot.
 // GEN: composite actions of s.n_slot entries and limits per area (`c`); else one entry per lane, whole-grid limits, `c` unused.
 template <bool GEN>
@@ -336,5 +341,6 @@ __global__ void topo_fanout_kernel(TopoDev g, TopoLanes s, int src, int dst0, in
   if (threadIdx.x < 2) s.flags[(size_t)dst * 2 + threadIdx.x] = s.flags[(size_t)src * 2 + threadIdx.x];
   if (threadIdx.x < s.n_slot) s.act[(size_t)dst * s.n_slot + threadIdx.x] = s.act[(size_t)src * s.n_slot + threadIdx.x];
 }
+#endif  // __HIPCC__ && GPF_TOPO_KERNEL
 
 }  // namespace gpf

@@ -6,7 +6,8 @@
 //   legality   Rules/LookParam.py:28-53 + Rules/PreventReconnection.py:23-60 against the lane's line and substation cooldowns.
 // Three parts: the static per-entry summary built on the host at upload (build_topo_mask_summary), the rule core of one (lane, entry)
 // (topo_mask_eval, topo_mask_eval_area over topo_mask_rules: plain C++, the ONE statement of the mask's rules, run by the kernel and by
-// the host emulators of tests/native/), and the kernel.  Without hipcc only the first two exist: the header then needs no HIP header.
+// the host emulators of tests/native/), and, for the one unit that defines GPF_TOPO_KERNEL (gridpf_capi_topo.hip), the kernel.  Without
+// hipcc only the first two exist: the header then needs no HIP header.
 //
 // Areas (gpf_set_topo_areas; Rules/rulesByArea.py:120-140, _lookparam_byarea): every substation carries one area, a line the area of its
 // ORIGIN substation (rulesByArea.py:91), and the two limits hold per area.  The summary then carries the area in bits 26-29 of every line
@@ -260,7 +261,7 @@ inline void topo_action_areas(const TopoMaskGrid& g, int n_act, const int* act_o
 // 64-bit words of a bit set over n elements
 GPF_TM_HD inline int tm_words(int n) { return (n + 63) >> 6; }
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && defined(GPF_TOPO_KERNEL)
 // the lane rows and grid maps the kernel reads (line_cd may be NULL: no line cooldowns, all zero)
 struct TopoMaskLanes {
   const int* topo; const int* line_cd; const int* sub_cd; const int* or_pos; const int* ex_pos;
@@ -310,6 +311,6 @@ __global__ __launch_bounds__(64) void topo_mask_kernel(TopoMaskTab tab, TopoMask
       for (int a = (int)a0 + tid; a < a1; a += 64) orow[a] = (unsigned char)topo_mask_eval(tab, a, live, lcd, scd, rules_on, max_line, max_sub);
   }
 }
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && GPF_TOPO_KERNEL
 
 }  // namespace gpf

@@ -31,7 +31,8 @@ def _engine(name, n, offsets):
     eng = PowerFlowEngine(m, n_lanes=n, device=0)
     eng.upload_chronics(eng.pack_chronics(ch["load_p"], ch["load_q"], ch["prod_p"], ch["prod_v"]))
     eng.set_lane_chronics(lane_offset=offsets)
-    eng.set_thermal_limits(ch["thermal_limits"])
+    if "thermal_limits" in ch:                     # (rte_case5_example has none)
+        eng.set_thermal_limits(ch["thermal_limits"])
     return m, eng
 
 
@@ -250,6 +251,58 @@ def test_auto_reset_of_a_lane_an_action_moved_is_rekeyed_and_cleared():
     assert np.array_equal(ra.out, rb.out, equal_nan=True) and np.array_equal(ra.status, rb.status)
     with pytest.raises(Exception):
         a.step(4, n_steps=2, auto_reset=True)      # lanes still on a moved class: a reset inside a multi-step launch is refused
+    a.close(); b.close()
+
+
+def test_copy_lanes_and_fanout_n1_carry_the_acting_state_and_the_moved_mark():
+    """Lane 1 splits substation 3 (another topology class, a substation cooldown, a last known busbar 2), lane 2 plays an index outside
+    the table (ambiguous).  copy_lanes and fanout_n1 give their destinations the sources' substation cooldowns, last known busbars and
+    flags.  Lane 4, the copy of lane 1, is then the only lane an action holds on another class than its reset topology's (lane 1 is
+    reset; the contingency lanes have the split rows as their reset topology): a multi-step auto-reset launch is refused for it alone,
+    and when its episode ends the auto-reset re-keys it -- the next step is bit-identical to a twin engine that got the rows through
+    set_topology -- and clears the mark."""
+    from grid2op_amd._capi import GridPFError
+    n = 8
+    offs = 3 * np.arange(n)
+    m, a = _engine("rte_case5_example", n, offs)
+    _, b = _engine("rte_case5_example", n, offs)
+    p_ex6, p_or7, p_load2 = int(m.line_ex_pos_topo_vect[6]), int(m.line_or_pos_topo_vect[7]), int(m.load_pos_topo_vect[2])
+    a.upload_topo_actions([{"set_bus": {p_ex6: 2, p_or7: 2}},        # 0: lines 6 and 7 on busbar 2 of substation 3
+                           {"set_bus": {p_load2: 2}}])               # 1: a load alone on busbar 2 of substation 4: the episode ends
+    a.set_topo_rules(max_sub_changed=1, max_line_status_changed=1, cooldown_sub=3, cooldown_line=0)
+    acting = ("topo", "scd", "lb", "ill", "amb")
+    a.set_lane_topo_actions(np.array([-1, 0, 7, -1, -1, -1, -1, -1], np.int32))
+    a.step(1, auto_reset=True)
+    s = _state(a)
+    assert s["scd"][1, 3] == 3 and s["lb"][1, p_ex6] == 2 and s["topo"][1, p_or7] == 2 and s["amb"][2] and not s["amb"][1] and not s["ill"].any()
+    assert not s["scd"][[0, 2]].any() and not s["done"].any()
+    a.copy_lanes(1, 4, 2)                              # lanes 4, 5 := lanes 1, 2
+    a.fanout_n1(1, 6, [-1, 0])                         # lanes 6, 7 := lane 1, lane 7 with line 0 out
+    c = _state(a)
+    for k in acting:
+        assert np.array_equal(c[k][4:6], s[k][1:3]) and np.array_equal(c[k][:4], s[k][:4]), k
+    for k in ("scd", "lb", "ill", "amb"):
+        assert np.array_equal(c[k][6], s[k][1]) and np.array_equal(c[k][7], s[k][1]), k
+    out0 = s["topo"][1].copy()
+    out0[[m.line_or_pos_topo_vect[0], m.line_ex_pos_topo_vect[0]]] = -1
+    assert np.array_equal(c["topo"][6], s["topo"][1]) and np.array_equal(c["topo"][7], out0)
+    a.reset(1, 1)
+    with pytest.raises(GridPFError, match="another topology class"):
+        a.step(2, n_steps=2, auto_reset=True)          # lane 4 took lane 1's mark with its rows
+    a.set_lane_topo_actions(np.array([-1, -1, -1, -1, 1, -1, 1, -1], np.int32))
+    a.step(2, auto_reset=True)
+    e = _state(a)
+    init = np.asarray(m.initial_topo_vect())
+    assert np.array_equal(a.episode()[2], [0, 0, 0, 0, 1, 0, 1, 0])
+    assert np.array_equal(e["topo"][4], init) and np.array_equal(e["topo"][6], s["topo"][1])      # each back on its own reset topology
+    assert not e["scd"][[4, 6]].any() and np.array_equal(e["lb"][4], np.maximum(init, 1)) and np.array_equal(e["lb"][6], s["topo"][1])
+    assert (e["scd"][[5, 7], 3] == [0, 2]).all()       # (lane 5 is lane 2, which applied nothing; lane 7 counts lane 1's cooldown down)
+    b.set_topology(e["topo"])
+    a.step(3, auto_reset=True)
+    b.step(3, auto_reset=True)
+    ra, rb = a.results(), b.results()
+    assert np.array_equal(ra.out, rb.out, equal_nan=True) and np.array_equal(ra.status, rb.status) and ra.converged.all()
+    a.step(4, n_steps=2, auto_reset=True)              # no lane is on a moved class any more
     a.close(); b.close()
 
 

@@ -9,8 +9,13 @@ comments, blank lines and assembler directives -- instructions and local labels 
 metadata do not enter.
 
     python tools/kernel_isa_digest.py [--root CHECKOUT] [--out FILE] [--only-aot step:1,2,2,2,1,false,false,false]
+
+--units 'gridpf_capi*.hip' lists the kernels of those units of grid2op_amd/csrc instead (no ahead-of-time variants): a change that moves
+kernels between units leaves every kernel's digest and line count as it was, in exactly one unit (local labels are hashed without the
+function's index in its unit).
 """
 import argparse
+import glob
 import hashlib
 import importlib.util
 import os
@@ -24,9 +29,10 @@ from concurrent.futures import ThreadPoolExecutor
 UNITS = ("gridpf_launch_step.hip", "gridpf_launch_runpf.hip")
 
 
-def kernel_digests(asm):
+def kernel_digests(asm, movable=False):
     """{kernel symbol: sha256 of its instruction lines} of one assembly listing (functions of type @function that are kernels or not:
-    every `.type NAME,@function` body up to its `.Lfunc_end`)."""
+    every `.type NAME,@function` body up to its `.Lfunc_end`).  movable: local labels lose the function's index in its unit (.LBB4_3 ->
+    .LBB_3), so that a kernel keeps its digest when it moves to another unit."""
     out = {}
     lines = asm.split("\n")
     i = 0
@@ -43,6 +49,8 @@ def kernel_digests(asm):
         i += 1
         while i < len(lines) and not re.match(r"^\.Lfunc_end\d+:", lines[i]):
             l = lines[i].split(";")[0].rstrip()
+            if movable:
+                l = re.sub(r"(\.L[A-Za-z_]+)\d+_(\d+)", r"\1_\2", l)
             if l.strip() and not re.match(r"^\s+\.", l):           # instructions and labels; no directives
                 h.update(l.strip().encode() + b"\n")
                 n += 1
@@ -59,7 +67,7 @@ def _asm(cmd, out):
         return f.read()
 
 
-def digest_lines(root, only_aot=None, jobs=8):
+def digest_lines(root, only_aot=None, jobs=8, units=None):
     csrc = os.path.join(root, "grid2op_amd", "csrc")
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     spec = importlib.util.spec_from_file_location("_ge_digest", os.path.join(root, "__graft_entry__.py"))
@@ -69,9 +77,9 @@ def digest_lines(root, only_aot=None, jobs=8):
     tmp = tempfile.mkdtemp(prefix="isa_digest_")
     work = []
     if only_aot is None:
-        for u in UNITS:
+        for u in UNITS if units is None else sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, units))):
             work.append((u, base + ["-fPIC", os.path.join(csrc, u), "-o", os.path.join(tmp, u + ".s")], os.path.join(tmp, u + ".s")))
-    for k, (_, hdr, kname, variant, flags) in enumerate(ge.aot_objects()):
+    for k, (_, hdr, kname, variant, flags) in enumerate([] if units else ge.aot_objects()):
         if kname is None or (only_aot is not None and f"{kname}:{variant}" != only_aot):
             continue
         src = os.path.join(tmp, f"aot{k}.hip")
@@ -92,7 +100,7 @@ def digest_lines(root, only_aot=None, jobs=8):
     m = re.search(r"clang version [^\n]*", ver)
     lines = ["# compiler: " + (m.group(0).strip() if m else "unknown")]
     for (tag, _, _), asm in zip(work, asms):
-        for name, (dig, n) in sorted(kernel_digests(asm).items()):
+        for name, (dig, n) in sorted(kernel_digests(asm, units is not None).items()):
             lines.append(f"{tag}  {name}  {n} lines  {dig}")
     shutil.rmtree(tmp, ignore_errors=True)
     return lines
@@ -103,9 +111,10 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--out", default=None)
     ap.add_argument("--only-aot", default=None)
+    ap.add_argument("--units", default=None)
     ap.add_argument("--jobs", type=int, default=8)
     a = ap.parse_args()
-    text = "\n".join(digest_lines(os.path.abspath(a.root), a.only_aot, a.jobs)) + "\n"
+    text = "\n".join(digest_lines(os.path.abspath(a.root), a.only_aot, a.jobs, a.units)) + "\n"
     if a.out:
         with open(a.out, "w") as f:
             f.write(text)
