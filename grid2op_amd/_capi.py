@@ -12,36 +12,11 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "GpfCursorDesc", "GpfCombinedDesc", "library_path", "EXPORTED_SYMBOLS"]
+__all__ = ["lib", "GridPFError", "GpfGridDesc", "GpfLayout", "GpfStepOpts", "GpfOpponentDesc", "GpfAlertDesc", "GpfRewardSlot", "GpfEpisodeDesc", "GpfCursorDesc", "GpfCombinedDesc", "library_path", "SIGNATURES", "EXPORTED_SYMBOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libgridpf.so"
 ABI_VERSION = 326          # include/gridpf.h GPF_ABI_VERSION
-
-EXPORTED_SYMBOLS = [
-    "gpf_last_error", "gpf_version", "gpf_set_deterministic", "gpf_device_count", "gpf_create", "gpf_destroy", "gpf_get_layout", "gpf_n_lanes",
-    "gpf_set_injections", "gpf_set_topology", "gpf_get_injections", "gpf_get_topology", "gpf_disconnect_line",
-    "gpf_reset_lanes", "gpf_copy_lanes", "gpf_fanout_n1", "gpf_runpf", "gpf_solve_lane", "gpf_get_results", "gpf_upload_chronics",
-    "gpf_upload_maintenance", "gpf_upload_hazards", "gpf_set_lane_chronics", "gpf_set_thermal_limits", "gpf_step", "gpf_step_n", "gpf_set_lane_redispatch", "gpf_set_gen_limits", "gpf_redispatch", "gpf_set_trajectory",
-    "gpf_get_trajectory", "gpf_get_trajectory_obs", "gpf_upload_forecasts", "gpf_simulate_batch", "gpf_set_overflow_count",
-    "gpf_set_storage_params", "gpf_set_env_dynamics", "gpf_set_lane_actions", "gpf_lane_actions_on_device", "gpf_get_env_state", "gpf_get_env_illegal", "gpf_set_env_illegal", "gpf_set_env_state", "gpf_set_gen_renewable", "gpf_set_lane_curtailment", "gpf_get_episode", "gpf_lane_capacity", "gpf_get_step_outputs", "gpf_sync",
-    "gpf_get_results_pinned", "gpf_set_profiling", "gpf_get_kernel_time", "gpf_get_plan", "gpf_device_pointers", "gpf_device_pointers_n",
-    "gpf_get_counters", "gpf_upload_outage_durations", "gpf_get_cooldown", "gpf_set_cooldown", "gpf_get_trajectory_cooldown", "gpf_ptdf_build", "gpf_ptdf_build_batch", "gpf_ptdf_batch_info", "gpf_ptdf_batch_get", "gpf_ptdf_get", "gpf_ptdf_flows", "gpf_get_ptdf_flows", "gpf_ptdf_flows_rows", "gpf_get_ptdf_flows_rows", "gpf_lodf_screen",
-    "gpf_jit_enable", "gpf_jit_disable", "gpf_jit_info", "gpf_jit_source", "gpf_jit_features", "gpf_jit_feature_word",
-    "gpf_set_topo_rules", "gpf_upload_topo_actions", "gpf_set_lane_topo_actions", "gpf_topo_actions_on_device", "gpf_get_sub_cooldown",
-    "gpf_set_sub_cooldown", "gpf_get_last_bus", "gpf_set_last_bus", "gpf_get_topo_flags", "gpf_topo_action_mask", "gpf_get_topo_action_mask",
-    "gpf_set_topo_areas", "gpf_set_topo_slots", "gpf_get_topo_action_areas",
-    "gpf_set_obs_clock", "gpf_set_obs_spec", "gpf_obs_vector", "gpf_obs_vector_trajectory", "gpf_get_obs_vector",
-    "gpf_set_opponent", "gpf_upload_opponent_draws", "gpf_upload_opponent_schedule", "gpf_get_opponent_state", "gpf_set_opponent_state",
-    "gpf_set_opponent_areas", "gpf_upload_opponent_area_schedule", "gpf_get_opponent_area_state", "gpf_set_opponent_area_state",
-    "gpf_get_opponent_attack_lines",
-    "gpf_set_alerts", "gpf_set_lane_alerts", "gpf_alerts_on_device", "gpf_alert_state_ints", "gpf_get_alert_state", "gpf_set_alert_state",
-    "gpf_get_alert_reward", "gpf_alert_device_pointers",
-    "gpf_set_rewards", "gpf_get_rewards", "gpf_rewards_eval", "gpf_reward_device_pointers",
-    "gpf_set_episode_limit", "gpf_get_episode_ends", "gpf_get_episode_stats", "gpf_episode_device_pointers",
-    "gpf_set_chronics_cursor", "gpf_upload_cursor_draws", "gpf_get_cursor_state", "gpf_set_cursor_state", "gpf_cursor_device_pointers",
-    "gpf_set_combined_actions", "gpf_get_action_flags", "gpf_combined_device_pointers",
-]
 N_ALERT_POINTERS = 3       # include/gridpf.h GPF_N_ALERT_POINTERS
 N_REWARD_POINTERS = 1      # include/gridpf.h GPF_N_REWARD_POINTERS
 N_EPISODE_POINTERS = 8     # include/gridpf.h GPF_N_EPISODE_POINTERS
@@ -62,6 +37,7 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _fp = C.POINTER(C.c_float)
 _bp = C.POINTER(C.c_uint8)
+_vpp = C.POINTER(C.c_void_p)
 
 
 class GpfGridDesc(C.Structure):
@@ -139,6 +115,147 @@ class GpfStepOpts(C.Structure):
                 ("is_dc", C.c_int32), ("auto_reset", C.c_int32), ("warm_start", C.c_int32), ("track_cooldown", C.c_int32), ("nb_ts_reco", C.c_int32)]
 
 
+def _sig(*argtypes, res=C.c_int):
+    return list(argtypes), res
+
+
+h, i32, i64, u32, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_double
+# The ONE statement of the C ABI on this side: symbol -> (argtypes, restype), in the order of include/gridpf.h's features.  `lib` binds
+# every row, EXPORTED_SYMBOLS is its keys, and tests/test_capi_symbols.py holds every row to the header's prototype.
+SIGNATURES = {
+    "gpf_last_error": _sig(res=C.c_char_p),
+    "gpf_version": _sig(),
+    "gpf_set_deterministic": _sig(h, i32),
+    "gpf_device_count": _sig(_ip),
+    "gpf_create": _sig(C.POINTER(GpfGridDesc), i32, i32, _vpp),
+    "gpf_destroy": _sig(h),
+    "gpf_get_layout": _sig(h, C.POINTER(GpfLayout)),
+    "gpf_n_lanes": _sig(h),
+    "gpf_set_injections": _sig(h, i32, i32, _dp),
+    "gpf_set_topology": _sig(h, i32, i32, _ip, _ip),
+    "gpf_get_injections": _sig(h, i32, i32, _dp),
+    "gpf_get_topology": _sig(h, i32, i32, _ip, _ip),
+    "gpf_disconnect_line": _sig(h, i32, i32),
+    "gpf_reset_lanes": _sig(h, i32, i32),
+    "gpf_copy_lanes": _sig(h, i32, i32, i32),
+    "gpf_fanout_n1": _sig(h, i32, i32, i32, _ip),
+    "gpf_runpf": _sig(h, i32, i32, i32, i32, f64),
+    "gpf_solve_lane": _sig(h, i32, _dp, _ip, _ip, i32, i32, f64, _fp, _ip, _ip, _bp, _ip, _dp, _dp),
+    "gpf_get_results": _sig(h, i32, i32, _fp, _ip, _ip, _bp, _ip, _dp, _dp),
+    "gpf_upload_chronics": _sig(h, i32, i32, _fp),
+    "gpf_upload_maintenance": _sig(h, i32, i32, _bp),
+    "gpf_upload_hazards": _sig(h, i32, i32, _bp),
+    "gpf_set_lane_chronics": _sig(h, _ip, _ip, _fp),
+    "gpf_set_thermal_limits": _sig(h, _fp),
+    "gpf_step": _sig(h, i32, i32, f64, f64, i32, f32, f32, i32, i32, i32),
+    "gpf_step_n": _sig(h, i32, i32, C.POINTER(GpfStepOpts)),
+    "gpf_set_lane_redispatch": _sig(h, _fp),
+    "gpf_set_gen_limits": _sig(h, _dp, _dp, _dp, _dp, _bp, f64),
+    "gpf_redispatch": _sig(h, i32, i32, _dp, _dp, _dp, _dp, _bp, _dp, i32, _bp, _fp),
+    "gpf_set_trajectory": _sig(h, i32, i32),
+    "gpf_get_trajectory": _sig(h, i32, i32, i32, i32, _fp, C.POINTER(C.c_int8)),
+    "gpf_get_trajectory_obs": _sig(h, i32, i32, i32, i32, _fp, _ip, _ip, _bp),
+    "gpf_upload_forecasts": _sig(h, i32, i32, i32, _fp),
+    "gpf_simulate_batch": _sig(h, i32, i32, i32, _ip, i32, _ip, _ip, _ip, i32, C.POINTER(GpfStepOpts)),
+    "gpf_set_overflow_count": _sig(h, i32, i32, _ip),
+    "gpf_set_storage_params": _sig(h, _dp, _dp, _dp, _dp, _dp, _fp, f64, i32),
+    "gpf_set_env_dynamics": _sig(h, i32, f64),
+    "gpf_set_lane_actions": _sig(h, _fp, _fp, i32),
+    "gpf_lane_actions_on_device": _sig(h, i32, i32, i32, i32),
+    "gpf_get_env_state": _sig(h, i32, i32, _fp, _fp, _fp, _bp, _fp, _fp, _fp, _fp),
+    "gpf_get_env_illegal": _sig(h, i32, i32, _ip),
+    "gpf_set_env_illegal": _sig(h, i32, i32, _ip),
+    "gpf_set_env_state": _sig(h, i32, i32, _fp, _fp, _fp, _bp, _fp, _fp, _fp, _fp),
+    "gpf_set_gen_renewable": _sig(h, _bp),
+    "gpf_set_lane_curtailment": _sig(h, _fp),
+    "gpf_get_episode": _sig(h, i32, i32, _bp, _ip),
+    "gpf_lane_capacity": _sig(h),
+    "gpf_get_step_outputs": _sig(h, i32, i32, _fp, _ip, _ip),
+    "gpf_sync": _sig(h),
+    "gpf_get_results_pinned": _sig(h, i32, i32, i32, _vpp),
+    "gpf_set_profiling": _sig(h, i32),
+    "gpf_get_kernel_time": _sig(h, _dp, C.POINTER(i64)),
+    "gpf_get_plan": _sig(h, _ip),
+    "gpf_device_pointers": _sig(h, _vpp, _vpp),
+    "gpf_device_pointers_n": _sig(h, _vpp, i32, _vpp),
+    "gpf_get_counters": _sig(h, C.POINTER(i64)),
+    "gpf_upload_outage_durations": _sig(h, i32, i32, C.POINTER(C.c_uint16)),
+    "gpf_get_cooldown": _sig(h, i32, i32, _ip),
+    "gpf_set_cooldown": _sig(h, i32, i32, _ip),
+    "gpf_get_trajectory_cooldown": _sig(h, i32, i32, i32, i32, C.POINTER(C.c_int16)),
+    "gpf_ptdf_build": _sig(h, i32),
+    "gpf_ptdf_build_batch": _sig(h, i32, i32, i32, _ip),
+    "gpf_ptdf_batch_info": _sig(h, _ip, _ip, _ip, _dp),
+    "gpf_ptdf_batch_get": _sig(h, i32, _dp, _dp),
+    "gpf_ptdf_get": _sig(h, _dp),
+    "gpf_ptdf_flows": _sig(h, i32, i32),
+    "gpf_get_ptdf_flows": _sig(h, i32, i32, _fp),
+    "gpf_ptdf_flows_rows": _sig(h, i32, i32, f64),
+    "gpf_get_ptdf_flows_rows": _sig(h, i32, i32, i32, i32, _fp),
+    "gpf_lodf_screen": _sig(h, i32, i32, _fp, _fp),
+    "gpf_jit_enable": _sig(h, C.c_char_p, C.c_char_p),
+    "gpf_jit_disable": _sig(h),
+    "gpf_jit_info": _sig(h, C.POINTER(i64), _dp, C.c_char_p, C.c_size_t),
+    "gpf_jit_source": _sig(h, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)),
+    "gpf_jit_features": _sig(h, i32),
+    "gpf_jit_feature_word": _sig(h, i32, C.POINTER(GpfStepOpts), u32, C.POINTER(u32)),
+    "gpf_set_topo_rules": _sig(h, i32, i32, i32, i32, i32),
+    "gpf_upload_topo_actions": _sig(h, i32, _ip, _ip, _bp),
+    "gpf_set_lane_topo_actions": _sig(h, _ip),
+    "gpf_topo_actions_on_device": _sig(h, i32),
+    "gpf_get_sub_cooldown": _sig(h, i32, i32, _ip),
+    "gpf_set_sub_cooldown": _sig(h, i32, i32, _ip),
+    "gpf_get_last_bus": _sig(h, i32, i32, _ip),
+    "gpf_set_last_bus": _sig(h, i32, i32, _ip),
+    "gpf_get_topo_flags": _sig(h, i32, i32, _bp),
+    "gpf_topo_action_mask": _sig(h, i32, i32, _bp, i64),
+    "gpf_get_topo_action_mask": _sig(h, i32, i32, _bp),
+    "gpf_set_topo_areas": _sig(h, i32, _ip),
+    "gpf_set_topo_slots": _sig(h, i32),
+    "gpf_get_topo_action_areas": _sig(h, C.POINTER(u32)),
+    "gpf_set_obs_clock": _sig(h, i32, C.POINTER(i64), i32, i32),
+    "gpf_set_obs_spec": _sig(h, i32, _ip, i32, _fp, _fp, i32),
+    "gpf_obs_vector": _sig(h, i32, i32, _fp, i64),
+    "gpf_obs_vector_trajectory": _sig(h, i32, i32, i32, i32, _fp),
+    "gpf_get_obs_vector": _sig(h, i32, i32, _fp),
+    "gpf_set_opponent": _sig(h, C.POINTER(GpfOpponentDesc)),
+    "gpf_upload_opponent_draws": _sig(h, i32, _dp),
+    "gpf_upload_opponent_schedule": _sig(h, _ip, _ip),
+    "gpf_get_opponent_state": _sig(h, i32, i32, _dp, _ip),
+    "gpf_set_opponent_state": _sig(h, i32, i32, _dp, _ip),
+    "gpf_set_opponent_areas": _sig(h, i32, _ip),
+    "gpf_upload_opponent_area_schedule": _sig(h, _ip, _ip),
+    "gpf_get_opponent_area_state": _sig(h, i32, i32, _ip),
+    "gpf_set_opponent_area_state": _sig(h, i32, i32, _ip),
+    "gpf_get_opponent_attack_lines": _sig(h, i32, i32, _bp),
+    "gpf_set_alerts": _sig(h, C.POINTER(GpfAlertDesc)),
+    "gpf_set_lane_alerts": _sig(h, C.POINTER(C.c_uint64)),
+    "gpf_alerts_on_device": _sig(h, i32),
+    "gpf_alert_state_ints": _sig(h, _ip),
+    "gpf_get_alert_state": _sig(h, i32, i32, _ip),
+    "gpf_set_alert_state": _sig(h, i32, i32, _ip),
+    "gpf_get_alert_reward": _sig(h, i32, i32, _fp),
+    "gpf_alert_device_pointers": _sig(h, _vpp, i32),
+    "gpf_set_rewards": _sig(h, i32, C.POINTER(GpfRewardSlot), _fp),
+    "gpf_get_rewards": _sig(h, i32, i32, _fp),
+    "gpf_rewards_eval": _sig(h, i32, i32, _bp, _fp, i64),
+    "gpf_reward_device_pointers": _sig(h, _vpp, i32),
+    "gpf_set_episode_limit": _sig(h, C.POINTER(GpfEpisodeDesc)),
+    "gpf_get_episode_ends": _sig(h, i32, i32, _bp, _bp, _ip, _fp),
+    "gpf_get_episode_stats": _sig(h, i32, i32, _dp, _dp, _ip, _ip),
+    "gpf_episode_device_pointers": _sig(h, _vpp, i32),
+    "gpf_set_chronics_cursor": _sig(h, C.POINTER(GpfCursorDesc)),
+    "gpf_upload_cursor_draws": _sig(h, i32, _dp),
+    "gpf_get_cursor_state": _sig(h, i32, i32, _ip),
+    "gpf_set_cursor_state": _sig(h, i32, i32, _ip),
+    "gpf_cursor_device_pointers": _sig(h, _vpp, i32),
+    "gpf_set_combined_actions": _sig(h, C.POINTER(GpfCombinedDesc)),
+    "gpf_get_action_flags": _sig(h, i32, i32, _bp),
+    "gpf_combined_device_pointers": _sig(h, _vpp, i32),
+}
+EXPORTED_SYMBOLS = list(SIGNATURES)
+del h, i32, i64, u32, f32, f64
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -166,142 +283,9 @@ def lib() -> C.CDLL:
         L = C.CDLL(path)
     except OSError as exc:
         raise GridPFError(f"cannot load {path}: {exc}") from exc
-    h = C.c_void_p
-    i32 = C.c_int32
-    L.gpf_last_error.restype = C.c_char_p
-    L.gpf_last_error.argtypes = []
-    L.gpf_version.restype = C.c_int
-    L.gpf_device_count.argtypes = [_ip]
-    L.gpf_set_deterministic.argtypes = [h, i32]
-    L.gpf_create.argtypes = [C.POINTER(GpfGridDesc), i32, i32, C.POINTER(h)]
-    L.gpf_destroy.argtypes = [h]
-    L.gpf_get_layout.argtypes = [h, C.POINTER(GpfLayout)]
-    L.gpf_n_lanes.argtypes = [h]
-    L.gpf_set_injections.argtypes = [h, i32, i32, _dp]
-    L.gpf_set_topology.argtypes = [h, i32, i32, _ip, _ip]
-    L.gpf_get_injections.argtypes = [h, i32, i32, _dp]
-    L.gpf_get_topology.argtypes = [h, i32, i32, _ip, _ip]
-    L.gpf_disconnect_line.argtypes = [h, i32, i32]
-    L.gpf_reset_lanes.argtypes = [h, i32, i32]
-    L.gpf_copy_lanes.argtypes = [h, i32, i32, i32]
-    L.gpf_fanout_n1.argtypes = [h, i32, i32, i32, _ip]
-    L.gpf_runpf.argtypes = [h, i32, i32, i32, i32, C.c_double]
-    L.gpf_get_results.argtypes = [h, i32, i32, _fp, _ip, _ip, _bp, _ip, _dp, _dp]
-    L.gpf_get_results_pinned.argtypes = [h, i32, i32, i32, C.POINTER(C.c_void_p)]
-    L.gpf_solve_lane.argtypes = [h, i32, _dp, _ip, _ip, i32, i32, C.c_double, _fp, _ip, _ip, _bp, _ip, _dp, _dp]
-    L.gpf_upload_chronics.argtypes = [h, i32, i32, _fp]
-    L.gpf_upload_maintenance.argtypes = [h, i32, i32, _bp]
-    L.gpf_upload_hazards.argtypes = [h, i32, i32, _bp]
-    L.gpf_set_lane_chronics.argtypes = [h, _ip, _ip, _fp]
-    L.gpf_set_thermal_limits.argtypes = [h, _fp]
-    L.gpf_step.argtypes = [h, i32, i32, C.c_double, C.c_double, i32, C.c_float, C.c_float, i32, i32, i32]
-    L.gpf_step_n.argtypes = [h, i32, i32, C.POINTER(GpfStepOpts)]
-    L.gpf_set_lane_redispatch.argtypes = [h, _fp]
-    L.gpf_set_gen_limits.argtypes = [h, _dp, _dp, _dp, _dp, _bp, C.c_double]
-    L.gpf_redispatch.argtypes = [h, i32, i32, _dp, _dp, _dp, _dp, _bp, _dp, i32, _bp, _fp]
-    L.gpf_set_trajectory.argtypes = [h, i32, i32]
-    L.gpf_get_trajectory_obs.argtypes = [h, i32, i32, i32, i32, _fp, _ip, _ip, _bp]
-    L.gpf_get_trajectory.argtypes = [h, i32, i32, i32, i32, _fp, C.POINTER(C.c_int8)]
-    L.gpf_upload_forecasts.argtypes = [h, i32, i32, i32, _fp]
-    L.gpf_simulate_batch.argtypes = [h, i32, i32, i32, _ip, i32, _ip, _ip, _ip, i32, C.POINTER(GpfStepOpts)]
-    L.gpf_set_overflow_count.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_storage_params.argtypes = [h, _dp, _dp, _dp, _dp, _dp, _fp, C.c_double, i32]
-    L.gpf_set_env_dynamics.argtypes = [h, i32, C.c_double]
-    L.gpf_set_lane_actions.argtypes = [h, _fp, _fp, i32]
-    L.gpf_lane_actions_on_device.argtypes = [h, i32, i32, i32, i32]
-    L.gpf_get_env_state.argtypes = [h, i32, i32, _fp, _fp, _fp, _bp, _fp, _fp, _fp, _fp]
-    L.gpf_get_env_illegal.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_env_illegal.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_env_state.argtypes = [h, i32, i32, _fp, _fp, _fp, _bp, _fp, _fp, _fp, _fp]
-    L.gpf_set_gen_renewable.argtypes = [h, _bp]
-    L.gpf_set_lane_curtailment.argtypes = [h, _fp]
-    L.gpf_get_episode.argtypes = [h, i32, i32, _bp, _ip]
-    L.gpf_lane_capacity.argtypes = [h]
-    L.gpf_get_step_outputs.argtypes = [h, i32, i32, _fp, _ip, _ip]
-    L.gpf_sync.argtypes = [h]
-    L.gpf_set_profiling.argtypes = [h, i32]
-    L.gpf_get_kernel_time.argtypes = [h, _dp, C.POINTER(C.c_int64)]
-    L.gpf_get_plan.argtypes = [h, C.POINTER(C.c_int32)]
-    L.gpf_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-    L.gpf_device_pointers_n.argtypes = [h, C.POINTER(C.c_void_p), i32, C.POINTER(C.c_void_p)]
-    L.gpf_ptdf_build.argtypes = [h, i32]
-    L.gpf_ptdf_get.argtypes = [h, _dp]
-    L.gpf_get_counters.argtypes = [h, C.POINTER(C.c_int64)]
-    L.gpf_get_cooldown.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_topo_rules.argtypes = [h, i32, i32, i32, i32, i32]
-    L.gpf_upload_topo_actions.argtypes = [h, i32, _ip, _ip, _bp]
-    L.gpf_set_lane_topo_actions.argtypes = [h, _ip]
-    L.gpf_topo_actions_on_device.argtypes = [h, i32]
-    L.gpf_get_sub_cooldown.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_sub_cooldown.argtypes = [h, i32, i32, _ip]
-    L.gpf_get_last_bus.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_last_bus.argtypes = [h, i32, i32, _ip]
-    L.gpf_get_topo_flags.argtypes = [h, i32, i32, _bp]
-    L.gpf_topo_action_mask.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]
-    L.gpf_get_topo_action_mask.argtypes = [h, i32, i32, _bp]
-    L.gpf_set_topo_areas.argtypes = [h, i32, _ip]
-    L.gpf_set_topo_slots.argtypes = [h, i32]
-    L.gpf_get_topo_action_areas.argtypes = [h, C.POINTER(C.c_uint32)]
-    L.gpf_set_obs_clock.argtypes = [h, i32, C.POINTER(C.c_int64), i32, i32]
-    L.gpf_set_obs_spec.argtypes = [h, i32, _ip, i32, _fp, _fp, i32]
-    L.gpf_obs_vector.argtypes = [h, i32, i32, C.c_void_p, C.c_int64]
-    L.gpf_obs_vector_trajectory.argtypes = [h, i32, i32, i32, i32, C.c_void_p]
-    L.gpf_get_obs_vector.argtypes = [h, i32, i32, _fp]
-    L.gpf_set_opponent.argtypes = [h, C.POINTER(GpfOpponentDesc)]
-    L.gpf_upload_opponent_draws.argtypes = [h, i32, _dp]
-    L.gpf_upload_opponent_schedule.argtypes = [h, _ip, _ip]
-    L.gpf_get_opponent_state.argtypes = [h, i32, i32, _dp, _ip]
-    L.gpf_set_opponent_state.argtypes = [h, i32, i32, _dp, _ip]
-    L.gpf_set_opponent_areas.argtypes = [h, i32, _ip]
-    L.gpf_upload_opponent_area_schedule.argtypes = [h, _ip, _ip]
-    L.gpf_get_opponent_area_state.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_opponent_area_state.argtypes = [h, i32, i32, _ip]
-    L.gpf_get_opponent_attack_lines.argtypes = [h, i32, i32, C.POINTER(C.c_uint8)]
-    L.gpf_set_alerts.argtypes = [h, C.POINTER(GpfAlertDesc)]
-    L.gpf_set_lane_alerts.argtypes = [h, C.POINTER(C.c_uint64)]
-    L.gpf_alerts_on_device.argtypes = [h, i32]
-    L.gpf_alert_state_ints.argtypes = [h, _ip]
-    L.gpf_get_alert_state.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_alert_state.argtypes = [h, i32, i32, _ip]
-    L.gpf_get_alert_reward.argtypes = [h, i32, i32, _fp]
-    L.gpf_alert_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
-    L.gpf_set_rewards.argtypes = [h, i32, C.POINTER(GpfRewardSlot), _fp]
-    L.gpf_get_rewards.argtypes = [h, i32, i32, _fp]
-    L.gpf_rewards_eval.argtypes = [h, i32, i32, C.c_void_p, C.c_void_p, C.c_int64]
-    L.gpf_reward_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
-    L.gpf_set_episode_limit.argtypes = [h, C.POINTER(GpfEpisodeDesc)]
-    L.gpf_get_episode_ends.argtypes = [h, i32, i32, _bp, _bp, _ip, _fp]
-    L.gpf_get_episode_stats.argtypes = [h, i32, i32, _dp, _dp, _ip, _ip]
-    L.gpf_episode_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
-    L.gpf_set_chronics_cursor.argtypes = [h, C.POINTER(GpfCursorDesc)]
-    L.gpf_upload_cursor_draws.argtypes = [h, i32, _dp]
-    L.gpf_get_cursor_state.argtypes = [h, i32, i32, _ip]
-    L.gpf_set_cursor_state.argtypes = [h, i32, i32, _ip]
-    L.gpf_cursor_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
-    L.gpf_set_combined_actions.argtypes = [h, C.POINTER(GpfCombinedDesc)]
-    L.gpf_get_action_flags.argtypes = [h, i32, i32, _bp]
-    L.gpf_combined_device_pointers.argtypes = [h, C.POINTER(C.c_void_p), i32]
-    L.gpf_upload_outage_durations.argtypes = [h, i32, i32, C.POINTER(C.c_uint16)]
-    L.gpf_set_cooldown.argtypes = [h, i32, i32, _ip]
-    L.gpf_get_trajectory_cooldown.argtypes = [h, i32, i32, i32, i32, C.POINTER(C.c_int16)]
-    L.gpf_ptdf_build_batch.argtypes = [h, i32, i32, i32, _ip]
-    L.gpf_ptdf_batch_info.argtypes = [h, _ip, _ip, _ip, _dp]
-    L.gpf_ptdf_batch_get.argtypes = [h, i32, _dp, _dp]
-    L.gpf_ptdf_flows.argtypes = [h, i32, i32]
-    L.gpf_get_ptdf_flows.argtypes = [h, i32, i32, _fp]
-    L.gpf_ptdf_flows_rows.argtypes = [h, i32, i32, C.c_double]
-    L.gpf_get_ptdf_flows_rows.argtypes = [h, i32, i32, i32, i32, _fp]
-    L.gpf_lodf_screen.argtypes = [h, i32, i32, _fp, _fp]
-    L.gpf_jit_enable.argtypes = [h, C.c_char_p, C.c_char_p]
-    L.gpf_jit_disable.argtypes = [h]
-    L.gpf_jit_info.argtypes = [h, C.POINTER(C.c_int64), _dp, C.c_char_p, C.c_size_t]
-    L.gpf_jit_source.argtypes = [h, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.gpf_jit_features.argtypes = [h, C.c_int32]
-    L.gpf_jit_feature_word.argtypes = [h, C.c_int32, C.POINTER(GpfStepOpts), C.c_uint32, C.POINTER(C.c_uint32)]
-    for name in EXPORTED_SYMBOLS:
+    for name, (argtypes, restype) in SIGNATURES.items():
         fn = getattr(L, name)
-        if name not in ("gpf_last_error",):
-            fn.restype = C.c_int
+        fn.argtypes, fn.restype = argtypes, restype
     got = L.gpf_version()
     if got != ABI_VERSION:               # a stale GRIDPF_LIB / an old build next to new Python: struct layouts and argument lists differ
         raise GridPFError(f"{path} has ABI version {got}, this binding needs {ABI_VERSION} (include/gridpf.h GPF_ABI_VERSION): rebuild "

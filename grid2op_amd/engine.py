@@ -345,12 +345,42 @@ class LaneResults:
         return self.status[:, 1]
 
 
+def _ptr(a: Optional[np.ndarray]):
+    """`ptr` with the ctypes element type of the array's own dtype."""
+    return None if a is None else ptr(a, np.ctypeslib.as_ctypes_type(a.dtype))
+
+
+def _fill_pointers(desc, arrays: dict):
+    """Point the pointer fields of a ctypes descriptor at the arrays of ``{field: array or None}``, each as the field's own pointer type
+    (an array of another element type is an error).  The CALLER keeps ``arrays`` referenced until the C call that reads ``desc`` returned."""
+    types = dict(desc._fields_)
+    for field, a in arrays.items():
+        if a is not None:
+            assert a.flags.c_contiguous and a.dtype == np.dtype(types[field]._type_), field
+            setattr(desc, field, a.ctypes.data_as(types[field]))
+
+
 class PowerFlowEngine:
     def __init__(self, model: GridModel, n_lanes: int = 1, device: int = 0, n_busbar: int = 2, deterministic: bool = False):
         self.model = model
         self.n_busbar = int(n_busbar)
         self._lib = _capi.lib()
         self._h = C.c_void_p()
+        # Feature state: every private attribute the methods below read is declared HERE, with the setter that owns it.  The three cached
+        # views alias engine-owned device buffers; the setter named drops the view because the library re-allocates the buffer there.
+        self._has_maint = self._has_hazard = self._has_outages = False      # upload_maintenance / upload_hazards
+        self._n_topo_act = 0                 # upload_topo_actions: entries of the action table
+        self._n_topo_slot = 1                # set_topo_slots
+        self._mask_view = None               # topo_action_mask's cache of device_views()["topo_mask"]; dropped by upload_topo_actions
+        self._opp_n_lines = self._opp_cap = 0     # set_opponent: attackable lines, schedule capacity (Geometric)
+        self._opp_n_area = 0                 # set_opponent_areas (set_opponent: back to 0)
+        self._alert = None                   # set_alerts: (A, W) while alerts are on; set_opponent / set_opponent_areas turn them off
+        self._traj_cap = 0                   # set_trajectory
+        self._n_reward_slot = 0              # set_rewards
+        self._rw_view = None                 # rewards_eval's cache of reward_views()["rewards"]; dropped by set_rewards
+        self._ep_on = self._cb_on = self._cur_on = False      # set_episode_limit / set_combined_actions / set_chronics_cursor
+        self._obs_spec = None                # set_obs_spec
+        self._obs_view = None                # observation_vector's cache of device_views()["obs"]; dropped by set_obs_spec
         m = model
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
@@ -360,40 +390,17 @@ class PowerFlowEngine:
             br_y[:, 2 * k + 1] = y.imag
         init_inj = np.concatenate([f64(m.gen_p0), f64(m.gen_vm0), f64(m.load_p0), f64(m.load_q0), f64(m.storage_p0),
                                    f64(m.storage_q0), f64(m.shunt_p0), f64(m.shunt_q0)])
-        keep = dict(
+        d = GpfGridDesc(n_sub=m.n_sub, n_busbar=self.n_busbar, n_line=m.n_line, n_gen=m.n_gen, n_load=m.n_load, n_storage=m.n_storage,
+                        n_shunt=m.n_shunt, dim_topo=m.dim_topo, sn_mva=m.sn_mva)
+        arrays = dict(                       # descriptor field -> array; referenced until gpf_create (which copies them) has returned
             sub_vn_kv=f64(m.sub_vn_kv), line_or_sub=i32(m.line_or_sub), line_ex_sub=i32(m.line_ex_sub),
-            line_or_pos=i32(m.line_or_pos_topo_vect), line_ex_pos=i32(m.line_ex_pos_topo_vect), br_y=br_y,
-            br_bdc=f64(m.br_bdc), gen_sub=i32(m.gen_sub), gen_pos=i32(m.gen_pos_topo_vect), gen_min_q=f64(m.gen_min_q),
+            line_or_pos_topo_vect=i32(m.line_or_pos_topo_vect), line_ex_pos_topo_vect=i32(m.line_ex_pos_topo_vect), br_y=br_y,
+            br_bdc=f64(m.br_bdc), gen_sub=i32(m.gen_sub), gen_pos_topo_vect=i32(m.gen_pos_topo_vect), gen_min_q=f64(m.gen_min_q),
             gen_max_q=f64(m.gen_max_q), gen_slack=np.ascontiguousarray(m.gen_slack, dtype=np.uint8),
-            load_sub=i32(m.load_sub), load_pos=i32(m.load_pos_topo_vect), sto_sub=i32(m.storage_sub),
-            sto_pos=i32(m.storage_pos_topo_vect), shunt_sub=i32(m.shunt_sub), shunt_fact=f64(m.shunt_fact),
+            load_sub=i32(m.load_sub), load_pos_topo_vect=i32(m.load_pos_topo_vect), storage_sub=i32(m.storage_sub),
+            storage_pos_topo_vect=i32(m.storage_pos_topo_vect), shunt_sub=i32(m.shunt_sub), shunt_fact=f64(m.shunt_fact),
             init_inj=init_inj, init_topo=i32(m.initial_topo_vect()), init_shunt_bus=i32(m.initial_shunt_bus()))
-        d = GpfGridDesc()
-        d.n_sub, d.n_busbar = m.n_sub, self.n_busbar
-        d.n_line, d.n_gen, d.n_load, d.n_storage, d.n_shunt, d.dim_topo = (m.n_line, m.n_gen, m.n_load, m.n_storage,
-                                                                              m.n_shunt, m.dim_topo)
-        d.sn_mva = m.sn_mva
-        d.sub_vn_kv = ptr(keep["sub_vn_kv"], C.c_double)
-        d.line_or_sub = ptr(keep["line_or_sub"], C.c_int32)
-        d.line_ex_sub = ptr(keep["line_ex_sub"], C.c_int32)
-        d.line_or_pos_topo_vect = ptr(keep["line_or_pos"], C.c_int32)
-        d.line_ex_pos_topo_vect = ptr(keep["line_ex_pos"], C.c_int32)
-        d.br_y = ptr(keep["br_y"], C.c_double)
-        d.br_bdc = ptr(keep["br_bdc"], C.c_double)
-        d.gen_sub = ptr(keep["gen_sub"], C.c_int32)
-        d.gen_pos_topo_vect = ptr(keep["gen_pos"], C.c_int32)
-        d.gen_min_q = ptr(keep["gen_min_q"], C.c_double)
-        d.gen_max_q = ptr(keep["gen_max_q"], C.c_double)
-        d.gen_slack = ptr(keep["gen_slack"], C.c_uint8)
-        d.load_sub = ptr(keep["load_sub"], C.c_int32)
-        d.load_pos_topo_vect = ptr(keep["load_pos"], C.c_int32)
-        d.storage_sub = ptr(keep["sto_sub"], C.c_int32)
-        d.storage_pos_topo_vect = ptr(keep["sto_pos"], C.c_int32)
-        d.shunt_sub = ptr(keep["shunt_sub"], C.c_int32)
-        d.shunt_fact = ptr(keep["shunt_fact"], C.c_double)
-        d.init_inj = ptr(keep["init_inj"], C.c_double)
-        d.init_topo = ptr(keep["init_topo"], C.c_int32)
-        d.init_shunt_bus = ptr(keep["init_shunt_bus"], C.c_int32)
+        _fill_pointers(d, arrays)
         check(self._lib.gpf_create(C.byref(d), int(n_lanes), int(device), C.byref(self._h)), "gpf_create")
         self._pid = os.getpid()          # HIP handles belong to the creating process (a forked child must not destroy them)
         if deterministic:
@@ -401,7 +408,7 @@ class PowerFlowEngine:
         self.n_lanes = int(n_lanes)
         self.device = int(device)
         lay = GpfLayout()
-        check(self._lib.gpf_get_layout(self._h, C.byref(lay)), "gpf_get_layout")
+        self._call("gpf_get_layout", C.byref(lay))
         self.layout = lay
         self.n_inj, self.n_out, self.n_chron, self.nb_total = lay.n_inj, lay.n_out, lay.n_chron, lay.nb_total
         sizes = dict(n_line=m.n_line, n_gen=m.n_gen, n_load=m.n_load, n_storage=m.n_storage, n_shunt=m.n_shunt)
@@ -433,12 +440,72 @@ class PowerFlowEngine:
     def set_deterministic(self, flag: bool = True):
         """Results are bit-identical from run to run on every grid by default; ``True`` additionally forces one wavefront per lane
         on grids with >= 64 substations (cross-check variant, ~20 % slower there)."""
-        check(self._lib.gpf_set_deterministic(self._h, int(bool(flag))), "gpf_set_deterministic")
+        self._call("gpf_set_deterministic", int(bool(flag)))
+
+    # ---- the plumbing every method below shares ------------------------------------------------------
+    def _call(self, name, *args):
+        """``name(handle, *args)`` of the library; `GridPFError` with the library's message when it fails."""
+        check(getattr(self._lib, name)(self._h, *args), name)
 
     def _range(self, lane0, n):
         if n is None:
             n = self.n_lanes - lane0
         return int(lane0), int(n)
+
+    def _get_rows(self, name, lane0, n, *specs, zeros=False):
+        """A row getter ``name(handle, lane0, n, out...)``: one ``[n, cols]`` array (``cols`` None: ``[n]``) per ``(cols, dtype)`` of
+        ``specs``, uninitialised or (``zeros``) zeroed before the call.  Returns the array, or the list of them."""
+        lane0, n = self._range(lane0, n)
+        outs = [(np.zeros if zeros else np.empty)(n if cols is None else (n, cols), dtype=dtype) for cols, dtype in specs]
+        self._call(name, lane0, n, *[_ptr(a) for a in outs])
+        return outs[0] if len(outs) == 1 else outs
+
+    def _set_rows(self, name, rows, cols, dtype, lane0):
+        """A row setter ``name(handle, lane0, n, rows)``: ``rows`` as contiguous ``[n, cols]`` of ``dtype``."""
+        rows = np.ascontiguousarray(rows, dtype=dtype).reshape(-1, cols)
+        self._call(name, int(lane0), rows.shape[0], _ptr(rows))
+
+    def _device_pointers(self, name, count):
+        """The pointer array of a ``gpf_*_device_pointers(handle, out, count)`` call."""
+        ptrs = (C.c_void_p * count)()
+        self._call(name, ptrs, count)
+        return ptrs
+
+    def _view(self, p, shape, typestr, steps=None):
+        """The engine-owned buffer at device pointer ``p`` as a torch tensor that ALIASES it (no copy): ``shape`` is a lane's, the buffer
+        holds one per lane of the engine's capacity (``steps``: per step and lane, as the trajectory buffers do) and the view is cut to
+        ``n_lanes``.  None for an absent buffer (null pointer) or an empty one."""
+        import torch
+        if not p or 0 in shape:
+            return None
+        full = (self._lib.gpf_lane_capacity(self._h),) + tuple(shape)
+        iface = {"shape": full if steps is None else (steps,) + full, "typestr": typestr, "data": (int(p), False), "version": 2, "strides": None}
+        holder = type("_Arr", (), {"__cuda_array_interface__": iface})()      # v2: torch.as_tensor wraps it without a copy
+        t = torch.as_tensor(holder, device=torch.device("cuda", self.device))
+        return t[:self.n_lanes] if steps is None else t[:, :self.n_lanes]
+
+    def _views(self, ptrs, table):
+        """``{key: view}`` of a table of (key, pointer index, lane shape, typestr) over the pointer array ``ptrs``."""
+        return {key: self._view(ptrs[idx], shape, typestr) for key, idx, shape, typestr in table}
+
+    def _out_rows(self, what, out, dtype, n, width, narrow_to_library):
+        """Pointer and row stride of a caller's ``out=`` tensor: 2-d CUDA of ``dtype`` ("uint8" / "float32") on this device, ``n`` rows,
+        unit column stride; ValueError otherwise.  Rows narrower than ``width`` (or, with several rows, a row stride below it) are the one
+        point the callers differ on: ``narrow_to_library`` passes the rows' width down as the stride, which the library refuses with its
+        own message; without it they are refused here."""
+        import torch
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == getattr(torch, dtype) and out.dim() == 2):
+            raise ValueError(f"{what}: out must be a 2-d {dtype} CUDA tensor")
+        ok = out.device.index == self.device and out.shape[0] == n and out.stride(1) == 1
+        if narrow_to_library:
+            if not ok:
+                raise ValueError(f"{what}: out must live on cuda:{self.device} and have {n} rows with unit column stride")
+            stride = int(out.stride(0)) if n > 1 and out.shape[1] >= width else int(out.shape[1])
+        else:
+            if not ok or out.shape[1] < width or (n > 1 and out.stride(0) < width):
+                raise ValueError(f"{what}: out must live on cuda:{self.device}, have {n} rows of >= {width} contiguous columns and a row stride >= {width}")
+            stride = int(out.stride(0)) if n > 1 else max(int(out.stride(0)), width)
+        return C.cast(out.data_ptr(), C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), stride
 
     # ---- state --------------------------------------------------------------------------------------
     def pack_injections(self, n: int = 1, **fields) -> np.ndarray:
@@ -449,14 +516,10 @@ class PowerFlowEngine:
         return inj
 
     def set_injections(self, inj: np.ndarray, lane0: int = 0):
-        inj = np.ascontiguousarray(inj, dtype=np.float64).reshape(-1, self.n_inj)
-        check(self._lib.gpf_set_injections(self._h, lane0, inj.shape[0], ptr(inj, C.c_double)), "gpf_set_injections")
+        self._set_rows("gpf_set_injections", inj, self.n_inj, np.float64, lane0)
 
     def get_injections(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
-        lane0, n = self._range(lane0, n)
-        inj = np.empty((n, self.n_inj), dtype=np.float64)
-        check(self._lib.gpf_get_injections(self._h, lane0, n, ptr(inj, C.c_double)), "gpf_get_injections")
-        return inj
+        return self._get_rows("gpf_get_injections", lane0, n, (self.n_inj, np.float64))
 
     def set_topology(self, topo: np.ndarray, shunt_bus: Optional[np.ndarray] = None, lane0: int = 0):
         topo = np.ascontiguousarray(topo, dtype=np.int32).reshape(-1, self.model.dim_topo)
@@ -464,29 +527,25 @@ class PowerFlowEngine:
         if shunt_bus is not None and self.model.n_shunt:
             sb = np.ascontiguousarray(shunt_bus, dtype=np.int32).reshape(-1, self.model.n_shunt)
             assert sb.shape[0] == topo.shape[0]
-        check(self._lib.gpf_set_topology(self._h, lane0, topo.shape[0], ptr(topo, C.c_int32), ptr(sb, C.c_int32)),
-              "gpf_set_topology")
+        self._call("gpf_set_topology", lane0, topo.shape[0], _ptr(topo), _ptr(sb))
 
     def get_topology(self, lane0: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-        lane0, n = self._range(lane0, n)
-        topo = np.empty((n, self.model.dim_topo), dtype=np.int32)
-        sb = np.empty((n, self.model.n_shunt), dtype=np.int32)
-        check(self._lib.gpf_get_topology(self._h, lane0, n, ptr(topo, C.c_int32), ptr(sb, C.c_int32)), "gpf_get_topology")
+        topo, sb = self._get_rows("gpf_get_topology", lane0, n, (self.model.dim_topo, np.int32), (self.model.n_shunt, np.int32))
         return topo, sb
 
     def disconnect_line(self, lane: int, line_id: int):
-        check(self._lib.gpf_disconnect_line(self._h, lane, line_id), "gpf_disconnect_line")
+        self._call("gpf_disconnect_line", lane, line_id)
 
     def reset(self, lane0: int = 0, n: Optional[int] = None):
         lane0, n = self._range(lane0, n)
-        check(self._lib.gpf_reset_lanes(self._h, lane0, n), "gpf_reset_lanes")
+        self._call("gpf_reset_lanes", lane0, n)
 
     def copy_lanes(self, src: int, dst: int, n: int = 1):
-        check(self._lib.gpf_copy_lanes(self._h, src, dst, n), "gpf_copy_lanes")
+        self._call("gpf_copy_lanes", src, dst, n)
 
     def fanout_n1(self, src_lane: int, dst_lane0: int, out_lines):
         ol = np.ascontiguousarray(out_lines, dtype=np.int32)
-        check(self._lib.gpf_fanout_n1(self._h, src_lane, dst_lane0, ol.size, ptr(ol, C.c_int32)), "gpf_fanout_n1")
+        self._call("gpf_fanout_n1", src_lane, dst_lane0, ol.size, _ptr(ol))
 
     def candidate_topologies(self, base_topo, actions, last_bus=None) -> np.ndarray:
         """``[len(actions), dim_topo]`` topology rows = ``base_topo`` modified by each candidate action, described as grid2op
@@ -548,7 +607,7 @@ class PowerFlowEngine:
         ``[n_tables, T, n_horizons, n_chron]``; None removes them.  Row ``r`` holds the forecast made at chronics row ``r``
         (Chronics/gridStateFromFileWithForecasts.py:311-353)."""
         if tables is None:
-            check(self._lib.gpf_upload_forecasts(self._h, 0, 0, 0, None), "gpf_upload_forecasts")
+            self._call("gpf_upload_forecasts", 0, 0, 0, None)
             return
         t = np.ascontiguousarray(tables, dtype=np.float32)
         if t.ndim == 2:
@@ -556,7 +615,7 @@ class PowerFlowEngine:
         if t.ndim == 3:
             t = t[:, :, None, :]
         assert t.ndim == 4 and t.shape[3] == self.n_chron, t.shape
-        check(self._lib.gpf_upload_forecasts(self._h, t.shape[0], t.shape[1], t.shape[2], ptr(t, C.c_float)), "gpf_upload_forecasts")
+        self._call("gpf_upload_forecasts", t.shape[0], t.shape[1], t.shape[2], _ptr(t))
 
     def pack_actions(self, actions):
         """Candidate actions (dicts as `candidate_topologies` takes them, plus ``"change_line_status": [line ids]`` and
@@ -597,16 +656,23 @@ class PowerFlowEngine:
         lb = None if last_bus is None else np.ascontiguousarray(last_bus, dtype=np.int32).reshape(src.size, self.model.dim_topo)
         o = GpfStepOpts(int(max_iter), float(tol_mva), float(rebalance), int(bool(cascade)), float(hard_overflow), float(soft_overflow),
                         int(nb_ts_allowed), int(max_rounds), int(bool(is_dc)), 0, 0, 0, 0)
-        check(self._lib.gpf_simulate_batch(self._h, int(t_obs), int(time_step), src.size, ptr(src, C.c_int32), len(actions),
-                                           ptr(off, C.c_int32), ptr(items if items.size else None, C.c_int32), ptr(lb, C.c_int32),
-                                           int(dst_lane0), C.byref(o)), "gpf_simulate_batch")
+        self._call("gpf_simulate_batch", int(t_obs), int(time_step), src.size, _ptr(src), len(actions), _ptr(off),
+                   _ptr(items if items.size else None), _ptr(lb), int(dst_lane0), C.byref(o))
         return src.size * len(actions)
 
     # ---- solve --------------------------------------------------------------------------------------
     def runpf(self, lane0: int = 0, n: Optional[int] = None, is_dc: bool = False, max_iter: int = 10,
               tol_mva: float = 1e-8):
         lane0, n = self._range(lane0, n)
-        check(self._lib.gpf_runpf(self._h, lane0, n, int(bool(is_dc)), int(max_iter), float(tol_mva)), "gpf_runpf")
+        self._call("gpf_runpf", lane0, n, int(bool(is_dc)), int(max_iter), float(tol_mva))
+
+    def _result_arrays(self, n, with_bus=True):
+        """out, topo_vect, shunt_bus, line_status (uint8), status, bus_vm, bus_va of ``n`` lanes, uninitialised (the last two None without
+        ``with_bus``): what `gpf_get_results` / `gpf_solve_lane` fill."""
+        m = self.model
+        arrs = [np.empty((n, cols), dtype=dt) for cols, dt in ((self.n_out, np.float32), (m.dim_topo, np.int32), (m.n_shunt, np.int32),
+                                                               (m.n_line, np.uint8), (4, np.int32))]
+        return arrs + [np.empty((n, self.nb_total), dtype=np.float64) if with_bus else None for _ in range(2)]
 
     def solve_lane(self, lane: int, inj: np.ndarray, topo: np.ndarray, shunt_bus: Optional[np.ndarray] = None, is_dc: bool = False,
                    max_iter: int = 10, tol_mva: float = 1e-8) -> LaneResults:
@@ -616,17 +682,9 @@ class PowerFlowEngine:
         inj = np.ascontiguousarray(inj, dtype=np.float64).reshape(self.n_inj)
         topo = np.ascontiguousarray(topo, dtype=np.int32).reshape(m.dim_topo)
         sb_in = None if not m.n_shunt else np.ascontiguousarray(shunt_bus, dtype=np.int32).reshape(m.n_shunt)
-        out = np.empty((1, self.n_out), dtype=np.float32)
-        tv = np.empty((1, m.dim_topo), dtype=np.int32)
-        sb = np.empty((1, m.n_shunt), dtype=np.int32)
-        ls = np.empty((1, m.n_line), dtype=np.uint8)
-        st = np.empty((1, 4), dtype=np.int32)
-        bvm = np.empty((1, self.nb_total), dtype=np.float64)
-        bva = np.empty((1, self.nb_total), dtype=np.float64)
-        check(self._lib.gpf_solve_lane(self._h, int(lane), ptr(inj, C.c_double), ptr(topo, C.c_int32), ptr(sb_in, C.c_int32),
-                                       int(bool(is_dc)), int(max_iter), float(tol_mva), ptr(out, C.c_float), ptr(tv, C.c_int32),
-                                       ptr(sb, C.c_int32), ptr(ls, C.c_uint8), ptr(st, C.c_int32), ptr(bvm, C.c_double),
-                                       ptr(bva, C.c_double)), "gpf_solve_lane")
+        out, tv, sb, ls, st, bvm, bva = self._result_arrays(1)
+        self._call("gpf_solve_lane", int(lane), _ptr(inj), _ptr(topo), _ptr(sb_in), int(bool(is_dc)), int(max_iter), float(tol_mva),
+                   _ptr(out), _ptr(tv), _ptr(sb), _ptr(ls), _ptr(st), _ptr(bvm), _ptr(bva))
         return LaneResults(out=out, topo_vect=tv, shunt_bus=sb, line_status=ls.astype(bool), status=st, bus_vm=bvm, bus_va=bva,
                            _slices=self.out_slices)
 
@@ -639,7 +697,7 @@ class PowerFlowEngine:
         if pinned:
             ptrs = (C.c_void_p * 8)()
             what = 0b0011111 | (0b1100000 if with_bus else 0)
-            check(self._lib.gpf_get_results_pinned(self._h, lane0, n, what, ptrs), "gpf_get_results_pinned")
+            self._call("gpf_get_results_pinned", lane0, n, what, ptrs)
 
             def arr(k, cols, ctype, dtype):
                 if not ptrs[k] or cols == 0:
@@ -649,16 +707,8 @@ class PowerFlowEngine:
                                shunt_bus=arr(2, m.n_shunt, C.c_int32, np.int32), line_status=arr(3, m.n_line, C.c_uint8, np.uint8).view(np.bool_),
                                status=arr(4, 4, C.c_int32, np.int32), bus_vm=arr(5, self.nb_total, C.c_double, np.float64) if with_bus else None,
                                bus_va=arr(6, self.nb_total, C.c_double, np.float64) if with_bus else None, _slices=self.out_slices)
-        out = np.empty((n, self.n_out), dtype=np.float32)
-        tv = np.empty((n, m.dim_topo), dtype=np.int32)
-        sb = np.empty((n, m.n_shunt), dtype=np.int32)
-        ls = np.empty((n, m.n_line), dtype=np.uint8)
-        st = np.empty((n, 4), dtype=np.int32)
-        bvm = np.empty((n, self.nb_total), dtype=np.float64) if with_bus else None
-        bva = np.empty((n, self.nb_total), dtype=np.float64) if with_bus else None
-        check(self._lib.gpf_get_results(self._h, lane0, n, ptr(out, C.c_float), ptr(tv, C.c_int32), ptr(sb, C.c_int32),
-                                        ptr(ls, C.c_uint8), ptr(st, C.c_int32), ptr(bvm, C.c_double), ptr(bva, C.c_double)),
-              "gpf_get_results")
+        out, tv, sb, ls, st, bvm, bva = self._result_arrays(n, with_bus)
+        self._call("gpf_get_results", lane0, n, _ptr(out), _ptr(tv), _ptr(sb), _ptr(ls), _ptr(st), _ptr(bvm), _ptr(bva))
         return LaneResults(out=out, topo_vect=tv, shunt_bus=sb, line_status=ls.astype(bool), status=st, bus_vm=bvm,
                            bus_va=bva, _slices=self.out_slices)
 
@@ -672,50 +722,39 @@ class PowerFlowEngine:
         if tables.ndim == 2:
             tables = tables[None]
         assert tables.shape[2] == self.n_chron, (tables.shape, self.n_chron)
-        check(self._lib.gpf_upload_chronics(self._h, tables.shape[0], tables.shape[1], ptr(tables, C.c_float)),
-              "gpf_upload_chronics")
+        self._call("gpf_upload_chronics", tables.shape[0], tables.shape[1], _ptr(tables))
         self.chron_T = tables.shape[1]
         self.chron_tables = tables.shape[0]
+
+    def _upload_line_table(self, name, table, dtype):
+        """A per-line table of the uploaded chronics, ``[n_tables, T, n_line]`` (or ``[T, n_line]``); None removes it."""
+        if table is None:
+            self._call(name, 0, 0, None)
+            return
+        t = np.ascontiguousarray(table, dtype=dtype)
+        if t.ndim == 2:
+            t = t[None]
+        assert t.shape[2] == self.model.n_line
+        self._call(name, t.shape[0], t.shape[1], _ptr(t))
 
     def upload_maintenance(self, maintenance):
         """Scheduled maintenance of the uploaded tables: ``[n_tables, T, n_line]`` (or ``[T, n_line]``) 0/1; None removes it."""
         self._has_maint = maintenance is not None
-        self._has_outages = self._has_maint or getattr(self, "_has_hazard", False)
-        if maintenance is None:
-            check(self._lib.gpf_upload_maintenance(self._h, 0, 0, None), "gpf_upload_maintenance")
-            return
-        mt = np.ascontiguousarray(maintenance, dtype=np.uint8)
-        if mt.ndim == 2:
-            mt = mt[None]
-        assert mt.shape[2] == self.model.n_line
-        check(self._lib.gpf_upload_maintenance(self._h, mt.shape[0], mt.shape[1], ptr(mt, C.c_uint8)), "gpf_upload_maintenance")
+        self._has_outages = self._has_maint or self._has_hazard
+        self._upload_line_table("gpf_upload_maintenance", maintenance, np.uint8)
 
     def upload_outage_durations(self, durations):
         """Remaining duration of the maintenance / hazard under way at every row, ``[n_tables, T, n_line]`` (or ``[T, n_line]``): what the line
         cooldowns are held at during an outage.  Only needed when the uploaded tables are a window of longer chronics (the library derives
         the durations from the outage tables otherwise); None: derived again."""
-        if durations is None:
-            check(self._lib.gpf_upload_outage_durations(self._h, 0, 0, None), "gpf_upload_outage_durations")
-            return
-        d = np.ascontiguousarray(np.minimum(np.asarray(durations), 65535), dtype=np.uint16)
-        if d.ndim == 2:
-            d = d[None]
-        assert d.shape[2] == self.model.n_line
-        check(self._lib.gpf_upload_outage_durations(self._h, d.shape[0], d.shape[1], d.ctypes.data_as(C.POINTER(C.c_uint16))), "gpf_upload_outage_durations")
+        self._upload_line_table("gpf_upload_outage_durations", None if durations is None else np.minimum(np.asarray(durations), 65535), np.uint16)
 
     def upload_hazards(self, hazards):
         """Hazards of the uploaded tables (``hazards.csv``: unplanned outages): ``[n_tables, T, n_line]`` (or ``[T, n_line]``) 0/1; None
         removes them.  Independent of the maintenance table; a line is out of service where either flags it."""
         self._has_hazard = hazards is not None
-        self._has_outages = self._has_hazard or getattr(self, "_has_maint", False)
-        if hazards is None:
-            check(self._lib.gpf_upload_hazards(self._h, 0, 0, None), "gpf_upload_hazards")
-            return
-        hz = np.ascontiguousarray(hazards, dtype=np.uint8)
-        if hz.ndim == 2:
-            hz = hz[None]
-        assert hz.shape[2] == self.model.n_line
-        check(self._lib.gpf_upload_hazards(self._h, hz.shape[0], hz.shape[1], ptr(hz, C.c_uint8)), "gpf_upload_hazards")
+        self._has_outages = self._has_hazard or self._has_maint
+        self._upload_line_table("gpf_upload_hazards", hazards, np.uint8)
 
     def set_lane_chronics(self, lane_table=None, lane_offset=None, lane_scale=None):
         lt = None if lane_table is None else np.ascontiguousarray(lane_table, dtype=np.int32)
@@ -727,13 +766,12 @@ class PowerFlowEngine:
             assert lo.size == self.n_lanes
         if ls is not None:
             assert ls.shape == (self.n_lanes, 2 * self.model.n_load)
-        check(self._lib.gpf_set_lane_chronics(self._h, ptr(lt, C.c_int32), ptr(lo, C.c_int32), ptr(ls, C.c_float)),
-              "gpf_set_lane_chronics")
+        self._call("gpf_set_lane_chronics", _ptr(lt), _ptr(lo), _ptr(ls))
 
     def set_thermal_limits(self, limit_a):
         lim = np.ascontiguousarray(limit_a, dtype=np.float32)
         assert lim.size == self.model.n_line
-        check(self._lib.gpf_set_thermal_limits(self._h, ptr(lim, C.c_float)), "gpf_set_thermal_limits")
+        self._call("gpf_set_thermal_limits", _ptr(lim))
 
     def step(self, t: int, max_iter: int = 10, tol_mva: float = 1e-8, rebalance: float = 0.0, cascade: bool = False,
              hard_overflow: float = 2.0, soft_overflow: float = 1.0, nb_ts_allowed: int = 2, max_rounds: int = 16,
@@ -746,10 +784,10 @@ class PowerFlowEngine:
         maintained at every step -- default: 10 (the reference's default) when lines can go out by themselves (``cascade`` or uploaded
         maintenance / hazard tables), else not tracked; -1 switches the tracking off."""
         if nb_ts_reco is None:
-            nb_ts_reco = 10 if (cascade or getattr(self, "_has_outages", False)) else -1
+            nb_ts_reco = 10 if (cascade or self._has_outages) else -1
         o = GpfStepOpts(int(max_iter), float(tol_mva), float(rebalance), int(bool(cascade)), float(hard_overflow), float(soft_overflow),
                         int(nb_ts_allowed), int(max_rounds), int(bool(is_dc)), int(bool(auto_reset)), int(bool(warm_start)), int(nb_ts_reco >= 0), max(int(nb_ts_reco), 0))
-        check(self._lib.gpf_step_n(self._h, int(t), int(n_steps), C.byref(o)), "gpf_step_n")
+        self._call("gpf_step_n", int(t), int(n_steps), C.byref(o))
 
     def set_lane_redispatch(self, delta_mw):
         """Per-lane additive generator set-point delta (MW, ``[n_lanes, n_gen]``; None switches it off): the redispatch the
@@ -757,7 +795,7 @@ class PowerFlowEngine:
         d = None if delta_mw is None else np.ascontiguousarray(delta_mw, dtype=np.float32)
         if d is not None:
             assert d.shape == (self.n_lanes, self.model.n_gen)
-        check(self._lib.gpf_set_lane_redispatch(self._h, ptr(d, C.c_float)), "gpf_set_lane_redispatch")
+        self._call("gpf_set_lane_redispatch", _ptr(d))
 
     def set_gen_limits(self, pmin, pmax, ramp_up, ramp_down, redispatchable, eps_poly: float = 1e-4):
         """Generator characteristics (``prods_charac.csv``: Pmin, Pmax, max_ramp_up, max_ramp_down, redispatchable) for
@@ -766,8 +804,7 @@ class PowerFlowEngine:
         a = [f64(pmin), f64(pmax), f64(ramp_up), f64(ramp_down)]
         r = np.ascontiguousarray(redispatchable, dtype=np.uint8)
         assert all(x.size == self.model.n_gen for x in a) and r.size == self.model.n_gen
-        check(self._lib.gpf_set_gen_limits(self._h, *[ptr(x, C.c_double) for x in a], ptr(r, C.c_uint8), float(eps_poly)),
-              "gpf_set_gen_limits")
+        self._call("gpf_set_gen_limits", *[_ptr(x) for x in a], _ptr(r), float(eps_poly))
 
     def redispatch(self, new_p, prev_p, actual, target, modified, rhs, lane0: int = 0, apply: bool = False):
         """The environment's redispatching automaton for a batch of lanes (``BaseEnv._compute_dispatch_vect``): rows
@@ -781,9 +818,8 @@ class PowerFlowEngine:
         rhs = np.ascontiguousarray(np.broadcast_to(np.asarray(rhs, dtype=np.float64), (n,)))
         ok = np.empty(n, dtype=np.uint8)
         after = np.empty((n, self.model.n_gen), dtype=np.float32)
-        check(self._lib.gpf_redispatch(self._h, int(lane0), n, ptr(new_p, C.c_double), ptr(prev_p, C.c_double), ptr(actual, C.c_double),
-                                       ptr(target, C.c_double), ptr(mod, C.c_uint8), ptr(rhs, C.c_double), int(bool(apply)),
-                                       ptr(ok, C.c_uint8), ptr(after, C.c_float)), "gpf_redispatch")
+        self._call("gpf_redispatch", int(lane0), n, _ptr(new_p), _ptr(prev_p), _ptr(actual), _ptr(target), _ptr(mod), _ptr(rhs),
+                   int(bool(apply)), _ptr(ok), _ptr(after))
         return ok.astype(bool), after
 
     TRAJ_RHO, TRAJ_OBS = 1, 2
@@ -796,14 +832,13 @@ class PowerFlowEngine:
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(self.model.n_storage)  # noqa: E731
         a = [f64(emax), f64(emin), f64(loss), f64(eff_charge), f64(eff_discharge)]
         c0 = np.ascontiguousarray(charge0, dtype=np.float32).reshape(self.model.n_storage)
-        check(self._lib.gpf_set_storage_params(self._h, *[ptr(x, C.c_double) for x in a], ptr(c0, C.c_float), float(delta_time_seconds),
-                                               int(bool(activate_loss))), "gpf_set_storage_params")
+        self._call("gpf_set_storage_params", *[_ptr(x) for x in a], _ptr(c0), float(delta_time_seconds), int(bool(activate_loss)))
 
     def set_env_dynamics(self, on: bool = True, tol_poly: float = 1e-2):
         """Switch the environment's injection dynamics on: every step of `step` then evolves the storage state of charge and
         re-solves the ramp-limited redispatch (BaseEnv.step's path between the chronics and the backend); needs `set_gen_limits`
         (and `set_storage_params` on a grid with storage units).  Resets the dynamics of every lane."""
-        check(self._lib.gpf_set_env_dynamics(self._h, int(bool(on)), float(tol_poly)), "gpf_set_env_dynamics")
+        self._call("gpf_set_env_dynamics", int(bool(on)), float(tol_poly))
         self.env_dynamics_on = bool(on)
 
     def set_lane_actions(self, redispatch=None, storage_power=None, hold_storage: bool = False):
@@ -812,7 +847,7 @@ class PowerFlowEngine:
         r = None if redispatch is None else np.ascontiguousarray(redispatch, dtype=np.float32).reshape(self.n_lanes, self.model.n_gen)
         s_ = None if storage_power is None or not self.model.n_storage else \
             np.ascontiguousarray(storage_power, dtype=np.float32).reshape(self.n_lanes, self.model.n_storage)
-        check(self._lib.gpf_set_lane_actions(self._h, ptr(r, C.c_float), ptr(s_, C.c_float), int(bool(hold_storage))), "gpf_set_lane_actions")
+        self._call("gpf_set_lane_actions", _ptr(r), _ptr(s_), int(bool(hold_storage)))
 
     def lane_actions_on_device(self, redispatch: bool = False, storage_power: bool = False, curtailment: bool = False,
                                hold_storage: bool = False):
@@ -820,16 +855,14 @@ class PowerFlowEngine:
         "act_curtail"]`` (on ``views["stream"]`` or ordered before the launch): say which buffers hold an action.  Same semantics as
         `set_lane_actions` / `set_lane_curtailment`, no PCIe transfer, no synchronisation -- the hand-over of an agent that lives next
         to the engine (curtailment ratios are NOT range-checked on this path)."""
-        check(self._lib.gpf_lane_actions_on_device(self._h, int(bool(redispatch)), int(bool(storage_power)), int(bool(curtailment)),
-                                                   int(bool(hold_storage))), "gpf_lane_actions_on_device")
+        self._call("gpf_lane_actions_on_device", int(bool(redispatch)), int(bool(storage_power)), int(bool(curtailment)), int(bool(hold_storage)))
 
     # ---- topology actions in the batched step (include/gridpf.h: gpf_upload_topo_actions) ------------------------------------
     def set_topo_rules(self, max_sub_changed: int = 1, max_line_status_changed: int = 1, cooldown_sub: int = 0, cooldown_line: int = 0,
                        legal_rules: bool = True):
         """Parameters.MAX_SUB_CHANGED / MAX_LINE_STATUS_CHANGED (DefaultRules; ``legal_rules=False``: AlwaysLegal) and
         NB_TIMESTEP_COOLDOWN_SUB / NB_TIMESTEP_COOLDOWN_LINE of the topology actions of the batched step."""
-        check(self._lib.gpf_set_topo_rules(self._h, int(bool(legal_rules)), int(max_sub_changed), int(max_line_status_changed),
-                                           int(cooldown_sub), int(cooldown_line)), "gpf_set_topo_rules")
+        self._call("gpf_set_topo_rules", int(bool(legal_rules)), int(max_sub_changed), int(max_line_status_changed), int(cooldown_sub), int(cooldown_line))
 
     def upload_topo_actions(self, actions) -> np.ndarray:
         """The action table of the topology actions (dicts as `pack_actions` takes them); returns the static ambiguity flags (bool ``[n]``).
@@ -838,8 +871,7 @@ class PowerFlowEngine:
         n = len(off) - 1
         amb = np.zeros(max(n, 1), dtype=np.uint8)
         items = np.ascontiguousarray(items, dtype=np.int32)
-        check(self._lib.gpf_upload_topo_actions(self._h, n, ptr(off, C.c_int32), ptr(items if items.size else None, C.c_int32),
-                                                ptr(amb, C.c_uint8)), "gpf_upload_topo_actions")
+        self._call("gpf_upload_topo_actions", n, _ptr(off), _ptr(items if items.size else None), _ptr(amb))
         self._n_topo_act = n
         self._mask_view = None               # (the engine-owned mask buffer is re-allocated with the table)
         return amb[:n].astype(bool)
@@ -850,7 +882,7 @@ class PowerFlowEngine:
         area of its origin substation.  None: whole-grid limits again (the default)."""
         n_sub = self.model.n_sub
         if areas is None or len(areas) == 0:
-            check(self._lib.gpf_set_topo_areas(self._h, 0, None), "gpf_set_topo_areas")
+            self._call("gpf_set_topo_areas", 0, None)
             return
         if np.ndim(areas[0]) == 0:
             sub_area = np.ascontiguousarray(areas, dtype=np.int32)
@@ -865,56 +897,48 @@ class PowerFlowEngine:
                     raise ValueError("set_topo_areas: a substation id is out of range or listed twice")
                 sub_area[subs] = k
             n_area = len(areas)
-        check(self._lib.gpf_set_topo_areas(self._h, n_area, ptr(sub_area, C.c_int32)), "gpf_set_topo_areas")
+        self._call("gpf_set_topo_areas", n_area, _ptr(sub_area))
 
     def set_topo_slots(self, n_slot: int = 1):
         """Table entries a lane plays per step (1..8): the concatenation, in slot order, of the non-empty slots' item lists is played as
         ONE action.  Changing it drops pending indices; ``device_views()["act_topo"]`` becomes ``[n_lanes, n_slot]``."""
-        check(self._lib.gpf_set_topo_slots(self._h, int(n_slot)), "gpf_set_topo_slots")
+        self._call("gpf_set_topo_slots", int(n_slot))
         self._n_topo_slot = int(n_slot)
 
     def topo_action_areas(self) -> np.ndarray:
         """uint32 ``[n_act]``: bit k set when the table entry can touch area k (every substation it names, both ends of every line it
         names).  Entries of the slots of one lane with pairwise disjoint area sets are applied exactly when each has mask byte 0."""
-        out = np.zeros(max(int(getattr(self, "_n_topo_act", 0)), 1), dtype=np.uint32)
-        check(self._lib.gpf_get_topo_action_areas(self._h, ptr(out, C.c_uint32)), "gpf_get_topo_action_areas")
-        return out[:int(getattr(self, "_n_topo_act", 0))]
+        out = np.zeros(max(int(self._n_topo_act), 1), dtype=np.uint32)
+        self._call("gpf_get_topo_action_areas", _ptr(out))
+        return out[:int(self._n_topo_act)]
 
     def set_lane_topo_actions(self, index):
         """Entries of the action table every lane plays at the NEXT launch (int ``[n_lanes]`` with one slot, ``[n_lanes, n_slot]`` else;
         -1 = empty slot, all empty = do nothing; None: none) -- that launch must be a one-step launch."""
-        a = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(self.n_lanes * int(getattr(self, "_n_topo_slot", 1)))
-        check(self._lib.gpf_set_lane_topo_actions(self._h, ptr(a, C.c_int32)), "gpf_set_lane_topo_actions")
+        a = None if index is None else np.ascontiguousarray(index, dtype=np.int32).reshape(self.n_lanes * int(self._n_topo_slot))
+        self._call("gpf_set_lane_topo_actions", _ptr(a))
 
     def topo_actions_on_device(self, on: bool = True):
         """The NEXT launch takes the indices written into ``device_views()["act_topo"]`` (on ``views["stream"]`` or ordered before it)."""
-        check(self._lib.gpf_topo_actions_on_device(self._h, int(bool(on))), "gpf_topo_actions_on_device")
-
-    def _topo_rows(self, fn, cols, dtype, ctype, lane0, n):
-        lane0, n = self._range(lane0, n)
-        out = np.empty((n, cols), dtype=dtype)
-        check(getattr(self._lib, fn)(self._h, lane0, n, ptr(out, ctype)), fn)
-        return out
+        self._call("gpf_topo_actions_on_device", int(bool(on)))
 
     def sub_cooldown(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """obs.time_before_cooldown_sub of the lanes, int32 ``[n, n_sub]``."""
-        return self._topo_rows("gpf_get_sub_cooldown", self.model.n_sub, np.int32, C.c_int32, lane0, n)
+        return self._get_rows("gpf_get_sub_cooldown", lane0, n, (self.model.n_sub, np.int32))
 
     def set_sub_cooldown(self, sub_cooldown, lane0: int = 0):
-        c = np.ascontiguousarray(sub_cooldown, dtype=np.int32).reshape(-1, self.model.n_sub)
-        check(self._lib.gpf_set_sub_cooldown(self._h, int(lane0), c.shape[0], ptr(c, C.c_int32)), "gpf_set_sub_cooldown")
+        self._set_rows("gpf_set_sub_cooldown", sub_cooldown, self.model.n_sub, np.int32, lane0)
 
     def last_bus(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Last known busbar of every element (where a reconnected line end goes back to), int32 ``[n, dim_topo]``."""
-        return self._topo_rows("gpf_get_last_bus", self.model.dim_topo, np.int32, C.c_int32, lane0, n)
+        return self._get_rows("gpf_get_last_bus", lane0, n, (self.model.dim_topo, np.int32))
 
     def set_last_bus(self, last_bus, lane0: int = 0):
-        c = np.ascontiguousarray(last_bus, dtype=np.int32).reshape(-1, self.model.dim_topo)
-        check(self._lib.gpf_set_last_bus(self._h, int(lane0), c.shape[0], ptr(c, C.c_int32)), "gpf_set_last_bus")
+        self._set_rows("gpf_set_last_bus", last_bus, self.model.dim_topo, np.int32, lane0)
 
     def topo_action_flags(self, lane0: int = 0, n: Optional[int] = None):
         """(is_illegal, is_ambiguous) bool ``[n]`` of the last launch that carried topology actions."""
-        f = self._topo_rows("gpf_get_topo_flags", 2, np.uint8, C.c_uint8, lane0, n)
+        f = self._get_rows("gpf_get_topo_flags", lane0, n, (2, np.uint8))
         return f[:, 0].astype(bool), f[:, 1].astype(bool)
 
     def topo_action_mask(self, lane0: int = 0, n: Optional[int] = None, out=None):
@@ -925,27 +949,19 @@ class PowerFlowEngine:
         ``device_views()["topo_mask"]`` (rewritten by the next call); ``out`` may be a caller's uint8 CUDA tensor ``[n, >= n_act]`` with unit
         column stride and any row stride >= n_act -- only the first ``n_act`` columns of its rows are written."""
         lane0, n = self._range(lane0, n)
-        n_act = int(getattr(self, "_n_topo_act", 0))
         if out is None:
-            check(self._lib.gpf_topo_action_mask(self._h, lane0, n, None, 0), "gpf_topo_action_mask")
-            if getattr(self, "_mask_view", None) is None:
+            self._call("gpf_topo_action_mask", lane0, n, None, 0)
+            if self._mask_view is None:
                 self._mask_view = self.device_views()["topo_mask"]
             return self._mask_view[lane0:lane0 + n]
-        import torch
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2):
-            raise ValueError("topo_action_mask: out must be a 2-d uint8 CUDA tensor")
-        if out.device.index != self.device or out.shape[0] != n or out.stride(1) != 1:
-            raise ValueError(f"topo_action_mask: out must live on cuda:{self.device} and have {n} rows with unit column stride")
-        # rows narrower than the table: the library refuses their width as the stride, with its message
-        stride = int(out.stride(0)) if n > 1 and out.shape[1] >= n_act else int(out.shape[1])
-        check(self._lib.gpf_topo_action_mask(self._h, lane0, n, C.c_void_p(out.data_ptr()), stride), "gpf_topo_action_mask")
-        return out[:, :n_act]
+        self._call("gpf_topo_action_mask", lane0, n, *self._out_rows("topo_action_mask", out, "uint8", n, self._n_topo_act, True))
+        return out[:, :self._n_topo_act]
 
     def topo_action_mask_host(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """`topo_action_mask` copied to the host: uint8 ``[n, n_act]`` (synchronous)."""
         lane0, n = self._range(lane0, n)
-        out = np.empty((n, int(getattr(self, "_n_topo_act", 0))), dtype=np.uint8)
-        check(self._lib.gpf_get_topo_action_mask(self._h, lane0, n, ptr(out if out.size else None, C.c_uint8)), "gpf_get_topo_action_mask")
+        out = np.empty((n, int(self._n_topo_act)), dtype=np.uint8)
+        self._call("gpf_get_topo_action_mask", lane0, n, _ptr(out if out.size else None))
         return out
 
     # ---- the opponent (include/gridpf.h gpf_set_opponent; grid2op_amd/csrc/gridpf_opponent.hpp) -------
@@ -959,7 +975,7 @@ class PowerFlowEngine:
         self._alert = None                   # gpf_set_opponent turns alerts off
         self._opp_n_lines = 0
         if kind is None or int(kind) == OPP_NONE:
-            check(self._lib.gpf_set_opponent(self._h, None), "gpf_set_opponent")
+            self._call("gpf_set_opponent", None)
             self._opp_cap = self._opp_n_area = 0
             return
         ids = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1)
@@ -968,43 +984,40 @@ class PowerFlowEngine:
             raise ValueError("set_opponent: rho_normalization must have one entry per attackable line")
         self._opp_n_lines = int(ids.size)
         d = GpfOpponentDesc()
-        d.kind, d.n_lines, d.line_ids, d.rho_normalization = int(kind), int(ids.size), ptr(ids if ids.size else None, C.c_int32), ptr(norm, C.c_double)
+        d.kind, d.n_lines, d.line_ids, d.rho_normalization = int(kind), int(ids.size), _ptr(ids if ids.size else None), _ptr(norm)
         d.attack_period, d.attack_hazard_rate, d.recovery_rate = int(attack_period), float(attack_hazard_rate), float(recovery_rate)
         d.recovery_minimum_duration, d.pmax_pmin_ratio, d.episode_max_time = int(recovery_minimum_duration), float(pmax_pmin_ratio), int(episode_max_time)
         d.init_budget, d.budget_per_ts = float(np.float32(init_budget)), float(np.float32(budget_per_ts))
         d.attack_duration, d.attack_cooldown, d.draw_source = int(attack_duration), int(attack_cooldown), int(draw_source)
         d.seed_lo, d.seed_hi, d.lane_base, d.schedule_cap = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(lane_base), int(schedule_cap)
-        check(self._lib.gpf_set_opponent(self._h, C.byref(d)), "gpf_set_opponent")
+        self._call("gpf_set_opponent", C.byref(d))
         self._opp_cap, self._opp_n_area = (int(schedule_cap) if int(kind) == OPP_GEOMETRIC else 0), 0
 
     def upload_opponent_draws(self, draws):
         """Table source: float64 ``[n_lanes, n_draw]`` uniforms in [0, 1), consumed per lane in event order; the cursors go back to 0."""
         u = np.ascontiguousarray(draws, dtype=np.float64).reshape(self.n_lanes, -1)
-        check(self._lib.gpf_upload_opponent_draws(self._h, u.shape[1], ptr(u if u.size else None, C.c_double)), "gpf_upload_opponent_draws")
+        self._call("gpf_upload_opponent_draws", u.shape[1], _ptr(u if u.size else None))
 
     def upload_opponent_schedule(self, schedule, count):
         """Geometric opponent, table source: int32 ``[n_lanes, k, 2]`` {waiting time, duration} (``k`` <= the schedule capacity) and the
         number of entries of every lane -- what the opponent's reset sampled."""
-        cap = int(getattr(self, "_opp_cap", 0))
+        cap = int(self._opp_cap)
         sch = np.asarray(schedule, dtype=np.int32).reshape(self.n_lanes, -1, 2)
         if sch.shape[1] > cap:
             raise ValueError(f"upload_opponent_schedule: {sch.shape[1]} entries per lane exceed the schedule capacity {cap}")
         full = np.zeros((self.n_lanes, max(cap, 1), 2), dtype=np.int32)
         full[:, :sch.shape[1]] = sch
         cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(count, dtype=np.int32), (self.n_lanes,)))
-        check(self._lib.gpf_upload_opponent_schedule(self._h, ptr(full, C.c_int32), ptr(cnt, C.c_int32)), "gpf_upload_opponent_schedule")
+        self._call("gpf_upload_opponent_schedule", _ptr(full), _ptr(cnt))
 
     def opponent_state(self, lane0: int = 0, n: Optional[int] = None) -> "OpponentState":
         """The lanes' opponent state with ``opponent_attack_line`` (-1: none) / ``opponent_attack_duration`` of the last launch (synchronous)."""
-        lane0, n = self._range(lane0, n)
-        bud, rows = np.zeros(n, dtype=np.float64), np.zeros((n, OPP_STATE_INTS), dtype=np.int32)
-        check(self._lib.gpf_get_opponent_state(self._h, lane0, n, ptr(bud, C.c_double), ptr(rows, C.c_int32)), "gpf_get_opponent_state")
-        return OpponentState.from_rows(bud, rows)
+        return OpponentState.from_rows(*self._get_rows("gpf_get_opponent_state", lane0, n, (None, np.float64), (OPP_STATE_INTS, np.int32), zeros=True))
 
     def set_opponent_state(self, state: "OpponentState", lane0: int = 0):
         bud = np.ascontiguousarray(state.budget, dtype=np.float64)
         rows = np.ascontiguousarray(state.rows())
-        check(self._lib.gpf_set_opponent_state(self._h, int(lane0), len(bud), ptr(bud, C.c_double), ptr(rows, C.c_int32)), "gpf_set_opponent_state")
+        self._call("gpf_set_opponent_state", int(lane0), len(bud), _ptr(bud), _ptr(rows))
 
     # ---- the multi-area opponent (include/gridpf.h gpf_set_opponent_areas) ----------------------------
     def set_opponent_areas(self, area_of_line):
@@ -1014,13 +1027,13 @@ class PowerFlowEngine:
         a = np.zeros(0, np.int32) if area_of_line is None else np.ascontiguousarray(area_of_line, dtype=np.int32).reshape(-1)
         n_area = int(a.max()) + 1 if a.size else 0
         self._alert = None                   # ... and so does gpf_set_opponent_areas
-        check(self._lib.gpf_set_opponent_areas(self._h, n_area, ptr(a if a.size else None, C.c_int32)), "gpf_set_opponent_areas")
+        self._call("gpf_set_opponent_areas", n_area, _ptr(a if a.size else None))
         self._opp_n_area = n_area
 
     def upload_opponent_area_schedule(self, schedule, count):
         """Table source: int32 ``[n_lanes, n_area, k, 2]`` {waiting time, duration} (``k`` <= the schedule capacity) and ``[n_lanes, n_area]``
         entries -- what every area's reset sampled."""
-        cap, na = int(getattr(self, "_opp_cap", 0)), int(getattr(self, "_opp_n_area", 0))
+        cap, na = int(self._opp_cap), int(self._opp_n_area)
         sch = np.asarray(schedule, dtype=np.int32)
         sch = np.broadcast_to(sch, (self.n_lanes,) + sch.shape[-3:]) if sch.ndim == 3 else sch.reshape(self.n_lanes, na, -1, 2)
         if sch.shape[2] > cap:
@@ -1028,24 +1041,21 @@ class PowerFlowEngine:
         full = np.zeros((self.n_lanes, na, max(cap, 1), 2), dtype=np.int32)
         full[:, :, :sch.shape[2]] = sch
         cnt = np.ascontiguousarray(np.broadcast_to(np.asarray(count, dtype=np.int32), (self.n_lanes, na)))
-        check(self._lib.gpf_upload_opponent_area_schedule(self._h, ptr(full, C.c_int32), ptr(cnt, C.c_int32)), "gpf_upload_opponent_area_schedule")
+        self._call("gpf_upload_opponent_area_schedule", _ptr(full), _ptr(cnt))
 
     def opponent_area_state(self, lane0: int = 0, n: Optional[int] = None) -> "OpponentAreaState":
         lane0, n = self._range(lane0, n)
-        rows = np.zeros((n, max(int(getattr(self, "_opp_n_area", 0)), 1), OPP_AREA_STATE_INTS), dtype=np.int32)
-        check(self._lib.gpf_get_opponent_area_state(self._h, lane0, n, ptr(rows, C.c_int32)), "gpf_get_opponent_area_state")
+        rows = np.zeros((n, max(int(self._opp_n_area), 1), OPP_AREA_STATE_INTS), dtype=np.int32)
+        self._call("gpf_get_opponent_area_state", lane0, n, _ptr(rows))
         return OpponentAreaState.from_rows(rows)
 
     def set_opponent_area_state(self, state: "OpponentAreaState", lane0: int = 0):
         rows = np.ascontiguousarray(state.rows())
-        check(self._lib.gpf_set_opponent_area_state(self._h, int(lane0), rows.shape[0], ptr(rows, C.c_int32)), "gpf_set_opponent_area_state")
+        self._call("gpf_set_opponent_area_state", int(lane0), rows.shape[0], _ptr(rows))
 
     def opponent_attack_lines(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """bool ``[n, n_line]``: ``info["opponent_attack_line"]`` of the last launch, with or without areas (synchronous)."""
-        lane0, n = self._range(lane0, n)
-        out = np.zeros((n, self.model.n_line), dtype=np.uint8)
-        check(self._lib.gpf_get_opponent_attack_lines(self._h, lane0, n, ptr(out, C.c_uint8)), "gpf_get_opponent_attack_lines")
-        return out.astype(bool)
+        return self._get_rows("gpf_get_opponent_attack_lines", lane0, n, (self.model.n_line, np.uint8), zeros=True).astype(bool)
 
     # ---- alerts and AlertReward (include/gridpf.h gpf_set_alerts; grid2op_amd/csrc/gridpf_alert.hpp) ----
     def set_alerts(self, time_window: Optional[int] = 12, reward_min_no_blackout=-1.0, reward_min_blackout=-10.0, reward_max_no_blackout=1.0,
@@ -1055,18 +1065,17 @@ class PowerFlowEngine:
         area), so call it after `set_opponent` / `set_opponent_areas`, which turn alerts off.  ``time_window`` None: off.  Every lane
         starts reset.  The end-of-episode bonus of ``AlertReward`` is paid on a step truncated by `set_episode_limit`, which carries it."""
         if time_window is None:
-            check(self._lib.gpf_set_alerts(self._h, None), "gpf_set_alerts")
+            self._call("gpf_set_alerts", None)
             self._alert = None
             return
         d = GpfAlertDesc(int(time_window), float(reward_min_no_blackout), float(reward_min_blackout), float(reward_max_no_blackout),
                          float(reward_max_blackout))
         self._alert = None
-        self._alert_host = (int(getattr(self, "_opp_n_lines", 0)), int(time_window))      # (a header-only handle refuses masks by it)
-        check(self._lib.gpf_set_alerts(self._h, C.byref(d)), "gpf_set_alerts")
-        self._alert = self._alert_host
+        self._call("gpf_set_alerts", C.byref(d))
+        self._alert = (self._opp_n_lines, int(time_window))
 
     def _alert_dims(self, what):
-        if getattr(self, "_alert", None) is None:
+        if self._alert is None:
             raise GridPFError(f"{what}: alerts are off (set_alerts)")
         return self._alert
 
@@ -1074,7 +1083,7 @@ class PowerFlowEngine:
         """The agent's alerts of the NEXT launch: bool ``[n_lanes, A]`` (A alertable lines, in the opponent's order) or uint64 ``[n_lanes]``
         masks (bit i = alertable line i); None: none.  Consumed by the launch."""
         if alerts is None:
-            check(self._lib.gpf_set_lane_alerts(self._h, None), "gpf_set_lane_alerts")
+            self._call("gpf_set_lane_alerts", None)
             return
         a = np.asarray(alerts)
         if a.ndim == 2:
@@ -1082,25 +1091,21 @@ class PowerFlowEngine:
                 raise ValueError("set_lane_alerts: at most 64 alertable lines")
             a = (a.astype(bool).astype(np.uint64) << np.arange(a.shape[1], dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
         a = np.ascontiguousarray(a, dtype=np.uint64).reshape(self.n_lanes)
-        check(self._lib.gpf_set_lane_alerts(self._h, a.ctypes.data_as(C.POINTER(C.c_uint64))), "gpf_set_lane_alerts")
+        self._call("gpf_set_lane_alerts", _ptr(a))
 
     def alerts_on_device(self, on: bool = True):
         """The NEXT launch takes the masks written into ``device_views()["act_alert"]`` (int64 ``[n_lanes]``: the bits of the uint64 mask; bits at
         or above A are dropped by the kernel)."""
-        check(self._lib.gpf_alerts_on_device(self._h, int(bool(on))), "gpf_alerts_on_device")
+        self._call("gpf_alerts_on_device", int(bool(on)))
 
     def alert_state(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """int32 ``[n, 8 A + 3 + 2 (W + 2) A]`` rows (include/gridpf.h gpf_get_alert_state; `alert_state_fields` names their parts)."""
         A, W = self._alert_dims("alert_state")
-        lane0, n = self._range(lane0, n)
-        rows = np.zeros((n, 8 * A + 3 + 2 * (W + 2) * A), dtype=np.int32)
-        check(self._lib.gpf_get_alert_state(self._h, lane0, n, ptr(rows, C.c_int32)), "gpf_get_alert_state")
-        return rows
+        return self._get_rows("gpf_get_alert_state", lane0, n, (8 * A + 3 + 2 * (W + 2) * A, np.int32), zeros=True)
 
     def set_alert_state(self, rows, lane0: int = 0):
         A, W = self._alert_dims("set_alert_state")
-        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 8 * A + 3 + 2 * (W + 2) * A)
-        check(self._lib.gpf_set_alert_state(self._h, int(lane0), r.shape[0], ptr(r, C.c_int32)), "gpf_set_alert_state")
+        self._set_rows("gpf_set_alert_state", rows, 8 * A + 3 + 2 * (W + 2) * A, np.int32, lane0)
 
     def alert_state_fields(self, rows) -> dict:
         """views of the parts of `alert_state` rows: the seven environment arrays ``[n, A]``, ``total_number_of_alert`` / ``current_id`` /
@@ -1118,21 +1123,18 @@ class PowerFlowEngine:
     def alert_reward(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """float32 ``[n]``: ``AlertReward`` of the last launch (0 on a lane that was reset or left alone); synchronous."""
         self._alert_dims("alert_reward")
-        lane0, n = self._range(lane0, n)
-        out = np.zeros(n, dtype=np.float32)
-        check(self._lib.gpf_get_alert_reward(self._h, lane0, n, ptr(out, C.c_float)), "gpf_get_alert_reward")
-        return out
+        return self._get_rows("gpf_get_alert_reward", lane0, n, (None, np.float32), zeros=True)
 
     def set_gen_renewable(self, renewable):
         """``gen_renewable`` mask (curtailment only acts on these generators); None switches curtailment off."""
         r = None if renewable is None else np.ascontiguousarray(renewable, dtype=np.uint8).reshape(self.model.n_gen)
-        check(self._lib.gpf_set_gen_renewable(self._h, ptr(r, C.c_uint8)), "gpf_set_gen_renewable")
+        self._call("gpf_set_gen_renewable", _ptr(r))
 
     def set_lane_curtailment(self, limit):
         """Curtailment action of the NEXT launch: ``[n_lanes, n_gen]`` ratios of pmax in [0, 1], -1 = no change (consumed by the
         launch's first step; the limits then stay in the lanes' state until changed)."""
         a = None if limit is None else np.ascontiguousarray(limit, dtype=np.float32).reshape(self.n_lanes, self.model.n_gen)
-        check(self._lib.gpf_set_lane_curtailment(self._h, ptr(a, C.c_float)), "gpf_set_lane_curtailment")
+        self._call("gpf_set_lane_curtailment", _ptr(a))
 
     def env_state(self, lane0: int = 0, n: Optional[int] = None) -> dict:
         """``target`` / ``actual`` dispatch, ``prev_p``, ``already_modified`` ``[n, n_gen]``, ``charge`` ``[n, n_storage]``,
@@ -1142,13 +1144,11 @@ class PowerFlowEngine:
         d = dict(target=np.empty((n, ng), np.float32), actual=np.empty((n, ng), np.float32), prev_p=np.empty((n, ng), np.float32),
                  already_modified=np.empty((n, ng), np.uint8), charge=np.empty((n, ns), np.float32), amount_prev=np.empty(n, np.float32),
                  curtail_limit=np.empty((n, ng), np.float32), curtail_prev=np.empty(n, np.float32))
-        check(self._lib.gpf_get_env_state(self._h, lane0, n, ptr(d["target"], C.c_float), ptr(d["actual"], C.c_float),
-                                          ptr(d["prev_p"], C.c_float), ptr(d["already_modified"], C.c_uint8),
-                                          ptr(d["charge"] if ns else None, C.c_float), ptr(d["amount_prev"], C.c_float),
-                                          ptr(d["curtail_limit"], C.c_float), ptr(d["curtail_prev"], C.c_float)), "gpf_get_env_state")
+        self._call("gpf_get_env_state", lane0, n, _ptr(d["target"]), _ptr(d["actual"]), _ptr(d["prev_p"]), _ptr(d["already_modified"]),
+                   _ptr(d["charge"] if ns else None), _ptr(d["amount_prev"]), _ptr(d["curtail_limit"]), _ptr(d["curtail_prev"]))
         d["already_modified"] = d["already_modified"].astype(bool)
         d["illegal"] = np.empty(n, np.int32)             # steps whose action BaseEnv.step would have cancelled as an illegal redispatch
-        check(self._lib.gpf_get_env_illegal(self._h, lane0, n, ptr(d["illegal"], C.c_int32)), "gpf_get_env_illegal")
+        self._call("gpf_get_env_illegal", lane0, n, _ptr(d["illegal"]))
         return d
 
     def set_env_state(self, lane0: int = 0, target=None, actual=None, prev_p=None, already_modified=None, charge=None, amount_prev=None,
@@ -1166,18 +1166,16 @@ class PowerFlowEngine:
         il = None if illegal is None else np.ascontiguousarray(illegal, dtype=np.int32).reshape(-1)
         n = next((x.shape[0] for x in arrs + [am, ch, ap, cl, cp] if x is not None), None)
         if il is not None:
-            check(self._lib.gpf_set_env_illegal(self._h, int(lane0), il.shape[0], ptr(il, C.c_int32)), "gpf_set_env_illegal")
+            self._call("gpf_set_env_illegal", int(lane0), il.shape[0], _ptr(il))
         if n is None:
             return
-        check(self._lib.gpf_set_env_state(self._h, int(lane0), n, ptr(arrs[0], C.c_float), ptr(arrs[1], C.c_float), ptr(arrs[2], C.c_float),
-                                          ptr(am, C.c_uint8), ptr(ch, C.c_float), ptr(ap, C.c_float), ptr(cl, C.c_float), ptr(cp, C.c_float)),
-              "gpf_set_env_state")
+        self._call("gpf_set_env_state", int(lane0), n, _ptr(arrs[0]), _ptr(arrs[1]), _ptr(arrs[2]), _ptr(am), _ptr(ch), _ptr(ap), _ptr(cl), _ptr(cp))
 
     def set_trajectory(self, n_steps_cap: int, what: int = 1):
         """Trajectory buffers of multi-step launches: ``what`` = `TRAJ_RHO` (rho + status of every step) or `TRAJ_OBS` (in
         addition the complete backend observation of every step: results row, topo_vect, shunt buses, line status).
         ``n_steps_cap = 0`` releases them."""
-        check(self._lib.gpf_set_trajectory(self._h, int(n_steps_cap), int(what)), "gpf_set_trajectory")
+        self._call("gpf_set_trajectory", int(n_steps_cap), int(what))
         self._traj_cap = int(n_steps_cap) if what else 0
 
     def trajectory(self, n_steps: int, step0: int = 0, lane0: int = 0, n: Optional[int] = None):
@@ -1185,8 +1183,7 @@ class PowerFlowEngine:
         lane0, n = self._range(lane0, n)
         rho = np.empty((n_steps, n, self.model.n_line), dtype=np.float32)
         st = np.empty((n_steps, n), dtype=np.int8)
-        check(self._lib.gpf_get_trajectory(self._h, int(step0), int(n_steps), lane0, n, ptr(rho, C.c_float), ptr(st, C.c_int8)),
-              "gpf_get_trajectory")
+        self._call("gpf_get_trajectory", int(step0), int(n_steps), lane0, n, _ptr(rho), _ptr(st))
         return rho, st
 
     def trajectory_obs(self, n_steps: int, step0: int = 0, lane0: int = 0, n: Optional[int] = None):
@@ -1198,8 +1195,7 @@ class PowerFlowEngine:
         tv = np.empty((n_steps, n, m.dim_topo), dtype=np.int32)
         sb = np.empty((n_steps, n, m.n_shunt), dtype=np.int32)
         ls = np.empty((n_steps, n, m.n_line), dtype=np.uint8)
-        check(self._lib.gpf_get_trajectory_obs(self._h, int(step0), int(n_steps), lane0, n, ptr(out, C.c_float), ptr(tv, C.c_int32),
-                                               ptr(sb, C.c_int32), ptr(ls, C.c_uint8)), "gpf_get_trajectory_obs")
+        self._call("gpf_get_trajectory_obs", int(step0), int(n_steps), lane0, n, _ptr(out), _ptr(tv), _ptr(sb), _ptr(ls))
         _, st = self.trajectory(n_steps, step0, lane0, n)
         res = []
         for k in range(n_steps):
@@ -1211,10 +1207,7 @@ class PowerFlowEngine:
 
     def episode(self, lane0: int = 0, n: Optional[int] = None):
         """(done ``[n]`` bool, steps survived since the last reset ``[n]``, auto-resets ``[n]``)."""
-        lane0, n = self._range(lane0, n)
-        done = np.empty(n, dtype=np.uint8)
-        sr = np.empty((n, 2), dtype=np.int32)
-        check(self._lib.gpf_get_episode(self._h, lane0, n, ptr(done, C.c_uint8), ptr(sr, C.c_int32)), "gpf_get_episode")
+        done, sr = self._get_rows("gpf_get_episode", lane0, n, (None, np.uint8), (2, np.int32))
         return done.astype(bool), sr[:, 0].copy(), sr[:, 1].copy()
 
     # ---- the environment's rewards (include/gridpf.h gpf_set_rewards; grid2op_amd/csrc/gridpf_reward.hpp) ----
@@ -1222,9 +1215,9 @@ class PowerFlowEngine:
         """The rewards of ``env.step`` on every lane of the one-step launches: ``slots`` is a list of up to 8 slots, each a `reward_config`
         result, a ``(kind, p)`` pair or a bare ``RW_*`` kind (the reference's ``reward_class`` first, then its ``other_rewards``);
         ``gen_cost_per_MW`` ``[n_gen]`` is needed by `RW_REDISP` / `RW_ECONOMIC`.  None or an empty list: off."""
-        self._rw_view = None
+        self._rw_view = None                 # (the engine-owned rewards are re-allocated for the new slot count)
         if not slots:
-            check(self._lib.gpf_set_rewards(self._h, 0, None, None), "gpf_set_rewards")
+            self._call("gpf_set_rewards", 0, None, None)
             self._n_reward_slot = 0
             return
         arr = (GpfRewardSlot * len(slots))()
@@ -1245,11 +1238,11 @@ class PowerFlowEngine:
         if gen_cost_per_MW is not None:
             cost = np.ascontiguousarray(gen_cost_per_MW, dtype=np.float32).reshape(self.model.n_gen)
         self._n_reward_slot = 0
-        check(self._lib.gpf_set_rewards(self._h, len(slots), arr, ptr(cost, C.c_float)), "gpf_set_rewards")
+        self._call("gpf_set_rewards", len(slots), arr, _ptr(cost))
         self._n_reward_slot = len(slots)
 
     def _reward_slots(self, what):
-        n = int(getattr(self, "_n_reward_slot", 0))
+        n = int(self._n_reward_slot)
         if n == 0:
             raise GridPFError(f"{what}: rewards are off (set_rewards)")
         return n
@@ -1257,23 +1250,13 @@ class PowerFlowEngine:
     def rewards(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """float32 ``[n, n_slot]``: the rewards of the last one-step launch (0 on a lane that was reset since); synchronous.  Refused after
         a multi-step launch, which computes none."""
-        ns = self._reward_slots("rewards")
-        lane0, n = self._range(lane0, n)
-        out = np.zeros((n, ns), dtype=np.float32)
-        check(self._lib.gpf_get_rewards(self._h, lane0, n, ptr(out, C.c_float)), "gpf_get_rewards")
-        return out
+        return self._get_rows("gpf_get_rewards", lane0, n, (self._reward_slots("rewards"), np.float32), zeros=True)
 
     def reward_views(self) -> dict:
         """``{"rewards": float32 torch tensor [n_lanes, n_slot]}`` ALIASING the engine-owned rewards (what a device-resident learner reads,
         no copy; order the reader on ``device_views()["stream"]``)."""
-        import torch
         ns = self._reward_slots("reward_views")
-        rp = (C.c_void_p * _capi.N_REWARD_POINTERS)()
-        check(self._lib.gpf_reward_device_pointers(self._h, rp, _capi.N_REWARD_POINTERS), "gpf_reward_device_pointers")
-        cap = self._lib.gpf_lane_capacity(self._h)
-        iface = {"shape": (cap, ns), "typestr": "<f4", "data": (int(rp[0]), False), "version": 2, "strides": None}
-        holder = type("_Arr", (), {"__cuda_array_interface__": iface})()
-        return {"rewards": torch.as_tensor(holder, device=torch.device("cuda", self.device))[:self.n_lanes]}
+        return self._views(self._device_pointers("gpf_reward_device_pointers", _capi.N_REWARD_POINTERS), [("rewards", 0, (ns,), "<f4")])
 
     def rewards_eval(self, lane0: int = 0, n: Optional[int] = None, flags=None, out=None):
         """The rewards of lanes ``[lane0, lane0 + n)`` on their CURRENT state (results row, rho, line status, done / status, dispatch, storage
@@ -1288,18 +1271,13 @@ class PowerFlowEngine:
             if not (isinstance(flags, torch.Tensor) and flags.is_cuda and flags.dtype == torch.uint8 and tuple(flags.shape) == (n, 2)
                     and flags.is_contiguous() and flags.device.index == self.device):
                 raise ValueError(f"rewards_eval: flags must be a contiguous uint8 CUDA tensor [{n}, 2] on cuda:{self.device}")
-            fp = C.c_void_p(flags.data_ptr())
+            fp = C.cast(flags.data_ptr(), C.POINTER(C.c_uint8))
         if out is None:
-            check(self._lib.gpf_rewards_eval(self._h, lane0, n, fp, None, 0), "gpf_rewards_eval")
-            if getattr(self, "_rw_view", None) is None:
+            self._call("gpf_rewards_eval", lane0, n, fp, None, 0)
+            if self._rw_view is None:
                 self._rw_view = self.reward_views()["rewards"]
             return self._rw_view[lane0:lane0 + n]
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2):
-            raise ValueError("rewards_eval: out must be a 2-d float32 CUDA tensor")
-        if out.device.index != self.device or out.shape[0] != n or out.stride(1) != 1:
-            raise ValueError(f"rewards_eval: out must live on cuda:{self.device} and have {n} rows with unit column stride")
-        stride = int(out.stride(0)) if n > 1 and out.shape[1] >= ns else int(out.shape[1])
-        check(self._lib.gpf_rewards_eval(self._h, lane0, n, fp, C.c_void_p(out.data_ptr()), stride), "gpf_rewards_eval")
+        self._call("gpf_rewards_eval", lane0, n, fp, *self._out_rows("rewards_eval", out, "float32", n, ns, True))
         return out[:, :ns]
 
     # ---- episode time limits (include/gridpf.h gpf_set_episode_limit; grid2op_amd/csrc/gridpf_episode.hpp) ----
@@ -1311,67 +1289,52 @@ class PowerFlowEngine:
         ``auto_reset`` a truncated lane restarts as a failed one does; while a limit is set multi-step launches are refused."""
         self._ep_on = False
         if max_steps is None:
-            check(self._lib.gpf_set_episode_limit(self._h, None), "gpf_set_episode_limit")
+            self._call("gpf_set_episode_limit", None)
             return
         d = GpfEpisodeDesc(0, None, float(per_timestep), float(alert_end_bonus))
-        lim = None
+        arrays = {}                          # referenced until the call has returned
         if np.ndim(max_steps) > 0:
-            lim = np.ascontiguousarray(max_steps, dtype=np.int32).reshape(self.n_lanes)
-            d.lane_max_steps = ptr(lim, C.c_int32)
-            on = True
+            arrays["lane_max_steps"] = np.ascontiguousarray(max_steps, dtype=np.int32).reshape(self.n_lanes)
         else:
             d.max_steps = int(max_steps)
-            on = d.max_steps > 0
-        check(self._lib.gpf_set_episode_limit(self._h, C.byref(d)), "gpf_set_episode_limit")
-        self._ep_on = on
+        _fill_pointers(d, arrays)
+        self._call("gpf_set_episode_limit", C.byref(d))
+        self._ep_on = bool(arrays) or d.max_steps > 0
 
     def _episode_on(self, what):
-        if not getattr(self, "_ep_on", False):
+        if not self._ep_on:
             raise GridPFError(f"{what}: episode limits are off (set_episode_limit)")
 
     def episode_ends(self, lane0: int = 0, n: Optional[int] = None) -> dict:
         """``terminated`` / ``truncated`` bool ``[n]``, ``length`` int32 ``[n]`` (``nb_time_step`` of the episode that ended in the last
         launch, else 0), ``duration_reward`` float32 ``[n]`` (``EpisodeDurationReward``); synchronous."""
         self._episode_on("episode_ends")
-        lane0, n = self._range(lane0, n)
-        te, tr = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
-        ln, du = np.zeros(n, np.int32), np.zeros(n, np.float32)
-        check(self._lib.gpf_get_episode_ends(self._h, lane0, n, ptr(te, C.c_uint8), ptr(tr, C.c_uint8), ptr(ln, C.c_int32), ptr(du, C.c_float)),
-              "gpf_get_episode_ends")
+        te, tr, ln, du = self._get_rows("gpf_get_episode_ends", lane0, n, (None, np.uint8), (None, np.uint8), (None, np.int32), (None, np.float32),
+                                        zeros=True)
         return dict(terminated=te.astype(bool), truncated=tr.astype(bool), length=ln, duration_reward=du)
 
     def episode_stats(self, lane0: int = 0, n: Optional[int] = None) -> dict:
         """``return_running`` / ``return_last`` float64 ``[n, n_slot]`` (sequential sums of the launches' float32 rewards; the episode under
         way / the last one that ended), ``length_last`` / ``n_episodes`` int32 ``[n]``; synchronous."""
         self._episode_on("episode_stats")
-        lane0, n = self._range(lane0, n)
-        ns = int(getattr(self, "_n_reward_slot", 0))
-        run, last = np.zeros((n, REWARD_MAX_SLOTS), np.float64), np.zeros((n, REWARD_MAX_SLOTS), np.float64)
-        ll, ne = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        check(self._lib.gpf_get_episode_stats(self._h, lane0, n, ptr(run, C.c_double), ptr(last, C.c_double), ptr(ll, C.c_int32), ptr(ne, C.c_int32)),
-              "gpf_get_episode_stats")
+        ns = self._n_reward_slot
+        run, last, ll, ne = self._get_rows("gpf_get_episode_stats", lane0, n, (REWARD_MAX_SLOTS, np.float64), (REWARD_MAX_SLOTS, np.float64),
+                                           (None, np.int32), (None, np.int32), zeros=True)
         return dict(return_running=run[:, :ns].copy(), return_last=last[:, :ns].copy(), length_last=ll, n_episodes=ne)
 
     def episode_views(self) -> dict:
         """Zero-copy torch tensors ALIASING the episode buffers (order the reader on ``device_views()["stream"]``): ``limit`` int32
         ``[n_lanes]`` (writable: the next launch reads it), ``terminated`` / ``truncated`` uint8 ``[n_lanes]``, ``length``,
         ``duration_reward``, ``return_running`` / ``return_last`` float64 ``[n_lanes, n_slot]``, ``length_last``, ``n_episodes``."""
-        import torch
         self._episode_on("episode_views")
-        ep = (C.c_void_p * _capi.N_EPISODE_POINTERS)()
-        check(self._lib.gpf_episode_device_pointers(self._h, ep, _capi.N_EPISODE_POINTERS), "gpf_episode_device_pointers")
-        cap = self._lib.gpf_lane_capacity(self._h)
-        dev = torch.device("cuda", self.device)
-        ns = int(getattr(self, "_n_reward_slot", 0))
-
-        def view(p, shape, typestr):
-            iface = {"shape": shape, "typestr": typestr, "data": (int(p), False), "version": 2, "strides": None}
-            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=dev)[:self.n_lanes]
-        flags = view(ep[1], (cap, 2), "|u1")
-        return {"limit": view(ep[0], (cap,), "<i4"), "terminated": flags[:, 0], "truncated": flags[:, 1], "length": view(ep[2], (cap,), "<i4"),
-                "duration_reward": view(ep[3], (cap,), "<f4"), "return_running": view(ep[4], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns],
-                "return_last": view(ep[5], (cap, REWARD_MAX_SLOTS), "<f8")[:, :ns], "length_last": view(ep[6], (cap,), "<i4"),
-                "n_episodes": view(ep[7], (cap,), "<i4")}
+        v = self._views(self._device_pointers("gpf_episode_device_pointers", _capi.N_EPISODE_POINTERS),
+                        [("limit", 0, (), "<i4"), ("flags", 1, (2,), "|u1"), ("length", 2, (), "<i4"), ("duration_reward", 3, (), "<f4"),
+                         ("running", 4, (REWARD_MAX_SLOTS,), "<f8"), ("last", 5, (REWARD_MAX_SLOTS,), "<f8"), ("length_last", 6, (), "<i4"),
+                         ("n_episodes", 7, (), "<i4")])
+        ns = self._n_reward_slot
+        return {"limit": v["limit"], "terminated": v["flags"][:, 0], "truncated": v["flags"][:, 1], "length": v["length"],
+                "duration_reward": v["duration_reward"], "return_running": v["running"][:, :ns], "return_last": v["last"][:, :ns],
+                "length_last": v["length_last"], "n_episodes": v["n_episodes"]}
 
     # ---- combined topology + injection actions (include/gridpf.h gpf_set_combined_actions; grid2op_amd/csrc/gridpf_combined.hpp) ----
     def set_combined_actions(self, on: bool = True, check_values: bool = True, storage_max_p_prod=None, storage_max_p_absorb=None):
@@ -1382,40 +1345,31 @@ class PowerFlowEngine:
         ``on=False`` brings the refusal of combined launches back."""
         self._cb_on = False
         if not on:
-            check(self._lib.gpf_set_combined_actions(self._h, None), "gpf_set_combined_actions")
+            self._call("gpf_set_combined_actions", None)
             return
         d = GpfCombinedDesc(1, 1 if check_values else 0, None, None)
-        keep = []
-        for name, v in (("storage_max_p_prod", storage_max_p_prod), ("storage_max_p_absorb", storage_max_p_absorb)):
-            if v is not None:
-                a = np.ascontiguousarray(v, dtype=np.float32).reshape(self.model.n_storage)
-                keep.append(a)
-                setattr(d, name, ptr(a, C.c_float))
-        check(self._lib.gpf_set_combined_actions(self._h, C.byref(d)), "gpf_set_combined_actions")
+        arrays = {name: None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(self.model.n_storage)
+                  for name, v in (("storage_max_p_prod", storage_max_p_prod), ("storage_max_p_absorb", storage_max_p_absorb))}
+        _fill_pointers(d, arrays)            # (referenced until the call has returned)
+        self._call("gpf_set_combined_actions", C.byref(d))
         self._cb_on = True
+
+    def _combined_on(self, what):
+        if not self._cb_on:
+            raise GridPFError(f"{what}: combined actions are off (set_combined_actions)")
 
     def action_flags(self, lane0: int = 0, n: Optional[int] = None) -> dict:
         """``is_illegal`` / ``is_ambiguous`` / ``is_illegal_redisp`` bool ``[n]`` and ``reason`` uint8 ``[n]`` (``GPF_CB_*``) of the whole
         step of the last one-step launch in combined mode; synchronous."""
-        if not getattr(self, "_cb_on", False):
-            raise GridPFError("action_flags: combined actions are off (set_combined_actions)")
-        lane0, n = self._range(lane0, n)
-        f = np.zeros((n, 4), np.uint8)
-        check(self._lib.gpf_get_action_flags(self._h, lane0, n, ptr(f, C.c_uint8)), "gpf_get_action_flags")
+        self._combined_on("action_flags")
+        f = self._get_rows("gpf_get_action_flags", lane0, n, (4, np.uint8), zeros=True)
         return dict(is_illegal=f[:, 0].astype(bool), is_ambiguous=f[:, 1].astype(bool), is_illegal_redisp=f[:, 2].astype(bool), reason=f[:, 3].copy())
 
     def combined_views(self) -> dict:
         """``{"flags": uint8 torch tensor [n_lanes, 4]}`` {is_illegal, is_ambiguous, is_illegal_redisp, reason} ALIASING the engine-owned
         flags of the last one-step launch (no copy; order the reader on ``device_views()["stream"]``)."""
-        import torch
-        if not getattr(self, "_cb_on", False):
-            raise GridPFError("combined_views: combined actions are off (set_combined_actions)")
-        cp = (C.c_void_p * _capi.N_COMBINED_POINTERS)()
-        check(self._lib.gpf_combined_device_pointers(self._h, cp, _capi.N_COMBINED_POINTERS), "gpf_combined_device_pointers")
-        cap = self._lib.gpf_lane_capacity(self._h)
-        iface = {"shape": (cap, 4), "typestr": "|u1", "data": (int(cp[0]), False), "version": 2, "strides": None}
-        holder = type("_Arr", (), {"__cuda_array_interface__": iface})()
-        return {"flags": torch.as_tensor(holder, device=torch.device("cuda", self.device))[:self.n_lanes]}
+        self._combined_on("combined_views")
+        return self._views(self._device_pointers("gpf_combined_device_pointers", _capi.N_COMBINED_POINTERS), [("flags", 0, (4,), "|u1")])
 
     # ---- the chronics cursor (include/gridpf.h gpf_set_chronics_cursor; grid2op_amd/csrc/gridpf_cursor.hpp) ----
     def set_chronics_cursor(self, order=None, policy="sequential", probabilities=None, first_row=0, next_pos=None, seed=None, lane_base: int = 0):
@@ -1429,71 +1383,56 @@ class PowerFlowEngine:
         an integer: Philox on (episodes started, lane + ``lane_base``).  While it is on multi-step launches are refused."""
         self._cur_on = False
         if order is False:
-            check(self._lib.gpf_set_chronics_cursor(self._h, None), "gpf_set_chronics_cursor")
+            self._call("gpf_set_chronics_cursor", None)
             return
         if order is None:
             order = np.arange(int(getattr(self, "chron_tables", 1)))
         order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
         pol = {"sequential": CURSOR_SEQUENTIAL, "sampled": CURSOR_SAMPLED}.get(policy, policy)
-        d = GpfCursorDesc(n_order=len(order), order=ptr(order, C.c_int32), policy=int(pol), lane_base=int(lane_base))
-        cdf = None
+        d = GpfCursorDesc(n_order=len(order), policy=int(pol), lane_base=int(lane_base))
+        arrays = dict(order=order)           # descriptor field -> array, referenced until the call has returned
         if pol == CURSOR_SAMPLED:
-            cdf = cursor_cdf(np.ones(len(order)) if probabilities is None else probabilities)
-            if len(cdf) != len(order):
+            arrays["cdf"] = cursor_cdf(np.ones(len(order)) if probabilities is None else probabilities)
+            if len(arrays["cdf"]) != len(order):
                 raise ValueError("probabilities: one per position of the order")
-            d.cdf = ptr(cdf, C.c_double)
-        keep = []
         for name, val, default in (("first_row", first_row, 0), ("next_pos", next_pos, 0 if pol == CURSOR_SEQUENTIAL else -1)):
             val = default if val is None else val
             if np.ndim(val) > 0:
-                arr = np.ascontiguousarray(val, dtype=np.int32).reshape(self.n_lanes)
-                keep.append(arr)
-                setattr(d, "lane_" + name, ptr(arr, C.c_int32))
+                arrays["lane_" + name] = np.ascontiguousarray(val, dtype=np.int32).reshape(self.n_lanes)
             else:
                 setattr(d, name, int(val))
+        _fill_pointers(d, arrays)
         if seed is None:
             d.draw_source = OPP_DRAWS_TABLE
         else:
             d.draw_source, d.seed_lo, d.seed_hi = OPP_DRAWS_PHILOX, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
-        check(self._lib.gpf_set_chronics_cursor(self._h, C.byref(d)), "gpf_set_chronics_cursor")
+        self._call("gpf_set_chronics_cursor", C.byref(d))
         self._cur_on = True
 
     def _cursor_on(self, what):
-        if not getattr(self, "_cur_on", False):
+        if not self._cur_on:
             raise GridPFError(f"{what}: the chronics cursor is off (set_chronics_cursor)")
 
     def upload_cursor_draws(self, draws):
         """``[n_lanes, n_draw]`` float64 uniforms in [0, 1) of the sampled policy, one per episode start and lane, consumed in order."""
         self._cursor_on("upload_cursor_draws")
         u = np.ascontiguousarray(draws, dtype=np.float64).reshape(self.n_lanes, -1)
-        check(self._lib.gpf_upload_cursor_draws(self._h, u.shape[1], ptr(u, C.c_double)), "gpf_upload_cursor_draws")
+        self._call("gpf_upload_cursor_draws", u.shape[1], _ptr(u))
 
     def chronics_cursor_state(self, lane0: int = 0, n: Optional[int] = None) -> "CursorState":
         self._cursor_on("chronics_cursor_state")
-        lane0, n = self._range(lane0, n)
-        rows = np.zeros((n, CURSOR_STATE_INTS), np.int32)
-        check(self._lib.gpf_get_cursor_state(self._h, lane0, n, ptr(rows, C.c_int32)), "gpf_get_cursor_state")
-        return CursorState.from_rows(rows)
+        return CursorState.from_rows(self._get_rows("gpf_get_cursor_state", lane0, n, (CURSOR_STATE_INTS, np.int32), zeros=True))
 
     def set_chronics_cursor_state(self, state: "CursorState", lane0: int = 0):
         self._cursor_on("set_chronics_cursor_state")
-        rows = np.ascontiguousarray(state.rows(), dtype=np.int32)
-        check(self._lib.gpf_set_cursor_state(self._h, lane0, rows.shape[0], ptr(rows, C.c_int32)), "gpf_set_cursor_state")
+        self._set_rows("gpf_set_cursor_state", state.rows(), CURSOR_STATE_INTS, np.int32, lane0)
 
     def cursor_views(self) -> dict:
         """Zero-copy torch tensors ALIASING the cursor's buffers (order the reader on ``device_views()["stream"]``), int32 ``[n_lanes]``:
         ``next_pos`` (writable: ``env.set_id`` on the device), ``pos``, ``n_started``."""
-        import torch
         self._cursor_on("cursor_views")
-        cp = (C.c_void_p * _capi.N_CURSOR_POINTERS)()
-        check(self._lib.gpf_cursor_device_pointers(self._h, cp, _capi.N_CURSOR_POINTERS), "gpf_cursor_device_pointers")
-        cap = self._lib.gpf_lane_capacity(self._h)
-        dev = torch.device("cuda", self.device)
-
-        def view(p):
-            iface = {"shape": (cap,), "typestr": "<i4", "data": (int(p), False), "version": 2, "strides": None}
-            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=dev)[:self.n_lanes]
-        return {"next_pos": view(cp[0]), "pos": view(cp[1]), "n_started": view(cp[2])}
+        return self._views(self._device_pointers("gpf_cursor_device_pointers", _capi.N_CURSOR_POINTERS),
+                           [("next_pos", 0, (), "<i4"), ("pos", 1, (), "<i4"), ("n_started", 2, (), "<i4")])
 
     # ---- zero-copy device views ------------------------------------------------------------------------------------------
     def device_views(self):
@@ -1511,51 +1450,31 @@ class PowerFlowEngine:
         import torch
         ptrs = (C.c_void_p * _capi.N_DEVICE_POINTERS)()
         stream = C.c_void_p()
-        check(self._lib.gpf_device_pointers_n(self._h, ptrs, _capi.N_DEVICE_POINTERS, C.byref(stream)), "gpf_device_pointers_n")
-        cap = self._lib.gpf_lane_capacity(self._h)
+        self._call("gpf_device_pointers_n", ptrs, _capi.N_DEVICE_POINTERS, C.byref(stream))
         m = self.model
-        dev = torch.device("cuda", self.device)
-
-        class _Arr:                          # __cuda_array_interface__ v2: torch.as_tensor wraps it without a copy
-            def __init__(self, p, shape, typestr):
-                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(p), False), "version": 2,
-                                                 "strides": None}
-
-        def view(idx, cols, typestr):
-            if cols == 0 or not ptrs[idx]:
-                return None
-            t = torch.as_tensor(_Arr(ptrs[idx], (cap, cols), typestr), device=dev)
-            return t[:self.n_lanes]
-        v = {"inj": view(0, self.n_inj, "<f8"), "topo": view(1, m.dim_topo, "<i4"), "out": view(3, self.n_out, "<f4"),
-             "topo_vect": view(4, m.dim_topo, "<i4"), "line_status": view(5, m.n_line, "|u1"), "status": view(6, 4, "<i4"),
-             "rho": view(8, m.n_line, "<f4"), "overflow_count": view(9, m.n_line, "<i4"), "done": view(10, 1, "|u1"),
-             "episode": view(11, 2, "<i4"), "bus_vm": view(12, self.nb_total, "<f8"), "bus_va": view(13, self.nb_total, "<f8"),
-             "disc_round": view(15, m.n_line, "<i4"),
-             "act_redispatch": view(22, m.n_gen, "<f4"), "act_storage": view(23, m.n_storage, "<f4"), "act_curtail": view(24, m.n_gen, "<f4"),
-             "target_dispatch": view(25, m.n_gen, "<f4"), "actual_dispatch": view(26, m.n_gen, "<f4"),
-             "storage_charge": view(27, m.n_storage, "<f4"),
-             "act_topo": view(28, int(getattr(self, "_n_topo_slot", 1)), "<i4"), "sub_cooldown": view(29, m.n_sub, "<i4"), "topo_flags": view(30, 2, "|u1"),
-             "last_bus": view(31, m.dim_topo, "<i4"),
-             "obs": view(32, self._obs_spec.dim if getattr(self, "_obs_spec", None) is not None else 0, "<f4"),
-             "topo_mask": view(33, int(getattr(self, "_n_topo_act", 0)), "|u1")}
-
-        def tview(idx, cols, typestr):       # trajectory buffers: [cap_steps][cap][cols]
-            if cols == 0 or not ptrs[idx] or not getattr(self, "_traj_cap", 0):
-                return None
-            t = torch.as_tensor(_Arr(ptrs[idx], (self._traj_cap, cap, cols), typestr), device=dev)
-            return t[:, :self.n_lanes]
-        v.update({"traj_rho": tview(16, m.n_line, "<f4"), "traj_status": tview(17, 1, "|i1"), "traj_out": tview(18, self.n_out, "<f4"),
-                  "traj_topo_vect": tview(19, m.dim_topo, "<i4"), "traj_shunt_bus": tview(20, m.n_shunt, "<i4"),
-                  "traj_line_status": tview(21, m.n_line, "|u1")})
-        if getattr(self, "_alert", None) is not None:          # alerts on: the masks of the next launch, the rewards, the observation block
-            ap = (C.c_void_p * _capi.N_ALERT_POINTERS)()
-            check(self._lib.gpf_alert_device_pointers(self._h, ap, _capi.N_ALERT_POINTERS), "gpf_alert_device_pointers")
-            A = self._alert[0]
-            v["act_alert"] = torch.as_tensor(_Arr(ap[0], (cap,), "<i8"), device=dev)[:self.n_lanes]
-            v["alert_reward"] = torch.as_tensor(_Arr(ap[1], (cap,), "<f4"), device=dev)[:self.n_lanes]
-            v["alert_obs"] = torch.as_tensor(_Arr(ap[2], (cap, 6 * A + 1), "<i4"), device=dev)[:self.n_lanes]
-        v["stream"] = torch.cuda.ExternalStream(stream.value, device=dev)
+        v = self._views(ptrs, [
+            ("inj", 0, (self.n_inj,), "<f8"), ("topo", 1, (m.dim_topo,), "<i4"), ("out", 3, (self.n_out,), "<f4"),
+            ("topo_vect", 4, (m.dim_topo,), "<i4"), ("line_status", 5, (m.n_line,), "|u1"), ("status", 6, (4,), "<i4"),
+            ("rho", 8, (m.n_line,), "<f4"), ("overflow_count", 9, (m.n_line,), "<i4"), ("done", 10, (1,), "|u1"),
+            ("episode", 11, (2,), "<i4"), ("bus_vm", 12, (self.nb_total,), "<f8"), ("bus_va", 13, (self.nb_total,), "<f8"),
+            ("disc_round", 15, (m.n_line,), "<i4"),
+            ("act_redispatch", 22, (m.n_gen,), "<f4"), ("act_storage", 23, (m.n_storage,), "<f4"), ("act_curtail", 24, (m.n_gen,), "<f4"),
+            ("target_dispatch", 25, (m.n_gen,), "<f4"), ("actual_dispatch", 26, (m.n_gen,), "<f4"),
+            ("storage_charge", 27, (m.n_storage,), "<f4"),
+            ("act_topo", 28, (self._n_topo_slot,), "<i4"), ("sub_cooldown", 29, (m.n_sub,), "<i4"), ("topo_flags", 30, (2,), "|u1"),
+            ("last_bus", 31, (m.dim_topo,), "<i4"),
+            ("obs", 32, (self._obs_spec.dim if self._obs_spec is not None else 0,), "<f4"),
+            ("topo_mask", 33, (self._n_topo_act,), "|u1")])
+        for key, idx, cols, typestr in (("traj_rho", 16, m.n_line, "<f4"), ("traj_status", 17, 1, "|i1"), ("traj_out", 18, self.n_out, "<f4"),
+                                        ("traj_topo_vect", 19, m.dim_topo, "<i4"), ("traj_shunt_bus", 20, m.n_shunt, "<i4"),
+                                        ("traj_line_status", 21, m.n_line, "|u1")):      # trajectory buffers: [cap_steps][cap][cols]
+            v[key] = self._view(ptrs[idx], (cols,), typestr, steps=self._traj_cap) if self._traj_cap else None
+        if self._alert is not None:          # alerts on: the masks of the next launch, the rewards, the observation block
+            v.update(self._views(self._device_pointers("gpf_alert_device_pointers", _capi.N_ALERT_POINTERS),
+                                 [("act_alert", 0, (), "<i8"), ("alert_reward", 1, (), "<f4"), ("alert_obs", 2, (6 * self._alert[0] + 1,), "<i4")]))
+        v["stream"] = torch.cuda.ExternalStream(stream.value, device=torch.device("cuda", self.device))
         return v
+
 
     # ---- observation vectors assembled on the device (include/gridpf.h: gpf_set_obs_spec; grid2op_amd/obs_spec.py) ----------------------
     def set_obs_clock(self, start, step_minutes: int = 5, max_step: Optional[int] = None):
@@ -1575,8 +1494,7 @@ class PowerFlowEngine:
         if max_step is None:
             max_step = max(int(getattr(self, "chron_T", 1)) - 1, 0)
         a = np.ascontiguousarray(mins, dtype=np.int64)
-        check(self._lib.gpf_set_obs_clock(self._h, a.size, a.ctypes.data_as(C.POINTER(C.c_int64)), int(step_minutes), int(max_step)),
-              "gpf_set_obs_clock")
+        self._call("gpf_set_obs_clock", a.size, _ptr(a), int(step_minutes), int(max_step))
 
     def set_obs_spec(self, spec, game_over_fill: bool = True):
         """The layout of the observation vectors (`grid2op_amd.obs_spec.ObsSpec`).  ``game_over_fill``: a lane whose last step ended its
@@ -1589,16 +1507,14 @@ class PowerFlowEngine:
         sub = np.ascontiguousarray(spec.subtract, dtype=np.float32)
         div = np.ascontiguousarray(spec.divide, dtype=np.float32)
         assert sub.size == spec.dim and div.size == spec.dim
-        check(self._lib.gpf_set_obs_spec(self._h, seg.shape[0], ptr(seg, C.c_int32), int(spec.dim), ptr(sub, C.c_float), ptr(div, C.c_float),
-                                         int(bool(game_over_fill))), "gpf_set_obs_spec")
+        self._call("gpf_set_obs_spec", seg.shape[0], _ptr(seg), int(spec.dim), _ptr(sub), _ptr(div), int(bool(game_over_fill)))
         self._obs_spec = spec
-        self._obs_view = None
+        self._obs_view = None                # (the engine-owned observation buffer is re-allocated for the new dim)
 
     def _obs_dim(self):
-        spec = getattr(self, "_obs_spec", None)
-        if spec is None:
+        if self._obs_spec is None:
             raise GridPFError("no observation spec is set (set_obs_spec)")
-        return spec.dim
+        return self._obs_spec.dim
 
     def observation_vector(self, lane0: int = 0, n: Optional[int] = None, out=None):
         """The observation vectors of lanes ``[lane0, lane0 + n)`` as a float32 torch tensor ``[n, dim]`` in device memory, written by one
@@ -1609,17 +1525,11 @@ class PowerFlowEngine:
         lane0, n = self._range(lane0, n)
         dim = self._obs_dim()
         if out is None:
-            check(self._lib.gpf_obs_vector(self._h, lane0, n, None, 0), "gpf_obs_vector")
-            if getattr(self, "_obs_view", None) is None:
+            self._call("gpf_obs_vector", lane0, n, None, 0)
+            if self._obs_view is None:
                 self._obs_view = self.device_views()["obs"]
             return self._obs_view[lane0:lane0 + n]
-        import torch
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2):
-            raise ValueError("observation_vector: out must be a 2-d float32 CUDA tensor")
-        if out.device.index != self.device or out.shape[0] != n or out.shape[1] < dim or out.stride(1) != 1 or (n > 1 and out.stride(0) < dim):
-            raise ValueError(f"observation_vector: out must live on cuda:{self.device}, have {n} rows of >= {dim} contiguous columns and a row stride >= {dim}")
-        check(self._lib.gpf_obs_vector(self._h, lane0, n, C.c_void_p(out.data_ptr()), int(out.stride(0)) if n > 1 else max(int(out.stride(0)), dim)),
-              "gpf_obs_vector")
+        self._call("gpf_obs_vector", lane0, n, *self._out_rows("observation_vector", out, "float32", n, dim, False))
         return out[:, :dim]
 
     def observation_trajectory(self, n_steps: int, step0: int = 0, lane0: int = 0, n: Optional[int] = None, out=None):
@@ -1635,57 +1545,42 @@ class PowerFlowEngine:
         if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (int(n_steps), n, dim)):
             raise ValueError(f"observation_trajectory: out must be a contiguous float32 CUDA tensor of shape {(int(n_steps), n, dim)}")
         torch.cuda.current_stream(out.device).synchronize()      # (a fresh allocation may still be in use by work queued on torch's stream)
-        check(self._lib.gpf_obs_vector_trajectory(self._h, int(step0), int(n_steps), lane0, n, C.c_void_p(out.data_ptr())),
-              "gpf_obs_vector_trajectory")
+        self._call("gpf_obs_vector_trajectory", int(step0), int(n_steps), lane0, n, C.cast(out.data_ptr(), C.POINTER(C.c_float)))
         return out
 
     def observation_vector_host(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """`observation_vector` copied to the host: float32 ``[n, dim]`` (synchronous)."""
-        lane0, n = self._range(lane0, n)
-        out = np.empty((n, self._obs_dim()), dtype=np.float32)
-        check(self._lib.gpf_get_obs_vector(self._h, lane0, n, ptr(out, C.c_float)), "gpf_get_obs_vector")
-        return out
+        return self._get_rows("gpf_get_obs_vector", lane0, n, (self._obs_dim(), np.float32))
 
     def set_overflow_count(self, counts, lane0: int = 0):
         """The protection counters (consecutive steps above the thermal limit, ``obs.timestep_overflow``) of lanes
         ``lane0 ...``: ``[n, n_line]`` ints."""
-        c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1, self.model.n_line)
-        check(self._lib.gpf_set_overflow_count(self._h, int(lane0), c.shape[0], ptr(c, C.c_int32)), "gpf_set_overflow_count")
+        self._set_rows("gpf_set_overflow_count", counts, self.model.n_line, np.int32, lane0)
 
     def cooldown(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """The environment's line cooldowns of the lanes (obs.time_before_cooldown_line; `step(nb_ts_reco=...)`), int32 ``[n, n_line]``."""
-        lane0, n = self._range(lane0, n)
-        out = np.empty((n, self.model.n_line), dtype=np.int32)
-        check(self._lib.gpf_get_cooldown(self._h, lane0, n, ptr(out, C.c_int32)), "gpf_get_cooldown")
-        return out
+        return self._get_rows("gpf_get_cooldown", lane0, n, (self.model.n_line, np.int32))
 
     def set_cooldown(self, line_cooldown, lane0: int = 0):
         """Restore the line cooldowns (an environment restored from an observation hands over obs.time_before_cooldown_line)."""
-        c = np.ascontiguousarray(line_cooldown, dtype=np.int32).reshape(-1, self.model.n_line)
-        check(self._lib.gpf_set_cooldown(self._h, int(lane0), c.shape[0], ptr(c, C.c_int32)), "gpf_set_cooldown")
+        self._set_rows("gpf_set_cooldown", line_cooldown, self.model.n_line, np.int32, lane0)
 
     def trajectory_cooldown(self, n_steps: int, step0: int = 0, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Line cooldowns after every step of the last multi-step launch, int16 ``[n_steps, n, n_line]`` (needs `set_trajectory`)."""
         lane0, n = self._range(lane0, n)
         out = np.empty((n_steps, n, self.model.n_line), dtype=np.int16)
-        check(self._lib.gpf_get_trajectory_cooldown(self._h, int(step0), int(n_steps), lane0, n, out.ctypes.data_as(C.POINTER(C.c_int16))), "gpf_get_trajectory_cooldown")
+        self._call("gpf_get_trajectory_cooldown", int(step0), int(n_steps), lane0, n, _ptr(out))
         return out
 
     def step_outputs(self, lane0: int = 0, n: Optional[int] = None):
-        lane0, n = self._range(lane0, n)
         nl = self.model.n_line
-        rho = np.empty((n, nl), dtype=np.float32)
-        oc = np.empty((n, nl), dtype=np.int32)
-        dr = np.empty((n, nl), dtype=np.int32)
-        check(self._lib.gpf_get_step_outputs(self._h, lane0, n, ptr(rho, C.c_float), ptr(oc, C.c_int32), ptr(dr, C.c_int32)),
-              "gpf_get_step_outputs")
-        return rho, oc, dr
+        return tuple(self._get_rows("gpf_get_step_outputs", lane0, n, (nl, np.float32), (nl, np.int32), (nl, np.int32)))
 
     # ---- measurement -------------------------------------------------------------------------------------
     # ---- DC sensitivity (PTDF) path: fixed topology, flows = PTDF * P_bus as one FP64 MFMA GEMM ----------------------
     def ptdf_build(self, lane: int = 0):
         """Factorise the DC system of the topology currently held by ``lane`` (once per topology)."""
-        check(self._lib.gpf_ptdf_build(self._h, int(lane)), "gpf_ptdf_build")
+        self._call("gpf_ptdf_build", int(lane))
 
     def ptdf_build_batch(self, lane0: int = 0, n: Optional[int] = None, with_lodf: bool = True, info: bool = True) -> dict:
         """PTDF (and LODF) tables of EVERY distinct topology the lanes ``[lane0, lane0 + n)`` hold right now, built on the device in
@@ -1695,7 +1590,7 @@ class PowerFlowEngine:
         flows), ``class_n`` (dimension of each reduced B'), ``kernel_ms``."""
         lane0, n = self._range(lane0, n)
         nc = C.c_int32(0)
-        check(self._lib.gpf_ptdf_build_batch(self._h, lane0, n, 1 if with_lodf else 0, C.byref(nc)), "gpf_ptdf_build_batch")
+        self._call("gpf_ptdf_build_batch", lane0, n, 1 if with_lodf else 0, C.byref(nc))
         if not info:                                        # asynchronous: the build kernel is queued, nobody waits (`ptdf_batch_info()` later)
             return {"n_classes": int(nc.value)}
         return self.ptdf_batch_info(n, nc.value)
@@ -1707,31 +1602,31 @@ class PowerFlowEngine:
         nc = C.c_int32(int(n_classes))
         lc, st, cn = np.empty(n, np.int32), np.empty(nc.value, np.int32), np.empty(nc.value, np.int32)
         ms = C.c_double(0.0)
-        check(self._lib.gpf_ptdf_batch_info(self._h, ptr(lc, C.c_int32), ptr(st, C.c_int32), ptr(cn, C.c_int32), C.byref(ms)), "gpf_ptdf_batch_info")
+        self._call("gpf_ptdf_batch_info", _ptr(lc), _ptr(st), _ptr(cn), C.byref(ms))
         return {"n_classes": int(nc.value), "lane_class": lc, "class_status": st, "class_n": cn, "kernel_ms": float(ms.value)}
 
     def ptdf_class(self, cls: int, lodf: bool = False):
         """PTDF [n_line, n_sub * n_busbar] of topology class ``cls`` of the last `ptdf_build_batch` (and its LODF [n_line, n_line])."""
         out = np.empty((self.model.n_line, self.nb_total), dtype=np.float64)
         lo = np.empty((self.model.n_line, self.model.n_line), dtype=np.float64) if lodf else None
-        check(self._lib.gpf_ptdf_batch_get(self._h, int(cls), ptr(out, C.c_double), ptr(lo, C.c_double)), "gpf_ptdf_batch_get")
+        self._call("gpf_ptdf_batch_get", int(cls), _ptr(out), _ptr(lo))
         return (out, lo) if lodf else out
 
     def ptdf(self) -> np.ndarray:
         """PTDF [n_line, n_sub * n_busbar] (MW of origin-side flow per MW injected at the bus, slack-referenced)."""
         out = np.empty((self.model.n_line, self.nb_total), dtype=np.float64)
-        check(self._lib.gpf_ptdf_get(self._h, ptr(out, C.c_double)), "gpf_ptdf_get")
+        self._call("gpf_ptdf_get", _ptr(out))
         return out
 
     def ptdf_flows(self, lane0: int = 0, n: Optional[int] = None, fetch: bool = True) -> Optional[np.ndarray]:
         """DC active-power flows (MW, float32 [n, n_line]) of the lanes' current injection rows (asynchronous launch;
         ``fetch=False`` leaves the result on the device)."""
         lane0, n = self._range(lane0, n)
-        check(self._lib.gpf_ptdf_flows(self._h, lane0, n), "gpf_ptdf_flows")
+        self._call("gpf_ptdf_flows", lane0, n)
         if not fetch:
             return None
         out = np.empty((n, self.model.n_line), dtype=np.float32)
-        check(self._lib.gpf_get_ptdf_flows(self._h, lane0, n, ptr(out, C.c_float)), "gpf_get_ptdf_flows")
+        self._call("gpf_get_ptdf_flows", lane0, n, _ptr(out))
         return out
 
     def ptdf_flows_rows(self, t0: int, n_rows: int, rebalance: float = 0.0, fetch: bool = True, lane0: int = 0, n: Optional[int] = None):
@@ -1739,12 +1634,12 @@ class PowerFlowEngine:
         ``n_lanes * n_rows`` rows): row ``j`` of lane ``k`` is chronics row ``(t0 + j + lane_offset[k]) mod T`` turned into injections
         as `step` does.  Returns float32 ``[n_rows, n, n_line]`` (MW at the origin side) of lanes ``[lane0, lane0 + n)``, or None with
         ``fetch=False`` (asynchronous)."""
-        check(self._lib.gpf_ptdf_flows_rows(self._h, int(t0), int(n_rows), float(rebalance)), "gpf_ptdf_flows_rows")
+        self._call("gpf_ptdf_flows_rows", int(t0), int(n_rows), float(rebalance))
         if not fetch:
             return None
         lane0, n = self._range(lane0, n)
         out = np.empty((n_rows, n, self.model.n_line), dtype=np.float32)
-        check(self._lib.gpf_get_ptdf_flows_rows(self._h, 0, int(n_rows), lane0, n, ptr(out, C.c_float)), "gpf_get_ptdf_flows_rows")
+        self._call("gpf_get_ptdf_flows_rows", 0, int(n_rows), lane0, n, _ptr(out))
         return out
 
     def lodf_screen(self, lane0: int = 0, n: Optional[int] = None, cap_mw: Optional[np.ndarray] = None) -> np.ndarray:
@@ -1754,22 +1649,22 @@ class PowerFlowEngine:
         lane0, n = self._range(lane0, n)
         out = np.empty((n, self.model.n_line), dtype=np.float32)
         cap = None if cap_mw is None else np.ascontiguousarray(cap_mw, dtype=np.float32)
-        check(self._lib.gpf_lodf_screen(self._h, lane0, n, ptr(cap, C.c_float), ptr(out, C.c_float)), "gpf_lodf_screen")
+        self._call("gpf_lodf_screen", lane0, n, _ptr(cap), _ptr(out))
         return out
 
     def sync(self):
-        check(self._lib.gpf_sync(self._h), "gpf_sync")
+        self._call("gpf_sync")
 
     def set_profiling(self, mode):
         """0/False: off; 1/True: one HIP event pair around the window of launches up to the next ``kernel_time()``;
         2: an event pair per launch (exact per-kernel durations, costs ~7 us of stream time per launch); 3 (inside a window): the
         window ends at this point of the stream (recorded asynchronously behind the launches issued so far)."""
-        check(self._lib.gpf_set_profiling(self._h, int(mode)), "gpf_set_profiling")
+        self._call("gpf_set_profiling", int(mode))
 
     def kernel_time(self) -> Tuple[float, int]:
         ms = C.c_double(0.0)
         n = C.c_int64(0)
-        check(self._lib.gpf_get_kernel_time(self._h, C.byref(ms), C.byref(n)), "gpf_get_kernel_time")
+        self._call("gpf_get_kernel_time", C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def specialize(self, enable: bool = True, cache_dir: str = None, verify: bool = True, features: bool = True) -> dict:
@@ -1787,15 +1682,15 @@ class PowerFlowEngine:
         grid-only kernel.  At most 4 feature words per kernel variant and engine are compiled at run time (further words run on the grid-only
         kernel; kernels built ahead of time do not count); without a compiler a missing feature kernel is silently the grid-only one.
         ``features=False``: grid-only kernels.  The self-test runs its launches both ways."""
-        check(self._lib.gpf_jit_features(self._h, int(bool(features))), "gpf_jit_features")
+        self._call("gpf_jit_features", int(bool(features)))
         if not enable:
-            check(self._lib.gpf_jit_disable(self._h), "gpf_jit_disable")
+            self._call("gpf_jit_disable")
             return self.specialization()
         if verify:
             self._verify_specialization(cache_dir)
         # (the kernel sources beside this package; $GRIDPF_JIT_SRC: those of another build -- same-box A/B runs of a library selected with $GRIDPF_LIB)
         src = (os.environ.get("GRIDPF_JIT_SRC") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")).encode()
-        check(self._lib.gpf_jit_enable(self._h, src, cache_dir.encode() if cache_dir else None), "gpf_jit_enable")
+        self._call("gpf_jit_enable", src, cache_dir.encode() if cache_dir else None)
         return self.specialization()
 
     def _verify_specialization(self, cache_dir=None, n_lanes: int = 64, n_steps: int = 8, T: int = 24):
@@ -1830,10 +1725,10 @@ class PowerFlowEngine:
 
             ref = run()
             src = (os.environ.get("GRIDPF_JIT_SRC") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")).encode()
-            check(twin._lib.gpf_jit_features(twin._h, 0), "gpf_jit_features")            # the grid-only kernels ...
-            check(twin._lib.gpf_jit_enable(twin._h, src, cache_dir.encode() if cache_dir else None), "gpf_jit_enable")
+            twin._call("gpf_jit_features", 0)            # the grid-only kernels ...
+            twin._call("gpf_jit_enable", src, cache_dir.encode() if cache_dir else None)
             got = run()
-            check(twin._lib.gpf_jit_features(twin._h, 1), "gpf_jit_features")            # ... and the same launches under their feature kernels
+            twin._call("gpf_jit_features", 1)            # ... and the same launches under their feature kernels
             got += run()
             ref = ref + ref
             info = twin.specialization()
@@ -1852,7 +1747,7 @@ class PowerFlowEngine:
         counts = (C.c_int64 * 6)()
         sec = C.c_double()
         text = C.create_string_buffer(2048)
-        check(self._lib.gpf_jit_info(self._h, counts, C.byref(sec), text, len(text)), "gpf_jit_info")
+        self._call("gpf_jit_info", counts, C.byref(sec), text, len(text))
         return {"enabled": bool(counts[0]), "compiled": int(counts[1]), "cached": int(counts[2]), "failed": int(counts[3]),
                 "launches": int(counts[4]), "aot": int(counts[5]), "seconds": float(sec.value), "variants": text.value.decode()}
 
@@ -1866,34 +1761,34 @@ class PowerFlowEngine:
         kw.update(step_kw)
         reco = kw["nb_ts_reco"]
         if reco is None:
-            reco = 10 if (kw["cascade"] or outages or getattr(self, "_has_outages", False)) else -1
+            reco = 10 if (kw["cascade"] or outages or self._has_outages) else -1
         o = GpfStepOpts(int(kw["max_iter"]), float(kw["tol_mva"]), float(kw["rebalance"]), int(bool(kw["cascade"])), float(kw["hard_overflow"]),
                         float(kw["soft_overflow"]), int(kw["nb_ts_allowed"]), int(kw["max_rounds"]), int(bool(kw["is_dc"])), int(bool(kw["auto_reset"])),
                         int(bool(kw["warm_start"])), int(reco >= 0), max(int(reco), 0))
         have = (1 if lane_scale else 0) | (4 if outages else 0) | (8 if gen_delta else 0) | (16 if trajectory_obs else 0)     # GPF_HAVE_*
         word = C.c_uint32(0)
-        check(self._lib.gpf_jit_feature_word(self._h, int(n_steps), C.byref(o), have, C.byref(word)), "gpf_jit_feature_word")
+        self._call("gpf_jit_feature_word", int(n_steps), C.byref(o), have, C.byref(word))
         return int(word.value)
 
     def specialization_header(self) -> str:
         """The generated header the specialised kernels are compiled with (gpf_jit_source): this grid's numbers as C literals."""
         need = C.c_size_t()
-        check(self._lib.gpf_jit_source(self._h, None, 0, C.byref(need)), "gpf_jit_source")
+        self._call("gpf_jit_source", None, 0, C.byref(need))
         buf = C.create_string_buffer(need.value + 1)
-        check(self._lib.gpf_jit_source(self._h, buf, len(buf), None), "gpf_jit_source")
+        self._call("gpf_jit_source", buf, len(buf), None)
         return buf.value.decode()
 
     def counters(self) -> dict:
         """Step launches issued since the engine was created and the kernel dispatches they took (a batch of a few residency rounds goes
         out as one dispatch per round)."""
         out = (C.c_int64 * 2)()
-        check(self._lib.gpf_get_counters(self._h, out), "gpf_get_counters")
+        self._call("gpf_get_counters", out)
         return {"step_launches": int(out[0]), "kernel_dispatches": int(out[1])}
 
     def plan(self) -> dict:
         """Diagnostics: the kernel configuration a launch over all lanes would use right now (gpf_get_plan)."""
         out = (C.c_int32 * 8)()
-        check(self._lib.gpf_get_plan(self._h, out), "gpf_get_plan")
+        self._call("gpf_get_plan", out)
         keys = ("busbars_per_block", "instances_per_wavefront", "wavefronts_per_instance", "staging_tier", "ybus_in_registers",
                 "dc_factors_kept", "lds_bytes", "topology_classes")
         return dict(zip(keys, [int(v) for v in out]))

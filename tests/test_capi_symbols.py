@@ -1,5 +1,6 @@
 """CPU-only checks of the C-ABI shared library: it loads, exports every symbol ``include/gridpf.h`` declares, and
 fails loudly (no CPU fallback) when no GPU is present."""
+import ctypes as C
 import os
 import re
 
@@ -52,17 +53,122 @@ def test_product_package_never_imports_the_oracle():
                 assert "pf_oracle" not in txt or f == "_capi.py" and "oracle/" in txt, f
 
 
-def test_layout_struct_matches_header():
-    from grid2op_amd._capi import GpfLayout, GpfGridDesc
+# ---- the whole binding against include/gridpf.h: structures, prototypes, constants -------------------------------------------------
+_C_SCALARS = {"int": C.c_int, "int8_t": C.c_int8, "int16_t": C.c_int16, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint8_t": C.c_uint8,
+              "uint16_t": C.c_uint16, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float,
+              "double": C.c_double}
+
+
+def _header():
     txt = open(os.path.join(ROOT, "include", "gridpf.h")).read()
-    lay = txt[txt.index("typedef struct gpf_layout"):txt.index("} gpf_layout;")]
-    lay = re.sub(r"/\*.*?\*/", "", lay, flags=re.S)
-    names = re.findall(r"\b([a-z_]+)\s*[,;]", lay.split("{", 1)[1])
-    assert names == [f[0] for f in GpfLayout._fields_]
-    desc = txt[txt.index("typedef struct gpf_grid_desc"):txt.index("} gpf_grid_desc;")]
-    desc = re.sub(r"/\*.*?\*/", "", desc, flags=re.S)
-    dnames = re.findall(r"\*?\s*([a-z_0-9]+)\s*[,;]", desc.split("{", 1)[1])
-    assert dnames == [f[0] for f in GpfGridDesc._fields_]
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+def _struct_class(c_name):
+    """gpf_step_opts -> _capi.GpfStepOpts"""
+    from grid2op_amd import _capi
+    return getattr(_capi, "".join(w.capitalize() for w in c_name.split("_")))
+
+
+def _ctype(base, stars, dims, param):
+    """The ctypes type of the C declaration ``base stars name dims`` as a structure field or (``param``) a function parameter."""
+    if base == "gpf_handle":
+        t = C.c_void_p
+    elif base == "void":
+        assert stars, "a void object"
+        t, stars = C.c_void_p, stars - 1
+    elif base == "char":
+        assert stars, "a plain char is not part of the ABI"
+        t, stars = C.c_char_p, stars - 1
+    elif base in _C_SCALARS:
+        t = _C_SCALARS[base]
+    else:
+        t = _struct_class(base)
+    for _ in range(stars):
+        t = C.POINTER(t)
+    if dims is not None:
+        t = C.POINTER(t) if param else t * int(dims)
+    return t
+
+
+def _declaration(text, param):
+    """(name, ctypes type) of every declarator of ``[const] T[*] a[, [*]b ...]`` / ``T a[k]``."""
+    m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(.*?)\s*", text, flags=re.S)
+    assert m, text
+    out = []
+    for d in m.group(2).split(","):
+        dm = re.fullmatch(r"\s*(\**)\s*(?:const\s+)?(\w+)\s*(?:\[\s*(\d*)\s*\])?\s*", d)
+        assert dm, text
+        out.append((dm.group(2), _ctype(m.group(1), len(dm.group(1)), dm.group(3), param)))
+    return out
+
+
+def _header_structs():
+    return {m.group(1): [f for decl in m.group(2).split(";") if decl.strip() for f in _declaration(decl, param=False)]
+            for m in re.finditer(r"typedef\s+struct\s+(gpf_\w+)\s*\{(.*?)\}\s*\1\s*;", _header(), flags=re.S)}
+
+
+def _header_prototypes():
+    out = {}
+    for m in re.finditer(r"(?:^|[;}])\s*(const\s+char\s*\*|int|void)\s*(gpf_\w+)\s*\(([^()]*)\)\s*;", _header(), flags=re.M):
+        ret, name, args = m.groups()
+        args = [] if args.strip() == "void" else [_declaration(a, param=True)[0][1] for a in args.split(",")]
+        out[name] = (args, C.c_char_p if "char" in ret else None if ret == "void" else C.c_int)
+    return out
+
+
+def test_every_structure_matches_header():
+    """Every ``typedef struct gpf_*`` of the header has a ctypes Structure with the same field names, in the same order, of the
+    corresponding types (the field names of GpfLayout and GpfGridDesc among them)."""
+    structs = _header_structs()
+    assert {"gpf_grid_desc", "gpf_layout", "gpf_step_opts", "gpf_opponent_desc", "gpf_alert_desc", "gpf_reward_slot", "gpf_episode_desc",
+            "gpf_combined_desc", "gpf_cursor_desc"} <= set(structs)
+    for c_name, fields in structs.items():
+        cls = _struct_class(c_name)
+        assert issubclass(cls, C.Structure)
+        assert [f[0] for f in cls._fields_] == [f[0] for f in fields], c_name
+        for (name, got), (_, want) in zip(cls._fields_, fields):
+            assert got is want, f"{c_name}.{name}: {got} in the binding, {want} in include/gridpf.h"
+
+
+def test_every_prototype_matches_signature_table():
+    """Every ``gpf_*`` prototype of the header has a row in `_capi.SIGNATURES` with as many ``argtypes``, each of the corresponding
+    ctypes type, and the corresponding ``restype`` -- and the loaded library carries exactly the table's rows."""
+    from grid2op_amd import _capi
+    protos = _header_prototypes()
+    assert sorted(protos) == _declared_functions() == sorted(_capi.SIGNATURES)
+    for name, (want_args, want_res) in protos.items():
+        got_args, got_res = _capi.SIGNATURES[name]
+        assert len(got_args) == len(want_args), f"{name}: {len(got_args)} argtypes, {len(want_args)} parameters in include/gridpf.h"
+        for k, (got, want) in enumerate(zip(got_args, want_args)):
+            assert got is want, f"{name} argument {k}: {got} in the binding, {want} in include/gridpf.h"
+        assert got_res is want_res, f"{name}: restype {got_res}, header {want_res}"
+    assert list(_capi.EXPORTED_SYMBOLS) == list(_capi.SIGNATURES)
+    import __graft_entry__ as entry
+    entry.build()
+    L = _capi.lib()
+    for name, (args, res) in _capi.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == list(args) and fn.restype is res, name
+
+
+def test_every_mirrored_constant_matches_header():
+    """Every ``#define GPF_<NAME> <integer>`` of the header that `_capi` or `engine` mirrors as ``<NAME>`` has the header's value there."""
+    from grid2op_amd import _capi, engine
+    defines = {}
+    for name, val in re.findall(r"^[ \t]*#[ \t]*define[ \t]+GPF_(\w+)[ \t]+([-+* \t0-9a-fA-FxX()]*[0-9a-fA-F)])[ \t]*$", _header(), flags=re.M):
+        defines[name] = int(eval(val, {"__builtins__": {}}))           # an integer literal or a parenthesised integer expression
+    matched = set()
+    for name, val in defines.items():
+        for mod in (_capi, engine):
+            if hasattr(mod, name):
+                assert getattr(mod, name) == val, f"{mod.__name__}.{name} = {getattr(mod, name)}, GPF_{name} = {val}"
+                matched.add(name)
+    must = {"ABI_VERSION", "N_DEVICE_POINTERS", "N_ALERT_POINTERS", "N_REWARD_POINTERS", "N_EPISODE_POINTERS", "N_CURSOR_POINTERS",
+            "N_COMBINED_POINTERS", "OPP_STATE_INTS", "OPP_AREA_STATE_INTS", "OPP_MAX_AREAS", "OPP_TIME_NONE", "CURSOR_STATE_INTS",
+            "REWARD_MAX_SLOTS", "RW_REDISP", "RW_L2RPN", "RW_LINES_CAPACITY", "RW_ECONOMIC", "RW_GAMEPLAY", "MASK_TOO_MANY_LINES",
+            "MASK_TOO_MANY_SUBS", "MASK_LINE_COOLDOWN", "MASK_SUB_COOLDOWN", "MASK_AMBIGUOUS", "ALERT_MAX_LINES", "ALERT_MAX_WINDOW"}
+    assert must <= matched, sorted(must - matched)
 
 
 def test_busbar_limit_is_declared_and_validated_before_the_device_is_touched(load_model):
