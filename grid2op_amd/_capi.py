@@ -23,6 +23,9 @@ N_EPISODE_POINTERS = 8     # include/gridpf.h GPF_N_EPISODE_POINTERS
 N_CURSOR_POINTERS = 3      # include/gridpf.h GPF_N_CURSOR_POINTERS
 N_COMBINED_POINTERS = 1    # include/gridpf.h GPF_N_COMBINED_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
+GRAPH_N_SECTIONS = 8       # include/gridpf.h GPF_GRAPH_N_SECTIONS
+GRAPH_N_FEATURES = 4       # include/gridpf.h GPF_GRAPH_N_FEATURES
+GRAPH_MAX_BUS = 1024       # include/gridpf.h GPF_GRAPH_MAX_BUS
 
 
 class GridPFError(RuntimeError):
@@ -218,6 +221,10 @@ SIGNATURES = {
     "gpf_obs_vector": _sig(h, i32, i32, _fp, i64),
     "gpf_obs_vector_trajectory": _sig(h, i32, i32, i32, i32, _fp),
     "gpf_get_obs_vector": _sig(h, i32, i32, _fp),
+    "gpf_set_graph_obs": _sig(h, i32, i32),
+    "gpf_graph_layout": _sig(h, _ip, _ip, _ip, _ip),
+    "gpf_graph_obs": _sig(h, i32, i32, _ip, _fp, _fp),
+    "gpf_graph_obs_host": _sig(h, i32, i32, _ip, _fp, _fp),
     "gpf_set_opponent": _sig(h, C.POINTER(GpfOpponentDesc)),
     "gpf_upload_opponent_draws": _sig(h, i32, _dp),
     "gpf_upload_opponent_schedule": _sig(h, _ip, _ip),

@@ -235,6 +235,12 @@ struct gpf_engine {
   int obs_clock_tables = 0, obs_step_minutes = 5, obs_max_step = 0;
   DevArr<int> obs_maint_next, obs_maint_durn;   // [chron_tables][chron_T][n_line] time_next_maintenance / duration_next_maintenance at every row
   long long obs_maint_gen = -1, maint_gen = 0;  // generation of the outage tables the look-ahead was derived from / current generation
+  // the observation as a bus graph (gridpf_graph.hpp, gridpf_capi_graph.hip): the static tables as one int blob, on the host and on the
+  // device, the staging buffers of gpf_graph_obs_host (grow-only), and whether the kernel may copy a lane's rows into LDS (GRIDPF_GRAPH_STAGE)
+  bool gr_on = false, gr_gof = true, gr_stage = true;
+  std::vector<int> h_gr_tab;
+  DevArr<int> gr_tab, gr_index;
+  DevArr<float> gr_feat, gr_dense;
   // the opponent of the batched acting path (gridpf_opponent.hpp, gridpf_capi_opp.hip): its configuration (host), the attackable lines and
   // their normalisation, the per-lane state, the draws table and the Geometric schedules
   int opp_kind = 0;                     // GPF_OPP_*; 0: off -- gpf_step_n launches nothing for it

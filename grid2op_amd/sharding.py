@@ -440,9 +440,10 @@ ROUTES = {
         "sync", "set_deterministic", "set_thermal_limits", "upload_maintenance", "upload_outage_durations", "upload_hazards", "upload_forecasts",
         "set_gen_limits", "set_gen_renewable", "set_storage_params", "set_env_dynamics", "set_trajectory", "set_obs_clock", "set_obs_spec",
         "lane_actions_on_device", "topo_actions_on_device", "alerts_on_device",        # each device's act_* buffers hold its own lanes
-        "set_topo_rules", "set_topo_areas", "set_topo_slots", "set_opponent_areas", "set_alerts", "set_rewards", "set_combined_actions"), {}),
+        "set_topo_rules", "set_topo_areas", "set_topo_slots", "set_opponent_areas", "set_alerts", "set_rewards", "set_combined_actions",
+        "set_graph_obs"), {}),
     # host-side helpers that depend on the grid alone
-    first: dict.fromkeys(("pack_injections", "pack_chronics", "topo_action_areas", "alert_state_fields"), {}),
+    first: dict.fromkeys(("pack_injections", "pack_chronics", "topo_action_areas", "alert_state_fields", "graph_layout"), {}),
     # one entry per device; the views are zero-copy torch tensors (global lane order = concatenation over the list)
     per_device: dict.fromkeys(("device_views", "reward_views", "episode_views", "cursor_views", "combined_views", "plan"), {}),
     # whole-batch per-lane arrays, cut by device block
@@ -455,11 +456,13 @@ ROUTES = {
     gather: {**dict.fromkeys((
         "reset", "get_injections", "get_topology", "step_outputs", "episode", "cooldown", "sub_cooldown", "last_bus", "env_state",
         "observation_vector_host", "topo_action_flags", "topo_action_mask_host", "opponent_state", "opponent_area_state",
-        "opponent_attack_lines", "alert_state", "alert_reward", "rewards", "episode_ends", "episode_stats", "chronics_cursor_state", "action_flags"), {}),
+        "opponent_attack_lines", "alert_state", "alert_reward", "rewards", "episode_ends", "episode_stats", "chronics_cursor_state", "action_flags",
+        "graph_observation_host"), {}),
         "trajectory": dict(steps=True, axis=1), "trajectory_cooldown": dict(steps=True, axis=1), "trajectory_obs": dict(steps=True)},
     # getters that leave their result on the devices: one tensor per shard, each on its own device and stream
     per_shard_tensor: {"observation_vector": dict(keys=("out",)), "topo_action_mask": dict(keys=("out",)),
-                       "rewards_eval": dict(keys=("flags", "out")), "observation_trajectory": dict(keys=("out",), steps=True)},
+                       "rewards_eval": dict(keys=("flags", "out")), "observation_trajectory": dict(keys=("out",), steps=True),
+                       "graph_observation": dict(keys=("out",))},     # (out: one (index, features, dense) tuple per shard)
     # setters of the rows that start at a lane
     scatter: {"set_injections": dict(rows="inj", width="n_inj"), "set_cooldown": dict(rows="line_cooldown", width="model.n_line"),
               "set_overflow_count": dict(rows="counts", width="model.n_line"), "set_sub_cooldown": dict(rows="sub_cooldown", width="model.n_sub"),

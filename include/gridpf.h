@@ -1044,6 +1044,60 @@ int gpf_obs_vector(gpf_handle h, int32_t lane0, int32_t n, float* out_dev, int64
 int gpf_obs_vector_trajectory(gpf_handle h, int32_t step0, int32_t n_steps, int32_t lane0, int32_t n, float* out_dev);
 int gpf_get_obs_vector(gpf_handle h, int32_t lane0, int32_t n, float* host_out);
 
+/* ---- the observation as a bus graph, assembled on the device (what graph-network policies read: BaseObservation.bus_connectivity_matrix,
+ * flow_bus_matrix and the node table of get_energy_graph, Observation/baseObservation.py:2081-2445, 2679-2710) -- one read-only side kernel on
+ * the engine's stream (grid2op_amd/csrc/gridpf_graph.hpp) over the lanes' CURRENT rows (topo_vect, shunt buses, the float32 results row, the
+ * substation cooldowns), as gpf_obs_vector reads them.  Definitions:
+ *   NB = n_sub * n_busbar.  Global bus id g = sub + (busbar - 1) * n_sub (GridObjects.local_bus_to_global).  A line is CONNECTED when both
+ *   of its topo_vect entries are > 0.  A global bus is LIVE when it holds an end of a connected line (_aux_fun_get_bus, :2081-2118); n_bus is
+ *   the number of live buses; the COMPACT id of a live bus is its rank among the live buses in ascending g.
+ * Index row, int32 [lane][width], the sections GPF_GRAPH_* in this order: n_bus (1) | load_bus (n_load) | gen_bus (n_gen) | storage_bus
+ *   (n_storage) | line_or_bus (n_line) | line_ex_bus (n_line) | shunt_bus (n_shunt) | bus_global (NB): the compact id of each element's bus,
+ *   and g of compact bus k (-1 for k >= n_bus).  An element whose busbar is <= 0, both ends of a line that is not connected and an element on
+ *   a busbar that is not live get -1.
+ * Node features, float32 [lane][NB][GPF_GRAPH_N_FEATURES], rows k >= n_bus all zero:
+ *   0 p  float64 sum from the float32 results row, starting at 0: + the bus's generators in index order, - its loads, - its storage units,
+ *        - its shunts, each class in index order; rounded once (the diagonal of flow_bus_matrix(active_flow=True), :2386-2432)
+ *   1 q  the same with gen_q, load_q, shunt_q (storage contributes nothing)
+ *   2 v  v_ex of the highest-index connected line with its extremity on the bus, else v_or of the highest-index connected line with its
+ *        origin on it (the overwrite order of :2694-2695)
+ *   3 cooldown  time_before_cooldown_sub of the bus's substation; 0 while the engine does not track it (gpf_set_topo_rules)
+ * Dense planes (optional), float32 [lane][3][NB][NB], zero outside [n_bus][n_bus]:
+ *   0 bus_connectivity_matrix (:2199-2205): 1 on the live diagonal and at [or][ex], [ex][or] of every connected line
+ *   1, 2 flow_bus_matrix, active and reactive (:2434-2441): the diagonal is the node's p / q; for i != j entry [i][j] is minus the float64
+ *        sum, over the connected lines in index order, of p_or of a line from i to j and p_ex of a line from j to i, rounded once (parallel
+ *        lines add up, as the reference's duplicate csr entries do)
+ * Game-over lanes (done), with game_over_fill != 0: n_bus = 1, every element section 0, bus_global[0] = 0 and the rest -1, features and
+ *   planes zero (:2163-2177, 2321-2330); with 0 the rows are computed from whatever the lane's buffers hold.
+ * Deviations from the reference, on purpose: disconnected elements get the -1 its docstrings promise (it returns the LAST bus, tmplate[-1]);
+ *   a shunt on any busbar is mapped by local_bus_to_global (its formula, :2350-2354, is only right on busbar 1); each sum is one float64
+ *   sum (it sums float32).  No floating-point atomics: results are the same bits in every run, at every place in the batch and in the host
+ *   emulator of tests/native/graph_emul.cpp.
+ *   gpf_set_graph_obs : on != 0 builds the static tables (substation -> elements, lines by substation pair) from the grid, on = 0 frees
+ *                       them.  GPF_E_INVALID when NB > GPF_GRAPH_MAX_BUS.
+ *   gpf_graph_layout  : offsets[GPF_GRAPH_N_SECTIONS] and widths[..] of the index row's sections, *index_width and *nb; any may be NULL.
+ *                       Works on a header-only handle.
+ *   gpf_graph_obs     : rows of lanes [lane0, lane0 + n) -> caller-owned DEVICE buffers index_out [n][width], features_out [n][NB][4]
+ *                       and, unless NULL, dense_out [n][3][NB][NB], all dense.  Asynchronous on the engine's stream (a
+ *                       memset of dense_out is queued ahead of the kernel).  Lane range, NULL outputs and "feature off" are refused before
+ *                       the device is touched.
+ *   gpf_graph_obs_host: the same into HOST arrays; synchronous. */
+#define GPF_GRAPH_N_BUS 0
+#define GPF_GRAPH_LOAD_BUS 1
+#define GPF_GRAPH_GEN_BUS 2
+#define GPF_GRAPH_STORAGE_BUS 3
+#define GPF_GRAPH_LINE_OR_BUS 4
+#define GPF_GRAPH_LINE_EX_BUS 5
+#define GPF_GRAPH_SHUNT_BUS 6
+#define GPF_GRAPH_BUS_GLOBAL 7
+#define GPF_GRAPH_N_SECTIONS 8
+#define GPF_GRAPH_N_FEATURES 4
+#define GPF_GRAPH_MAX_BUS 1024
+int gpf_set_graph_obs(gpf_handle h, int32_t on, int32_t game_over_fill);
+int gpf_graph_layout(gpf_handle h, int32_t* offsets, int32_t* widths, int32_t* index_width, int32_t* nb);
+int gpf_graph_obs(gpf_handle h, int32_t lane0, int32_t n, int32_t* index_out, float* features_out, float* dense_out);
+int gpf_graph_obs_host(gpf_handle h, int32_t lane0, int32_t n, int32_t* index_out, float* features_out, float* dense_out);
+
 /* Trajectory buffers of multi-step launches (n_steps_cap = 0 or what = 0 releases them).
  *   GPF_TRAJ_RHO: rho [cap][n_lanes][n_line] and status [cap][n_lanes] of every step of the last gpf_step_n.
  *   GPF_TRAJ_OBS: in addition the complete backend observation of every step -- results row out [cap][n_lanes][n_out]
