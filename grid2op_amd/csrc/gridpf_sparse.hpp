@@ -686,30 +686,49 @@ __device__ inline bool block_lu_solve(const SymDev& S, PP prog, double* __restri
   return ok;
 }
 
-// ---- item words of the flat program RESIDENT in registers (instance-group kernels) ---------------------------------------------
+// ---- the lane's items of the flat program RESIDENT in registers (instance-group kernels) -----------------------------------------
 // Lane t executes item t of pass k of the same flat program in every sweep of every Newton iteration of every step of a launch, and
 // the instance-group kernels (IPW > 1: the small grids) read those words from global memory (see solve_instance_sparse: PROG_LDS): a
 // dependent L2 round trip at the head of both sweeps, 8 times per env step, and a vmcnt wait in front of every pass.  Their programs
-// are a handful of passes (14 substations: 5 forward + 1 back at group width 32), so the lane's words of EVERY pass are loaded ONCE per launch, before the
-// step loop, and the sweeps take them from registers: no global load is left in the Newton loop.  Grid-specialised build: the pass
-// counts are literals, the walk unrolls to exactly the passes of the grid and the words are 2 VGPRs per pass.  Shipped build:
-// GPF_WR_CAP_F forward and GPF_WR_CAP_B back passes are held (16 VGPRs: the back substitution of these grids is one pass; with 8 + 8 the
-// shipped kernels with the injection dynamics went to 256 VGPRs and 24 ... 40 bytes of scratch); a program with more passes in either
-// sweep (block-uniform) streams as before.
-// The two variants issue the same arithmetic on the same operands in the same order.  -DGPF_NO_WORDS_RES: developer A/B build, streaming only.
+// are a handful of passes (14 substations: 5 forward + 1 back at group width 32), so what the lane needs of EVERY pass is loaded ONCE per
+// launch, before the step loop, and the sweeps take it from registers: no global load is left in the Newton loop.  Two forms:
+//  * ADDRESSES (mode 2; grid-specialised build of the grid's own program: the pass counts are literals, the walk unrolls to exactly the
+//    passes of the grid).  What a sweep uses is not the item's two words but the LDS byte addresses of its blocks, group base included:
+//    dst, l, u, p of a forward item (4 VGPRs per pass), u, dj, dst of a back item (3; the column's right-hand side is dj + rhs_field0).
+//    The sweeps issue their ds_read_b128 / ds_add_f64 on these registers with the row-1 half as an immediate offset: the four "base +
+//    16-bit field" adds per pass of every iteration of every step are gone.  The two per-pass predicates are read off the destination
+//    address where they are used: GPF_NO_ITEM for "no item for this lane in this pass", below `lim` = base + rhs_field0 for "the
+//    destination is a matrix block, not a right-hand-side pseudo-slot" -- one VALU compare each instead of eleven loop-invariant 64-bit
+//    lane masks that the compiler hoisted, spilled to VGPR lanes and read back in every pass (see block_lu_flat).  14 substations:
+//    5 * 4 + 3 + 2 = 25 VGPRs instead of 12; the headline kernel has them (222 of 256 VGPRs, no scratch).
+//  * WORDS (mode 1; shipped build and the kernels of the topology classes, whose pass counts are run-time values): GPF_WR_CAP_F forward
+//    and GPF_WR_CAP_B back passes of two words each (16 VGPRs: the back substitution of these grids is one pass; with 8 + 8 the
+//    shipped kernels with the injection dynamics went to 256 VGPRs and 24 ... 40 bytes of scratch, and with the addresses of 6 + 2 passes
+//    to 96 ... 140 bytes), decoded by every pass; a program with more passes in either sweep (block-uniform) streams as before.
+// All variants issue the same arithmetic on the same operands in the same order.  -DGPF_NO_WORDS_RES: developer A/B build, streaming only.
 constexpr int GPF_WR_CAP_F = 6, GPF_WR_CAP_B = 2;
-template <bool ON> struct FlatWords { };
-template <> struct FlatWords<true> { unsigned f[2 * GPF_WR_CAP_F], b[2 * GPF_WR_CAP_B]; };
+typedef __attribute__((address_space(3))) char lds_char;
+typedef __attribute__((address_space(3))) double lds_double;
+typedef double gpf_d2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) gpf_d2 lds_d2;
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)reinterpret_cast<size_t>((const lds_char*)p); }
+__device__ __forceinline__ lds_char* lds_at(unsigned a) { return reinterpret_cast<lds_char*>((size_t)a); }
+constexpr unsigned GPF_NO_ITEM = 0xffffffffu;
+template <int MODE> struct FlatWords { };
+template <> struct FlatWords<1> { unsigned f[2 * GPF_WR_CAP_F], b[2 * GPF_WR_CAP_B]; };
+template <> struct FlatWords<2> { unsigned f[4 * GPF_WR_CAP_F], b[3 * GPF_WR_CAP_B], base, lim; };
 #ifdef GPF_NO_WORDS_RES
-template <int NB, int IPW, int WPI> constexpr bool flat_words_ct() { return false; }
+template <int NB, int IPW, int WPI, bool TC = true> constexpr int flat_words_ct() { return 0; }
+#elif defined(GPF_JIT)
+template <int NB, int IPW, int WPI, bool TC = true> constexpr int flat_words_ct() { return NB == 1 && IPW > 1 && WPI == 1 ? (TC ? 1 : 2) : 0; }
 #else
-template <int NB, int IPW, int WPI> constexpr bool flat_words_ct() { return NB == 1 && IPW > 1 && WPI == 1; }
+template <int NB, int IPW, int WPI, bool TC = true> constexpr int flat_words_ct() { return NB == 1 && IPW > 1 && WPI == 1 ? 1 : 0; }
 #endif
 __device__ __forceinline__ bool flat_words_fit(const FlatDev& F) { return F.n_fwd <= GPF_WR_CAP_F && F.n_back <= GPF_WR_CAP_B; }
 template <int GW, class PP>
-__device__ __forceinline__ void flat_words_load(FlatWords<false>&, const FlatDev&, PP, int) {}
+__device__ __forceinline__ void flat_words_load(FlatWords<0>&, const FlatDev&, PP, int, const double*) {}
 template <int GW, class PP>
-__device__ __forceinline__ void flat_words_load(FlatWords<true>& W, const FlatDev& F, PP prog, int tid) {
+__device__ __forceinline__ void flat_words_load(FlatWords<1>& W, const FlatDev& F, PP prog, int tid, const double*) {
   const bool fit = flat_words_fit(F);
 #pragma unroll
   for (int k = 0; k < GPF_WR_CAP_F; ++k) {             // (every pass is GW items of two words, 0xffffffff: no item for this lane)
@@ -724,6 +743,37 @@ __device__ __forceinline__ void flat_words_load(FlatWords<true>& W, const FlatDe
     W.b[2 * k + 1] = on_b ? (unsigned)prog[F.back_off + 2 * tid + 2 * GW * k + 1] : 0u;
   }
 }
+template <int GW, class PP>
+__device__ __forceinline__ void flat_words_load(FlatWords<2>& W, const FlatDev& F, PP prog, int tid, const double* A) {
+  const bool fit = flat_words_fit(F);
+  const unsigned base = lds_addr(A);
+  W.base = base;
+  W.lim = base + (unsigned)F.rhs_field0;
+#pragma unroll
+  for (int k = 0; k < GPF_WR_CAP_F; ++k) {
+    const bool on_f = fit && k < F.n_fwd;
+    const unsigned w0 = on_f ? (unsigned)prog[2 * tid + 2 * GW * k] : 0xffffffffu;
+    const unsigned w1 = on_f ? (unsigned)prog[2 * tid + 2 * GW * k + 1] : 0u;
+    W.f[4 * k] = w0 != 0xffffffffu ? base + (w0 & 0xffffu) : GPF_NO_ITEM;
+    W.f[4 * k + 1] = base + (w0 >> 16);
+    W.f[4 * k + 2] = base + (w1 & 0xffffu);
+    W.f[4 * k + 3] = base + (w1 >> 16);
+  }
+#pragma unroll
+  for (int k = 0; k < GPF_WR_CAP_B; ++k) {
+    const bool on_b = fit && k < F.n_back;
+    const unsigned w0 = on_b ? (unsigned)prog[F.back_off + 2 * tid + 2 * GW * k] : 0xffffffffu;
+    const unsigned w1 = on_b ? (unsigned)prog[F.back_off + 2 * tid + 2 * GW * k + 1] : 0u;
+    W.b[3 * k] = w0 != 0xffffffffu ? base + (w0 & 0xffffu) : GPF_NO_ITEM;
+    W.b[3 * k + 1] = base + (w0 >> 16) - (unsigned)F.rhs_field0;
+    W.b[3 * k + 2] = base + w1;
+  }
+  // (opaque from here on: the compiler would otherwise keep the words and redo "base + field" where an address is used)
+#pragma unroll
+  for (int i = 0; i < 4 * GPF_WR_CAP_F; ++i) asm volatile("" : "+v"(W.f[i]));
+#pragma unroll
+  for (int i = 0; i < 3 * GPF_WR_CAP_B; ++i) asm volatile("" : "+v"(W.b[i]));
+}
 
 // ---- flat-program sweeps (gridpf_symbolic.hpp: FlatProg) -------------------------------------------------------------------
 // Block LU + solve with 2x2 blocks on the flat program.  A: row 0 of every (pseudo-)slot at A + slot * 2, row 1 at
@@ -733,10 +783,10 @@ __device__ __forceinline__ void flat_words_load(FlatWords<true>& W, const FlatDe
 // deferred scaling pass is gone): the back substitution accumulates s_p -= A_pj inv(D_j) s_j with ds_add_f64 and the caller forms
 // x_p = inv(D_p) s_p where it consumes the solution (flat_solution).  What a phase costs is its instruction count: no level headers,
 // no bounds / clamps, no "trailing update or right-hand side?" selects, byte offsets instead of slot indices.
-// RES: the lane's item words come from W (flat_words_load, registers) instead of `prog`: no load in the sweeps.
-template <int GW, class PP = const int*, bool RES = false>
+// RES: the lane's item words (1) or item addresses (2) come from W (flat_words_load, registers) instead of `prog`: no load in the sweeps.
+template <int GW, class PP = const int*, int RES = 0>
 __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restrict__ A, size_t HS, int tid, long long* dbg = nullptr,
-                                     const FlatWords<RES>* W = nullptr) {
+                                     FlatWords<RES>* W = nullptr) {
 #ifdef GPF_TIMING
   const long long t_lu0 = __builtin_readcyclecounter();
 #endif
@@ -778,6 +828,42 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
       }
     }
   };
+  // The same item on the lane's resident addresses (FlatWords<true>): row 1 of a block is the constant HS * 8 bytes behind row 0, an
+  // immediate offset of the LDS instruction.  "The lane has an item in this pass" and "the destination is a matrix block" are read off
+  // the destination address where they are used -- the registers are made opaque at the head of the sweeps, so that the compiler does
+  // not hoist the two compares of every pass out of the Newton loop as 64-bit lane masks (eleven of them: they were spilled to VGPR
+  // lanes and read back in every pass).
+  if constexpr (RES == 2) {
+#pragma unroll
+    for (int k = 0; k < GPF_WR_CAP_F; ++k) asm volatile("" : "+v"(W->f[4 * k]));
+#pragma unroll
+    for (int k = 0; k < GPF_WR_CAP_B; ++k) asm volatile("" : "+v"(W->b[3 * k]));
+  }
+  auto fwd_item_res = [&](const int k) {
+    if constexpr (RES == 2) {
+      const unsigned ad = W->f[4 * k];
+      if (ad != GPF_NO_ITEM) {
+        const lds_char* const pp = lds_at(W->f[4 * k + 3]);
+        const lds_char* const pl = lds_at(W->f[4 * k + 1]);
+        const lds_char* const pu = lds_at(W->f[4 * k + 2]);
+        lds_char* const pd = lds_at(ad);
+        const gpf_d2 dA = *reinterpret_cast<const lds_d2*>(pp), dB = *reinterpret_cast<const lds_d2*>(pp + HS * 8);
+        const gpf_d2 lA = *reinterpret_cast<const lds_d2*>(pl), lB = *reinterpret_cast<const lds_d2*>(pl + HS * 8);
+        const gpf_d2 uA = *reinterpret_cast<const lds_d2*>(pu), uB = *reinterpret_cast<const lds_d2*>(pu + HS * 8);
+        const double rd = -fast_rcp(fma(dA.x, dB.y, -dA.y * dB.x));
+        const double t00 = fma(lA.x, dB.y, -lA.y * dB.x), t01 = fma(lA.y, dA.x, -lA.x * dA.y);
+        const double t10 = fma(lB.x, dB.y, -lB.y * dB.x), t11 = fma(lB.y, dA.x, -lB.x * dA.y);
+        double* const d0_ = (double*)reinterpret_cast<lds_double*>(pd);
+        double* const d1_ = (double*)reinterpret_cast<lds_double*>(pd + HS * 8);
+        atomicAdd(&d0_[0], fma(t00, uA.x, t01 * uB.x) * rd);
+        atomicAdd(&d1_[0], fma(t10, uA.x, t11 * uB.x) * rd);
+        if (ad < W->lim) {
+          atomicAdd(&d0_[1], fma(t00, uA.y, t01 * uB.y) * rd);
+          atomicAdd(&d1_[1], fma(t10, uA.y, t11 * uB.y) * rd);
+        }
+      }
+    }
+  };
   // Walk of a sweep's passes: lane t executes item t of every pass, then the phase boundary.
   //  * The words of pass k + 1 are fetched before pass k computes; PF2 (several wavefronts per instance, whose phase boundary does not
   //    wait for global loads): those of pass k + 2, through three register pairs in rotation -- a plain copy "next = the one after"
@@ -800,11 +886,15 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
       else GPF_LSYNC();                                                                                                            \
       GPF_PASS_T((TB_) + k);                                                                                                       \
     };                                                                                                                             \
-    if constexpr (RES) {             /* resident words: a fully unrolled walk over register pairs, no load */                      \
+    if constexpr (RES == 2) {        /* resident addresses: a fully unrolled walk over the lane's registers, no load, no decode */  \
+      _Pragma("unroll")                                                                                                            \
+      for (int k = 0; k < (CAP_); ++k)                                                                                             \
+        if (k < n_pass_) { ITEM_##_res(k); GPF_LSYNC(); GPF_PASS_T((TB_) + k); }   /* (GW < WAVE: no solo passes) */              \
+    } else if constexpr (RES == 1) { /* resident words: a fully unrolled walk over register pairs, no load */                      \
       _Pragma("unroll")                                                                                                            \
       for (int k = 0; k < (CAP_); ++k)                                                                                             \
         if (k < n_pass_) step_(W->WR_[2 * k], W->WR_[2 * k + 1], k);                                                               \
-    } else {                                                                                                                       \
+    } else {                                                                                                                  \
     int at = (at0_) + 2 * tid;                                                                                                     \
     unsigned p0 = (unsigned)prog[at], p1 = (unsigned)prog[at + 1];                                                                 \
     if (PF2) {                                                                                                                     \
@@ -848,6 +938,24 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
       atomicAdd(FL_D(a1, w1), -fma(uB.x, x0, uB.y * x1));
     }
   };
+  auto back_item_res = [&](const int k) {
+    if constexpr (RES == 2) {
+      const unsigned au = W->b[3 * k];
+      if (au != GPF_NO_ITEM) {
+        const lds_char* const pu = lds_at(au);
+        const lds_char* const pdj = lds_at(W->b[3 * k + 1]);
+        const lds_char* const pj = pdj + F.rhs_field0;
+        lds_char* const pd = lds_at(W->b[3 * k + 2]);
+        const gpf_d2 uA = *reinterpret_cast<const lds_d2*>(pu), uB = *reinterpret_cast<const lds_d2*>(pu + HS * 8);
+        const gpf_d2 dA = *reinterpret_cast<const lds_d2*>(pdj), dB = *reinterpret_cast<const lds_d2*>(pdj + HS * 8);
+        const double s0 = *reinterpret_cast<const lds_double*>(pj), s1 = *reinterpret_cast<const lds_double*>(pj + HS * 8);
+        const double rd = fast_rcp(fma(dA.x, dB.y, -dA.y * dB.x));
+        const double x0 = fma(dB.y, s0, -dA.y * s1) * rd, x1 = fma(dA.x, s1, -dB.x * s0) * rd;
+        atomicAdd((double*)reinterpret_cast<lds_double*>(pd), -fma(uA.x, x0, uA.y * x1));
+        atomicAdd((double*)reinterpret_cast<lds_double*>(pd + HS * 8), -fma(uB.x, x0, uB.y * x1));
+      }
+    }
+  };
   GPF_WALK(F.n_back, F.back_off, F.solo_back, false, back_item, 1 + F.n_fwd, b, GPF_WR_CAP_B)
 #ifdef GPF_TIMING
   if (dbg) { dbg[0] = t_lu1 - t_lu0; dbg[1] = (long long)__builtin_readcyclecounter() - t_lu1; }
@@ -861,9 +969,9 @@ __device__ inline bool block_lu_flat(const FlatDev& F, PP prog, double* __restri
 // the forward sweep), COMPACT: as one double per slot (CarveP::Adc) instead of element [0][0] of the row-0 half; only the
 // right-hand-side items of the forward sweep and the back substitution run.  On return the first entry of pseudo-slot p holds
 // s_p = d_p * theta_p (the caller divides by the pivot, like the 2x2 sweep's callers apply inv(D_p)).
-template <int GW, bool FACTOR, bool COMPACT, class PP = const int*, bool RES = false>
+template <int GW, bool FACTOR, bool COMPACT, class PP = const int*, int RES = 0>
 __device__ inline bool scalar_lu_flat(const FlatDev& F, PP prog, double* __restrict__ A, double* __restrict__ fac, int tid,
-                                      long long* dbg = nullptr, const FlatWords<RES>* W = nullptr) {
+                                      long long* dbg = nullptr, FlatWords<RES>* W = nullptr) {
 #ifdef GPF_TIMING
   const long long t_lu0 = __builtin_readcyclecounter();
 #endif
@@ -886,6 +994,13 @@ __device__ inline bool scalar_lu_flat(const FlatDev& F, PP prog, double* __restr
       atomicAdd(dst, -(al * x) * fast_rcp(d));
     }
   };
+  // (resident addresses: the scalar sweeps work on the fields, address - base; they run once per solve at most, not in the Newton loop)
+  auto fwd_item_res = [&](const int k) {
+    if constexpr (RES == 2) {
+      const unsigned ad = W->f[4 * k], bs = W->base;
+      fwd_item(ad != GPF_NO_ITEM ? ((ad - bs) | ((W->f[4 * k + 1] - bs) << 16)) : 0xffffffffu, (W->f[4 * k + 2] - bs) | ((W->f[4 * k + 3] - bs) << 16));
+    }
+  };
 #undef GPF_PASS_T
 #define GPF_PASS_T(i_) do {} while (0)
   GPF_WALK(F.n_fwd, 0, F.solo_fwd, F.n_back > 0 && (F.solo_back & 1), fwd_item, 0, f, GPF_WR_CAP_F)
@@ -896,6 +1011,12 @@ __device__ inline bool scalar_lu_flat(const FlatDev& F, PP prog, double* __restr
     if (w0 != 0xffffffffu) {
       const unsigned fj = w0 >> 16;
       atomicAdd(FL_D(a0, w1), -(*facp(w0 & 0xffffu) * *FL_D(a0, fj)) * fast_rcp(*facp(fj - (unsigned)F.rhs_field0)));
+    }
+  };
+  auto back_item_res = [&](const int k) {
+    if constexpr (RES == 2) {
+      const unsigned au = W->b[3 * k], bs = W->base;
+      back_item(au != GPF_NO_ITEM ? ((au - bs) | ((W->b[3 * k + 1] - bs + (unsigned)F.rhs_field0) << 16)) : 0xffffffffu, W->b[3 * k + 2] - bs);
     }
   };
   GPF_WALK(F.n_back, F.back_off, F.solo_back, false, back_item, 0, b, GPF_WR_CAP_B)
@@ -954,7 +1075,7 @@ struct TopoState {
 constexpr int YR_PASSES = 4;
 template <int NB, int STAGE, int IPW, int WPI, bool TC, bool YR = false>
 __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, const SymDev& S, const FlatDev& FL, const StatView<STAGE>& sv, CarveP<NB>& c, double2* yreg, unsigned* rcreg,
-                                            const FlatWords<flat_words_ct<NB, IPW, WPI>()>& FW, int inst, int is_dc, int max_iter,
+                                            FlatWords<flat_words_ct<NB, IPW, WPI, TC>()>& FW, int inst, int is_dc, int max_iter,
                                             double tol_pu, int tid, const SolveCtl& ctl, TopoState& ts, int& n_iter_out, int& nb_out, float& a_or_first GPF_STAMPS_PARAM) {
   typedef Grp<IPW, WPI> G;
   constexpr int GW = G::GW;
@@ -1327,7 +1448,7 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
   const int* const flat_g = STAGE == 0 ? sv.prog.p : S.flat[gw_index(GW)];     // (tier 0: the view already points at the global copy)
   constexpr bool PROG_LDS = STAGE >= 1 && IPW == 1;
   // (instance-group kernels: the words are in registers for the whole launch, FlatWords, unless the program has too many passes)
-  constexpr bool WRES = flat_words_ct<NB, IPW, WPI>();
+  constexpr int WRES = flat_words_ct<NB, IPW, WPI, TC>();         // 0: streamed, 1: resident words, 2: resident addresses
   const bool wres = WRES && flat_words_fit(FL);                 // block-uniform; a literal in the grid-specialised build
   auto lu_ac = [&](long long* dbg) -> bool {
     if (BS == 2) {
@@ -1521,6 +1642,17 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
       GPF_LSYNC();
       GPF_STAMPS(10);
       // (assembler comments, no instruction: tests/test_step_kernel_words_resident.py finds the loop in the disassembly by them)
+      // JACOBIAN ONLY FOR AN EVALUATION THAT IS FACTORISED (instance-group kernels with resident item addresses).  The last evaluation of a
+      // solve finds convergence: its Jacobian blocks, diagonal block and right-hand side are read by nobody.  The pair phase keeps T_uv, T_vu
+      // and 1/|V| of its two ends in registers and only accumulates S; the mismatch phase forms S_i, the mismatch and the verdict; what the
+      // LU reads is written behind the block-uniform exit test, in front of the phase boundary that was there already.  Same values, same
+      // number of phase boundaries, the order of the atomics untouched.  The other kernels write where they compute, as before.
+#ifdef GPF_NO_LATE_J
+      constexpr bool LATE_J = false;            // developer A/B build: resident addresses, Jacobian written where it is computed
+#else
+      constexpr bool LATE_J = WRES == 2;
+#endif
+      double j_tr, j_ti, j_sr, j_si, j_ivmu, j_ivmv, j_dtr, j_dti, j_mp, j_mq;
       asm volatile("; GPF_NEWTON_NWR_BEGIN" ::: "memory");
       while (true) {
         // ---- pair phase: T_uv, T_vu -> the two off-diagonal Jacobian blocks, S_u += T_uv, S_v += T_vu
@@ -1531,10 +1663,12 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
           const double2 yuv = NWR_YUV, yvu = NWR_YVU;
           t_of(yuv, efu.x, efu.y, efv.x, efv.y, tr_, ti_);
           t_of(yvu, efv.x, efv.y, efu.x, efu.y, sr_, si_);
+          if (!LATE_J) {
           *reinterpret_cast<double2*>(b_uv0) = make_double2((uP && vP) ? ti_ : 0.0, (uP && vQ) ? tr_ * ivmv : 0.0);
           *reinterpret_cast<double2*>(b_uv1) = make_double2((uQ && vP) ? -tr_ : 0.0, (uQ && vQ) ? ti_ * ivmv : 0.0);
           *reinterpret_cast<double2*>(b_vu0) = make_double2((vP && uP) ? si_ : 0.0, (vP && uQ) ? sr_ * ivmu : 0.0);
           *reinterpret_cast<double2*>(b_vu1) = make_double2((vQ && uP) ? -sr_ : 0.0, (vQ && uQ) ? si_ * ivmu : 0.0);
+          } else { j_tr = tr_; j_ti = ti_; j_sr = sr_; j_si = si_; j_ivmu = ivmu; j_ivmv = ivmv; }
           if (acc_u) { atomicAdd(SreP(u), tr_); atomicAdd(SimP(u), ti_); }
           if (acc_v) { atomicAdd(SreP(v), sr_); atomicAdd(SimP(v), si_); }
         }
@@ -1550,18 +1684,32 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
           double tr_, ti_;
           t_of(ydiag, e, f, e, f, tr_, ti_);
           if (diag_on) { Sr += tr_; Si += ti_; }
+          if (!LATE_J) {
           const double2 r0 = make_double2(rowP ? ti_ : 0.0, (rowP && rowQ) ? tr_ * ivm : 0.0);
           const double2 r1 = make_double2((rowQ && rowP) ? -tr_ : 0.0, rowQ ? ti_ * ivm : 0.0);
           *reinterpret_cast<double2*>(Ad0) = make_double2(rowP ? r0.x - Si : 1.0, rowQ ? fma(Sr, ivm, r0.y) : r0.y);
           *reinterpret_cast<double2*>(Ad1) = make_double2(rowQ ? r1.x + Sr : r1.x, rowQ ? fma(Si, ivm, r1.y) : 1.0);
+          }
           const double mp = rowP ? (Sr - psp) : 0.0;
           const double mq = rowQ ? (Si - qsp) : 0.0;
-          *rhsT(ib) = -mp; *rhsV(ib) = -mq;
+          if (!LATE_J) { *rhsT(ib) = -mp; *rhsV(ib) = -mq; }
+          else { j_dtr = tr_; j_dti = ti_; j_mp = mp; j_mq = mq; }
           const double am = fmax(fabs(mp), fabs(mq));
           if (!(am <= 1e300)) bad = true;
           fabs_mis = am;
         }
-        if (!done) {
+        if (LATE_J) {
+          // the same verdict without a branch per test (groups that are done take no part): numerical failure, then convergence, then
+          // the iteration limit, else one more iteration
+          // (`bad` is !(fabs_mis <= 1e300): a lane without a bus holds 0)
+          const bool a_bad = G::any(!(fabs_mis <= 1e300)), a_open = G::any(!(fabs_mis < tol_pu));
+          const bool live = !done, f_bad = live && a_bad, f_conv = live && !a_bad && !a_open, f_more = live && !a_bad && a_open;
+          const bool below = it < max_iter;
+          status = f_bad ? 1 : status;
+          converged = converged || f_conv;
+          done = done || f_bad || f_conv || (f_more && !below);
+          it += (f_more && below) ? 1 : 0;
+        } else if (!done) {
           const unsigned fl = G::template any2<0>(!(fabs_mis < tol_pu), bad);
           if (fl & 2u) { status = 1; done = true; }
           else if (!(fl & 1u)) { converged = true; done = true; }
@@ -1569,6 +1717,21 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
           else ++it;
         }
         if (G::block_all_u(done)) break;
+        if constexpr (LATE_J) {               // this evaluation is factorised: now its Jacobian blocks and right-hand side
+          if (p_on) {
+            *reinterpret_cast<double2*>(b_uv0) = make_double2((uP && vP) ? j_ti : 0.0, (uP && vQ) ? j_tr * j_ivmv : 0.0);
+            *reinterpret_cast<double2*>(b_uv1) = make_double2((uQ && vP) ? -j_tr : 0.0, (uQ && vQ) ? j_ti * j_ivmv : 0.0);
+            *reinterpret_cast<double2*>(b_vu0) = make_double2((vP && uP) ? j_si : 0.0, (vP && uQ) ? j_sr * j_ivmu : 0.0);
+            *reinterpret_cast<double2*>(b_vu1) = make_double2((vQ && uP) ? -j_sr : 0.0, (vQ && uQ) ? j_si * j_ivmu : 0.0);
+          }
+          if (b_on) {
+            const double2 r0 = make_double2(rowP ? j_dti : 0.0, (rowP && rowQ) ? j_dtr * ivm : 0.0);
+            const double2 r1 = make_double2((rowQ && rowP) ? -j_dtr : 0.0, rowQ ? j_dti * ivm : 0.0);
+            *reinterpret_cast<double2*>(Ad0) = make_double2(rowP ? r0.x - Si : 1.0, rowQ ? fma(Sr, ivm, r0.y) : r0.y);
+            *reinterpret_cast<double2*>(Ad1) = make_double2(rowQ ? r1.x + Sr : r1.x, rowQ ? fma(Si, ivm, r1.y) : 1.0);
+            *rhsT(ib) = -j_mp; *rhsV(ib) = -j_mq;
+          }
+        }
         GPF_LSYNC();
         if (it == 1) GPF_STAMPS(12);
 #ifdef GPF_TIMING
@@ -1601,9 +1764,17 @@ __device__ inline int solve_instance_sparse(const DevParamsS* __restrict__ P, co
           *SreP(ib) = 0.0;
           *SimP(ib) = 0.0;
         }
+        if (LATE_J && (S.nslot - S.nslot_y) * 2 <= GW) {      // (a literal there: one trip per lane at the most, tid < GW -- no loop)
+          const int i = S.nslot_y * 2 + tid;
+          if (i < S.nslot * 2) { c.A[i] = 0.0; c.A[HS + i] = 0.0; }
+        } else
         for (int i = S.nslot_y * 2 + tid; i < S.nslot * 2; i += GW) { c.A[i] = 0.0; c.A[HS + i] = 0.0; }
         GPF_LSYNC();
-        if (!done && G::template any2<1>(!ok || !piv_ok, !fin) != 0u) { status = 4; done = true; }
+        if (LATE_J) {
+          const bool f_num = !done && G::any(!ok || !piv_ok || !fin);
+          status = f_num ? 4 : status;
+          done = done || f_num;
+        } else if (!done && G::template any2<1>(!ok || !piv_ok, !fin) != 0u) { status = 4; done = true; }
         if (it == 1) GPF_STAMPS(14);
         asm volatile("; GPF_NEWTON_NWR_BACKEDGE" ::: "memory");
       }
@@ -2219,8 +2390,8 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void runpf_sparse_kerne
   ctl.otraj = false; ctl.orow = inst; ctl.write_topo = true; ctl.inj_regs = false; ctl.tc_rebuild = false;
   TopoState ts;
   ts.status = 0; ts.nb = 0; ts.dc_base = false; ts.dc_out = -1; ts.gen_base = false; ts.tc[0] = ts.tc[1] = -1;
-  FlatWords<flat_words_ct<NB, IPW, WPI>()> FW;
-  flat_words_load<GW>(FW, FL, gptr(S.flat[GWI]), tid);
+  FlatWords<flat_words_ct<NB, IPW, WPI, TC>()> FW;
+  flat_words_load<GW>(FW, FL, gptr(S.flat[GWI]), tid, c.A);
   const int st = solve_instance_sparse<NB, STAGE, IPW, WPI, TC, YR>(P, S, FL, sv, c, yreg, rcreg, FW, inst, is_dc, max_iter, tol_pu, tid, ctl, ts, n_iter, nb, a_first GPF_STAMPS_ARG);
   GPF_SYNC();
   if (st != 0) write_nan_results<GW>(g, P->b, inst, tid, inst, false);
@@ -2722,8 +2893,8 @@ __global__ __launch_bounds__(WAVE * WPI, GPF_MINW(MINW)) void step_sparse_kernel
   const bool tobs = b.traj_out != nullptr;
   // the lane's item words of the flat program, once per launch (the block's program is the same for every step: the grid's, or the one of
   // the topology class the host packed the block's lanes by)
-  FlatWords<flat_words_ct<NB, IPW, WPI>()> FW;
-  flat_words_load<GW>(FW, FL, gptr(S.flat[GWI]), tid0);
+  FlatWords<flat_words_ct<NB, IPW, WPI, TC>()> FW;
+  flat_words_load<GW>(FW, FL, gptr(S.flat[GWI]), tid0, c.A);      // (the group's LDS carve is the same in every step: GPF_REDERIVE)
   for (int step = 0; step < sa.n_steps; ++step) {
     GPF_REDERIVE();
     const bool last = step + 1 == sa.n_steps;
