@@ -315,20 +315,25 @@ gpf::Symbolic build_symbolic_resident(const gpf::GridDev& g, int n_rows, int n_l
   return S;
 }
 
-int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb);
+int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb, bool list_tail = false);
 
 // p: the plan of the range (or of its single-busbar lanes when the batch is mixed); pb.sparse_nb != 0: second launch for
 // the lanes that have a split substation (both then run from device lane lists)
 int plan_launch(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb) {
   const bool whole = (lane0 == 0 && n == e->n_lanes);
   if (whole && e->plan_valid) { p = e->plan_cached; pb = e->plan_b_cached; return GPF_OK; }
+  // the batch's plan is made anew: whatever invalidated it invalidated the N-1 screen's plans too, and plan_valid is about to say
+  // "nothing changed" again (n1_plans makes its two, calls this last and only then marks them valid)
+  if (whole) e->n1_plan_valid = false;
   int rc = plan_launch_uncached(e, lane0, n, p, pb);
   if (!whole && (p.n_list || pb.n_list)) e->plan_valid = false;     // the device lane lists were overwritten
   if (rc == GPF_OK && whole) { e->plan_cached = p; e->plan_b_cached = pb; e->plan_valid = true; }
   return rc;
 }
 
-int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb) {
+// list_tail: a range of unsplit lanes that does not end on an instance group runs from a lane list padded with ghost lanes, on the
+// groups the whole batch runs on (a contiguous range would fall back to narrower groups: other bits and a slower kernel on small grids)
+int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb, bool list_tail) {
   pb = LaunchPlan{};
   p = LaunchPlan{};
   p.ipw = 1;
@@ -473,6 +478,21 @@ int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchP
         return GPF_OK;
       }
     }
+    if (list_tail && mb == 1) {
+      const int full = e->ipw_override ? e->ipw_override : (e->g.n_sub <= 8 ? 4 : e->g.n_sub <= 24 ? 2 : 1);
+      LaunchPlan q = p;
+      if (full > 1 && (lane0 % full || (n % full && lane0 + n != e->n_lanes)) && plan_sparse(1, n, 0, true, q) && q.ipw == full) {
+        std::vector<int> la(n);
+        for (int k = 0; k < n; ++k) la[k] = lane0 + k;
+        while (la.size() % 4) la.push_back(e->n_lanes);               // ghost lane (pristine state, never read back)
+        if (e->list_a.n < la.size() + 4) HIP_TRY(e->list_a.alloc(std::max<size_t>(la.size() + 4, (size_t)e->cap_lanes + 8) * 2));
+        HIP_TRY(hipMemcpyAsync(e->list_a.p, la.data(), la.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));                     // the host vector goes out of scope
+        q.n_list = n; q.list = e->list_a.p;
+        p = q;
+        return GPF_OK;
+      }
+    }
     if ((mb == 1 || blocks_ok) && plan_sparse(mb == 1 ? 1 : e->g.n_busbar, n, lane0, false, p)) return GPF_OK;
     if (mb > 1 && !blocks_ok)
       return fail(GPF_E_CAPACITY, "a lane with a split substation has no topology class (GRIDPF_NO_CLASSES / GRIDPF_NO_PARTITION set, or the class "
@@ -585,6 +605,17 @@ int reset_lanes_unchecked(gpf_engine* e, int lane0, int n) {
 }
 
 }  // namespace
+
+// the plan of a lane range on device lane lists of the caller's: the planner fills list_a / list_b / list_c, which stand in for the
+// caller's three for the duration of the call (the batch's cached plan and its lists are untouched)
+int plan_launch_own(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb, DevArr<int>* lists, bool list_tail) {
+  DevArr<int>* mine[3] = {&e->list_a, &e->list_b, &e->list_c};
+  auto swap_all = [&]() { for (int i = 0; i < 3; ++i) { std::swap(mine[i]->p, lists[i].p); std::swap(mine[i]->n, lists[i].n); std::swap(mine[i]->cap, lists[i].cap); } };
+  swap_all();
+  const int rc = plan_launch_uncached(e, lane0, n, p, pb, list_tail);
+  swap_all();
+  return rc;
+}
 
 gpf_engine::~gpf_engine() {
   if (dry) return;                      // (a header-only handle owns no device resource)
@@ -1175,8 +1206,16 @@ int gpf_runpf(gpf_handle e, int32_t lane0, int32_t n, int32_t is_dc, int32_t max
   if (!check_range(e, lane0, n)) return fail(GPF_E_INVALID, "gpf_runpf: bad range");
   if (n == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
+  return runpf_range(e, lane0, n, is_dc, max_iter, tol_mva, nullptr, nullptr);
+}
+
+}  // extern "C"
+// gpf_runpf on a checked range; pre_p / pre_pb: the range's plan, made by the caller (else it is planned here)
+int runpf_range(gpf_engine* e, int lane0, int n, int is_dc, int max_iter, double tol_mva, const LaunchPlan* pre_p, const LaunchPlan* pre_pb) {
   LaunchPlan p, pb;
-  int rc = plan_launch(e, lane0, n, p, pb);
+  int rc = GPF_OK;
+  if (pre_p) { p = *pre_p; pb = *pre_pb; }
+  else rc = plan_launch(e, lane0, n, p, pb);
   if (rc != GPF_OK) return rc;
   gpf::Bufs b = e->bufs();
   const double tol_pu = tol_mva / e->g.sn_mva;
@@ -1193,6 +1232,7 @@ int gpf_runpf(gpf_handle e, int32_t lane0, int32_t n, int32_t is_dc, int32_t max
   if (e->window) { ++e->win_launches; e->win_marked = false; }
   return GPF_OK;
 }
+extern "C" {
 
 // A blocking hipStreamSynchronize wakes up 10-15 us after the stream drained (interrupt + scheduler): a consumer of short launches
 // (one 20-step launch of 14 substations is 0.4 ms, a one-lane runpf 30 us) pays that on every synchronisation.  Poll the stream for up
@@ -1453,6 +1493,7 @@ int gpf_set_lane_chronics(gpf_handle e, const int32_t* lane_table, const int32_t
     std::fill(e->h_lane_forecast.begin(), e->h_lane_forecast.end(), 0);       // every lane is back on the chronics tables
     std::fill(e->h_lane_n1.begin(), e->h_lane_n1.end(), 0);
     if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, 0, e->cap_lanes, 0));
+    if (e->n1_on) { int rc_n = n1_mark_lanes(e); if (rc_n != GPF_OK) return rc_n; }   // (the screen's contingency lanes stay what they are)
   }
   if (lane_scale) {
     if (!e->lane_scale.p) {
@@ -1491,9 +1532,11 @@ gpf::StepArgs make_step_args(const gpf_step_opts* o, int lane0, int t0, int T, i
 
 // n_steps env steps of lanes [lane0, lane0 + n) from time index t0 (T rows per chronics table in `b.chron`)
 int step_range(gpf_engine* e, const gpf::Bufs& b_in, int lane0, int n, int t0, int T, int n_steps, const gpf_step_opts* o, const char* who,
-               bool keep_state = false) {
+               bool keep_state = false, const LaunchPlan* pre_p = nullptr, const LaunchPlan* pre_pb = nullptr) {
   LaunchPlan p, pb;
-  int rc = plan_launch(e, lane0, n, p, pb);
+  int rc = GPF_OK;
+  if (pre_p) { p = *pre_p; pb = *pre_pb; }                // (the N-1 screen's plan of the environment lanes, lane lists of its own)
+  else rc = plan_launch(e, lane0, n, p, pb);
   if (rc != GPF_OK) return rc;
   if (e->env_on) {
     const int lanes = p.wpi > 1 ? 64 : 64 / std::max(p.ipw, 1);
@@ -1599,6 +1642,9 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if ((e->cur_on || e->cur_host_on) && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with the chronics cursor on (gpf_set_chronics_cursor) a launch must be a one-step launch (a lane "
                                "that restarts inside a launch would start a scenario there): use n_steps = 1");
+  if ((e->n1_on || e->n1_host_on) && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: with the N-1 screen on (gpf_set_n1_screen) a launch must be a one-step launch (the contingencies "
+                               "are those of the state one step leaves): use n_steps = 1");
   if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_step_n: no chronics uploaded");
   if (e->traj_cap && n_steps > e->traj_cap)
     return fail(GPF_E_INVALID, "gpf_step_n: n_steps exceeds the trajectory buffer (gpf_set_trajectory sizes it; 0 releases it)");
@@ -1662,7 +1708,13 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = reward_prestep(e);
     if (rc != GPF_OK) return rc;
   }
-  rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
+  if (e->n1_on) {                           // the N-1 screen: only the environment lanes are stepped, on a cached plan of their range
+    rc = n1_plans(e);
+    if (rc != GPF_OK) return rc;
+    rc = step_range(e, e->bufs(), 0, e->n1_n_env, t0, e->chron_T, n_steps, o, "gpf_step_n", true, &e->n1_env_p, &e->n1_env_pb);
+  } else {
+    rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
+  }
   if (rc != GPF_OK) return rc;
   // lanes an action moved to another class than their reset topology's: an auto-reset puts them back, the host re-keys them (with an
   // episode limit set the truncated lanes join the list, and it is read back once, behind episode_kernel)
@@ -1674,7 +1726,13 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if (e->ta_on) {                           // the cooldowns and last known busbars the step leaves
     rc = topo_poststep(e, acts, n_steps, list_resets);
     if (rc != GPF_OK) return rc;
-    if (list_resets && !e->ep_on) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
+    // (the screen plans its contingency lanes on the classes of the rows the step left: the lanes that auto-reset are re-keyed in front
+    //  of it; behind episode_kernel the list is read again, with the truncated lanes -- a lane noted twice has not changed the second time)
+    if (list_resets && (!e->ep_on || e->n1_on)) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
+  }
+  if (e->n1_on) {                           // N1Reward's copies: behind the step and what the topology post-step leaves, in front of the
+    rc = n1_screen(e, o->max_iter, o->tol_mva);   // rewards (GPF_RW_N1 reads the table) and of episode_kernel (it resets truncated lanes)
+    if (rc != GPF_OK) return rc;
   }
   if (e->al_on) {                           // the reward of the step, on its done flag
     rc = alert_poststep(e);

@@ -27,6 +27,7 @@ void kind_params(int kind, int& n_p, int& i_dts) {
 }
 
 void rewards_off(gpf_engine* e) {
+  e->n1_slots = false;
   e->rw_on = false; e->rw_n_slot = 0; e->rw_cost_on = false;
   e->rw_slots.release(); e->rw_cost.release(); e->rw_out.release(); e->rw_ill_snap.release();
 }
@@ -66,7 +67,9 @@ int reward_poststep(gpf_engine* e, bool topo_flags, bool combined) {
   if (e->env_on) { d.ill_now = e->env_illegal.p; d.ill_snap = e->rw_ill_snap.p; }
   if (e->ep_on) { d.ep_limit = e->ep_limit.p; d.episode = e->episode.p; }     // a step at the lane's limit is the reference's is_done
   d.reward = e->rw_out.p; d.row_stride = e->rw_n_slot;
-  return reward_launch(e, d, 0, e->n_lanes);
+  int rc = reward_launch(e, d, 0, e->n_lanes);
+  if (rc == GPF_OK && e->n1_slots) rc = n1_fill_slots(e, 0, e->n_lanes, e->rw_out.p, e->rw_n_slot);     // GPF_RW_N1: the screen's table entries
+  return rc;
 }
 
 int reward_reset_lanes(gpf_engine* e, int lane0, int n) {
@@ -91,6 +94,7 @@ int gpf_set_rewards(gpf_handle e, int32_t n_slot, const gpf_reward_slot* slots, 
   for (int s = 0; s < n_slot; ++s) {
     const int kind = slots[s].kind;
     const std::string sl = at + "slot " + std::to_string(s) + ": ";
+    if (kind == GPF_RW_N1) continue;       // (checked below, against the screen)
     if (kind < GPF_RW_REDISP || kind > GPF_RW_GAMEPLAY) return fail(GPF_E_INVALID, sl + "unknown kind " + std::to_string(kind));
     int n_p, i_dts;
     kind_params(kind, n_p, i_dts);
@@ -105,6 +109,7 @@ int gpf_set_rewards(gpf_handle e, int32_t n_slot, const gpf_reward_slot* slots, 
       if (!std::isfinite(gen_cost_per_mw[i]) || gen_cost_per_mw[i] < 0.f)
         return fail(GPF_E_INVALID, at + "gen_cost_per_mw[" + std::to_string(i) + "] is negative or not finite");
   }
+  { int rc_n = n1_check_slots(e, n_slot, slots); if (rc_n != GPF_OK) return rc_n; }
   if (e->dry) return fail(GPF_E_DEVICE, "gpf_set_rewards: header-only handle: no HIP device");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -118,6 +123,7 @@ int gpf_set_rewards(gpf_handle e, int32_t n_slot, const gpf_reward_slot* slots, 
   if (err == hipSuccess) err = hipMemset(e->rw_ill_snap.p, 0, cap * sizeof(int));
   if (err != hipSuccess) { rewards_off(e); HIP_TRY(err); }
   e->rw_n_slot = n_slot; e->rw_cost_on = need_cost; e->rw_on = true;
+  { int rc_n = n1_set_slots(e, n_slot, slots); if (rc_n != GPF_OK) { rewards_off(e); return rc_n; } }
   if (e->ep_on) return episode_rewards_changed(e);    // the returns of another slot table mean nothing for this one
   return GPF_OK;
 }
@@ -147,7 +153,9 @@ int gpf_rewards_eval(gpf_handle e, int32_t lane0, int32_t n, const uint8_t* flag
   d.eval_flags = flags_dev;
   d.reward = out_dev ? out_dev : e->rw_out.p + (size_t)lane0 * e->rw_n_slot;
   d.row_stride = out_dev ? (long long)row_stride : (long long)e->rw_n_slot;
-  return reward_launch(e, d, lane0, n);
+  int rc = reward_launch(e, d, lane0, n);
+  if (rc == GPF_OK && e->n1_slots) rc = n1_fill_slots(e, lane0, n, d.reward, d.row_stride);      // GPF_RW_N1: the last launch's table entries
+  return rc;
 }
 
 int gpf_reward_device_pointers(gpf_handle e, void** out, int32_t n) {

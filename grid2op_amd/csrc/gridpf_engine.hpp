@@ -297,7 +297,19 @@ struct gpf_engine {
   DevArr<int> cb_ill_snap;
   DevArr<float> cb_max_prod, cb_max_absorb;
   DevArr<unsigned long long> ta_sto_word;
-  std::vector<char> h_lane_n1;          // 1: the lane is a contingency lane of gpf_fanout_n1 (until gpf_set_lane_chronics)
+  // the N-1 screen (gridpf_n1.hpp, gridpf_capi_n1.hip): lanes [0, n1_n_env) are environments, lane n1_n_env + i K + k is contingency k of
+  // environment i; the watched lines (host and device), the values [n_env][K] and the summary of the last one-step launch, the table index
+  // of every reward slot (-1: not a GPF_RW_N1 slot) and the launch plans of the two lane ranges with device lane lists of their own (valid
+  // while plan_valid and n1_plan_valid both hold: whatever invalidates the batch's plan invalidates them).  n1_host_on: a header-only handle
+  // was given a valid screen (gpf_step_n refuses multi-step launches there too)
+  bool n1_on = false, n1_host_on = false, n1_slots = false, n1_plan_valid = false;
+  int n1_n_env = 0, n1_K = 0;
+  std::vector<int> h_n1_lines;
+  DevArr<int> n1_lines, n1_info, n1_slot_idx;
+  DevArr<float> n1_value, n1_worst;
+  LaunchPlan n1_env_p{}, n1_env_pb{}, n1_con_p{}, n1_con_pb{};
+  DevArr<int> n1_env_lists[3], n1_con_lists[3];
+  std::vector<char> h_lane_n1;          // 1: the lane is a contingency lane of gpf_fanout_n1 or of the screen (until gpf_set_lane_chronics)
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
   bool has_delta = false;
@@ -508,6 +520,24 @@ int combined_cancel(gpf_engine* e, bool acts);
 int combined_settle(gpf_engine* e, bool acts, bool screened);
 int combined_reset_lanes(gpf_engine* e, int lane0, int n);
 hipError_t combined_copy_lanes(gpf_engine* e, int src, int dst, int n);
+
+// gridpf_capi.hip, for the N-1 screen: the plan of a lane range with the caller's device lane lists (list_a / list_b / list_c of the engine
+// and the batch's cached plan are left alone), and gpf_runpf's launch on a range with a plan made that way
+// (list_tail: a range that does not end on an instance group keeps the batch's group width, from a ghost-padded lane list)
+int plan_launch_own(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb, DevArr<int>* lists, bool list_tail = false);
+int runpf_range(gpf_engine* e, int lane0, int n, int is_dc, int max_iter, double tol_mva, const LaunchPlan* pre_p, const LaunchPlan* pre_pb);
+
+// gridpf_capi_n1.hip: the screen's plans brought up to date (the contingency lanes take their environments' planning entries; no work
+// while nothing invalidated the batch's plan), the screen itself, queued behind the step and the topology post-step of a one-step launch
+// (fan-out, the power flows of the contingency lanes, values, summary), the GPF_RW_N1 slots of lanes [lane0, lane0 + n) from the table
+// into `reward`, what gpf_set_rewards does to the slot indices (refusals included), and the skip byte / contingency mark of the
+// contingency lanes (gpf_set_lane_chronics clears them for every lane)
+int n1_plans(gpf_engine* e);
+int n1_screen(gpf_engine* e, int max_iter, double tol_mva);
+int n1_fill_slots(gpf_engine* e, int lane0, int n, float* reward, long long row_stride);
+int n1_check_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots);
+int n1_set_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots);
+int n1_mark_lanes(gpf_engine* e);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

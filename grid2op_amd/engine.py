@@ -206,6 +206,7 @@ GRAPH_SECTIONS = ("n_bus", "load_bus", "gen_bus", "storage_bus", "line_or_bus", 
 GRAPH_N_BUS, GRAPH_LOAD_BUS, GRAPH_GEN_BUS, GRAPH_STORAGE_BUS, GRAPH_LINE_OR_BUS, GRAPH_LINE_EX_BUS, GRAPH_SHUNT_BUS, GRAPH_BUS_GLOBAL = range(8)
 
 RW_REDISP, RW_L2RPN, RW_LINES_CAPACITY, RW_ECONOMIC, RW_GAMEPLAY = 1, 2, 3, 4, 5      # include/gridpf.h GPF_RW_*
+RW_N1 = 7                            # include/gridpf.h GPF_RW_N1: p[0] = index into the watched lines of `PowerFlowEngine.set_n1_screen`
 REWARD_MAX_SLOTS = 8
 REWARD_KINDS = {"RedispReward": RW_REDISP, "L2RPNReward": RW_L2RPN, "LinesCapacityReward": RW_LINES_CAPACITY, "EconomicReward": RW_ECONOMIC,
                 "GameplayReward": RW_GAMEPLAY}
@@ -381,6 +382,7 @@ class PowerFlowEngine:
         self._alert = None                   # set_alerts: (A, W) while alerts are on; set_opponent / set_opponent_areas turn them off
         self._traj_cap = 0                   # set_trajectory
         self._n_reward_slot = 0              # set_rewards
+        self._n1 = None                      # set_n1_screen: (n_env, K)
         self._rw_view = None                 # rewards_eval's cache of reward_views()["rewards"]; dropped by set_rewards
         self._ep_on = self._cb_on = self._cur_on = False      # set_episode_limit / set_combined_actions / set_chronics_cursor
         self._obs_spec = None                # set_obs_spec
@@ -1340,6 +1342,63 @@ class PowerFlowEngine:
         return {"limit": v["limit"], "terminated": v["flags"][:, 0], "truncated": v["flags"][:, 1], "length": v["length"],
                 "duration_reward": v["duration_reward"], "return_running": v["running"][:, :ns], "return_last": v["last"][:, :ns],
                 "length_last": v["length_last"], "n_episodes": v["n_episodes"]}
+
+    # ---- the N-1 screen (include/gridpf.h gpf_set_n1_screen; grid2op_amd/csrc/gridpf_n1.hpp) ----
+    def set_n1_screen(self, lines, n_env: Optional[int] = None):
+        """``N1Reward`` for the watched ``lines`` on every environment lane of the one-step launches: lanes ``[0, n_env)`` are the
+        environments (the only lanes `step` then steps), lane ``n_env + i * K + k`` is environment ``i`` with ``lines[k]`` out, solved in
+        the same launch.  ``n_env`` None: as many as fit, ``n_lanes // (1 + K)``.  None or an empty list: off.  A reward slot
+        ``(RW_N1, [k])`` of `set_rewards` is the value of ``lines[k]``; while the screen is on multi-step launches are refused."""
+        if lines is None or len(lines) == 0:
+            self._call("gpf_set_n1_screen", 0, None, 0)
+            self._n1 = None
+            return
+        ln = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1)
+        ne = self.n_lanes // (1 + ln.size) if n_env is None else int(n_env)
+        self._call("gpf_set_n1_screen", ne, _ptr(ln), ln.size)      # (a refused call leaves the screen as it was)
+        self._n1 = (ne, int(ln.size))
+
+    def _n1_range(self, what, lane0, n):
+        """The environments among lanes ``[lane0, lane0 + n)`` (the whole range by default): first environment, count, K."""
+        if getattr(self, "_n1", None) is None:
+            raise GridPFError(f"{what}: the N-1 screen is off (set_n1_screen)")
+        ne, K = self._n1
+        lane0, n = self._range(lane0, n)
+        a, b = min(max(lane0, 0), ne), min(max(lane0 + n, 0), ne)
+        return a, max(b - a, 0), K
+
+    def n1_values(self, lane0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """float32 ``[n_env', K]``: the ``N1Reward`` values of the last one-step launch for the environment lanes inside lanes
+        ``[lane0, lane0 + n)`` (0: the step ended the episode, -1: the contingency's power flow diverged); synchronous."""
+        a, m, K = self._n1_range("n1_values", lane0, n)
+        out = np.zeros((m, K), np.float32)
+        self._call("gpf_get_n1_values", a, m, _ptr(out))
+        return out
+
+    def n1_summary(self, lane0: int = 0, n: Optional[int] = None) -> dict:
+        """``worst`` float32, ``arg_worst`` / ``n_insecure`` / ``n_diverged`` int32, each ``[n_env']``, of the environment lanes inside
+        lanes ``[lane0, lane0 + n)``: the contingency that ranks first (a diverged one outranks every value, the lowest index wins a tie)
+        and its value, the contingencies above 1 or diverged, the diverged ones; synchronous."""
+        a, m, _ = self._n1_range("n1_summary", lane0, n)
+        w, aw, ni, nd = np.zeros(m, np.float32), np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        self._call("gpf_get_n1_summary", a, m, _ptr(w), _ptr(aw), _ptr(ni), _ptr(nd))
+        return dict(worst=w, arg_worst=aw, n_insecure=ni, n_diverged=nd)
+
+    def n1_views(self) -> dict:
+        """Zero-copy torch tensors ALIASING the screen's buffers (order the reader on ``device_views()["stream"]``): ``values`` float32
+        ``[n_env, K]``, ``worst`` float32 ``[n_env]``, ``arg_worst`` / ``n_insecure`` / ``n_diverged`` int32 ``[n_env]``, ``lines`` int32
+        ``[K]``."""
+        import torch
+        _, _, K = self._n1_range("n1_views", 0, None)
+        ptrs = self._device_pointers("gpf_n1_device_pointers", _capi.N_N1_POINTERS)
+
+        def view(p, shape, typestr):
+            iface = {"shape": shape, "typestr": typestr, "data": (int(p), False), "version": 2, "strides": None}
+            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=torch.device("cuda", self.device))
+        ne = self._n1[0]
+        info = view(ptrs[2], (ne, 3), "<i4")
+        return {"values": view(ptrs[0], (ne, K), "<f4"), "worst": view(ptrs[1], (ne,), "<f4"), "arg_worst": info[:, 0], "n_insecure": info[:, 1],
+                "n_diverged": info[:, 2], "lines": view(ptrs[3], (K,), "<i4")}
 
     # ---- combined topology + injection actions (include/gridpf.h gpf_set_combined_actions; grid2op_amd/csrc/gridpf_combined.hpp) ----
     def set_combined_actions(self, on: bool = True, check_values: bool = True, storage_max_p_prod=None, storage_max_p_absorb=None):

@@ -756,6 +756,7 @@ int gpf_alert_device_pointers(gpf_handle h, void** out, int32_t n);
 #define GPF_RW_LINES_CAPACITY 3
 #define GPF_RW_ECONOMIC 4
 #define GPF_RW_GAMEPLAY 5
+#define GPF_RW_N1 7                /* N1Reward (Reward/n1Reward.py:64-101): p[0] = index into the watched lines of gpf_set_n1_screen (below) */
 typedef struct gpf_reward_slot {
   int32_t kind;                    /* GPF_RW_* */
   double p[6];                     /* the kind's parameters, in the order above; the rest is ignored */
@@ -807,8 +808,8 @@ int gpf_reward_device_pointers(gpf_handle h, void** out, int32_t n);
  *                   out[6] length_last, out[7] n_episodes int32 [lanes] (lanes = gpf_lane_capacity).  n must be GPF_N_EPISODE_POINTERS.
  *   The getters fail with "episode limits are off" while the feature is off.
  * gpf_reset_lanes zeroes every episode buffer of the lanes (not their limits); gpf_copy_lanes copies them with the limits; gpf_fanout_n1
- * and gpf_simulate_batch leave them alone.  OUT OF SCOPE: truncation inside multi-step launches, CombinedReward, N1Reward (the scenario
- * of the next episode: gpf_set_chronics_cursor below). */
+ * and gpf_simulate_batch leave them alone.  OUT OF SCOPE: truncation inside multi-step launches, CombinedReward (the scenario
+ * of the next episode: gpf_set_chronics_cursor below; N1Reward: gpf_set_n1_screen below). */
 #define GPF_N_EPISODE_POINTERS 8
 typedef struct gpf_episode_desc {
   int32_t max_steps;               /* the limit of every lane (0: none) ... */
@@ -821,6 +822,50 @@ int gpf_get_episode_ends(gpf_handle h, int32_t lane0, int32_t n, uint8_t* termin
 int gpf_get_episode_stats(gpf_handle h, int32_t lane0, int32_t n, double* return_running, double* return_last, int32_t* length_last,
                           int32_t* n_episodes);
 int gpf_episode_device_pointers(gpf_handle h, void** out, int32_t n);
+
+/* ---- the N-1 screen of the batched acting path (grid2op_amd/csrc/gridpf_n1.hpp): the reference's N1Reward (Reward/n1Reward.py:64-101),
+ * one per watched line, for every environment lane of a ONE-STEP launch.  After env.step the reference copies the backend's state, takes
+ * line l_id out (n1Reward.py:78-88), runs one power flow (:89-96) and returns max(a_or / thermal_limit) (:97-101).  Here the copies are
+ * ordinary lanes: lanes [0, n_env) are the environments, lane n_env + i K + k is contingency k of environment i.  While the screen is on
+ *   - gpf_step_n steps lanes [0, n_env) only (their results are bit-identical to a launch without the screen) and refuses n_steps != 1; every other side kernel of the launch runs over all lanes as before, and every getter reads the
+ *     contingency lanes like any lane: lane n_env + i K + k holds the whole post-contingency observation;
+ *   - behind the step and the topology post-step, in front of the reward and episode kernels, the launch queues: n1_fanout_kernel (the
+ *     contingency lane takes the environment's injection row, its topology row -- after the agent's action, the opponent's attack,
+ *     maintenance and protection trips -- with both ends of the watched line at -1, and its shunt buses; a watched line that is already
+ *     out leaves the base case), ONE plain AC power flow of lanes [n_env, n_env (1 + K)) with the launch's max_iter and tol_mva (DC
+ *     initialisation, no cascade, no dynamics, no cooldowns: what gpf_runpf does), n1_reduce_kernel and n1_summary_kernel.  No host
+ *     work per environment or per contingency and no synchronisation: the watched lines were uploaded once, the plans of the two lane
+ *     ranges are cached with lane lists of their own and re-made only after something invalidated the batch's plan (a topology class
+ *     of an environment lane changed, a reset, gpf_set_topology ...); the contingency lanes then take their environments' planning
+ *     entries (a single line outage never changes a lane's topology class);
+ *   - value[i][k] float32: is_done (failed or truncated, as the rewards take it) -> 0 (BaseReward's reward_min, N1Reward sets none); the
+ *     power flow did not converge -> -1; else max over the lines of a_or / th with th[th <= 1] = 1, ONE float32 division per line and an
+ *     exact maximum (share t of 64 takes lines t, t + 64, ..., a fixed butterfly): the same bits in every run and at every lane;
+ *   - summary of environment i: arg_worst = the contingency that ranks first (a diverged one outranks every value, then the larger
+ *     value, then the lower k), worst = its value (-1 when one diverged), n_insecure = the values > 1 or diverged, n_diverged;
+ *   - a reward slot of kind GPF_RW_N1 with p[0] = k is value[lane][k] on an environment lane (0 on a contingency lane): it enters the
+ *     episode returns like any slot, and gpf_rewards_eval returns the last launch's table entry for it.  gpf_set_rewards refuses the
+ *     kind while the screen is off and an index outside [0, K); more than GPF_REWARD_MAX_SLOTS watched lines are read from the table.
+ * Instance groups: on small grids the step kernel packs 4 (<= 8 substations) or 2 (<= 24) lanes into a wavefront.  The environment lanes
+ * keep the groups, and so the bits, of a launch without the screen whatever n_env is: a range that does not end on a group runs from a
+ * lane list padded with ghost lanes.  The contingency range is planned as gpf_runpf plans a lane range (narrower groups when it does
+ * not start on one: choose n_env a multiple of the group width for the fastest power flows).
+ *   gpf_set_n1_screen : lines [n_lines] watched line ids; n_lines = 0 turns the screen off.  Refused before the device is touched (on a
+ *                       header-only handle too): a negative n_lines, a line id outside [0, n_line), n_env <= 0, n_env (1 + n_lines) >
+ *                       n_lanes, and any change while a GPF_RW_N1 slot is set (set the rewards anew afterwards).  The contingency lanes
+ *                       start no scenario of their own (the chronics cursor's skip byte, as after gpf_fanout_n1).
+ *   gpf_get_n1_values : value[n][K] of environments [lane0, lane0 + n) within [0, n_env), of the last launch (0 before the first).
+ *   gpf_get_n1_summary: worst [n] float32, arg_worst / n_insecure / n_diverged [n] int32; any pointer may be NULL.
+ *   gpf_n1_device_pointers : out[0] value float32 [n_env][K], out[1] worst float32 [n_env], out[2] int32 [n_env][3] {arg_worst,
+ *                       n_insecure, n_diverged}, out[3] the watched lines int32 [K].  n must be GPF_N_N1_POINTERS.
+ *   The getters fail with "the N-1 screen is off" while it is off.
+ * OUT OF SCOPE: a DC or LODF screen (gpf_lodf_screen), other contingencies than single lines, the screen inside multi-step launches,
+ * gpf_simulate_batch or trajectory mode, skipping the power flows of lanes that are done (solved and ignored). */
+#define GPF_N_N1_POINTERS 4
+int gpf_set_n1_screen(gpf_handle h, int32_t n_env, const int32_t* lines, int32_t n_lines);
+int gpf_get_n1_values(gpf_handle h, int32_t lane0, int32_t n, float* value);
+int gpf_get_n1_summary(gpf_handle h, int32_t lane0, int32_t n, float* worst, int32_t* arg_worst, int32_t* n_insecure, int32_t* n_diverged);
+int gpf_n1_device_pointers(gpf_handle h, void** out, int32_t n);
 
 /* ---- combined topology + injection actions of the batched acting path (grid2op_amd/csrc/gridpf_combined.hpp): one action with a
  * topology part (the table indices above) and an injection part (redispatch / storage / curtailment rows), lane by lane, in a one-step
