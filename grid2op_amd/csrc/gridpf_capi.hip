@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "gridpf_engine.hpp"
+#include "gridpf_lookahead.hpp"             // (la_maintenance_ahead; its kernels exist in gridpf_capi_lookahead.hip only)
 #include "gridpf_redispatch.hpp"
 #include "gridpf_topo.hpp"
 
@@ -324,7 +325,7 @@ int plan_launch(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb) 
   if (whole && e->plan_valid) { p = e->plan_cached; pb = e->plan_b_cached; return GPF_OK; }
   // the batch's plan is made anew: whatever invalidated it invalidated the N-1 screen's plans too, and plan_valid is about to say
   // "nothing changed" again (n1_plans makes its two, calls this last and only then marks them valid)
-  if (whole) e->n1_plan_valid = false;
+  if (whole) e->n1_plan_valid = e->la_plan_valid = false;    // (the look-ahead's two plans are cached the same way: la_plans)
   int rc = plan_launch_uncached(e, lane0, n, p, pb);
   if (!whole && (p.n_list || pb.n_list)) e->plan_valid = false;     // the device lane lists were overwritten
   if (rc == GPF_OK && whole) { e->plan_cached = p; e->plan_b_cached = pb; e->plan_valid = true; }
@@ -1494,6 +1495,7 @@ int gpf_set_lane_chronics(gpf_handle e, const int32_t* lane_table, const int32_t
     std::fill(e->h_lane_n1.begin(), e->h_lane_n1.end(), 0);
     if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, 0, e->cap_lanes, 0));
     if (e->n1_on) { int rc_n = n1_mark_lanes(e); if (rc_n != GPF_OK) return rc_n; }   // (the screen's contingency lanes stay what they are)
+    if (e->la_on) { int rc_l = la_mark_lanes(e); if (rc_l != GPF_OK) return rc_l; }   // (... and the look-ahead's scratch lanes)
   }
   if (lane_scale) {
     if (!e->lane_scale.p) {
@@ -1605,6 +1607,38 @@ void apply_topo_action(const gpf_engine* e, int* row, int* sb, const int* last, 
   gpf::apply_topo_action(m, row, sb, last, items, n_items, or_before.data(), ex_before.data(), 0, 1, gpf::NoSync{});
 }
 }  // namespace
+
+// gpf_simulate_batch stage 3 and the look-ahead: simulate_prepare_kernel on the engine's stream
+int simulate_prepare(gpf_engine* e, const int* src_lanes_dev, int n_act, int n_dst, int dst0, int t_obs, int time_step) {
+  const bool fc = time_step > 0;
+  if (e->has_scale && !e->lane_scale.p) return fail(GPF_E_INVALID, "gpf_simulate_batch: internal (lane_scale)");
+  hipLaunchKernelGGL(gpf::simulate_prepare_kernel, dim3((unsigned)n_dst), dim3(64), 0, e->stream, e->g, e->bufs(), src_lanes_dev, n_act, n_dst,
+                     dst0, t_obs, e->chron_T, fc ? e->fc_h : 1, time_step, e->lane_table.p, e->lane_offset.p,
+                     e->has_scale ? e->lane_scale.p : nullptr, e->has_delta ? e->lane_gen_delta.p : nullptr);
+  HIP_TRY(hipGetLastError());
+  return GPF_OK;
+}
+
+// gpf_simulate_batch stage 4 and the look-ahead: ONE step of scratch lanes [lane0, lane0 + n) on the chronics (time_step 0) or forecast
+// tables (no trajectory rows: these are scratch lanes).  With the injection dynamics on it is ONE do-nothing step of the dynamics (the
+// candidates are topology actions: no redispatch / storage part): pending injection actions are set aside for the duration of the call.
+int simulate_step(gpf_engine* e, int lane0, int n, int time_step, const gpf_step_opts* o, const char* who, const LaunchPlan* pre_p, const LaunchPlan* pre_pb) {
+  struct ActGuard {
+    gpf_engine* e; bool r, s, c;
+    explicit ActGuard(gpf_engine* e_) : e(e_), r(e_->env_act_r), s(e_->env_act_s), c(e_->env_act_c) { e->env_act_r = e->env_act_s = e->env_act_c = false; }
+    ~ActGuard() { e->env_act_r = r; e->env_act_s = s; e->env_act_c = c; }
+  } act_guard(e);
+  const bool fc = time_step > 0;
+  gpf::Bufs b = e->bufs();
+  if (fc) b.chron = e->forecast.p;
+  b.maint = nullptr;
+  b.maint_dur = nullptr;               // (the cursor of a scratch lane is a row of the FORECAST tables: the outage tables have no such rows)
+  b.traj_rho = nullptr; b.traj_status = nullptr; b.traj_out = nullptr; b.traj_topo = nullptr; b.traj_shb = nullptr; b.traj_lstat = nullptr; b.traj_cap = 0;
+  gpf_step_opts oo = *o;
+  oo.auto_reset = 0; oo.warm_start = 0;
+  oo.track_cooldown = 0;               // one look-ahead step: the cooldowns copied from the source lanes stand
+  return step_range(e, b, lane0, n, 0, fc ? e->chron_T * e->fc_h : e->chron_T, 1, &oo, who, false, pre_p, pre_pb);
+}
 extern "C" {
 
 // The launch-feature word (gridpf_host.hpp: gpf_step_features) of a DESCRIBED gpf_step_n launch over all lanes of the engine: the engine's
@@ -1645,6 +1679,9 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if ((e->n1_on || e->n1_host_on) && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with the N-1 screen on (gpf_set_n1_screen) a launch must be a one-step launch (the contingencies "
                                "are those of the state one step leaves): use n_steps = 1");
+  if ((e->la_on || e->la_host_on) && n_steps != 1)
+    return fail(GPF_E_INVALID, "gpf_step_n: with the look-ahead set (gpf_set_lookahead) a launch must be a one-step launch (the scratch lanes "
+                               "behind the environments are not stepped): use n_steps = 1");
   if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_step_n: no chronics uploaded");
   if (e->traj_cap && n_steps > e->traj_cap)
     return fail(GPF_E_INVALID, "gpf_step_n: n_steps exceeds the trajectory buffer (gpf_set_trajectory sizes it; 0 releases it)");
@@ -1712,6 +1749,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = n1_plans(e);
     if (rc != GPF_OK) return rc;
     rc = step_range(e, e->bufs(), 0, e->n1_n_env, t0, e->chron_T, n_steps, o, "gpf_step_n", true, &e->n1_env_p, &e->n1_env_pb);
+  } else if (e->la_on) {                    // the look-ahead: likewise (its scratch lanes are stepped by gpf_lookahead alone)
+    rc = la_plans(e);
+    if (rc != GPF_OK) return rc;
+    rc = step_range(e, e->bufs(), 0, e->la_n_env, t0, e->chron_T, n_steps, o, "gpf_step_n", true, &e->la_env_p, &e->la_env_pb);
   } else {
     rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
   }
@@ -1832,7 +1873,8 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
   // BaseEnv._update_vector_with_timestep, baseEnv.py:4768-4825): a forecast `time_step` >= 1 steps ahead has the lines out whose
   // NEXT maintenance (the one obs.time_next_maintenance / duration_next_maintenance describe: the first flagged row from the
   // observation's row on) covers row idx + time_step -- it begins there (first_ts_maintenance) or is under way
-  // (still_in_maintenance).  Hazards are not forecast by the reference.  The line goes out BEFORE the candidate action is applied.
+  // (still_in_maintenance): la_maintenance_ahead, gridpf_lookahead.hpp.  Hazards are not forecast by the reference.  The line goes out
+  // BEFORE the candidate action is applied.
   std::vector<std::vector<int>> maint_out(n_src);
   if (time_step >= 1 && !e->h_maint.empty()) {
     const int T = e->chron_T;
@@ -1841,15 +1883,8 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
       int idx = (t_obs + e->h_lane_offset[src]) % T;
       if (idx < 0) idx += T;
       const unsigned char* M = e->h_maint.data() + (size_t)e->h_lane_table[src] * T * g.n_line;
-      for (int l = 0; l < g.n_line; ++l) {
-        int s_ = idx;
-        while (s_ < T && !M[(size_t)s_ * g.n_line + l]) ++s_;          // start of the next maintenance (idx itself: under way)
-        const int tgt = idx + time_step;
-        if (s_ >= T || tgt < s_ || tgt >= T) continue;
-        bool in = true;
-        for (int r = s_; r <= tgt && in; ++r) in = M[(size_t)r * g.n_line + l] != 0;
-        if (in) maint_out[b].push_back(l);
-      }
+      for (int l = 0; l < g.n_line; ++l)
+        if (gpf::la_maintenance_ahead(M, T, g.n_line, idx, time_step, l)) maint_out[b].push_back(l);
     }
   }
   for (int b = 0; b < n_src; ++b)
@@ -1868,12 +1903,8 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
   const double tm3 = sim_timing ? now_us() : 0.0;
   // 3. everything else of the source lanes + the chronics / forecast row to step on, on the device
   const bool fc = time_step > 0;
-  const int T_eff = fc ? e->chron_T * e->fc_h : e->chron_T;
-  if (e->has_scale && !e->lane_scale.p) return fail(GPF_E_INVALID, "gpf_simulate_batch: internal (lane_scale)");
-  hipLaunchKernelGGL(gpf::simulate_prepare_kernel, dim3((unsigned)n_dst), dim3(64), 0, e->stream, e->g, e->bufs(), e->sim_src.p, n_act, (int)n_dst,
-                     dst_lane0, t_obs, e->chron_T, fc ? e->fc_h : 1, time_step, e->lane_table.p, e->lane_offset.p,
-                     e->has_scale ? e->lane_scale.p : nullptr, e->has_delta ? e->lane_gen_delta.p : nullptr);
-  HIP_TRY(hipGetLastError());
+  rc = simulate_prepare(e, e->sim_src.p, n_act, (int)n_dst, dst_lane0, t_obs, time_step);
+  if (rc != GPF_OK) return rc;
   for (long long q = 0; q < n_dst; ++q) {                     // host mirror of what the kernel writes
     const int src = src_lanes[q / n_act];
     int idx = (t_obs + e->h_lane_offset[src]) % e->chron_T;
@@ -1883,25 +1914,10 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
     e->h_lane_forecast[dst_lane0 + q] = 1;          // its cursor is an ABSOLUTE row (of the forecast tables when time_step > 0), not an offset to t
   }
   if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, dst_lane0, (int)n_dst, 1));
-  // with the injection dynamics on, the scratch lanes start from their source's dispatch / storage / curtailment state and take
-  // ONE do-nothing step of the dynamics on the forecast (the candidates are topology actions: no redispatch / storage part)
-  struct ActGuard {
-    gpf_engine* e; bool r, s, c;
-    explicit ActGuard(gpf_engine* e_) : e(e_), r(e_->env_act_r), s(e_->env_act_s), c(e_->env_act_c) { e->env_act_r = e->env_act_s = e->env_act_c = false; }
-    ~ActGuard() { e->env_act_r = r; e->env_act_s = s; e->env_act_c = c; }
-  } act_guard(e);
   if (e->env_on) { rc = env_copy_from(e, e->sim_src.p, n_act, (int)n_dst, dst_lane0); if (rc != GPF_OK) return rc; }
-  // 4. ONE step of the destination range on the forecast tables (no trajectory rows: these are scratch lanes)
-  gpf::Bufs b = e->bufs();
-  if (fc) b.chron = e->forecast.p;
-  b.maint = nullptr;
-  b.maint_dur = nullptr;               // (the cursor of a scratch lane is a row of the FORECAST tables: the outage tables have no such rows)
-  b.traj_rho = nullptr; b.traj_status = nullptr; b.traj_out = nullptr; b.traj_topo = nullptr; b.traj_shb = nullptr; b.traj_lstat = nullptr; b.traj_cap = 0;
-  gpf_step_opts oo = *o;
-  oo.auto_reset = 0; oo.warm_start = 0;
-  oo.track_cooldown = 0;               // one look-ahead step: the cooldowns copied from the source lanes stand
+  // 4. ONE step of the destination range on the forecast tables
   const double tm4 = sim_timing ? now_us() : 0.0;
-  rc = step_range(e, b, dst_lane0, (int)n_dst, 0, T_eff, 1, &oo, "gpf_simulate_batch");
+  rc = simulate_step(e, dst_lane0, (int)n_dst, time_step, o, "gpf_simulate_batch", nullptr, nullptr);
   if (sim_timing)
     fprintf(stderr, "[gridpf] simulate_batch %lld lanes: gather + sync %.0f us, candidate rows %.0f, gpf_set_topology %.0f, prepare + mirror %.0f, plan + launch %.0f\n",
             n_dst, tm1 - tm0, tm2 - tm1, tm3 - tm2, tm4 - tm3, now_us() - tm4);

@@ -147,6 +147,8 @@ int gpf_set_n1_screen(gpf_handle e, int32_t n_env, const int32_t* lines, int32_t
     n1_release(e);
     return GPF_OK;
   }
+  if (e->la_on || e->la_host_on)
+    return fail(GPF_E_INVALID, at + "the look-ahead (gpf_set_lookahead) is set and claims the lanes behind the environments: switch it off first");
   if (n_lines < 0 || !lines) return fail(GPF_E_INVALID, at + "negative n_lines, or no lines");
   for (int k = 0; k < n_lines; ++k)
     if (lines[k] < 0 || lines[k] >= e->g.n_line)

@@ -10,9 +10,7 @@
 #include "gridpf_engine.hpp"
 #include "gridpf_combined.hpp"
 
-namespace {
-constexpr size_t TOPO_LDS_LIMIT = 64 * 1024;      // LDS of one workgroup
-
+// the argument blocks of the acting path's kernels (the look-ahead's play kernel takes the same two)
 gpf::TopoDev topo_dev(const gpf_engine* e) {
   const gpf::GridDev& g = e->g;
   gpf::TopoDev d{};
@@ -29,6 +27,9 @@ gpf::TopoLanes topo_lanes(const gpf_engine* e) {
   t.n_slot = e->ta_n_slot;
   return t;
 }
+
+namespace {
+constexpr size_t TOPO_LDS_LIMIT = 64 * 1024;      // LDS of one workgroup
 
 // composite actions (more than one slot) or limits per area: the pre-step runs its GEN instantiation
 bool topo_general(const gpf_engine* e) { return e->ta_n_slot > 1 || e->ta_n_area > 0; }

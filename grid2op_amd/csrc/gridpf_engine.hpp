@@ -309,6 +309,20 @@ struct gpf_engine {
   DevArr<float> n1_value, n1_worst;
   LaunchPlan n1_env_p{}, n1_env_pb{}, n1_con_p{}, n1_con_pb{};
   DevArr<int> n1_env_lists[3], n1_con_lists[3];
+  // the look-ahead screen (gridpf_lookahead.hpp, gridpf_capi_lookahead.hip): lanes [0, la_n_env) are environments, lane la_n_env + i K + k
+  // is scratch lane (i, k); the candidates, the outputs of the last call, the moved list of the play kernel (count | lane ids, rows) with the
+  // rows the host last noted for the scratch lanes, the scheduled maintenance alone (the device's outage table is its union with the
+  // hazards) and the launch plans of the two lane ranges, cached as the N-1 screen caches its own.  la_host_on: a header-only handle was
+  // given a valid look-ahead (gpf_step_n refuses multi-step launches there too)
+  bool la_on = false, la_host_on = false, la_plan_valid = false, la_noted_stale = true;
+  int la_n_env = 0, la_K = 0;
+  long long la_maint_gen = -1;          // generation of the outage tables la_maint was uploaded from
+  DevArr<int> la_cand, la_best, la_info, la_list, la_list_rows, la_noted, la_src;
+  DevArr<float> la_value, la_best_value;
+  DevArr<unsigned char> la_flags, la_maint;
+  LaunchPlan la_env_p{}, la_env_pb{}, la_sim_p{}, la_sim_pb{};
+  DevArr<int> la_env_lists[3], la_sim_lists[3];
+  HostPin<int> la_pin;                  // pinned read-back block: count | lane ids | rows
   std::vector<char> h_lane_n1;          // 1: the lane is a contingency lane of gpf_fanout_n1 or of the screen (until gpf_set_lane_chronics)
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)
@@ -472,7 +486,10 @@ int env_copy_from(gpf_engine* e, const int* src_lanes_dev, int n_act, int n_dst,
 // gridpf_capi_topo.hip: topo_prestep_kernel in front of a launch (acts: it carries topology actions) with the read-back of the lanes it
 // moved to another topology class, topo_poststep_kernel behind it (list_resets: lanes that auto-reset are listed), the read-back of that
 // list into the planner's bookkeeping (moved: the rows are action results, else reset topologies) and the feature's share of
-// gpf_reset_lanes / gpf_copy_lanes / gpf_fanout_n1
+// gpf_reset_lanes / gpf_copy_lanes / gpf_fanout_n1; in front of them the argument blocks of its kernels (grid maps and lane rows, the
+// acting path's per-lane state), which the look-ahead's play kernel takes too
+gpf::TopoDev topo_dev(const gpf_engine* e);
+gpf::TopoLanes topo_lanes(const gpf_engine* e);
 int topo_prestep(gpf_engine* e, bool acts);
 int topo_poststep(gpf_engine* e, bool acts, int n_steps, bool list_resets);
 int topo_readback(gpf_engine* e, bool moved);
@@ -538,6 +555,17 @@ int n1_fill_slots(gpf_engine* e, int lane0, int n, float* reward, long long row_
 int n1_check_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots);
 int n1_set_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots);
 int n1_mark_lanes(gpf_engine* e);
+
+// gridpf_capi.hip, for the look-ahead: simulate_prepare_kernel on scratch lanes dst0 + q, q < n_dst, of sources src_lanes_dev[q / n_act]
+// (everything of a source that is not topology, and the chronics or forecast row to step on), one step of a lane range as gpf_simulate_batch
+// takes it (no cooldown tracking, no auto-reset, no outage tables, no trajectory; pending injection actions stay pending), on a plan of
+// the caller's, and the multi-step refusal's test
+int simulate_prepare(gpf_engine* e, const int* src_lanes_dev, int n_act, int n_dst, int dst0, int t_obs, int time_step);
+int simulate_step(gpf_engine* e, int lane0, int n, int time_step, const gpf_step_opts* o, const char* who, const LaunchPlan* pre_p, const LaunchPlan* pre_pb);
+// gridpf_capi_lookahead.hip: the plans of the two lane ranges brought up to date, and the marks of the scratch lanes (their chronics
+// cursor is an absolute row, they start no scenario of their own; gpf_set_lane_chronics clears the marks of every lane)
+int la_plans(gpf_engine* e);
+int la_mark_lanes(gpf_engine* e);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }
 

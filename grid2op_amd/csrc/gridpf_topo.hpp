@@ -18,9 +18,12 @@
 //
 // Two parts: what the host shares (apply_topo_action, the argument blocks, the LDS size of the pre-step: gridpf_capi.hip's
 // gpf_simulate_batch and the engine of gridpf_engine.hpp include the header for these) and, for the one unit that defines GPF_TOPO_KERNEL
-// (gridpf_capi_topo.hip), the kernels.
+// (gridpf_capi_topo.hip), the kernels.  Steps 1-4 on the device are topo_play_lane, a __device__ function: the unit that defines
+// GPF_LA_KERNEL (gridpf_capi_lookahead.hip) gets it too, for the play kernel of gridpf_lookahead.hpp, and none of the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <limits.h>
 
 #include "gridpf_episode.hpp"
 #include "gridpf_topo_mask.hpp"
@@ -114,17 +117,22 @@ __host__ __device__ inline size_t topo_prestep_lds_ints(int dim_topo, int n_line
   return max_items < 0 ? base : base + 3 * (size_t)max_items + (size_t)dim_topo + 2 * (size_t)n_line + 2 * TM_MAX_AREAS;
 }
 
-#if defined(__HIPCC__) && defined(GPF_TOPO_KERNEL)
-// Steps 1-4 for one lane per 64-thread block (one wavefront), its rows staged in LDS.  act_on = 0: only the auto-reset snapshot.
-// GEN: composite actions of s.n_slot entries and limits per area (`c`); else one entry per lane, whole-grid limits, `c` unused.
-template <bool GEN>
-__global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab, TopoLanes s, TopoRules r, TopoComp c, int n_lanes, int act_on) {
-  extern __shared__ int lds[];
-  const int lane = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
-  if (lane >= n_lanes) return;
+#if defined(__HIPCC__) && (defined(GPF_TOPO_KERNEL) || defined(GPF_LA_KERNEL))
+// Where the look-ahead's play kernel (gridpf_lookahead.hpp) departs from the pre-step: the table index comes from the candidate buffer,
+// the planner's question is asked against the row the host last NOTED for the lane (noted[0] == INT_MIN: none), which is rewritten when
+// the lane is listed, and the list is the look-ahead's own.
+struct TopoLook { int act; int* noted; int* list; int* list_rows; };
+
+// Steps 1-4 for one lane by one 64-thread block (one wavefront), its rows staged in LDS: the ONE statement of them on the device, for
+// topo_prestep_kernel and la_play_kernel.  GEN: composite actions of s.n_slot entries and limits per area (`c`); else one entry per
+// lane, whole-grid limits, `c` unused.  LOOK: the lane is a scratch lane that already holds its environment's rows, cooldowns and last
+// known busbars; an ambiguous or illegal entry leaves them (the do-nothing row) and the lane still goes through the planner's
+// question.  Returns the verdict, uniform over the block: 1 illegal, 2 ambiguous, 0 neither.
+template <bool GEN, bool LOOK>
+__device__ __forceinline__ int topo_play_lane(const TopoDev& g, const TopoTab& tab, const TopoLanes& s, const TopoRules& r, const TopoComp& c,
+                                              int* lds, int lane, const TopoLook& k, int tid, int nth) {
+  static_assert(!(GEN && LOOK), "the look-ahead plays single table entries");
   const int D = g.dim_topo, L = g.n_line, S = g.n_sub, NS = g.n_shunt, NBB = g.n_busbar;
-  if (tid == 0) s.ep_snap[lane] = g.episode[(size_t)lane * 2 + 1];
-  if (!act_on) return;
   unsigned char* aff = s.aff + (size_t)lane * (L + S);
   for (int i = tid; i < L + S; i += nth) aff[i] = 0;
   int a = -1, n_items = 0;
@@ -140,12 +148,13 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
     // tab.amb is not consulted, even with one slot (areas only), where it would answer: the run-time pass below is the one rule for
     // every GEN launch, an ambiguous single entry costs one gather and one pass over the dense arrays before the lane stops
   } else {
-    a = s.act[lane];
+    a = LOOK ? k.act : s.act[lane];
     amb = a < -1 || a >= tab.n_act || (a >= 0 && tab.amb[a]);
   }
-  if (a == -1 || amb) {                                        // (uniform over the block)
+  bool play = !(a == -1 || amb);                               // (uniform over the block)
+  if (!play) {
     if (tid == 0) { s.flags[(size_t)lane * 2] = 0; s.flags[(size_t)lane * 2 + 1] = amb ? 1 : 0; }
-    return;
+    if constexpr (!LOOK) return amb ? 2 : 0;
   }
   int* row = lds;                 // [D] the row being acted on
   int* prev = row + D;            // [D] the row before the action
@@ -167,7 +176,7 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
   int* swl = setl + L;            //      [L] change_line_status
   int* acnt = swl + L;            //      [2][TM_MAX_AREAS] aff lines / aff subs per area
   int* gath = acnt + 2 * TM_MAX_AREAS;   // [max_items][3] the concatenated item list
-  const int* items = tab.items + 3 * (size_t)tab.off[a];
+  const int* items = play ? tab.items + 3 * (size_t)tab.off[a] : nullptr;
   if constexpr (GEN) {
     int at = 0;
     for (int k = 0; k < s.n_slot; ++k) {                       // (uniform) slot after slot, every thread a stride of the slot's ints
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
     if (tid < 2 * TM_MAX_AREAS) acnt[tid] = 0;
     items = gath;
   } else {
-    n_items = tab.off[a + 1] - tab.off[a];
+    n_items = play ? tab.off[a + 1] - tab.off[a] : 0;
   }
   const int* trow = g.topo + (size_t)lane * D;
   for (int i = tid; i < D; i += nth) { const int v = trow[i]; row[i] = v; prev[i] = v; setv[i] = 0; eff[i] = 0; }
@@ -211,7 +220,7 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
     __syncthreads();
     if (cnt[7]) {
       if (tid == 0) { s.flags[(size_t)lane * 2] = 0; s.flags[(size_t)lane * 2 + 1] = 1; }
-      return;
+      return 2;
     }
   }
   for (int i = tid; i < D; i += nth) eff[i] = (eff[i] || setv[i] != 0) ? 1 : 0;
@@ -249,27 +258,33 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
     __syncthreads();
     illegal = r.on && (cnt[0] > r.max_line || cnt[1] > r.max_sub || cnt[2] != 0);
   }
-  if (tid == 0) { s.flags[(size_t)lane * 2] = illegal ? 1 : 0; s.flags[(size_t)lane * 2 + 1] = 0; }
-  if (illegal) return;
-  for (int l = tid; l < L; l += nth) aff[l] = (unsigned char)imp[l];
-  for (int i = tid; i < S; i += nth) aff[L + i] = (unsigned char)subf[i];
-  // 4. application
-  struct BlockSync { __device__ void operator()() const { __syncthreads(); } };
-  const TopoMaps m{g.line_or_pos, g.line_ex_pos, L};
-  apply_topo_action(m, row, NS ? sbr : nullptr, s.last_bus + (size_t)lane * D, items, n_items, or_b, ex_b, tid, nth, BlockSync{});
+  if (tid == 0 && play) { s.flags[(size_t)lane * 2] = illegal ? 1 : 0; s.flags[(size_t)lane * 2 + 1] = 0; }   // (LOOK, not played: no items, never illegal)
+  if (illegal) { if constexpr (!LOOK) return 1; }
+  if (!illegal) {                                              // (LOOK: an illegal entry leaves the do-nothing row)
+    for (int l = tid; l < L; l += nth) aff[l] = (unsigned char)imp[l];
+    for (int i = tid; i < S; i += nth) aff[L + i] = (unsigned char)subf[i];
+    // 4. application
+    struct BlockSync { __device__ void operator()() const { __syncthreads(); } };
+    const TopoMaps m{g.line_or_pos, g.line_ex_pos, L};
+    apply_topo_action(m, row, NS ? sbr : nullptr, s.last_bus + (size_t)lane * D, items, n_items, or_b, ex_b, tid, nth, BlockSync{});
+  }
+  const int verdict = (illegal ? 1 : 0) | (amb ? 2 : 0);
   // planning: the lane's topology class key (gridpf_capi.hip topo_class_of: busbar of every line end, an open end counting as
   // busbar 1, + the busbars >= 2 that carry an element) or its live busbars per substation (count_lane) changed -> host bookkeeping
+  // (LOOK: changed against the row the host last noted for this scratch lane, not against the row before the action)
+  const int* was = LOOK ? k.noted : prev;
+  const int* sb_was = LOOK ? k.noted + D : sbp;
   auto bb = [NBB](int v) { return v >= 2 && v <= NBB ? v : 1; };
   for (int p = tid; p < D; p += nth) {
-    const int v0 = prev[p], v1 = row[p], sub = s.pos_sub[p], o = s.pos_other[p];
+    const int v0 = was[p], v1 = row[p], sub = s.pos_sub[p], o = s.pos_other[p];
     if (o >= 0 && bb(v0) != bb(v1)) cnt[3] = 1;
     if (bb(v0) >= 2) used0[sub * NBB + v0 - 1] = 1;
     if (bb(v1) >= 2) used1[sub * NBB + v1 - 1] = 1;
-    if (v0 >= 1 && v0 <= NBB && (o < 0 || prev[o] >= 1)) act0[sub * NBB + v0 - 1] = 1;
+    if (v0 >= 1 && v0 <= NBB && (o < 0 || was[o] >= 1)) act0[sub * NBB + v0 - 1] = 1;
     if (v1 >= 1 && v1 <= NBB && (o < 0 || row[o] >= 1)) act1[sub * NBB + v1 - 1] = 1;
   }
   for (int i = tid; i < NS; i += nth) {
-    const int sub = g.shunt_sub[i], v0 = sbp[i], v1 = sbr[i];
+    const int sub = g.shunt_sub[i], v0 = sb_was[i], v1 = sbr[i];
     if (bb(v0) >= 2) used0[sub * NBB + v0 - 1] = 1;
     if (bb(v1) >= 2) used1[sub * NBB + v1 - 1] = 1;
     if (v0 >= 1 && v0 <= NBB) act0[sub * NBB + v0 - 1] = 1;
@@ -282,16 +297,35 @@ __global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab
     atomicMax(&cnt[4], c0); atomicMax(&cnt[5], c1);
   }
   __syncthreads();
-  const bool moved = cnt[3] != 0 || (cnt[4] > 1 ? cnt[4] : 1) != (cnt[5] > 1 ? cnt[5] : 1);
+  bool moved = cnt[3] != 0 || (cnt[4] > 1 ? cnt[4] : 1) != (cnt[5] > 1 ? cnt[5] : 1);
+  if constexpr (LOOK) moved = moved || k.noted[0] == INT_MIN;
   int* orow = g.topo + (size_t)lane * D;
   for (int i = tid; i < D; i += nth) orow[i] = row[i];
   for (int i = tid; i < NS; i += nth) g.shunt_bus[(size_t)lane * NS + i] = sbr[i];
-  if (!moved) return;
-  if (tid == 0) { const int slot = atomicAdd(&s.list[0], 1); s.list[1 + slot] = lane; cnt[6] = slot; }
-  __syncthreads();
-  int* dst = s.list_rows + (size_t)cnt[6] * (D + NS);
+  if (!moved) return verdict;
+  int* list = LOOK ? k.list : s.list;
+  if (tid == 0) { const int slot = atomicAdd(&list[0], 1); list[1 + slot] = lane; cnt[6] = slot; }
+  __syncthreads();                                             // (behind the last read of `was`, too)
+  int* dst = (LOOK ? k.list_rows : s.list_rows) + (size_t)cnt[6] * (D + NS);
   for (int i = tid; i < D; i += nth) dst[i] = row[i];
   for (int i = tid; i < NS; i += nth) dst[D + i] = sbr[i];
+  if constexpr (LOOK) {
+    for (int i = tid; i < D; i += nth) k.noted[i] = row[i];
+    for (int i = tid; i < NS; i += nth) k.noted[D + i] = sbr[i];
+  }
+  return verdict;
+}
+
+#ifdef GPF_TOPO_KERNEL
+// Steps 1-4 for one lane per 64-thread block (topo_play_lane).  act_on = 0: only the auto-reset snapshot.
+template <bool GEN>
+__global__ __launch_bounds__(64) void topo_prestep_kernel(TopoDev g, TopoTab tab, TopoLanes s, TopoRules r, TopoComp c, int n_lanes, int act_on) {
+  extern __shared__ int lds[];
+  const int lane = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
+  if (lane >= n_lanes) return;
+  if (tid == 0) s.ep_snap[lane] = g.episode[(size_t)lane * 2 + 1];
+  if (!act_on) return;
+  topo_play_lane<GEN, false>(g, tab, s, r, c, lds, lane, TopoLook{}, tid, nth);
 }
 
 // Step 5 for one lane per 64-thread block.  had_act: the launch (one step) carried topology actions; else n_steps do-nothing steps.
@@ -341,6 +375,7 @@ __global__ void topo_fanout_kernel(TopoDev g, TopoLanes s, int src, int dst0, in
   if (threadIdx.x < 2) s.flags[(size_t)dst * 2 + threadIdx.x] = s.flags[(size_t)src * 2 + threadIdx.x];
   if (threadIdx.x < s.n_slot) s.act[(size_t)dst * s.n_slot + threadIdx.x] = s.act[(size_t)src * s.n_slot + threadIdx.x];
 }
-#endif  // __HIPCC__ && GPF_TOPO_KERNEL
+#endif  // GPF_TOPO_KERNEL
+#endif  // __HIPCC__ && (GPF_TOPO_KERNEL || GPF_LA_KERNEL)
 
 }  // namespace gpf

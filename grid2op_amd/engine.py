@@ -206,6 +206,7 @@ GRAPH_SECTIONS = ("n_bus", "load_bus", "gen_bus", "storage_bus", "line_or_bus", 
 GRAPH_N_BUS, GRAPH_LOAD_BUS, GRAPH_GEN_BUS, GRAPH_STORAGE_BUS, GRAPH_LINE_OR_BUS, GRAPH_LINE_EX_BUS, GRAPH_SHUNT_BUS, GRAPH_BUS_GLOBAL = range(8)
 
 RW_REDISP, RW_L2RPN, RW_LINES_CAPACITY, RW_ECONOMIC, RW_GAMEPLAY = 1, 2, 3, 4, 5      # include/gridpf.h GPF_RW_*
+LA_ILLEGAL, LA_AMBIGUOUS, LA_DONE = 1, 2, 4      # include/gridpf.h GPF_LA_*: the flag bits of `PowerFlowEngine.lookahead`
 RW_N1 = 7                            # include/gridpf.h GPF_RW_N1: p[0] = index into the watched lines of `PowerFlowEngine.set_n1_screen`
 REWARD_MAX_SLOTS = 8
 REWARD_KINDS = {"RedispReward": RW_REDISP, "L2RPNReward": RW_L2RPN, "LinesCapacityReward": RW_LINES_CAPACITY, "EconomicReward": RW_ECONOMIC,
@@ -383,6 +384,7 @@ class PowerFlowEngine:
         self._traj_cap = 0                   # set_trajectory
         self._n_reward_slot = 0              # set_rewards
         self._n1 = None                      # set_n1_screen: (n_env, K)
+        self._la = None                      # set_lookahead: (n_env, K)
         self._rw_view = None                 # rewards_eval's cache of reward_views()["rewards"]; dropped by set_rewards
         self._ep_on = self._cb_on = self._cur_on = False      # set_episode_limit / set_combined_actions / set_chronics_cursor
         self._obs_spec = None                # set_obs_spec
@@ -1399,6 +1401,86 @@ class PowerFlowEngine:
         info = view(ptrs[2], (ne, 3), "<i4")
         return {"values": view(ptrs[0], (ne, K), "<f4"), "worst": view(ptrs[1], (ne,), "<f4"), "arg_worst": info[:, 0], "n_insecure": info[:, 1],
                 "n_diverged": info[:, 2], "lines": view(ptrs[3], (K,), "<i4")}
+
+    # ---- the look-ahead screen (include/gridpf.h gpf_set_lookahead; grid2op_amd/csrc/gridpf_lookahead.hpp) ----
+    def set_lookahead(self, n_cand: int, n_env: Optional[int] = None):
+        """``obs.simulate`` of ``n_cand`` action-table entries per environment in one call (`lookahead`): lanes ``[0, n_env)`` are the
+        environments (the only lanes `step` then steps), lane ``n_env + i * n_cand + k`` is the scratch lane of candidate ``k`` of
+        environment ``i``.  ``n_env`` None: as many as fit, ``n_lanes // (1 + n_cand)``.  0 or None: off.  Needs an uploaded action
+        table; refused with composite slots, areas or the N-1 screen on; while it is set multi-step launches are refused."""
+        if not n_cand:
+            self._call("gpf_set_lookahead", 0, 0)
+            self._la = None
+            return
+        K = int(n_cand)
+        ne = self.n_lanes // (1 + K) if n_env is None else int(n_env)
+        self._la = None
+        try:
+            self._call("gpf_set_lookahead", ne, K)
+        except GridPFError as exc:
+            if "header-only handle" in str(exc):     # (the library keeps a valid setting there, so that every later refusal can be shown)
+                self._la = (ne, K)
+            raise
+        self._la = (ne, K)
+
+    def _la_range(self, what, lane0, n):
+        """The environments among lanes ``[lane0, lane0 + n)`` (the whole range by default): first environment, count, K."""
+        if getattr(self, "_la", None) is None:
+            raise GridPFError(f"{what}: the look-ahead is off (set_lookahead)")
+        ne, K = self._la
+        lane0, n = self._range(lane0, n)
+        a, b = min(max(lane0, 0), ne), min(max(lane0 + n, 0), ne)
+        return a, max(b - a, 0), K
+
+    def lookahead(self, t_obs: int, time_step: int = 1, candidates=None, max_iter: int = 10, tol_mva: float = 1e-8, rebalance: float = 0.0,
+                  cascade: bool = False, hard_overflow: float = 2.0, soft_overflow: float = 1.0, nb_ts_allowed: int = 2, max_rounds: int = 16,
+                  is_dc: bool = False):
+        """Environment ``i``'s candidates -- ``candidates`` int32 ``[n_env, K]`` of table indices (-1: do nothing), or None: what was
+        written into ``lookahead_views()["cand"]`` on ``device_views()["stream"]`` -- are played under the environment's rules on copies of
+        lane ``i`` and stepped once on the forecast ``time_step`` steps ahead (0: the observation's own injections), as `simulate_batch`
+        steps its candidates, and reduced on the device (asynchronous): ``value`` (the simulated ``rho.max()``, +inf when the step ended
+        the episode), ``flags`` (`LA_ILLEGAL` | `LA_AMBIGUOUS` | `LA_DONE`), ``best`` (the playable slot with the lowest value, -1: none)
+        -- `lookahead_views` / `lookahead_values`.  The environments are not touched and nothing plays the choice::
+
+            v, la = eng.device_views(), eng.lookahead_views()
+            pick = la["cand"].gather(1, la["best"].clamp(min=0).long()[:, None])[:, 0]
+            v["act_topo"][:n_env, 0] = torch.where(la["best"] >= 0, pick, -1)
+        """
+        cand = None
+        if candidates is not None:
+            if getattr(self, "_la", None) is None:
+                raise GridPFError("lookahead: the look-ahead is off (set_lookahead)")
+            cand = np.ascontiguousarray(candidates, dtype=np.int32)
+            if cand.shape != self._la:
+                raise ValueError(f"lookahead: candidates must be [n_env, K] = {list(self._la)}, got {list(cand.shape)}")
+        o = GpfStepOpts(int(max_iter), float(tol_mva), float(rebalance), int(bool(cascade)), float(hard_overflow), float(soft_overflow),
+                        int(nb_ts_allowed), int(max_rounds), int(bool(is_dc)), 0, 0, 0, 0)
+        self._call("gpf_lookahead", int(t_obs), int(time_step), _ptr(cand), C.byref(o))
+
+    def lookahead_values(self, lane0: int = 0, n: Optional[int] = None) -> dict:
+        """``value`` float32 / ``flags`` uint8 ``[n_env', K]``, ``best`` int32 / ``best_value`` float32 ``[n_env']``, ``n_playable`` /
+        ``n_done`` int32 ``[n_env']`` of the last `lookahead`, for the environment lanes inside lanes ``[lane0, lane0 + n)``; synchronous."""
+        a, m, K = self._la_range("lookahead_values", lane0, n)
+        value, flags = np.zeros((m, K), np.float32), np.zeros((m, K), np.uint8)
+        best, bv, info = np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros((m, 2), np.int32)
+        self._call("gpf_get_lookahead", a, m, _ptr(value), _ptr(flags), _ptr(best), _ptr(bv), _ptr(info))
+        return dict(value=value, flags=flags, best=best, best_value=bv, n_playable=info[:, 0].copy(), n_done=info[:, 1].copy())
+
+    def lookahead_views(self) -> dict:
+        """Zero-copy torch tensors ALIASING the look-ahead's buffers (order the reader or writer on ``device_views()["stream"]``): ``cand``
+        int32 ``[n_env, K]`` (the candidates a `lookahead` without ``candidates`` plays), ``value`` float32 / ``flags`` uint8
+        ``[n_env, K]``, ``best`` int32 / ``best_value`` float32 ``[n_env]``, ``n_playable`` / ``n_done`` int32 ``[n_env]``."""
+        import torch
+        _, _, K = self._la_range("lookahead_views", 0, None)
+        ptrs = self._device_pointers("gpf_lookahead_device_pointers", _capi.N_LOOKAHEAD_POINTERS)
+
+        def view(p, shape, typestr):
+            iface = {"shape": shape, "typestr": typestr, "data": (int(p), False), "version": 2, "strides": None}
+            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=torch.device("cuda", self.device))
+        ne = self._la[0]
+        info = view(ptrs[5], (ne, 2), "<i4")
+        return {"cand": view(ptrs[0], (ne, K), "<i4"), "value": view(ptrs[1], (ne, K), "<f4"), "flags": view(ptrs[2], (ne, K), "|u1"),
+                "best": view(ptrs[3], (ne,), "<i4"), "best_value": view(ptrs[4], (ne,), "<f4"), "n_playable": info[:, 0], "n_done": info[:, 1]}
 
     # ---- combined topology + injection actions (include/gridpf.h gpf_set_combined_actions; grid2op_amd/csrc/gridpf_combined.hpp) ----
     def set_combined_actions(self, on: bool = True, check_values: bool = True, storage_max_p_prod=None, storage_max_p_absorb=None):

@@ -867,6 +867,57 @@ int gpf_get_n1_values(gpf_handle h, int32_t lane0, int32_t n, float* value);
 int gpf_get_n1_summary(gpf_handle h, int32_t lane0, int32_t n, float* worst, int32_t* arg_worst, int32_t* n_insecure, int32_t* n_diverged);
 int gpf_n1_device_pointers(gpf_handle h, void** out, int32_t n);
 
+/* ---- the look-ahead screen: per-lane candidates of the action table simulated on the device (grid2op_amd/csrc/gridpf_lookahead.hpp) ----
+ * What an agent does with obs.simulate at every step (Observation/baseObservation.py:3365-3670 -> Environment/_obsEnv.py): simulate its
+ * K best actions and play the one with the lowest simulated rho.max() that is legal and does not end the episode.  Here environment i
+ * is lane i < n_env, its candidates are K indices into the uploaded action table (gpf_upload_topo_actions) in a device buffer, and
+ * candidate (i, k) is played on scratch lane n_env + i K + k -- the layout of the N-1 screen and of gpf_simulate_batch with
+ * dst_lane0 = n_env.  One gpf_lookahead call:
+ *   - the scratch lane takes everything gpf_simulate_batch copies from a source (injection row, protection counters, line cooldowns,
+ *     chronics table and the absolute chronics / forecast row, jitter, redispatch delta, dynamics state) and the environment's topology
+ *     and shunt rows, substation cooldowns and last known busbars, all from the device;
+ *   - scheduled maintenance ahead of the observation takes its lines out before the action (_ObsEnv.init, _obsEnv.py:361-385: the rule
+ *     of gpf_simulate_batch, stated once for both);
+ *   - entry cand[i][k] goes through steps 1-4 of the acting path (ambiguity, impact, LookParam + PreventReconnection with the
+ *     environment's cooldowns and gpf_set_topo_rules, _BackendAction.__iadd__): the code of the topology pre-step, not a copy.  -1 is the
+ *     do-nothing candidate; an index outside the table is ambiguous; an ambiguous or illegal entry leaves the do-nothing row and its flag;
+ *   - the scratch lanes are stepped ONCE as gpf_simulate_batch steps them (no cooldown tracking, no auto-reset, no outage tables, no
+ *     opponent), time_step 0 on the observation's own injections, time_step >= 1 on the uploaded forecasts;
+ *   - value[i][k] float32 = the maximum over the lines of the scratch lane's rho row as the step wrote it (a maximum of stored float32:
+ *     exact in any order), +inf when the simulated step ended the episode; flags[i][k] = GPF_LA_ILLEGAL | GPF_LA_AMBIGUOUS (what
+ *     sim_info["is_illegal"] / ["is_ambiguous"] say; for a valid index, set exactly when gpf_topo_action_mask's byte is non-zero) |
+ *     GPF_LA_DONE; best[i] = the slot with flags == 0 and the lowest value, the lowest k on a tie, -1 (best_value +inf) when no slot is
+ *     playable; info[i] = {playable slots, done slots}.
+ * The environment lanes are only read: their rows, cooldowns, flags, pending actions and the planner's record of them stay as they were.
+ * Nothing plays the choice: write table[cand[i][best[i]]] (or -1) into act_topo and step.  While the look-ahead is set gpf_step_n steps
+ * lanes [0, n_env) only and refuses multi-step launches; the scratch lanes stay readable (gpf_get_results, gpf_get_step_outputs) on
+ * their range.  Host work: one read-back of the count of scratch lanes whose topology class or busbar count left the one the planner
+ * noted, then only those lanes' rows; the plans of the two lane ranges are cached.  Forecast horizons beyond 1 use the observation's
+ * cooldowns unchanged (the reference counts them down by time_step - 1).
+ *   gpf_set_lookahead : n_cand = 0 switches it off.  Refused before the device is touched (on a header-only handle too): no action
+ *                       table, composite slots (gpf_set_topo_slots > 1), rules by area (gpf_set_topo_areas), n_env <= 0,
+ *                       n_env (1 + n_cand) > n_lanes, the N-1 screen on (and gpf_set_n1_screen while this is set: both claim the lanes
+ *                       behind the environments), a grid whose rows do not fit the 64 KiB of LDS of the play kernel.
+ *   gpf_lookahead     : cand [n_env][n_cand] from the host, or NULL: what is in the engine-owned device buffer (out[0] below), written
+ *                       on the engine's stream.  Refused: off, a horizon without forecasts (gpf_simulate_batch's reason), combined mode
+ *                       with injection actions pending, the table checks above.
+ *   gpf_get_lookahead : the outputs of environments [env0, env0 + n) of the last call; any pointer may be NULL.
+ *   gpf_lookahead_device_pointers : out[0] cand int32 [n_env][K], out[1] value float32 [n_env][K], out[2] flags uint8 [n_env][K], out[3]
+ *                       best int32 [n_env], out[4] best_value float32 [n_env], out[5] info int32 [n_env][2].  n must be
+ *                       GPF_N_LOOKAHEAD_POINTERS.
+ *   The getters fail with "the look-ahead is off" while it is off.
+ * OUT OF SCOPE: composite slots and rules by area, injection candidates (redispatch, storage, curtailment), chained horizons (a scratch
+ * lane as an environment), the opponent inside the look-ahead, simulated rewards as a pinned feature (gpf_rewards_eval on the scratch
+ * range works as after gpf_simulate_batch), playing the choice inside the call, the look-ahead inside multi-step launches. */
+#define GPF_N_LOOKAHEAD_POINTERS 6
+#define GPF_LA_ILLEGAL 1
+#define GPF_LA_AMBIGUOUS 2
+#define GPF_LA_DONE 4
+int gpf_set_lookahead(gpf_handle h, int32_t n_env, int32_t n_cand);
+int gpf_lookahead(gpf_handle h, int32_t t_obs, int32_t time_step, const int32_t* cand, const gpf_step_opts* opts);
+int gpf_get_lookahead(gpf_handle h, int32_t env0, int32_t n, float* value, uint8_t* flags, int32_t* best, float* best_value, int32_t* info);
+int gpf_lookahead_device_pointers(gpf_handle h, void** out, int32_t n);
+
 /* ---- combined topology + injection actions of the batched acting path (grid2op_amd/csrc/gridpf_combined.hpp): one action with a
  * topology part (the table indices above) and an injection part (redispatch / storage / curtailment rows), lane by lane, in a one-step
  * launch.  OFF by default: without this call gpf_step_n refuses such a launch and queues exactly what it queued before.  Paths relative

@@ -1,0 +1,356 @@
+"""The look-ahead screen on the device (include/gridpf.h gpf_set_lookahead / gpf_lookahead, grid2op_amd/csrc/gridpf_lookahead.hpp): the
+recordings of the unmodified reference's obs.simulate on per-step candidate lists (tests/golden/lookahead_*.npz, one environment lane per
+recorded step), the call against `simulate_batch` on a fresh engine, the flags against `topo_action_mask_host`, environment lanes that
+the look-ahead leaves alone, the shapes at which the kernels take another path, and DC.
+
+Bounds: flags, topology rows and line status against the recording exactly; rho and value within 3e-5 (tests/lookahead_ref.RHO_TOL: what
+tests/test_gpu_simulate.py holds this step kernel to against the same kind of recording); value against the scratch lane's own rho row,
+best against the restatement on the device's own value and flags, and everything against `simulate_batch`, bit for bit."""
+import json
+
+import numpy as np
+import pytest
+
+import lookahead_ref as LA
+from conftest import golden_path
+from topo_rules_ref import TopoRules, pack_actions
+
+pytestmark = pytest.mark.gpu
+
+TABLE14 = [{"set_line_status": [(3, -1)]}, {"set_line_status": [(3, +1)]}, {"set_line_status": [(7, -1)]}, {"change_line_status": [12]},
+           {"set_bus": {24: 2, 25: 1, 26: 2, 27: 1, 28: 2, 29: 1, 30: 2}}, {"set_bus": {p: 1 for p in range(24, 31)}},
+           {"set_line_status": [(3, -1), (7, -1)]}, {"set_line_status": [(3, +1)], "change_line_status": [3]}, {"set_line_status": [(17, -1)]}]
+
+
+def _table(fx):
+    return [{k: ({int(p): int(b) for p, b in v.items()} if isinstance(v, dict) else v) for k, v in a.items()} for a in json.loads(str(fx["table_json"]))]
+
+
+def _engine(grid, n_lanes, offsets=None, horizons=1):
+    from grid2op_amd.engine import PowerFlowEngine
+    from grid2op_amd.grid_model import GridModel
+    m = GridModel.load_npz(golden_path(f"{grid}.grid.npz"))
+    ch = dict(np.load(golden_path(f"{grid}.chronics.npz")))
+    if "prod_v" not in ch:
+        ch["prod_v"] = np.tile((m.gen_vm0 * m.sub_vn_kv[m.gen_sub]).astype(np.float32), (ch["prod_p"].shape[0], 1))
+    eng = PowerFlowEngine(m, n_lanes=n_lanes, device=0)
+    tab = eng.pack_chronics(ch["load_p"], ch["load_q"], ch["prod_p"], ch["prod_v"])[:48]
+    eng.upload_chronics(tab)
+    eng.upload_forecasts(np.stack([tab * np.float32(1.0 + 0.01 * (h + 1)) for h in range(horizons)], axis=1)[None])
+    eng.set_lane_chronics(lane_offset=7 * np.arange(n_lanes) if offsets is None else np.asarray(offsets))
+    if "thermal_limits" in ch:
+        eng.set_thermal_limits(ch["thermal_limits"])
+    return m, eng
+
+
+def _check_outputs(eng, n_env, K):
+    """what every call must leave: value = the scratch lane's own rho.max() bit for bit (+inf and LA_DONE on a done lane), the summary =
+    the restatement on the device's own value and flags, views = getters"""
+    got = eng.lookahead_values()
+    rho = eng.step_outputs(n_env, n_env * K)[0].reshape(n_env, K, -1)
+    done = eng.episode(n_env, n_env * K)[0].reshape(n_env, K).astype(bool)
+    assert got["value"].shape == (n_env, K) and got["flags"].shape == (n_env, K)
+    assert np.array_equal((got["flags"] & LA.DONE) != 0, done)
+    assert np.isinf(got["value"][done]).all() and got["value"][~done].tobytes() == rho.max(axis=2)[~done].tobytes()
+    for i in range(n_env):
+        best, bv, n_ok, n_done = LA.summary(got["value"][i], got["flags"][i])
+        assert (got["best"][i], got["best_value"][i].tobytes(), got["n_playable"][i], got["n_done"][i]) == (best, bv.tobytes(), n_ok, n_done), i
+    v = eng.lookahead_views()
+    eng.sync()
+    for key in ("value", "flags", "best", "best_value", "n_playable", "n_done"):
+        assert np.array_equal(v[key].cpu().numpy(), got[key]), key
+    return got, rho, done
+
+
+@pytest.mark.parametrize("grid,fixture", [("l2rpn_case14_sandbox", "lookahead_case14.npz"), ("l2rpn_neurips_2020_track1", "lookahead_maintenance_neurips36.npz")])
+def test_recorded_states_one_call_per_horizon(grid, fixture, load_model, load_npz):
+    """Step s of the recording is environment lane s with its own K candidates.  Second file: a maintenance begins at the next row of one
+    of the states, and a candidate names the maintained line."""
+    from grid2op_amd.engine import PowerFlowEngine
+    m, fx = load_model(grid), load_npz(fixture)
+    S, K = fx["cand"].shape
+    row0 = int(fx["row0"])
+    eng = PowerFlowEngine(m, n_lanes=S * (1 + K), device=0)
+    eng.upload_chronics(eng.pack_chronics(fx["ch_load_p"], fx["ch_load_q"], fx["ch_prod_p"], fx["ch_prod_v"]))
+    eng.upload_forecasts(eng.pack_chronics(fx["fc_load_p"], fx["fc_load_q"], fx["fc_prod_p"], fx["fc_prod_v"]))
+    if "maintenance" in fx:
+        eng.upload_maintenance(fx["maintenance"])
+    eng.set_thermal_limits(fx["thermal_limit"])
+    off = np.zeros(S * (1 + K), np.int32)
+    off[:S] = fx["row"] - row0
+    eng.set_lane_chronics(lane_offset=off)
+    max_sub, max_line, cd_sub, cd_line = (int(v) for v in fx["params"])
+    eng.set_topo_rules(max_sub_changed=max_sub, max_line_status_changed=max_line, cooldown_sub=cd_sub, cooldown_line=cd_line)
+    eng.upload_topo_actions(_table(fx))
+    eng.set_topology(fx["topo_vect"].astype(np.int32), lane0=0)
+    eng.set_last_bus(np.maximum(fx["last_bus"].astype(np.int32), 1), lane0=0)
+    eng.set_overflow_count(fx["timestep_overflow"].astype(np.int32), lane0=0)
+    eng.set_cooldown(fx["cooldown_line"].astype(np.int32), lane0=0)
+    eng.set_sub_cooldown(fx["cooldown_sub"].astype(np.int32), lane0=0)
+    eng.set_lookahead(K, S)
+    kw = dict(cascade=True, hard_overflow=float(fx["hard_overflow"]), nb_ts_allowed=int(fx["nb_ts_allowed"]))
+    n_pinned = 0
+    for ts in (0, 1):
+        eng.lookahead(0, ts, fx["cand"], **kw)
+        got, rho, done = _check_outputs(eng, S, K)
+        r = eng.results(S, S * K, with_bus=False)
+        rec_flags = fx[f"sim{ts}_flags"]
+        assert np.array_equal(got["flags"], rec_flags), (ts, got["flags"], rec_flags)
+        for s in range(S):
+            for k in np.flatnonzero(~done[s]):
+                q = s * K + k
+                assert np.array_equal(r.topo_vect[q], fx[f"sim{ts}_topo_vect"][s][k]), (ts, s, k)
+                assert np.array_equal(r.line_status[q], fx[f"sim{ts}_line_status"][s][k]), (ts, s, k)
+                err = float(np.abs(rho[s, k] - fx[f"sim{ts}_rho"][s][k]).max())
+                print(f"ts {ts} state {s} slot {k}: max |rho - recorded| = {err:.2e}")
+                assert err < LA.RHO_TOL, (ts, s, k, err)
+                assert abs(float(got["value"][s, k]) - float(fx[f"sim{ts}_rho"][s][k].max())) < LA.RHO_TOL, (ts, s, k)
+            rec_val = np.where(rec_flags[s] & LA.DONE, np.inf, fx[f"sim{ts}_rho"][s].max(axis=1)).astype(np.float32)
+            if LA.margin(rec_val, rec_flags[s]) > LA.MARGIN:
+                assert got["best"][s] == LA.summary(rec_val, rec_flags[s])[0], (ts, s)
+                n_pinned += 1
+    assert n_pinned >= 0.9 * 2 * S
+    # the environments were only read
+    assert np.array_equal(eng.get_topology(0, S)[0], fx["topo_vect"]) and np.array_equal(eng.cooldown(0, S), fx["cooldown_line"])
+    assert np.array_equal(eng.sub_cooldown(0, S), fx["cooldown_sub"]) and np.array_equal(eng.last_bus(0, S), np.maximum(fx["last_bus"], 1))
+    eng.close()
+
+
+def _sources_in_different_states(m, eng, n_env):
+    """lane 1 with a line out whose origin was last seen on busbar 2, lane 2 with substation 1's elements spread over two busbars"""
+    topo = np.tile(m.initial_topo_vect(), (n_env, 1)).astype(np.int32)
+    last = np.ones((n_env, m.dim_topo), np.int32)
+    lo, le = m.line_or_pos_topo_vect, m.line_ex_pos_topo_vect
+    topo[1, lo[2]] = topo[1, le[2]] = -1
+    last[1, lo[2]] = 2
+    from topo_rules_ref import topo_pos_sub
+    pos = np.flatnonzero(topo_pos_sub(m) == 1)
+    if n_env > 2:
+        topo[2, pos[::2]] = 2
+        last[2, pos[::2]] = 2
+    eng.set_topology(topo, lane0=0)
+    eng.set_last_bus(last, lane0=0)
+    return topo, last
+
+
+@pytest.mark.parametrize("grid,is_dc", [("rte_case5_example", False), ("l2rpn_case14_sandbox", False), ("l2rpn_case14_sandbox", True)])
+def test_scratch_lanes_equal_simulate_batch_on_a_fresh_engine(grid, is_dc):
+    """n_env = 3, K = 5, AlwaysLegal, the same legal list in every row: results rows, topology rows and rho of the scratch lanes are those of
+    `simulate_batch(dst_lane0 = n_env)` with the same candidates and the lanes' last known busbars, bit for bit -- AC and DC."""
+    n_env, K = 3, 5
+    n = n_env * (1 + K)
+    m, eng = _engine(grid, n)
+    _, twin = _engine(grid, n)
+    pos = int(m.load_pos_topo_vect[0])
+    table = [{"set_line_status": [(1, -1)]}, {"set_line_status": [(2, +1)]}, {"change_line_status": [4]}, {"set_bus": {int(m.line_or_pos_topo_vect[2]): 2}},
+             {"set_bus": {pos: 2, int(m.gen_pos_topo_vect[0]): 2}}, {"set_line_status": [(0, -1), (3, -1)]}]
+    eng.set_topo_rules(legal_rules=False)
+    eng.upload_topo_actions(table)
+    for e in (eng, twin):
+        _sources_in_different_states(m, e, n_env)
+    eng.set_lookahead(K, n_env)
+    for ts, idx in ((1, [0, 1, 3, 4, 5]), (0, [2, 1, 4, 0, 3])):
+        eng.lookahead(3, ts, np.tile(np.array(idx, np.int32), (n_env, 1)), is_dc=is_dc)
+        twin.simulate_batch(3, np.arange(n_env), [table[k] for k in idx], dst_lane0=n_env, time_step=ts, last_bus=eng.last_bus(0, n_env), is_dc=is_dc)
+        a, b = eng.results(n_env, n_env * K), twin.results(n_env, n_env * K)
+        for f in ("out", "topo_vect", "shunt_bus", "line_status", "status"):
+            assert getattr(a, f).tobytes() == getattr(b, f).tobytes(), (ts, f)
+        assert eng.step_outputs(n_env, n_env * K)[0].tobytes() == twin.step_outputs(n_env, n_env * K)[0].tobytes()
+        assert eng.get_topology(n_env, n_env * K)[0].tobytes() == twin.get_topology(n_env, n_env * K)[0].tobytes()
+        got, _, done = _check_outputs(eng, n_env, K)
+        assert (got["flags"] & 3 == 0).all() and a.converged.reshape(n_env, K)[~done].all()
+        assert np.array_equal(eng.get_topology(0, n_env)[0], twin.get_topology(0, n_env)[0])
+    eng.close(); twin.close()
+
+
+def _acting(eng, n_lanes, n_env, t, n_act):
+    act = np.full(n_lanes, -1, np.int32)
+    act[:n_env] = (np.arange(n_env) * 2 + t) % n_act if t % 3 != 2 else -1
+    return act
+
+
+def test_flags_are_the_action_masks_and_a_flagged_slot_does_nothing():
+    """After three acting steps with cooldowns: for every (lane, entry) of the table flags & 3 != 0 exactly when `topo_action_mask_host` is
+    non-zero; an index of n_act or -2 is ambiguous; a flagged slot's rows are the do-nothing slot's rows."""
+    n_env, n_act = 4, len(TABLE14)
+    K = n_act + 3
+    n = n_env * (1 + K)
+    m, eng = _engine("l2rpn_case14_sandbox", n)
+    eng.set_topo_rules(max_sub_changed=1, max_line_status_changed=1, cooldown_sub=3, cooldown_line=3)
+    eng.upload_topo_actions(TABLE14)
+    eng.set_lookahead(K, n_env)
+    for t in range(3):
+        eng.set_lane_topo_actions(_acting(eng, n, n_env, t, n_act))
+        eng.step(t, nb_ts_reco=10)
+    assert (eng.cooldown(0, n_env) > 0).any() and (eng.sub_cooldown(0, n_env) > 0).any()
+    mask = eng.topo_action_mask_host(0, n_env)
+    cand = np.tile(np.concatenate([np.arange(n_act), [-1, n_act, -2]]).astype(np.int32), (n_env, 1))
+    eng.lookahead(3, 1, cand)
+    got, _, _ = _check_outputs(eng, n_env, K)
+    assert np.array_equal((got["flags"][:, :n_act] & 3) != 0, mask != 0) and (mask != 0).any() and (mask == 0).any()
+    off, items = pack_actions(TABLE14)
+    amb = TopoRules(m, off, items).ambiguous
+    assert np.array_equal((got["flags"][:, :n_act] & LA.AMBIGUOUS) != 0, np.tile(amb, (n_env, 1))) and amb.any()
+    assert (got["flags"][:, n_act] & 3 == 0).all() and (got["flags"][:, n_act + 1:] & 3 == LA.AMBIGUOUS).all()
+    r = eng.results(n_env, n_env * K)
+    topo = eng.get_topology(n_env, n_env * K)[0].reshape(n_env, K, -1)
+    out = r.out.reshape(n_env, K, -1)
+    for i in range(n_env):
+        for k in np.flatnonzero(got["flags"][i] & 3):
+            assert np.array_equal(topo[i, k], topo[i, n_act]) and out[i, k].tobytes() == out[i, n_act].tobytes(), (i, k)
+    eng.close()
+
+
+def test_environment_lanes_are_undisturbed_and_the_pending_action_is_played():
+    """Two engines, the same acting episode of ten steps with topology actions written on the device: one calls `lookahead` between writing
+    the action and every step and has n_env (1 + K) lanes, the other never does and has n_env lanes.  Results, cooldowns, flags, last
+    known busbars and episode counters of the environment lanes are bit-identical at every step."""
+    import torch
+    n_env, K, n_act = 5, 4, len(TABLE14)
+    seen = {}
+    for mode in ("look", "plain"):
+        n = n_env * (1 + K) if mode == "look" else n_env
+        m, eng = _engine("l2rpn_case14_sandbox", n, 5 * np.arange(n))
+        eng.set_topo_rules(max_sub_changed=1, max_line_status_changed=1, cooldown_sub=3, cooldown_line=3)
+        eng.upload_topo_actions(TABLE14)
+        if mode == "look":
+            eng.set_lookahead(K, n_env)
+        views = eng.device_views()
+        rows = []
+        for t in range(10):
+            act = _acting(eng, n, n_env, t, n_act)
+            with torch.cuda.stream(views["stream"]):
+                views["act_topo"].copy_(torch.from_numpy(act.reshape(-1, 1)).to(views["act_topo"].device))
+            eng.topo_actions_on_device()
+            if mode == "look":
+                cand = (np.arange(n_env * K).reshape(n_env, K) * 3 + t) % (n_act + 1) - 1
+                eng.lookahead(t, 1, cand.astype(np.int32), cascade=True)
+                assert eng.lookahead_values()["n_playable"].sum() >= 1
+            eng.step(t, cascade=True, nb_ts_reco=10)
+            r = eng.results(0, n_env)
+            ill, amb = eng.topo_action_flags(0, n_env)
+            if t % 3 != 2:
+                assert (ill | amb | (r.topo_vect != m.initial_topo_vect()).any(axis=1)).any() or t == 0      # the written action was played
+            rows.append(tuple(x.tobytes() for x in (r.out, r.topo_vect, r.status, r.line_status, r.bus_vm, r.bus_va, ill, amb, eng.cooldown(0, n_env),
+                                                   eng.sub_cooldown(0, n_env), eng.last_bus(0, n_env), eng.get_topology(0, n_env)[0])
+                              + eng.episode(0, n_env) + eng.step_outputs(0, n_env)))
+        seen[mode] = rows
+        eng.close()
+    for t, (a, b) in enumerate(zip(seen["look"], seen["plain"])):
+        assert a == b, (t, [i for i, (x, y) in enumerate(zip(a, b)) if x != y])
+    assert len({row[1] for row in seen["plain"]}) >= 4                                                        # the topology did change along the way
+
+
+@pytest.mark.parametrize("grid,n_env,K", [("l2rpn_case14_sandbox", 3, 1), ("rte_case5_example", 2, 70), ("l2rpn_case14_sandbox", 5, 6)])
+def test_shapes_device_candidates_second_call_and_off(grid, n_env, K):
+    """K = 1, K = 70 (two trips of the summary's strided loop), an odd n_env; candidates handed over through ``lookahead_views()["cand"]``
+    against the same from the host, bit for bit; a second call with all-new candidates against a fresh engine's first call; off: `step`
+    steps every lane again."""
+    import torch
+    n = n_env * (1 + K)
+    m, eng = _engine(grid, n)
+    _, fresh = _engine(grid, n)
+    table = [{"set_line_status": [(l, -1)]} for l in range(min(m.n_line, 6))] + [{"change_line_status": [1]}, {"set_line_status": [(0, +1)], "change_line_status": [0]}]
+    n_act = len(table)
+    for e in (eng, fresh):
+        e.set_topo_rules(max_sub_changed=1, max_line_status_changed=1)
+        e.upload_topo_actions(table)
+        e.set_lookahead(K, n_env)
+    first = ((np.arange(n_env * K).reshape(n_env, K) * 5) % (n_act + 1) - 1).astype(np.int32)
+    second = ((np.arange(n_env * K).reshape(n_env, K) * 3 + 2) % (n_act + 1) - 1).astype(np.int32)
+    eng.lookahead(2, 1, first)
+    host, _, _ = _check_outputs(eng, n_env, K)
+    v, dv = eng.lookahead_views(), eng.device_views()
+    with torch.cuda.stream(dv["stream"]):
+        v["cand"].copy_(torch.from_numpy(second).to(v["cand"].device))
+    eng.lookahead(2, 1)                                                    # the candidates written on the device
+    dev, _, _ = _check_outputs(eng, n_env, K)
+    fresh.lookahead(2, 1, second)
+    want, _, _ = _check_outputs(fresh, n_env, K)
+    for key in want:
+        assert dev[key].tobytes() == want[key].tobytes(), key
+    a, b = eng.results(n_env, n_env * K), fresh.results(n_env, n_env * K)
+    assert a.out.tobytes() == b.out.tobytes() and a.topo_vect.tobytes() == b.topo_vect.tobytes()
+    assert (host["flags"] != dev["flags"]).any() or (host["value"] != dev["value"]).any()
+    # off: every lane is stepped again
+    before = eng.episode()[1].copy()
+    eng.step(3)
+    assert np.array_equal(eng.episode()[1] - before, (np.arange(n) < n_env).astype(before.dtype))
+    eng.set_lookahead(0)
+    eng.set_lane_chronics(lane_offset=7 * np.arange(n))
+    before = eng.episode()[1].copy()
+    eng.step(4)
+    assert (eng.episode()[1] - before == 1).all()
+    eng.close(); fresh.close()
+
+
+def test_large_rows_with_env_dynamics_equal_simulate_batch(load_model, load_npz):
+    """118 substations, 186 lines (three trips of the reduce kernel's strided loop, the largest rows in LDS), n_env = 2, K = 3, the
+    injection dynamics on: the scratch lanes take their environment's dynamics state, and equal `simulate_batch` on a twin bit for bit."""
+    from grid2op_amd.engine import PowerFlowEngine
+    name = "l2rpn_wcci_2022_dev"
+    m, fx = load_model(name), load_npz(f"envdyn_{name}.npz")
+    n_env, K = 2, 3
+    n = n_env * (1 + K)
+    table = [{"set_line_status": [(5, -1)]}, {"set_line_status": [(100, -1)]}, {"change_line_status": [185]}, {"set_line_status": [(64, -1)]}]
+    engs = []
+    for _ in range(2):
+        eng = PowerFlowEngine(m, n_lanes=n, device=0)
+        tab = eng.pack_chronics(fx["ch_load_p"], fx["ch_load_q"], fx["ch_prod_p"], fx["ch_prod_v"])
+        eng.upload_chronics(tab)
+        eng.upload_forecasts((tab * np.float32(1.01))[None, :, None, :])
+        eng.set_thermal_limits(fx["thermal_limit"])
+        eng.set_gen_limits(fx["pmin"], fx["pmax"], fx["ramp_up"], fx["ramp_down"], fx["redispatchable"], eps_poly=float(fx["eps_poly"]))
+        if m.n_storage:
+            eng.set_storage_params(fx["storage_Emax"], fx["storage_Emin"], fx["storage_loss"], fx["storage_charging_efficiency"],
+                                   fx["storage_discharging_efficiency"], fx["storage_charge0"], float(fx["delta_time_seconds"]), bool(fx["activate_storage_loss"]))
+        eng.set_env_dynamics(True, tol_poly=float(fx["tol_poly"]))
+        off = np.zeros(n, np.int32)
+        off[:n_env] = (int(fx["row"][0]), int(fx["row"][0]) + 2)
+        eng.set_lane_chronics(lane_offset=off)
+        eng.set_env_state(0, prev_p=np.tile(fx["ch_prod_p"][int(fx["row"][0]) - 1], (n, 1)))
+        eng.set_topo_rules(legal_rules=False)
+        eng.upload_topo_actions(table)
+        engs.append(eng)
+    eng, twin = engs
+    eng.set_lookahead(K, n_env)
+    for e in engs:                                                         # two environment steps first: a dynamics state to take over
+        e.step(0)
+        e.step(1)
+    idx = [3, 0, 2]
+    eng.lookahead(2, 1, np.tile(np.array(idx, np.int32), (n_env, 1)))
+    twin.simulate_batch(2, np.arange(n_env), [table[k] for k in idx], dst_lane0=n_env, time_step=1, last_bus=eng.last_bus(0, n_env))
+    a, b = eng.results(n_env, n_env * K), twin.results(n_env, n_env * K)
+    assert a.out.tobytes() == b.out.tobytes() and a.topo_vect.tobytes() == b.topo_vect.tobytes() and a.converged.all()
+    sa, sb = eng.env_state(n_env, n_env * K), twin.env_state(n_env, n_env * K)
+    for key in sa:
+        assert np.asarray(sa[key]).tobytes() == np.asarray(sb[key]).tobytes(), key
+    got, _, done = _check_outputs(eng, n_env, K)
+    assert not done.any() and (got["flags"] == 0).all() and (got["best"] >= 0).all()
+    eng.close(); twin.close()
+
+
+def test_a_sharded_engine_over_one_device_agrees_with_the_plain_engine():
+    from grid2op_amd.grid_model import GridModel
+    from grid2op_amd.sharding import ShardedEngine
+    n_env, K = 3, 4
+    n = n_env * (1 + K)
+    m, eng = _engine("l2rpn_case14_sandbox", n)
+    se = ShardedEngine(GridModel.load_npz(golden_path("l2rpn_case14_sandbox.grid.npz")), n, devices=[0])
+    ch = dict(np.load(golden_path("l2rpn_case14_sandbox.chronics.npz")))
+    tab = eng.pack_chronics(ch["load_p"], ch["load_q"], ch["prod_p"], ch["prod_v"])[:48]
+    se.upload_chronics(tab)
+    se.upload_forecasts((tab * np.float32(1.01))[None, :, None, :])
+    se.set_lane_chronics(lane_offset=7 * np.arange(n))
+    se.set_thermal_limits(ch["thermal_limits"])
+    cand = ((np.arange(n_env * K).reshape(n_env, K) * 2) % (len(TABLE14) + 1) - 1).astype(np.int32)
+    for e in (eng, se):
+        e.set_topo_rules(max_sub_changed=1, max_line_status_changed=1)
+        e.upload_topo_actions(TABLE14)
+        e.set_lookahead(K, n_env)
+        e.lookahead(1, 1, cand)
+    a, b = eng.lookahead_values(), se.lookahead_values()
+    for key in a:
+        assert a[key].tobytes() == b[key].tobytes(), key
+    assert len(se.lookahead_views()) == 1 and np.array_equal(se.lookahead_views()[0]["cand"].cpu().numpy(), cand)
+    eng.close(); se.close()
