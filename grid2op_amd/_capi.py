@@ -22,6 +22,7 @@ N_REWARD_POINTERS = 1      # include/gridpf.h GPF_N_REWARD_POINTERS
 N_EPISODE_POINTERS = 8     # include/gridpf.h GPF_N_EPISODE_POINTERS
 N_N1_POINTERS = 4          # include/gridpf.h GPF_N_N1_POINTERS
 N_LOOKAHEAD_POINTERS = 6   # include/gridpf.h GPF_N_LOOKAHEAD_POINTERS
+N_LOOKAHEAD_CHAIN_POINTERS = 5   # include/gridpf.h GPF_N_LOOKAHEAD_CHAIN_POINTERS
 N_CURSOR_POINTERS = 3      # include/gridpf.h GPF_N_CURSOR_POINTERS
 N_COMBINED_POINTERS = 1    # include/gridpf.h GPF_N_COMBINED_POINTERS
 N_DEVICE_POINTERS = 34     # include/gridpf.h GPF_N_DEVICE_POINTERS
@@ -261,6 +262,10 @@ SIGNATURES = {
     "gpf_lookahead": _sig(h, i32, i32, _ip, C.POINTER(GpfStepOpts)),
     "gpf_get_lookahead": _sig(h, i32, i32, _fp, _bp, _ip, _fp, _ip),
     "gpf_lookahead_device_pointers": _sig(h, _vpp, i32),
+    "gpf_set_lookahead_chain": _sig(h, i32),
+    "gpf_lookahead_chain": _sig(h, i32, i32, _ip, i32, C.POINTER(GpfStepOpts)),
+    "gpf_get_lookahead_chain": _sig(h, i32, i32, _ip, _fp, _fp, _ip, _ip),
+    "gpf_lookahead_chain_device_pointers": _sig(h, _vpp, i32),
     "gpf_set_chronics_cursor": _sig(h, C.POINTER(GpfCursorDesc)),
     "gpf_upload_cursor_draws": _sig(h, i32, _dp),
     "gpf_get_cursor_state": _sig(h, i32, i32, _ip),

@@ -323,6 +323,12 @@ struct gpf_engine {
   LaunchPlan la_env_p{}, la_env_pb{}, la_sim_p{}, la_sim_pb{};
   DevArr<int> la_env_lists[3], la_sim_lists[3];
   HostPin<int> la_pin;                  // pinned read-back block: count | lane ids | rows
+  // the look-ahead chain (gpf_set_lookahead_chain): the sticky record of every scratch lane over up to lc_max steps and the fall-back slot
+  // of every environment.  lc_host_on: a header-only handle was given a valid chain
+  bool lc_on = false, lc_host_on = false;
+  int lc_max = 0;
+  DevArr<int> lc_survived, lc_fallback, lc_fallback_steps;
+  DevArr<float> lc_peak, lc_value_h;
   std::vector<char> h_lane_n1;          // 1: the lane is a contingency lane of gpf_fanout_n1 or of the screen (until gpf_set_lane_chronics)
   bool last_track_cooldown = false;     // whether the last gpf_step_n maintained the line cooldowns (and so wrote traj_cool)
   int last_t0 = 0, last_n_steps = 1;    // time index and step count of the last gpf_step_n (the chronics row each lane's last step read)

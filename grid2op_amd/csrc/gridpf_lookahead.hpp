@@ -12,6 +12,11 @@
 //   the kernels       la_play_kernel (one wavefront per scratch lane: the environment's topology-side state, maintenance ahead, steps 1-4
 //                     of gridpf_topo.hpp through topo_play_lane), la_reduce_kernel (one wavefront per scratch lane) and la_summary_kernel
 //                     (one wavefront per environment), for the one unit that defines GPF_LA_KERNEL (gridpf_capi_lookahead.hip)
+//   the chain         gpf_set_lookahead_chain / gpf_lookahead_chain: the candidate, then do-nothing steps on the consecutive forecast rows
+//                     la_chain_row of one observation (obs.get_forecast_env, Observation/baseObservation.py:4724-4842), the lines of
+//                     la_maintenance_ahead out before each; per scratch lane the sticky record la_chain_step keeps (steps survived, peak
+//                     over the survived steps, value = +inf from the failing step on) and per environment the fall-back slot
+//                     la_chain_outranks picks; la_chain_kernel between two steps, la_chain_summary_kernel at the end
 // A maximum of stored float32 values is exact in any order and the ranking is a total order, so the fixed butterfly of gridpf_n1.hpp
 // (share t of 64 takes elements t, t + 64, ...; partners 32, 16, 8, 4, 2, 1) gives the same bits in every run.  Without hipcc only the
 // rules exist: the header then needs no HIP header.
@@ -87,6 +92,49 @@ GPF_LA_HD inline bool la_maintenance_ahead(const unsigned char* M, int T, int n_
   if (s > tgt) return false;
   for (int r = s; r <= tgt; ++r) if (!M[(size_t)r * n_line + l]) return false;
   return true;
+}
+
+// ---- the chain: step 1 is the look-ahead's own step, steps 2 .. H are do-nothing steps on the forecast rows of the same observation ----
+// row of the forecast tables ([table][T][n_h][n_chron], n_h rows per observation) that step h >= 1 of the observation at row idx runs on
+GPF_LA_HD inline int la_chain_row(int n_h, int idx, int h) { return n_h * idx + (h - 1); }
+
+// The sticky record of one scratch lane: the step kernel overwrites the lane's done flag at every step, the chain keeps the first failure.
+// survived: steps completed before the first failure; peak: maximum of rho over the survived steps (-inf: none); value: maximum of the
+// per-step values so far, +inf once the lane has failed.
+struct LaChainState { int survived; float peak, value; };
+GPF_LA_HD inline LaChainState la_chain_start() { return LaChainState{0, -INFINITY, -INFINITY}; }
+// step h (1, 2, ... in order) left `done` and the row maximum rho_max: the step's value, +inf from the failing step on.  A lane that
+// failed earlier is solved and ignored: whatever the later steps leave, its record stands.
+GPF_LA_HD inline float la_chain_step(LaChainState& s, int h, bool done, float rho_max) {
+  const bool alive = s.survived == h - 1 && !done;
+  if (alive) { s.survived = h; s.peak = fmaxf(s.peak, rho_max); }
+  const float vh = alive ? rho_max : INFINITY;
+  s.value = fmaxf(s.value, vh);
+  return vh;
+}
+GPF_LA_HD inline bool la_chain_failed(const LaChainState& s, int h) { return s.survived < h; }
+// a fall-back is a slot whose action was played as asked: neither illegal nor ambiguous (it may well end the episode within the horizon)
+GPF_LA_HD inline bool la_chain_eligible(unsigned flags) { return (flags & (unsigned)(LA_ILLEGAL | LA_AMBIGUOUS)) == 0; }
+// candidate a outranks b as an environment's fall-back: more survived steps, then the lower peak, then the lower slot (a total order;
+// a slot index < 0: no such candidate)
+GPF_LA_HD inline bool la_chain_outranks(int sa, float pa, int ka, int sb, float pb, int kb) {
+  if (ka < 0) return false;
+  if (kb < 0) return true;
+  if (sa != sb) return sa > sb;
+  if (pa != pb) return pa < pb;
+  return ka < kb;
+}
+// what play = 0 / 1 / 2 leaves as the environment's table index: nothing / the best slot's, else -1 / the best's, else the fall-back's, else -1
+GPF_LA_HD inline int la_chain_pick(int play, int best, int fallback) { return best >= 0 ? best : (play == 2 ? fallback : -1); }
+
+// one environment's fall-back with plain loops (the host emulator; la_chain_summary_kernel runs the same rules with one wavefront)
+struct LaFallback { int slot, steps; };
+inline LaFallback la_fallback_serial(const int* survived, const float* peak, const unsigned char* flags, int K) {
+  int fs = 0, fk = -1;
+  float fp = INFINITY;
+  for (int k = 0; k < K; ++k)
+    if (la_chain_outranks(survived[k], peak[k], la_chain_eligible(flags[k]) ? k : -1, fs, fp, fk)) { fs = survived[k]; fp = peak[k]; fk = k; }
+  return LaFallback{fk, fk >= 0 ? fs : 0};
 }
 
 }  // namespace gpf
@@ -198,6 +246,100 @@ __global__ __launch_bounds__(64 * LA_WPB) void la_summary_kernel(LaDev d) {
   if (tid == 0) {
     d.best[env] = bk; d.best_value[env] = bv;
     d.info[(size_t)env * 2] = n_ok; d.info[(size_t)env * 2 + 1] = n_done;
+  }
+}
+
+// what the chain's kernels read and write beyond LaDev
+struct LaChainDev {
+  int* survived;                     // [n_env][K]
+  float* peak;                       // [n_env][K]
+  float* value_h;                    // [n_env][K][max_steps]
+  int* fallback;                     // [n_env]
+  int* fallback_steps;               // [n_env]
+  int* lane_offset;                  // [lanes] (LaDev::lane_offset, writable: the scratch lanes' rows move)
+  int* topo;                         // [lanes][dim_topo]
+  int* topo0;                        // [lanes][dim_topo]
+  const int* line_or_pos;            // [n_line]
+  const int* line_ex_pos;
+  int* act;                          // [lanes] the acting path's table indices (one slot per lane), written when play != 0
+  int dim_topo, n_line, n_h, max_steps;
+};
+
+// Queued behind step h of the chain, one wavefront per scratch lane: the sticky reduce of step h, then -- advance != 0 -- the lane's move
+// to step h + 1: its chronics cursor goes to the next forecast row of the same observation, and the lines whose maintenance covers that
+// row go out in its topology row and in the row an auto-reset would restore.  No action: the next step is a do-nothing step.
+__global__ __launch_bounds__(64 * LA_WPB) void la_chain_kernel(LaDev d, LaChainDev c, int h, int advance) {
+  const int tid = threadIdx.x & 63;
+  const int q = blockIdx.x * LA_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform: the rows are scalar addresses)
+  if (q >= d.n_env * d.K) return;
+  const int L = c.n_line;
+  const size_t lane = (size_t)d.n_env + q;
+  float a = la_strided_max(tid, L, d.rho + lane * L);
+#pragma unroll
+  for (int m = LA_SHARES / 2; m >= 1; m >>= 1) a = fmaxf(a, __shfl_xor(a, m));
+  const bool done = d.done[lane] != 0;
+  if (tid == 0) {
+    LaChainState s = h == 1 ? la_chain_start() : LaChainState{c.survived[q], c.peak[q], d.value[q]};
+    c.value_h[(size_t)q * c.max_steps + (h - 1)] = la_chain_step(s, h, done, a);
+    c.survived[q] = s.survived; c.peak[q] = s.peak; d.value[q] = s.value;
+    if (la_chain_failed(s, h)) d.flags[q] = (unsigned char)(d.flags[q] | LA_DONE);
+  }
+  if (!advance) return;
+  const size_t src = (size_t)(q / d.K);
+  int idx = (d.t_obs + d.lane_offset[src]) % d.T;
+  if (idx < 0) idx += d.T;
+  if (tid == 0) c.lane_offset[lane] = la_chain_row(c.n_h, idx, h + 1);
+  if (!d.maint) return;
+  const unsigned char* M = d.maint + (size_t)d.lane_table[src] * d.T * L;
+  int* t = c.topo + lane * c.dim_topo;
+  int* t0 = c.topo0 + lane * c.dim_topo;
+  for (int l = tid; l < L; l += LA_SHARES) {
+    if (!la_maintenance_ahead(M, d.T, L, idx, h + 1, l)) continue;
+    const int po = c.line_or_pos[l], pe = c.line_ex_pos[l];
+    t[po] = -1; t[pe] = -1;
+    t0[po] = -1; t0[pe] = -1;
+  }
+}
+
+// One wavefront per environment: la_summary_kernel's summary over the chain's value and flags, the fall-back slot, and -- play != 0 --
+// the chosen slot's table index into the acting path's action buffer of the environment's lane.
+__global__ __launch_bounds__(64 * LA_WPB) void la_chain_summary_kernel(LaDev d, LaChainDev c, int play) {
+  const int tid = threadIdx.x & 63;
+  const int env = blockIdx.x * LA_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (env >= d.n_env) return;
+  const float* row = d.value + (size_t)env * d.K;
+  const unsigned char* fl = d.flags + (size_t)env * d.K;
+  const int* sv = c.survived + (size_t)env * d.K;
+  const float* pk = c.peak + (size_t)env * d.K;
+  float bv = INFINITY, fp = INFINITY;
+  int bk = -1, n_ok = 0, n_done = 0, fk = -1, fs = 0;
+  for (int k = tid; k < d.K; k += LA_SHARES) {
+    const unsigned f = fl[k];
+    const bool ok = la_playable(f);
+    if (la_outranks(row[k], ok ? k : -1, bv, bk)) { bv = row[k]; bk = k; }
+    if (la_chain_outranks(sv[k], pk[k], la_chain_eligible(f) ? k : -1, fs, fp, fk)) { fs = sv[k]; fp = pk[k]; fk = k; }
+    n_ok += ok ? 1 : 0;
+    n_done += (f & LA_DONE) ? 1 : 0;
+  }
+#pragma unroll
+  for (int m = LA_SHARES / 2; m >= 1; m >>= 1) {
+    const float ov = __shfl_xor(bv, m);
+    const int ok = __shfl_xor(bk, m);
+    if (la_outranks(ov, ok, bv, bk)) { bv = ov; bk = ok; }
+    const int os = __shfl_xor(fs, m), ofk = __shfl_xor(fk, m);
+    const float op = __shfl_xor(fp, m);
+    if (la_chain_outranks(os, op, ofk, fs, fp, fk)) { fs = os; fp = op; fk = ofk; }
+    n_ok += __shfl_xor(n_ok, m);
+    n_done += __shfl_xor(n_done, m);
+  }
+  if (tid == 0) {
+    d.best[env] = bk; d.best_value[env] = bv;
+    d.info[(size_t)env * 2] = n_ok; d.info[(size_t)env * 2 + 1] = n_done;
+    c.fallback[env] = fk; c.fallback_steps[env] = fk >= 0 ? fs : 0;
+    if (play) {
+      const int slot = la_chain_pick(play, bk, fk);
+      c.act[env] = slot >= 0 ? d.cand[(size_t)env * d.K + slot] : -1;
+    }
   }
 }
 

@@ -385,6 +385,7 @@ class PowerFlowEngine:
         self._n_reward_slot = 0              # set_rewards
         self._n1 = None                      # set_n1_screen: (n_env, K)
         self._la = None                      # set_lookahead: (n_env, K)
+        self._lc = None                      # set_lookahead_chain: max_steps
         self._rw_view = None                 # rewards_eval's cache of reward_views()["rewards"]; dropped by set_rewards
         self._ep_on = self._cb_on = self._cur_on = False      # set_episode_limit / set_combined_actions / set_chronics_cursor
         self._obs_spec = None                # set_obs_spec
@@ -1408,6 +1409,7 @@ class PowerFlowEngine:
         environments (the only lanes `step` then steps), lane ``n_env + i * n_cand + k`` is the scratch lane of candidate ``k`` of
         environment ``i``.  ``n_env`` None: as many as fit, ``n_lanes // (1 + n_cand)``.  0 or None: off.  Needs an uploaded action
         table; refused with composite slots, areas or the N-1 screen on; while it is set multi-step launches are refused."""
+        self._lc = None                      # (the chain's buffers have the look-ahead's shape: the library releases them)
         if not n_cand:
             self._call("gpf_set_lookahead", 0, 0)
             self._la = None
@@ -1481,6 +1483,72 @@ class PowerFlowEngine:
         info = view(ptrs[5], (ne, 2), "<i4")
         return {"cand": view(ptrs[0], (ne, K), "<i4"), "value": view(ptrs[1], (ne, K), "<f4"), "flags": view(ptrs[2], (ne, K), "|u1"),
                 "best": view(ptrs[3], (ne,), "<i4"), "best_value": view(ptrs[4], (ne,), "<f4"), "n_playable": info[:, 0], "n_done": info[:, 1]}
+
+    # ---- the look-ahead chain (include/gridpf.h gpf_set_lookahead_chain; grid2op_amd/csrc/gridpf_lookahead.hpp) ----
+    def set_lookahead_chain(self, max_steps: int):
+        """Chains of up to ``max_steps`` forecast steps on the scratch lanes of `set_lookahead` (`lookahead_chain`).  0 or None: off;
+        `set_lookahead` switches it off as well."""
+        self._lc = None
+        if not max_steps:
+            self._call("gpf_set_lookahead_chain", 0)
+            return
+        try:
+            self._call("gpf_set_lookahead_chain", int(max_steps))
+        except GridPFError as exc:
+            if "header-only handle" in str(exc):     # (the library keeps a valid setting there, so that every later refusal can be shown)
+                self._lc = int(max_steps)
+            raise
+        self._lc = int(max_steps)
+
+    def _lc_range(self, what, lane0, n):
+        if getattr(self, "_lc", None) is None or getattr(self, "_la", None) is None:
+            raise GridPFError(f"{what}: the chain is off (set_lookahead_chain)")
+        return self._la_range(what, lane0, n) + (self._lc,)
+
+    def lookahead_chain(self, t_obs: int, n_steps: int, candidates=None, play: int = 0, max_iter: int = 10, tol_mva: float = 1e-8,
+                        rebalance: float = 0.0, cascade: bool = False, hard_overflow: float = 2.0, soft_overflow: float = 1.0,
+                        nb_ts_allowed: int = 2, max_rounds: int = 16, is_dc: bool = False):
+        """``obs.get_forecast_env()`` for every candidate of every environment in one call: `lookahead` ``(t_obs, 1)``, then do-nothing
+        steps on forecast horizons 2 .. ``n_steps`` of the same observation, the lines of a maintenance that begins on the way taken out,
+        overflow counters and protections running (asynchronous).  ``value`` / ``flags`` / ``best`` of `lookahead_values` then speak of
+        the chain (``value``: the maximum of ``rho.max()`` over the steps, +inf and `LA_DONE` when any step ended the episode);
+        `lookahead_chain_values` / `lookahead_chain_views` hold ``survived``, ``peak``, ``value_h``, ``fallback``.  ``play``: 1 writes the
+        table index of the best slot (-1 without one) into ``device_views()["act_topo"]`` of the environment's lane and arms it as
+        `topo_actions_on_device` does, 2 falls back on ``fallback`` before -1; 0 leaves the acting path alone."""
+        cand = None
+        if candidates is not None:
+            if getattr(self, "_la", None) is None:
+                raise GridPFError("lookahead_chain: the look-ahead is off (set_lookahead)")
+            cand = np.ascontiguousarray(candidates, dtype=np.int32)
+            if cand.shape != self._la:
+                raise ValueError(f"lookahead_chain: candidates must be [n_env, K] = {list(self._la)}, got {list(cand.shape)}")
+        o = GpfStepOpts(int(max_iter), float(tol_mva), float(rebalance), int(bool(cascade)), float(hard_overflow), float(soft_overflow),
+                        int(nb_ts_allowed), int(max_rounds), int(bool(is_dc)), 0, 0, 0, 0)
+        self._call("gpf_lookahead_chain", int(t_obs), int(n_steps), _ptr(cand), int(play), C.byref(o))
+
+    def lookahead_chain_values(self, lane0: int = 0, n: Optional[int] = None) -> dict:
+        """``survived`` int32 / ``peak`` float32 ``[n_env', K]``, ``value_h`` float32 ``[n_env', K, max_steps]`` (columns below the last
+        call's ``n_steps``), ``fallback`` / ``fallback_steps`` int32 ``[n_env']`` of the last `lookahead_chain`, for the environment lanes
+        inside lanes ``[lane0, lane0 + n)``; synchronous."""
+        a, m, K, H = self._lc_range("lookahead_chain_values", lane0, n)
+        survived, peak, value_h = np.zeros((m, K), np.int32), np.zeros((m, K), np.float32), np.zeros((m, K, H), np.float32)
+        fb, fbs = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        self._call("gpf_get_lookahead_chain", a, m, _ptr(survived), _ptr(peak), _ptr(value_h), _ptr(fb), _ptr(fbs))
+        return dict(survived=survived, peak=peak, value_h=value_h, fallback=fb, fallback_steps=fbs)
+
+    def lookahead_chain_views(self) -> dict:
+        """Zero-copy torch tensors ALIASING the chain's buffers (order the reader on ``device_views()["stream"]``): ``survived`` int32 /
+        ``peak`` float32 ``[n_env, K]``, ``value_h`` float32 ``[n_env, K, max_steps]``, ``fallback`` / ``fallback_steps`` int32 ``[n_env]``."""
+        import torch
+        _, _, K, H = self._lc_range("lookahead_chain_views", 0, None)
+        ptrs = self._device_pointers("gpf_lookahead_chain_device_pointers", _capi.N_LOOKAHEAD_CHAIN_POINTERS)
+
+        def view(p, shape, typestr):
+            iface = {"shape": shape, "typestr": typestr, "data": (int(p), False), "version": 2, "strides": None}
+            return torch.as_tensor(type("_Arr", (), {"__cuda_array_interface__": iface})(), device=torch.device("cuda", self.device))
+        ne = self._la[0]
+        return {"survived": view(ptrs[0], (ne, K), "<i4"), "peak": view(ptrs[1], (ne, K), "<f4"), "value_h": view(ptrs[2], (ne, K, H), "<f4"),
+                "fallback": view(ptrs[3], (ne,), "<i4"), "fallback_steps": view(ptrs[4], (ne,), "<i4")}
 
     # ---- combined topology + injection actions (include/gridpf.h gpf_set_combined_actions; grid2op_amd/csrc/gridpf_combined.hpp) ----
     def set_combined_actions(self, on: bool = True, check_values: bool = True, storage_max_p_prod=None, storage_max_p_absorb=None):

@@ -441,11 +441,13 @@ ROUTES = {
         "set_gen_limits", "set_gen_renewable", "set_storage_params", "set_env_dynamics", "set_trajectory", "set_obs_clock", "set_obs_spec",
         "lane_actions_on_device", "topo_actions_on_device", "alerts_on_device",        # each device's act_* buffers hold its own lanes
         "set_topo_rules", "set_topo_areas", "set_topo_slots", "set_opponent_areas", "set_alerts", "set_rewards", "set_combined_actions",
-        "set_graph_obs", "set_n1_screen", "set_lookahead", "lookahead"), {}),    # (the look-ahead: one device block each)
+        "set_graph_obs", "set_n1_screen", "set_lookahead", "lookahead",         # (the look-ahead: one device block each)
+        "set_lookahead_chain", "lookahead_chain"), {}),
     # host-side helpers that depend on the grid alone
     first: dict.fromkeys(("pack_injections", "pack_chronics", "topo_action_areas", "alert_state_fields", "graph_layout"), {}),
     # one entry per device; the views are zero-copy torch tensors (global lane order = concatenation over the list)
-    per_device: dict.fromkeys(("device_views", "reward_views", "episode_views", "cursor_views", "combined_views", "plan", "n1_views", "lookahead_views"), {}),
+    per_device: dict.fromkeys(("device_views", "reward_views", "episode_views", "cursor_views", "combined_views", "plan", "n1_views", "lookahead_views",
+                                "lookahead_chain_views"), {}),
     # whole-batch per-lane arrays, cut by device block
     cut: {**dict.fromkeys(("set_lane_chronics", "set_lane_redispatch", "set_lane_actions", "set_lane_curtailment", "set_lane_topo_actions",
                            "set_lane_alerts"), {}),
@@ -457,7 +459,7 @@ ROUTES = {
         "reset", "get_injections", "get_topology", "step_outputs", "episode", "cooldown", "sub_cooldown", "last_bus", "env_state",
         "observation_vector_host", "topo_action_flags", "topo_action_mask_host", "opponent_state", "opponent_area_state",
         "opponent_attack_lines", "alert_state", "alert_reward", "rewards", "episode_ends", "episode_stats", "chronics_cursor_state", "action_flags",
-        "graph_observation_host", "n1_values", "n1_summary", "lookahead_values"), {}),
+        "graph_observation_host", "n1_values", "n1_summary", "lookahead_values", "lookahead_chain_values"), {}),
         "trajectory": dict(steps=True, axis=1), "trajectory_cooldown": dict(steps=True, axis=1), "trajectory_obs": dict(steps=True)},
     # getters that leave their result on the devices: one tensor per shard, each on its own device and stream
     per_shard_tensor: {"observation_vector": dict(keys=("out",)), "topo_action_mask": dict(keys=("out",)),

@@ -906,9 +906,10 @@ int gpf_n1_device_pointers(gpf_handle h, void** out, int32_t n);
  *                       best int32 [n_env], out[4] best_value float32 [n_env], out[5] info int32 [n_env][2].  n must be
  *                       GPF_N_LOOKAHEAD_POINTERS.
  *   The getters fail with "the look-ahead is off" while it is off.
- * OUT OF SCOPE: composite slots and rules by area, injection candidates (redispatch, storage, curtailment), chained horizons (a scratch
- * lane as an environment), the opponent inside the look-ahead, simulated rewards as a pinned feature (gpf_rewards_eval on the scratch
- * range works as after gpf_simulate_batch), playing the choice inside the call, the look-ahead inside multi-step launches. */
+ * OUT OF SCOPE: composite slots and rules by area, injection candidates (redispatch, storage, curtailment), a scratch lane as an
+ * environment (chained horizons and playing the choice inside the call: the look-ahead chain below), the opponent inside the look-ahead,
+ * simulated rewards as a pinned feature (gpf_rewards_eval on the scratch range works as after gpf_simulate_batch), the look-ahead inside
+ * multi-step launches. */
 #define GPF_N_LOOKAHEAD_POINTERS 6
 #define GPF_LA_ILLEGAL 1
 #define GPF_LA_AMBIGUOUS 2
@@ -917,6 +918,50 @@ int gpf_set_lookahead(gpf_handle h, int32_t n_env, int32_t n_cand);
 int gpf_lookahead(gpf_handle h, int32_t t_obs, int32_t time_step, const int32_t* cand, const gpf_step_opts* opts);
 int gpf_get_lookahead(gpf_handle h, int32_t env0, int32_t n, float* value, uint8_t* flags, int32_t* best, float* best_value, int32_t* info);
 int gpf_lookahead_device_pointers(gpf_handle h, void** out, int32_t n);
+
+/* ---- the look-ahead chain: candidates held over several forecast steps (grid2op_amd/csrc/gridpf_lookahead.hpp) ----
+ * What agents do with obs.get_forecast_env() (Observation/baseObservation.py:4724-4842) or chained sim_obs.simulate: play the candidate,
+ * do nothing for the rest of the forecast horizon, keep the action only if the grid survives -- a line above its limit that the
+ * protections trip nb_ts_allowed steps later, the cascade behind the trip and a maintenance that begins two steps ahead are invisible
+ * to a one-step look-ahead.  A chain of n_steps = H on the scratch lanes of gpf_set_lookahead, scratch lane q = (environment i, slot k):
+ *   - step 1 is exactly gpf_lookahead(t_obs, 1): the lane becomes its environment (protection counters included), the candidate is played
+ *     under the environment's rules, the lane is stepped once on forecast row n_h idx (idx: the observation's row);
+ *   - steps h = 2 .. H: the lane's chronics cursor moves to forecast row n_h idx + (h - 1), every line whose scheduled maintenance covers
+ *     row idx + h (the rule of the look-ahead, from the table it keeps) goes out in the lane's topology row and in the row an auto-reset
+ *     would restore, no action is played, and the scratch range is stepped once more on the cached plan.  The step kernel counts the
+ *     overflows and trips lines on its own; with gpf_set_env_dynamics on every step is one more do-nothing step of the dynamics.  There
+ *     is no read-back and no re-planning between steps: a line outage never changes a lane's planning class;
+ *   - per step, sticky (the step kernel overwrites `done` at every step): survived[q] = the steps completed before the first failure (H:
+ *     none failed, 0: step 1 failed); later steps of a failed lane are solved and ignored; value_h[q][h - 1] = the maximum of the lane's
+ *     float32 rho row after step h, +inf from the failing step on;
+ *   - value[q] = the maximum of value_h over the horizon (+inf if the lane failed anywhere), GPF_LA_DONE = it failed anywhere; value,
+ *     flags, best, best_value and info keep the meaning of gpf_lookahead with "the step" read as "the chain" (the look-ahead's own
+ *     buffers: gpf_get_lookahead); peak[q] = the maximum over the survived steps only, -inf when survived is 0;
+ *   - fallback[i] = among the slots that are neither illegal nor ambiguous the one with the most survived steps, then the lowest peak,
+ *     then the lowest k (-1: none), fallback_steps[i] its survived steps: what an agent plays when every candidate fails in the horizon;
+ *   - play = 1 writes the table index of slot best[i] (-1 without one) into the acting path's action buffer of lane i (act_topo), play =
+ *     2 that of best[i], else of fallback[i], else -1, and marks the buffer as written on the device (gpf_topo_actions_on_device(1)): the
+ *     next gpf_step_n plays the choice.  play = 0 leaves the buffer and the pending actions alone.
+ * n_steps = 1 is gpf_lookahead(t_obs, 1) bit for bit.  The environment lanes are only read (play writes their action index alone).
+ *   gpf_set_lookahead_chain : max_steps = 0 releases it, and so does gpf_set_lookahead(.., 0) or a new gpf_set_lookahead.  Refused before
+ *                       the device is touched: negative max_steps, the look-ahead off.
+ *   gpf_lookahead_chain : cand as gpf_lookahead.  Refused before the device is touched: the look-ahead off, the chain off, n_steps < 1,
+ *                       n_steps > max_steps, n_steps > the uploaded forecast horizons (gpf_lookahead's refusal of that horizon), play
+ *                       outside 0 .. 2, play without one action slot per lane, and everything gpf_lookahead refuses.
+ *   gpf_get_lookahead_chain : environments [env0, env0 + n) of the last call: survived int32 [n][K], peak float32 [n][K], value_h float32
+ *                       [n][K][max_steps] (columns < n_steps of the last call), fallback / fallback_steps int32 [n]; any may be NULL.
+ *   gpf_lookahead_chain_device_pointers : out[0] survived, out[1] peak, out[2] value_h, out[3] fallback, out[4] fallback_steps.  n must be
+ *                       GPF_N_LOOKAHEAD_CHAIN_POINTERS.
+ *   The getters fail with "the chain is off" while it is off.
+ * OUT OF SCOPE: candidates after step 1; cooldown counting on the scratch lanes (do-nothing steps need none: the observation's
+ * cooldowns stand); hazards and the opponent inside the chain; the chain as ONE multi-step launch over the consecutive forecast rows
+ * (bit-identical by the guarantee of multi-step launches, and the next speed-up); composite slots and areas. */
+#define GPF_N_LOOKAHEAD_CHAIN_POINTERS 5
+int gpf_set_lookahead_chain(gpf_handle h, int32_t max_steps);
+int gpf_lookahead_chain(gpf_handle h, int32_t t_obs, int32_t n_steps, const int32_t* cand, int32_t play, const gpf_step_opts* opts);
+int gpf_get_lookahead_chain(gpf_handle h, int32_t env0, int32_t n, int32_t* survived, float* peak, float* value_h, int32_t* fallback,
+                            int32_t* fallback_steps);
+int gpf_lookahead_chain_device_pointers(gpf_handle h, void** out, int32_t n);
 
 /* ---- combined topology + injection actions of the batched acting path (grid2op_amd/csrc/gridpf_combined.hpp): one action with a
  * topology part (the table indices above) and an injection part (redispatch / storage / curtailment rows), lane by lane, in a one-step
