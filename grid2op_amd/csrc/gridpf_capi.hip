@@ -323,9 +323,8 @@ int plan_launch_uncached(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchP
 int plan_launch(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb) {
   const bool whole = (lane0 == 0 && n == e->n_lanes);
   if (whole && e->plan_valid) { p = e->plan_cached; pb = e->plan_b_cached; return GPF_OK; }
-  // the batch's plan is made anew: whatever invalidated it invalidated the N-1 screen's plans too, and plan_valid is about to say
-  // "nothing changed" again (n1_plans makes its two, calls this last and only then marks them valid)
-  if (whole) e->n1_plan_valid = e->la_plan_valid = false;    // (the look-ahead's two plans are cached the same way: la_plans)
+  // whatever invalidated the batch's plan invalidated the fan's two (fan_plans makes them, calls this last and only then marks them valid)
+  if (whole) e->fan.plans_valid = false;
   int rc = plan_launch_uncached(e, lane0, n, p, pb);
   if (!whole && (p.n_list || pb.n_list)) e->plan_valid = false;     // the device lane lists were overwritten
   if (rc == GPF_OK && whole) { e->plan_cached = p; e->plan_b_cached = pb; e->plan_valid = true; }
@@ -616,6 +615,27 @@ int plan_launch_own(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& 
   const int rc = plan_launch_uncached(e, lane0, n, p, pb, list_tail);
   swap_all();
   return rc;
+}
+
+int fan_plans(gpf_engine* e) {
+  LaneFan& f = e->fan;
+  if (e->plan_valid && f.plans_valid) return GPF_OK;
+  f.plans_valid = false;
+  ++f.plans_gen;
+  // (the environment lanes run on the instance groups of a launch without the fan, whatever n_env is: their bits are that launch's)
+  int rc = plan_launch_own(e, 0, f.n_env, f.env.p, f.env.pb, f.env.lists, true);
+  if (rc == GPF_OK) rc = plan_launch_own(e, f.n_env, f.n_sec(), f.sec.p, f.sec.pb, f.sec.lists);
+  // the batch's own plan, last: from here on plan_valid says "nothing that plans depend on has changed", for these two as well
+  int32_t whole[8];
+  if (rc == GPF_OK) rc = gpf_get_plan(e, whole);
+  f.plans_valid = rc == GPF_OK;
+  return rc;
+}
+
+int fan_mark_lanes(gpf_engine* e, std::vector<char>& flags, int mark) {
+  std::fill_n(flags.begin() + e->fan.n_env, e->fan.n_sec(), (char)mark);
+  if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, e->fan.n_env, e->fan.n_sec(), mark));     // secondary lanes start no scenario of their own
+  return GPF_OK;
 }
 
 gpf_engine::~gpf_engine() {
@@ -1065,6 +1085,53 @@ bool note_lane_row(gpf_engine* e, int lane, const int* t, const int* sb) {
   return true;
 }
 
+void lane_inherit(gpf_engine* e, int dst, int src, bool copy_mirror) {
+  const gpf::GridDev& g = e->g;
+  e->lane_nb[dst] = e->lane_nb[src]; e->lane_nj[dst] = e->lane_nj[src]; e->lane_mb[dst] = e->lane_mb[src]; e->lane_class[dst] = e->lane_class[src];
+  if (!copy_mirror) { e->h_lane_topo[(size_t)dst * g.dim_topo] = INT_MIN; return; }
+  std::copy_n(e->h_lane_topo.begin() + (size_t)src * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)dst * g.dim_topo);
+  if (g.n_shunt) std::copy_n(e->h_lane_sb.begin() + (size_t)src * g.n_shunt, g.n_shunt, e->h_lane_sb.begin() + (size_t)dst * g.n_shunt);
+}
+
+int moved_list_readback(gpf_engine* e, MovedList& ml, int lane_lo, int lane_hi, const char* who, const std::function<void(int)>& per_lane) {
+  const gpf::GridDev& g = e->g;
+  const size_t w = (size_t)g.dim_topo + g.n_shunt, cap = (size_t)(lane_hi - lane_lo), need = 1 + cap + cap * w;
+  if (ml.pin.n < need) { HIP_TRY(hipStreamSynchronize(e->stream)); HIP_TRY(ml.pin.reserve(need)); }
+  int* const block = ml.pin.p;
+  HIP_TRY(hipMemcpyAsync(block, ml.list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const int cnt = block[0];
+  if (cnt <= 0) return GPF_OK;
+  if (!moved_list_count_ok(cnt, lane_lo, lane_hi)) return fail(GPF_E_DEVICE, std::string(who) + " count)");
+  HIP_TRY(hipMemcpyAsync(block + 1, ml.list.p + 1, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(block + 1 + cap, ml.rows.p, (size_t)cnt * w * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  bool changed = false;
+  const int bad = moved_list_visit(block, w, lane_lo, lane_hi, [&](int lane, const int* t) {
+    changed |= note_lane_row(e, lane, t, g.n_shunt ? t + g.dim_topo : nullptr);
+    if (per_lane) per_lane(lane);
+  });
+  if (bad) return fail(GPF_E_DEVICE, std::string(who) + " lane)");
+  if (changed) e->plan_valid = false;
+  return GPF_OK;
+}
+
+int check_action_items(gpf_engine* e, const char* who, int n_items, const int32_t* items, bool* bus_items) {
+  const gpf::GridDev& g = e->g;
+  bool bus = false;
+  for (int q = 0; q < n_items; ++q) {
+    const int kind = items[3 * q], id = items[3 * q + 1], v = items[3 * q + 2];
+    const bool pos_kind = kind == GPF_ACT_SET_BUS || kind == GPF_ACT_CHANGE_BUS, line_kind = kind == GPF_ACT_SET_LINE_STATUS || kind == GPF_ACT_CHANGE_LINE_STATUS;
+    if (!(pos_kind || line_kind || kind == GPF_ACT_SET_SHUNT_BUS) || id < 0 || (pos_kind && id >= g.dim_topo) || (line_kind && id >= g.n_line) ||
+        (kind == GPF_ACT_SET_SHUNT_BUS && id >= g.n_shunt) || ((kind == GPF_ACT_SET_BUS || kind == GPF_ACT_SET_SHUNT_BUS) && (v < -1 || v > g.n_busbar)) ||
+        (kind == GPF_ACT_CHANGE_BUS && g.n_busbar != 2))
+      return fail(GPF_E_INVALID, std::string(who) + ": bad action item (kind, id or bus; change_bus needs exactly 2 busbars per substation)");
+    bus |= kind == GPF_ACT_CHANGE_BUS || kind == GPF_ACT_SET_SHUNT_BUS || (kind == GPF_ACT_SET_BUS && v != 0);
+  }
+  if (bus_items) *bus_items = bus;
+  return GPF_OK;
+}
+
 namespace {
 // gpf_set_topology.  `engine_rows`: the rows were built by the library itself in its own PINNED block (gpf_simulate_batch: validated
 // action items applied to rows that came from the device) -- no validation pass, the uploads are true asynchronous DMA and nothing is
@@ -1171,9 +1238,7 @@ int gpf_copy_lanes(gpf_handle e, int32_t src, int32_t dst, int32_t n) {
   if (e->cur_on && err == hipSuccess) err = cursor_copy_lanes(e, src, dst, n);
   if (e->cb_on && err == hipSuccess) err = combined_copy_lanes(e, src, dst, n);
   HIP_TRY(err);
-  for (int k = 0; k < n; ++k) { e->lane_nb[dst + k] = e->lane_nb[src + k]; e->lane_nj[dst + k] = e->lane_nj[src + k]; e->lane_mb[dst + k] = e->lane_mb[src + k]; e->lane_class[dst + k] = e->lane_class[src + k];
-    std::copy_n(e->h_lane_topo.begin() + (size_t)(src + k) * g.dim_topo, g.dim_topo, e->h_lane_topo.begin() + (size_t)(dst + k) * g.dim_topo);
-    if (g.n_shunt) std::copy_n(e->h_lane_sb.begin() + (size_t)(src + k) * g.n_shunt, g.n_shunt, e->h_lane_sb.begin() + (size_t)(dst + k) * g.n_shunt); }
+  for (int k = 0; k < n; ++k) lane_inherit(e, dst + k, src + k, true);
   e->plan_valid = false;
   return GPF_OK;
 }
@@ -1196,8 +1261,7 @@ int gpf_fanout_n1(gpf_handle e, int32_t src, int32_t dst0, int32_t n_out, const 
   if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, dst0, n_out, 1));     // contingency lanes start no scenario of their own
   std::fill_n(e->h_lane_n1.begin() + dst0, n_out, 1);
   HIP_TRY(hipStreamSynchronize(e->stream));   // out_lines may be reused by the caller
-  for (int k = 0; k < n_out; ++k) { e->lane_nb[dst0 + k] = e->lane_nb[src]; e->lane_nj[dst0 + k] = e->lane_nj[src]; e->lane_mb[dst0 + k] = e->lane_mb[src]; e->lane_class[dst0 + k] = e->lane_class[src];
-    e->h_lane_topo[(size_t)(dst0 + k) * e->g.dim_topo] = INT_MIN; }     // a line was forced off on the device: mirror unknown
+  for (int k = 0; k < n_out; ++k) lane_inherit(e, dst0 + k, src, false);     // a line was forced off on the device: mirror unknown
   topo_unmoved(e, dst0, n_out);                 // (fanout_kernel writes the contingency row as the lanes' reset topology too)
   e->plan_valid = false;
   return GPF_OK;
@@ -1494,8 +1558,8 @@ int gpf_set_lane_chronics(gpf_handle e, const int32_t* lane_table, const int32_t
     std::fill(e->h_lane_forecast.begin(), e->h_lane_forecast.end(), 0);       // every lane is back on the chronics tables
     std::fill(e->h_lane_n1.begin(), e->h_lane_n1.end(), 0);
     if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, 0, e->cap_lanes, 0));
-    if (e->n1_on) { int rc_n = n1_mark_lanes(e); if (rc_n != GPF_OK) return rc_n; }   // (the screen's contingency lanes stay what they are)
-    if (e->la_on) { int rc_l = la_mark_lanes(e); if (rc_l != GPF_OK) return rc_l; }   // (... and the look-ahead's scratch lanes)
+    if (e->fan.on(FanOwner::n1_screen)) { int rc_n = fan_mark_lanes(e, e->h_lane_n1, 1); if (rc_n != GPF_OK) return rc_n; }   // (the screen's contingency lanes stay what they are)
+    if (e->fan.on(FanOwner::lookahead)) { int rc_l = la_mark_lanes(e); if (rc_l != GPF_OK) return rc_l; }   // (... and the look-ahead's scratch lanes)
   }
   if (lane_scale) {
     if (!e->lane_scale.p) {
@@ -1676,10 +1740,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
   if ((e->cur_on || e->cur_host_on) && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with the chronics cursor on (gpf_set_chronics_cursor) a launch must be a one-step launch (a lane "
                                "that restarts inside a launch would start a scenario there): use n_steps = 1");
-  if ((e->n1_on || e->n1_host_on) && n_steps != 1)
+  if (e->fan.owned_by(FanOwner::n1_screen) && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with the N-1 screen on (gpf_set_n1_screen) a launch must be a one-step launch (the contingencies "
                                "are those of the state one step leaves): use n_steps = 1");
-  if ((e->la_on || e->la_host_on) && n_steps != 1)
+  if (e->fan.owned_by(FanOwner::lookahead) && n_steps != 1)
     return fail(GPF_E_INVALID, "gpf_step_n: with the look-ahead set (gpf_set_lookahead) a launch must be a one-step launch (the scratch lanes "
                                "behind the environments are not stepped): use n_steps = 1");
   if (!e->chron.p || e->chron_T <= 0) return fail(GPF_E_INVALID, "gpf_step_n: no chronics uploaded");
@@ -1716,6 +1780,7 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
                                "only counted down by a launch that maintains the line cooldowns)");
   HIP_TRY(hipSetDevice(e->device));
   int rc = GPF_OK;
+  const bool n1 = e->fan.on(FanOwner::n1_screen);
   if (e->cur_on) {                          // first: every kernel behind it reads the scenario of a lane that starts an episode
     rc = cursor_prestep(e, t0);
     if (rc != GPF_OK) return rc;
@@ -1745,14 +1810,10 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     rc = reward_prestep(e);
     if (rc != GPF_OK) return rc;
   }
-  if (e->n1_on) {                           // the N-1 screen: only the environment lanes are stepped, on a cached plan of their range
-    rc = n1_plans(e);
+  if (e->fan.on()) {                        // only the environment lanes are stepped, on the fan's cached plan (the secondary lanes are their owner's)
+    rc = n1 ? n1_plans(e) : fan_plans(e);
     if (rc != GPF_OK) return rc;
-    rc = step_range(e, e->bufs(), 0, e->n1_n_env, t0, e->chron_T, n_steps, o, "gpf_step_n", true, &e->n1_env_p, &e->n1_env_pb);
-  } else if (e->la_on) {                    // the look-ahead: likewise (its scratch lanes are stepped by gpf_lookahead alone)
-    rc = la_plans(e);
-    if (rc != GPF_OK) return rc;
-    rc = step_range(e, e->bufs(), 0, e->la_n_env, t0, e->chron_T, n_steps, o, "gpf_step_n", true, &e->la_env_p, &e->la_env_pb);
+    rc = step_range(e, e->bufs(), 0, e->fan.n_env, t0, e->chron_T, n_steps, o, "gpf_step_n", true, &e->fan.env.p, &e->fan.env.pb);
   } else {
     rc = step_range(e, e->bufs(), 0, e->n_lanes, t0, e->chron_T, n_steps, o, "gpf_step_n", true);
   }
@@ -1769,9 +1830,9 @@ int gpf_step_n(gpf_handle e, int32_t t0, int32_t n_steps, const gpf_step_opts* o
     if (rc != GPF_OK) return rc;
     // (the screen plans its contingency lanes on the classes of the rows the step left: the lanes that auto-reset are re-keyed in front
     //  of it; behind episode_kernel the list is read again, with the truncated lanes -- a lane noted twice has not changed the second time)
-    if (list_resets && (!e->ep_on || e->n1_on)) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
+    if (list_resets && (!e->ep_on || n1)) { rc = topo_readback(e, false); if (rc != GPF_OK) return rc; }
   }
-  if (e->n1_on) {                           // N1Reward's copies: behind the step and what the topology post-step leaves, in front of the
+  if (n1) {                                 // N1Reward's copies: behind the step and what the topology post-step leaves, in front of the
     rc = n1_screen(e, o->max_iter, o->tol_mva);   // rewards (GPF_RW_N1 reads the table) and of episode_kernel (it resets truncated lanes)
     if (rc != GPF_OK) return rc;
   }
@@ -1834,14 +1895,7 @@ int gpf_simulate_batch(gpf_handle e, int32_t t_obs, int32_t time_step, int32_t n
   const int n_items_total = act_off[n_act];
   if (act_off[0] != 0 || (n_items_total > 0 && !act_items)) return fail(GPF_E_INVALID, "gpf_simulate_batch: bad action offsets");
   for (int k = 0; k < n_act; ++k) if (act_off[k + 1] < act_off[k]) return fail(GPF_E_INVALID, "gpf_simulate_batch: bad action offsets");
-  for (int q = 0; q < n_items_total; ++q) {
-    const int kind = act_items[3 * q], id = act_items[3 * q + 1], v = act_items[3 * q + 2];
-    const bool pos_kind = kind == GPF_ACT_SET_BUS || kind == GPF_ACT_CHANGE_BUS, line_kind = kind == GPF_ACT_SET_LINE_STATUS || kind == GPF_ACT_CHANGE_LINE_STATUS;
-    if (!(pos_kind || line_kind || kind == GPF_ACT_SET_SHUNT_BUS) || id < 0 || (pos_kind && id >= g.dim_topo) || (line_kind && id >= g.n_line) ||
-        (kind == GPF_ACT_SET_SHUNT_BUS && id >= g.n_shunt) || ((kind == GPF_ACT_SET_BUS || kind == GPF_ACT_SET_SHUNT_BUS) && (v < -1 || v > g.n_busbar)) ||
-        (kind == GPF_ACT_CHANGE_BUS && g.n_busbar != 2))
-      return fail(GPF_E_INVALID, "gpf_simulate_batch: bad action item (kind, id or bus; change_bus needs exactly 2 busbars per substation)");
-  }
+  if (int rc_i = check_action_items(e, "gpf_simulate_batch", n_items_total, act_items, nullptr)) return rc_i;
   HIP_TRY(hipSetDevice(e->device));
   static const bool sim_timing = getenv("GRIDPF_SIM_TIMING") != nullptr;        // developer: stage times of the call on stderr
   auto now_us = [] { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e-3; };

@@ -58,7 +58,7 @@ int episode_poststep(gpf_engine* e, bool auto_reset, bool track_cooldown, bool l
     d.env_already = e->env_already.p; d.env_fresh = e->env_fresh.p; d.env_illegal = e->env_illegal.p;
   }
   if (e->ta_on) { d.sub_cd = e->ta_sub_cd.p; d.last_bus = e->ta_last_bus.p; }
-  if (list_resets) { d.list = e->ta_list.p; d.list_rows = e->ta_list_rows.p; d.shunt_bus = e->shunt_bus.p; }
+  if (list_resets) { d.list = e->ta_moved_list.list.p; d.list_rows = e->ta_moved_list.rows.p; d.shunt_bus = e->shunt_bus.p; }
   const unsigned blocks = (unsigned)((e->n_lanes + gpf::EP_WPB - 1) / gpf::EP_WPB);
   hipLaunchKernelGGL(gpf::episode_kernel, dim3(blocks), dim3(64 * gpf::EP_WPB), 0, e->stream, d, e->n_lanes);
   HIP_TRY(hipGetLastError());

@@ -3,7 +3,7 @@
 // gpf_lookahead_chain_device_pointers) and the host side of the kernels of gridpf_lookahead.hpp, on the engine of
 // gridpf_engine.hpp.  Everything a call can get wrong is refused here, before the device is touched.  A call in which no scratch lane
 // changed its topology class does no host work that grows with n_env x K: the candidates are played on the device, the plans of the
-// two lane ranges are cached (la_plans) and the play kernel's list of moved lanes is read back count first.
+// two lane ranges are cached (fan_plans) and the play kernel's list of moved lanes is read back count first.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -18,6 +18,7 @@ static_assert(gpf::LA_ILLEGAL == GPF_LA_ILLEGAL && gpf::LA_AMBIGUOUS == GPF_LA_A
 
 namespace {
 constexpr size_t LA_LDS_LIMIT = 64 * 1024;        // LDS of one workgroup
+constexpr FanOwner LA = FanOwner::lookahead;
 
 void la_chain_release(gpf_engine* e) {
   e->lc_on = e->lc_host_on = false;
@@ -27,30 +28,19 @@ void la_chain_release(gpf_engine* e) {
 
 void la_release(gpf_engine* e) {
   la_chain_release(e);                      // (its buffers have the look-ahead's shape)
-  e->la_on = e->la_host_on = e->la_plan_valid = false;
-  e->la_noted_stale = true;
-  e->la_n_env = e->la_K = 0;
-  e->la_maint_gen = -1;
-  e->la_cand.release(); e->la_best.release(); e->la_info.release(); e->la_list.release(); e->la_list_rows.release(); e->la_noted.release();
+  e->la_noted_gen = e->la_maint_gen = -1;
+  e->la_cand.release(); e->la_best.release(); e->la_info.release(); e->la_moved_list.release(); e->la_noted.release();
   e->la_src.release(); e->la_value.release(); e->la_best_value.release(); e->la_flags.release(); e->la_maint.release();
-  for (int i = 0; i < 3; ++i) { e->la_env_lists[i].release(); e->la_sim_lists[i].release(); }
-}
-
-// the scratch lanes are ordinary lanes again
-int la_unmark_lanes(gpf_engine* e) {
-  const int ne = e->la_n_env, nc = ne * e->la_K;
-  std::fill_n(e->h_lane_forecast.begin() + ne, nc, 0);
-  if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, ne, nc, 0));
-  return GPF_OK;
+  e->fan.release();
 }
 
 gpf::LaDev la_dev(const gpf_engine* e, int t_obs, int time_step) {
   gpf::LaDev d{};
   d.cand = e->la_cand.p; d.flags = e->la_flags.p; d.value = e->la_value.p; d.best = e->la_best.p; d.best_value = e->la_best_value.p;
-  d.info = e->la_info.p; d.list = e->la_list.p; d.list_rows = e->la_list_rows.p; d.noted = e->la_noted.p;
+  d.info = e->la_info.p; d.list = e->la_moved_list.list.p; d.list_rows = e->la_moved_list.rows.p; d.noted = e->la_noted.p;
   d.maint = e->la_maint.n ? e->la_maint.p : nullptr; d.lane_table = e->lane_table.p; d.lane_offset = e->lane_offset.p;
   d.rho = e->rho.p; d.done = e->done.p;
-  d.n_env = e->la_n_env; d.K = e->la_K; d.T = e->chron_T; d.t_obs = t_obs; d.time_step = time_step;
+  d.n_env = e->fan.n_env; d.K = e->fan.K; d.T = e->chron_T; d.t_obs = t_obs; d.time_step = time_step;
   return d;
 }
 
@@ -76,10 +66,10 @@ int la_check_table(const gpf_engine* e, const std::string& at) {
 // the rows the host last noted for the scratch lanes -> la_noted (an unknown mirror stays INT_MIN in front: the play kernel lists the lane)
 int la_upload_noted(gpf_engine* e) {
   const gpf::GridDev& g = e->g;
-  const size_t w = (size_t)g.dim_topo + g.n_shunt, nc = (size_t)e->la_n_env * e->la_K;
+  const size_t w = (size_t)g.dim_topo + g.n_shunt, nc = (size_t)e->fan.n_sec();
   std::vector<int> rows(nc * w);
   for (size_t q = 0; q < nc; ++q) {
-    const size_t lane = (size_t)e->la_n_env + q;
+    const size_t lane = (size_t)e->fan.n_env + q;
     std::copy_n(e->h_lane_topo.begin() + lane * g.dim_topo, g.dim_topo, rows.begin() + q * w);
     if (g.n_shunt) std::copy_n(e->h_lane_sb.begin() + lane * g.n_shunt, g.n_shunt, rows.begin() + q * w + g.dim_topo);
   }
@@ -88,45 +78,10 @@ int la_upload_noted(gpf_engine* e) {
   return GPF_OK;
 }
 
-// The compact list la_play_kernel left (count, lane ids, rows) -> the host's per-lane planning bookkeeping, in lane order, as
-// topo_readback does it -- without ta_moved: a scratch lane never counts as "moved" (it is never auto-reset).
-int la_readback(gpf_engine* e) {
-  const gpf::GridDev& g = e->g;
-  const size_t w = (size_t)g.dim_topo + g.n_shunt, nc = (size_t)e->la_n_env * e->la_K;
-  const size_t need = 1 + nc + nc * w;
-  if (e->la_pin.n < need) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(e->la_pin.reserve(need));
-  }
-  HIP_TRY(hipMemcpyAsync(e->la_pin.p, e->la_list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int cnt = e->la_pin.p[0];
-  if (cnt <= 0) return GPF_OK;
-  if ((size_t)cnt > nc) return fail(GPF_E_DEVICE, "gpf_lookahead: internal (read-back count)");
-  int* ids = e->la_pin.p + 1;
-  int* rows = ids + nc;
-  HIP_TRY(hipMemcpyAsync(ids, e->la_list.p + 1, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(rows, e->la_list_rows.p, (size_t)cnt * w * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  std::vector<int> order(cnt);                             // lane order: classes are created in the order gpf_set_topology would create them
-  for (int i = 0; i < cnt; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [ids](int a, int b) { return ids[a] < ids[b]; });
-  bool changed = false;
-  for (int i : order) {
-    const int lane = ids[i];
-    if (lane < e->la_n_env || (size_t)lane >= (size_t)e->la_n_env + nc) return fail(GPF_E_DEVICE, "gpf_lookahead: internal (read-back lane)");
-    const int* t = rows + (size_t)i * w;
-    changed |= note_lane_row(e, lane, t, g.n_shunt ? t + g.dim_topo : nullptr);
-  }
-  if (changed) e->plan_valid = false;
-  return GPF_OK;
-}
-
-
 // what gpf_lookahead and gpf_lookahead_chain refuse alike, before the device is touched
 int la_check(const gpf_engine* e, const char* who, int time_step) {
   const std::string at = std::string(who) + ": ";
-  if (!e->la_on && !e->la_host_on) return fail(GPF_E_INVALID, at + "the look-ahead is off (gpf_set_lookahead)");
+  if (!e->fan.owned_by(LA)) return fail(GPF_E_INVALID, at + "the look-ahead is off (gpf_set_lookahead)");
   int rc = la_check_table(e, at);
   if (rc != GPF_OK) return rc;
   if (time_step < 0 || time_step > e->fc_h)                 // (fc_h: 0 without uploaded forecasts)
@@ -144,7 +99,7 @@ int la_play_and_step(gpf_engine* e, const char* who, int t_obs, int time_step, c
   const std::string at = std::string(who) + ": ";
   int rc = GPF_OK;
   const gpf::GridDev& g = e->g;
-  const int ne = e->la_n_env, K = e->la_K, nc = ne * K;
+  const int ne = e->fan.n_env, K = e->fan.K, nc = e->fan.n_sec();
   for (int i = 0; i < ne; ++i)
     if (e->h_lane_forecast[i])
       return fail(GPF_E_INVALID, at + "an environment lane is itself a scratch lane of an earlier gpf_simulate_batch (its chronics cursor is an absolute "
@@ -164,12 +119,12 @@ int la_play_and_step(gpf_engine* e, const char* who, int t_obs, int time_step, c
   }
   e->la_maint_gen = e->maint_gen;
   // whatever invalidated the plans may have re-keyed scratch lanes on the host (gpf_set_topology, gpf_reset_lanes, gpf_copy_lanes ...)
-  if (e->la_noted_stale || !(e->plan_valid && e->la_plan_valid)) { rc = la_upload_noted(e); if (rc != GPF_OK) return rc; }
+  if (e->la_noted_gen != e->fan.plans_gen || !(e->plan_valid && e->fan.plans_valid)) { rc = la_upload_noted(e); if (rc != GPF_OK) return rc; }
   // 1. everything of the environments that is not topology, and the chronics / forecast row to step on
   rc = simulate_prepare(e, e->la_src.p, K, nc, ne, t_obs, time_step);
   if (rc != GPF_OK) return rc;
   // 2. the topology side and the candidates, under the environments' rules
-  HIP_TRY(hipMemsetAsync(e->la_list.p, 0, sizeof(int), e->stream));
+  HIP_TRY(hipMemsetAsync(e->la_moved_list.list.p, 0, sizeof(int), e->stream));
   const gpf::TopoTab tab{e->ta_off.p, e->ta_items.p, e->ta_amb.p, e->ta_n_act};
   const size_t lds = gpf::topo_prestep_lds_ints(g.dim_topo, g.n_line, g.n_sub, g.n_shunt, g.n_busbar) * sizeof(int);
   const gpf::LaDev d = la_dev(e, t_obs, time_step);
@@ -177,42 +132,24 @@ int la_play_and_step(gpf_engine* e, const char* who, int t_obs, int time_step, c
   HIP_TRY(hipGetLastError());
   e->dev_topo_dirty = true;
   if (e->env_on) { rc = env_copy_from(e, e->la_src.p, K, nc, ne); if (rc != GPF_OK) return rc; }
-  // 3. the scratch lanes whose topology class or busbar count left the one the host noted: ONE compact read-back
-  rc = la_readback(e);
+  // 3. the scratch lanes whose topology class or busbar count left the one the host noted: ONE compact read-back (no per-lane work: a
+  // scratch lane is never auto-reset)
+  rc = moved_list_readback(e, e->la_moved_list, ne, ne + nc, "gpf_lookahead: internal (read-back", nullptr);
   if (rc != GPF_OK) return rc;
-  rc = la_plans(e);
+  rc = fan_plans(e);
   if (rc != GPF_OK) return rc;
-  e->la_noted_stale = false;                // (la_noted and the host's mirrors of the scratch lanes agree: the read-back noted what the kernel wrote)
+  e->la_noted_gen = e->fan.plans_gen;       // (la_noted and the host's mirrors of the scratch lanes agree: the read-back noted what the kernel wrote)
   // 4. ONE step of the scratch range, as gpf_simulate_batch steps it
-  return simulate_step(e, ne, nc, time_step, o, who, &e->la_sim_p, &e->la_sim_pb);
+  return simulate_step(e, ne, nc, time_step, o, who, &e->fan.sec.p, &e->fan.sec.pb);
 }
 
 }  // namespace
 
 int la_mark_lanes(gpf_engine* e) {
-  const int ne = e->la_n_env, nc = ne * e->la_K;
-  std::fill_n(e->h_lane_forecast.begin() + ne, nc, 1);     // (gpf_simulate_batch refuses them as sources: chained horizons are out of scope)
-  for (int q = 0; q < nc; ++q) e->h_lane_table[(size_t)ne + q] = e->h_lane_table[q / e->la_K];      // (their offsets are absolute rows: not mirrored)
-  if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, ne, nc, 1));
-  return GPF_OK;
-}
-
-int la_plans(gpf_engine* e) {
-  if (e->plan_valid && e->la_plan_valid) return GPF_OK;
-  const int ne = e->la_n_env, K = e->la_K;
-  e->la_plan_valid = false;
-  e->la_noted_stale = true;                 // (whatever invalidated the plans may have re-keyed scratch lanes on the host)
-  // (the environment lanes run on the instance groups of a launch without the look-ahead, whatever n_env is: their bits are that launch's)
-  int rc = plan_launch_own(e, 0, ne, e->la_env_p, e->la_env_pb, e->la_env_lists, true);
-  if (rc != GPF_OK) return rc;
-  rc = plan_launch_own(e, ne, ne * K, e->la_sim_p, e->la_sim_pb, e->la_sim_lists);
-  if (rc != GPF_OK) return rc;
-  // the batch's own plan, last: from here on plan_valid says "nothing that plans depend on has changed", for these two as well
-  int32_t whole[8];
-  rc = gpf_get_plan(e, whole);
-  if (rc != GPF_OK) return rc;
-  e->la_plan_valid = true;
-  return GPF_OK;
+  const LaneFan& f = e->fan;
+  for (int i = 0; i < f.n_env; ++i)
+    for (int k = 0; k < f.K; ++k) e->h_lane_table[f.lane(i, k)] = e->h_lane_table[i];      // (their offsets are absolute rows: not mirrored)
+  return fan_mark_lanes(e, e->h_lane_forecast, 1);     // (gpf_simulate_batch refuses them as sources: chained horizons are out of scope)
 }
 
 extern "C" {
@@ -221,10 +158,11 @@ int gpf_set_lookahead(gpf_handle e, int32_t n_env, int32_t n_cand) {
   if (!e) return fail(GPF_E_INVALID, "gpf_set_lookahead: null");
   const std::string at = "gpf_set_lookahead: ";
   if (n_cand == 0) {
-    if (e->la_on) {
+    if (!e->fan.owned_by(LA)) return GPF_OK;
+    if (e->fan.on(LA)) {
       HIP_TRY(hipSetDevice(e->device));
       HIP_TRY(hipStreamSynchronize(e->stream));
-      int rc = la_unmark_lanes(e);
+      int rc = fan_mark_lanes(e, e->h_lane_forecast, 0);   // the scratch lanes are ordinary lanes again
       if (rc != GPF_OK) return rc;
       e->plan_valid = false;
     }
@@ -233,7 +171,7 @@ int gpf_set_lookahead(gpf_handle e, int32_t n_env, int32_t n_cand) {
   }
   if (n_cand < 0) return fail(GPF_E_INVALID, at + "negative n_cand");
   if (n_env <= 0) return fail(GPF_E_INVALID, at + "n_env must be positive");
-  if (e->n1_on || e->n1_host_on)
+  if (e->fan.owned_by(FanOwner::n1_screen))
     return fail(GPF_E_INVALID, at + "the N-1 screen (gpf_set_n1_screen) is on and claims the lanes behind the environments: switch it off first");
   int rc = la_check_table(e, at);
   if (rc != GPF_OK) return rc;
@@ -245,12 +183,12 @@ int gpf_set_lookahead(gpf_handle e, int32_t n_env, int32_t n_cand) {
     return fail(GPF_E_CAPACITY, at + "the grid's rows do not fit the 64 KiB of LDS of the play kernel");
   if (e->dry) {
     la_release(e);
-    e->la_host_on = true; e->la_n_env = n_env; e->la_K = n_cand;
+    e->fan.claim(LA, n_env, n_cand, true);
     return fail(GPF_E_DEVICE, "gpf_set_lookahead: header-only handle: no HIP device");
   }
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->la_on) { rc = la_unmark_lanes(e); if (rc != GPF_OK) return rc; }
+  if (e->fan.on(LA)) { rc = fan_mark_lanes(e, e->h_lane_forecast, 0); if (rc != GPF_OK) return rc; }
   la_release(e);
   const size_t ne = (size_t)n_env, nc = ne * (size_t)n_cand, w = (size_t)g.dim_topo + g.n_shunt;
   std::vector<int> none(nc, -1), iota(ne);
@@ -262,17 +200,16 @@ int gpf_set_lookahead(gpf_handle e, int32_t n_env, int32_t n_cand) {
   if (err == hipSuccess) err = e->la_best.alloc(ne);
   if (err == hipSuccess) err = e->la_best_value.alloc(ne);
   if (err == hipSuccess) err = e->la_info.alloc(ne * 2);
-  if (err == hipSuccess) err = e->la_list.alloc(nc + 1);
-  if (err == hipSuccess) err = e->la_list_rows.alloc(nc * w);
+  if (err == hipSuccess) err = e->la_moved_list.alloc(nc, w);
   if (err == hipSuccess) err = e->la_noted.alloc(nc * w);
   if (err == hipSuccess) err = hipMemset(e->la_value.p, 0, nc * sizeof(float));
   if (err == hipSuccess) err = hipMemset(e->la_flags.p, 0, nc);
   if (err == hipSuccess) err = hipMemset(e->la_best.p, 0xff, ne * sizeof(int));
   if (err == hipSuccess) err = hipMemset(e->la_best_value.p, 0, ne * sizeof(float));
   if (err == hipSuccess) err = hipMemset(e->la_info.p, 0, ne * 2 * sizeof(int));
-  if (err == hipSuccess) err = hipMemset(e->la_list.p, 0, (nc + 1) * sizeof(int));
+  if (err == hipSuccess) err = hipMemset(e->la_moved_list.list.p, 0, (nc + 1) * sizeof(int));
   if (err != hipSuccess) { la_release(e); HIP_TRY(err); }
-  e->la_n_env = n_env; e->la_K = n_cand; e->la_on = true;
+  e->fan.claim(LA, n_env, n_cand, false);
   rc = la_mark_lanes(e);
   if (rc == GPF_OK) rc = la_upload_noted(e);
   if (rc != GPF_OK) la_release(e);
@@ -288,7 +225,7 @@ int gpf_lookahead(gpf_handle e, int32_t t_obs, int32_t time_step, const int32_t*
   rc = la_play_and_step(e, "gpf_lookahead", t_obs, time_step, cand, o);
   if (rc != GPF_OK) return rc;
   // 5. values, flags, the best playable slot
-  const int ne = e->la_n_env, nc = ne * e->la_K;
+  const int ne = e->fan.n_env, nc = e->fan.n_sec();
   const gpf::LaDev d = la_dev(e, t_obs, time_step);
   hipLaunchKernelGGL(gpf::la_reduce_kernel, dim3((unsigned)((nc + gpf::LA_WPB - 1) / gpf::LA_WPB)), dim3(64 * gpf::LA_WPB), 0, e->stream, d, e->g.n_line);
   HIP_TRY(hipGetLastError());
@@ -306,7 +243,7 @@ int gpf_set_lookahead_chain(gpf_handle e, int32_t max_steps) {
     return GPF_OK;
   }
   if (max_steps < 0) return fail(GPF_E_INVALID, at + "negative max_steps");
-  if (!e->la_on && !e->la_host_on) return fail(GPF_E_INVALID, at + "the look-ahead is off (gpf_set_lookahead): the chain runs on its scratch lanes");
+  if (!e->fan.owned_by(LA)) return fail(GPF_E_INVALID, at + "the look-ahead is off (gpf_set_lookahead): the chain runs on its scratch lanes");
   if (e->dry) {
     la_chain_release(e);
     e->lc_host_on = true; e->lc_max = max_steps;
@@ -315,7 +252,7 @@ int gpf_set_lookahead_chain(gpf_handle e, int32_t max_steps) {
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   la_chain_release(e);
-  const size_t ne = (size_t)e->la_n_env, nc = ne * (size_t)e->la_K;
+  const size_t ne = (size_t)e->fan.n_env, nc = (size_t)e->fan.n_sec();
   hipError_t err = e->lc_survived.alloc(nc);
   if (err == hipSuccess) err = e->lc_peak.alloc(nc);
   if (err == hipSuccess) err = e->lc_value_h.alloc(nc * (size_t)max_steps);
@@ -335,7 +272,7 @@ int gpf_lookahead_chain(gpf_handle e, int32_t t_obs, int32_t n_steps, const int3
   if (!e || !o) return fail(GPF_E_INVALID, "gpf_lookahead_chain: null");
   const char* who = "gpf_lookahead_chain";
   const std::string at = "gpf_lookahead_chain: ";
-  if (!e->la_on && !e->la_host_on) return fail(GPF_E_INVALID, at + "the look-ahead is off (gpf_set_lookahead)");
+  if (!e->fan.owned_by(LA)) return fail(GPF_E_INVALID, at + "the look-ahead is off (gpf_set_lookahead)");
   if (!e->lc_on && !e->lc_host_on) return fail(GPF_E_INVALID, at + "the chain is off (gpf_set_lookahead_chain)");
   if (n_steps < 1) return fail(GPF_E_INVALID, at + "n_steps must be at least 1");
   if (n_steps > e->lc_max)
@@ -351,7 +288,7 @@ int gpf_lookahead_chain(gpf_handle e, int32_t t_obs, int32_t n_steps, const int3
   // step 1: gpf_lookahead(t_obs, 1) up to its step
   rc = la_play_and_step(e, who, t_obs, 1, cand, o);
   if (rc != GPF_OK) return rc;
-  const int ne = e->la_n_env, nc = ne * e->la_K;
+  const int ne = e->fan.n_env, nc = e->fan.n_sec();
   const gpf::LaDev d = la_dev(e, t_obs, 1);
   const gpf::LaChainDev c = la_chain_dev(e);
   const dim3 grid_q((unsigned)((nc + gpf::LA_WPB - 1) / gpf::LA_WPB)), grid_e((unsigned)((ne + gpf::LA_WPB - 1) / gpf::LA_WPB)), block(64 * gpf::LA_WPB);
@@ -361,7 +298,7 @@ int gpf_lookahead_chain(gpf_handle e, int32_t t_obs, int32_t n_steps, const int3
     HIP_TRY(hipGetLastError());
     if (h == n_steps) break;
     // a do-nothing step on the cached plan: a line outage never changes a lane's planning class
-    rc = simulate_step(e, ne, nc, h + 1, o, who, &e->la_sim_p, &e->la_sim_pb);
+    rc = simulate_step(e, ne, nc, h + 1, o, who, &e->fan.sec.p, &e->fan.sec.pb);
     if (rc != GPF_OK) return rc;
   }
   hipLaunchKernelGGL(gpf::la_chain_summary_kernel, grid_e, block, 0, e->stream, d, c, (int)play);
@@ -373,10 +310,10 @@ int gpf_lookahead_chain(gpf_handle e, int32_t t_obs, int32_t n_steps, const int3
 int gpf_get_lookahead_chain(gpf_handle e, int32_t env0, int32_t n, int32_t* survived, float* peak, float* value_h, int32_t* fallback, int32_t* fallback_steps) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_lookahead_chain: null");
   if (!e->lc_on) return fail(GPF_E_INVALID, "gpf_get_lookahead_chain: the chain is off (gpf_set_lookahead_chain)");
-  if (env0 < 0 || n < 0 || env0 + n > e->la_n_env) return fail(GPF_E_INVALID, "gpf_get_lookahead_chain: bad environment range");
+  if (env0 < 0 || n < 0 || env0 + n > e->fan.n_env) return fail(GPF_E_INVALID, "gpf_get_lookahead_chain: bad environment range");
   if (n == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
-  const size_t K = (size_t)e->la_K, H = (size_t)e->lc_max;
+  const size_t K = (size_t)e->fan.K, H = (size_t)e->lc_max;
   if (survived) HIP_TRY(hipMemcpyAsync(survived, e->lc_survived.p + env0 * K, n * K * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   if (peak) HIP_TRY(hipMemcpyAsync(peak, e->lc_peak.p + env0 * K, n * K * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   if (value_h) HIP_TRY(hipMemcpyAsync(value_h, e->lc_value_h.p + env0 * K * H, n * K * H * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -396,11 +333,11 @@ int gpf_lookahead_chain_device_pointers(gpf_handle e, void** out, int32_t n) {
 
 int gpf_get_lookahead(gpf_handle e, int32_t env0, int32_t n, float* value, uint8_t* flags, int32_t* best, float* best_value, int32_t* info) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_lookahead: null");
-  if (!e->la_on) return fail(GPF_E_INVALID, "gpf_get_lookahead: the look-ahead is off (gpf_set_lookahead)");
-  if (env0 < 0 || n < 0 || env0 + n > e->la_n_env) return fail(GPF_E_INVALID, "gpf_get_lookahead: bad environment range");
+  if (!e->fan.on(LA)) return fail(GPF_E_INVALID, "gpf_get_lookahead: the look-ahead is off (gpf_set_lookahead)");
+  if (env0 < 0 || n < 0 || env0 + n > e->fan.n_env) return fail(GPF_E_INVALID, "gpf_get_lookahead: bad environment range");
   if (n == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
-  const size_t K = (size_t)e->la_K;
+  const size_t K = (size_t)e->fan.K;
   if (value) HIP_TRY(hipMemcpyAsync(value, e->la_value.p + env0 * K, n * K * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   if (flags) HIP_TRY(hipMemcpyAsync(flags, e->la_flags.p + env0 * K, n * K, hipMemcpyDeviceToHost, e->stream));
   if (best) HIP_TRY(hipMemcpyAsync(best, e->la_best.p + env0, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -412,7 +349,7 @@ int gpf_get_lookahead(gpf_handle e, int32_t env0, int32_t n, float* value, uint8
 
 int gpf_lookahead_device_pointers(gpf_handle e, void** out, int32_t n) {
   if (!e || !out || n != GPF_N_LOOKAHEAD_POINTERS) return fail(GPF_E_INVALID, "gpf_lookahead_device_pointers: null, or n is not GPF_N_LOOKAHEAD_POINTERS");
-  if (!e->la_on) return fail(GPF_E_INVALID, "gpf_lookahead_device_pointers: the look-ahead is off (gpf_set_lookahead)");
+  if (!e->fan.on(LA)) return fail(GPF_E_INVALID, "gpf_lookahead_device_pointers: the look-ahead is off (gpf_set_lookahead)");
   out[0] = e->la_cand.p; out[1] = e->la_value.p; out[2] = e->la_flags.p; out[3] = e->la_best.p; out[4] = e->la_best_value.p; out[5] = e->la_info.p;
   return GPF_OK;
 }

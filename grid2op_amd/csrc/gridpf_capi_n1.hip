@@ -1,7 +1,7 @@
 // gridpf_capi_n1.hip -- the N-1 screen's entry points of the C ABI (include/gridpf.h: gpf_set_n1_screen, gpf_get_n1_values,
 // gpf_get_n1_summary, gpf_n1_device_pointers) and the host side of the kernels of gridpf_n1.hpp, on the engine of gridpf_engine.hpp.
 // Everything a screen can get wrong is refused here, before the device is touched.  A launch in which no environment lane changed its
-// topology class does no host work that grows with n_env x K: the plans of the two lane ranges are cached (n1_plans).
+// topology class does no host work that grows with n_env x K: the plans of the two lane ranges are cached (fan_plans).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -16,12 +16,19 @@ static_assert(gpf::RW_N1 == GPF_RW_N1, "kinds");
 
 namespace {
 
+constexpr FanOwner N1 = FanOwner::n1_screen;
+
 void n1_release(gpf_engine* e) {
-  e->n1_on = e->n1_host_on = e->n1_slots = e->n1_plan_valid = false;
-  e->n1_n_env = e->n1_K = 0;
-  e->h_n1_lines.clear();
+  e->n1_slots = false;
   e->n1_lines.release(); e->n1_info.release(); e->n1_slot_idx.release(); e->n1_value.release(); e->n1_worst.release();
-  for (int i = 0; i < 3; ++i) { e->n1_env_lists[i].release(); e->n1_con_lists[i].release(); }
+  e->fan.release();
+}
+
+// the screen that is set goes (the stream has drained): its contingency lanes are ordinary lanes again
+int n1_off(gpf_engine* e) {
+  if (e->fan.on(N1)) { int rc = fan_mark_lanes(e, e->h_lane_n1, 0); if (rc != GPF_OK) return rc; }
+  n1_release(e);
+  return GPF_OK;
 }
 
 gpf::N1Dev n1_dev(const gpf_engine* e) {
@@ -32,7 +39,7 @@ gpf::N1Dev n1_dev(const gpf_engine* e) {
   d.out = e->out.p; d.status = e->status.p; d.done = e->done.p; d.thermal = e->thermal_limit.p;
   if (e->ep_on) { d.ep_limit = e->ep_limit.p; d.episode = e->episode.p; }       // a step at the lane's limit is the reference's is_done
   d.value = e->n1_value.p; d.worst = e->n1_worst.p; d.info = e->n1_info.p;
-  d.n_env = e->n1_n_env; d.K = e->n1_K; d.n_inj = g.n_inj; d.dim_topo = g.dim_topo; d.n_shunt = g.n_shunt; d.n_line = g.n_line;
+  d.n_env = e->fan.n_env; d.K = e->fan.K; d.n_inj = g.n_inj; d.dim_topo = g.dim_topo; d.n_shunt = g.n_shunt; d.n_line = g.n_line;
   d.n_out = g.n_out; d.off_a_or = e->oo.a_or;
   return d;
 }
@@ -46,36 +53,14 @@ int slot_index(const gpf_reward_slot& s) {
 
 }  // namespace
 
-int n1_mark_lanes(gpf_engine* e) {
-  const int ne = e->n1_n_env, nc = ne * e->n1_K;
-  std::fill_n(e->h_lane_n1.begin() + ne, nc, 1);
-  if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, ne, nc, 1));       // contingency lanes start no scenario of their own
-  return GPF_OK;
-}
-
 int n1_plans(gpf_engine* e) {
-  if (e->plan_valid && e->n1_plan_valid) return GPF_OK;
-  const int ne = e->n1_n_env, K = e->n1_K;
+  const LaneFan& f = e->fan;
   // a contingency lane carries its environment's planning entries (a single line outage never changes a lane's topology class); the
   // host's mirror of its sent topology is unknown
-  for (int i = 0; i < ne; ++i)
-    for (int k = 0; k < K; ++k) {
-      const size_t lane = (size_t)ne + (size_t)i * K + k;
-      e->lane_nb[lane] = e->lane_nb[i]; e->lane_nj[lane] = e->lane_nj[i]; e->lane_mb[lane] = e->lane_mb[i]; e->lane_class[lane] = e->lane_class[i];
-      e->h_lane_topo[lane * e->g.dim_topo] = INT_MIN;
-    }
-  e->n1_plan_valid = false;
-  // (the environment lanes run on the instance groups of a launch without the screen, whatever n_env is: their bits are that launch's)
-  int rc = plan_launch_own(e, 0, ne, e->n1_env_p, e->n1_env_pb, e->n1_env_lists, true);
-  if (rc != GPF_OK) return rc;
-  rc = plan_launch_own(e, ne, ne * K, e->n1_con_p, e->n1_con_pb, e->n1_con_lists);
-  if (rc != GPF_OK) return rc;
-  // the batch's own plan, last: from here on plan_valid says "nothing that plans depend on has changed", for these two as well
-  int32_t whole[8];
-  rc = gpf_get_plan(e, whole);
-  if (rc != GPF_OK) return rc;
-  e->n1_plan_valid = true;
-  return GPF_OK;
+  if (!(e->plan_valid && f.plans_valid))
+    for (int i = 0; i < f.n_env; ++i)
+      for (int k = 0; k < f.K; ++k) lane_inherit(e, f.lane(i, k), i, false);
+  return fan_plans(e);
 }
 
 int n1_screen(gpf_engine* e, int max_iter, double tol_mva) {
@@ -85,7 +70,7 @@ int n1_screen(gpf_engine* e, int max_iter, double tol_mva) {
   const int nc = d.n_env * d.K;
   hipLaunchKernelGGL(gpf::n1_fanout_kernel, dim3((unsigned)nc), dim3(64), 0, e->stream, d);
   HIP_TRY(hipGetLastError());
-  rc = runpf_range(e, d.n_env, nc, 0, max_iter, tol_mva, &e->n1_con_p, &e->n1_con_pb);
+  rc = runpf_range(e, d.n_env, nc, 0, max_iter, tol_mva, &e->fan.sec.p, &e->fan.sec.pb);
   if (rc != GPF_OK) return rc;
   hipLaunchKernelGGL(gpf::n1_reduce_kernel, dim3((unsigned)((nc + gpf::N1_WPB - 1) / gpf::N1_WPB)), dim3(64 * gpf::N1_WPB), 0, e->stream, d);
   HIP_TRY(hipGetLastError());
@@ -96,9 +81,9 @@ int n1_screen(gpf_engine* e, int max_iter, double tol_mva) {
 
 int n1_fill_slots(gpf_engine* e, int lane0, int n, float* reward, long long row_stride) {
   const int total = n * e->rw_n_slot;
-  if (total <= 0 || lane0 >= e->n1_n_env) return GPF_OK;
+  if (total <= 0 || lane0 >= e->fan.n_env) return GPF_OK;
   hipLaunchKernelGGL(gpf::n1_slot_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->n1_value.p, e->n1_slot_idx.p,
-                     e->rw_n_slot, e->n1_n_env, e->n1_K, lane0, n, reward, row_stride);
+                     e->rw_n_slot, e->fan.n_env, e->fan.K, lane0, n, reward, row_stride);
   HIP_TRY(hipGetLastError());
   return GPF_OK;
 }
@@ -107,7 +92,7 @@ int n1_check_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots) {
   for (int s = 0; s < n_slot; ++s) {
     if (slots[s].kind != GPF_RW_N1) continue;
     const std::string sl = "gpf_set_rewards: slot " + std::to_string(s) + ": ";
-    const int K = e->n1_on ? e->n1_K : (e->n1_host_on ? (int)e->h_n1_lines.size() : 0);
+    const int K = e->fan.owned_by(N1) ? e->fan.K : 0;
     if (K == 0) return fail(GPF_E_INVALID, sl + "GPF_RW_N1 needs the N-1 screen (gpf_set_n1_screen), which is off");
     const int idx = slot_index(slots[s]);
     if (idx < 0 || idx >= K)
@@ -137,17 +122,11 @@ int gpf_set_n1_screen(gpf_handle e, int32_t n_env, const int32_t* lines, int32_t
   const std::string at = "gpf_set_n1_screen: ";
   if (e->n1_slots) return fail(GPF_E_INVALID, at + "a reward slot of kind GPF_RW_N1 reads the screen's table: set the rewards anew (gpf_set_rewards) first");
   if (n_lines == 0) {
-    if (e->n1_on) {
-      HIP_TRY(hipSetDevice(e->device));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-      const int ne = e->n1_n_env, nc = ne * e->n1_K;
-      std::fill_n(e->h_lane_n1.begin() + ne, nc, 0);
-      if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, ne, nc, 0));
-    }
-    n1_release(e);
-    return GPF_OK;
+    if (!e->fan.owned_by(N1)) return GPF_OK;
+    if (e->fan.on(N1)) { HIP_TRY(hipSetDevice(e->device)); HIP_TRY(hipStreamSynchronize(e->stream)); }
+    return n1_off(e);
   }
-  if (e->la_on || e->la_host_on)
+  if (e->fan.owned_by(FanOwner::lookahead))
     return fail(GPF_E_INVALID, at + "the look-ahead (gpf_set_lookahead) is set and claims the lanes behind the environments: switch it off first");
   if (n_lines < 0 || !lines) return fail(GPF_E_INVALID, at + "negative n_lines, or no lines");
   for (int k = 0; k < n_lines; ++k)
@@ -158,17 +137,13 @@ int gpf_set_n1_screen(gpf_handle e, int32_t n_env, const int32_t* lines, int32_t
     return fail(GPF_E_CAPACITY, at + std::to_string(n_env) + " environments x (1 + " + std::to_string(n_lines) + " watched lines) need " +
                                 std::to_string((long long)n_env * (1 + (long long)n_lines)) + " lanes, the engine has " + std::to_string(e->n_lanes));
   if (e->dry) {
-    e->n1_host_on = true;
-    e->h_n1_lines.assign(lines, lines + n_lines);
+    e->fan.claim(N1, n_env, n_lines, true);
     return fail(GPF_E_DEVICE, "gpf_set_n1_screen: header-only handle: no HIP device");
   }
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->n1_on) {                           // the lanes of the screen that was on are ordinary lanes again
-    std::fill_n(e->h_lane_n1.begin() + e->n1_n_env, e->n1_n_env * e->n1_K, 0);
-    if (e->cur_on) HIP_TRY(cursor_mark_lanes(e, e->n1_n_env, e->n1_n_env * e->n1_K, 0));
-  }
-  n1_release(e);
+  int rc = n1_off(e);
+  if (rc != GPF_OK) return rc;
   const size_t ne = (size_t)n_env, K = (size_t)n_lines;
   hipError_t err = e->n1_lines.upload(lines, K);
   if (err == hipSuccess) err = e->n1_value.alloc(ne * K);
@@ -178,9 +153,8 @@ int gpf_set_n1_screen(gpf_handle e, int32_t n_env, const int32_t* lines, int32_t
   if (err == hipSuccess) err = hipMemset(e->n1_worst.p, 0, ne * sizeof(float));
   if (err == hipSuccess) err = hipMemset(e->n1_info.p, 0, ne * 3 * sizeof(int));
   if (err != hipSuccess) { n1_release(e); HIP_TRY(err); }
-  e->h_n1_lines.assign(lines, lines + n_lines);
-  e->n1_n_env = n_env; e->n1_K = n_lines; e->n1_on = true;
-  int rc = n1_mark_lanes(e);
+  e->fan.claim(N1, n_env, n_lines, false);
+  rc = fan_mark_lanes(e, e->h_lane_n1, 1);
   if (rc == GPF_OK) HIP_TRY(hipStreamSynchronize(e->stream));
   if (rc != GPF_OK) n1_release(e);
   return rc;
@@ -188,19 +162,19 @@ int gpf_set_n1_screen(gpf_handle e, int32_t n_env, const int32_t* lines, int32_t
 
 int gpf_get_n1_values(gpf_handle e, int32_t lane0, int32_t n, float* value) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_n1_values: null");
-  if (!e->n1_on) return fail(GPF_E_INVALID, "gpf_get_n1_values: the N-1 screen is off (gpf_set_n1_screen)");
-  if (lane0 < 0 || n < 0 || lane0 + n > e->n1_n_env || (!value && n)) return fail(GPF_E_INVALID, "gpf_get_n1_values: bad environment range or null");
+  if (!e->fan.on(N1)) return fail(GPF_E_INVALID, "gpf_get_n1_values: the N-1 screen is off (gpf_set_n1_screen)");
+  if (lane0 < 0 || n < 0 || lane0 + n > e->fan.n_env || (!value && n)) return fail(GPF_E_INVALID, "gpf_get_n1_values: bad environment range or null");
   if (n == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipMemcpyAsync(value, e->n1_value.p + (size_t)lane0 * e->n1_K, (size_t)n * e->n1_K * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(value, e->n1_value.p + (size_t)lane0 * e->fan.K, (size_t)n * e->fan.K * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return GPF_OK;
 }
 
 int gpf_get_n1_summary(gpf_handle e, int32_t lane0, int32_t n, float* worst, int32_t* arg_worst, int32_t* n_insecure, int32_t* n_diverged) {
   if (!e) return fail(GPF_E_INVALID, "gpf_get_n1_summary: null");
-  if (!e->n1_on) return fail(GPF_E_INVALID, "gpf_get_n1_summary: the N-1 screen is off (gpf_set_n1_screen)");
-  if (lane0 < 0 || n < 0 || lane0 + n > e->n1_n_env) return fail(GPF_E_INVALID, "gpf_get_n1_summary: bad environment range");
+  if (!e->fan.on(N1)) return fail(GPF_E_INVALID, "gpf_get_n1_summary: the N-1 screen is off (gpf_set_n1_screen)");
+  if (lane0 < 0 || n < 0 || lane0 + n > e->fan.n_env) return fail(GPF_E_INVALID, "gpf_get_n1_summary: bad environment range");
   if (n == 0) return GPF_OK;
   HIP_TRY(hipSetDevice(e->device));
   std::vector<int> info((size_t)n * 3);
@@ -217,7 +191,7 @@ int gpf_get_n1_summary(gpf_handle e, int32_t lane0, int32_t n, float* worst, int
 
 int gpf_n1_device_pointers(gpf_handle e, void** out, int32_t n) {
   if (!e || !out || n != GPF_N_N1_POINTERS) return fail(GPF_E_INVALID, "gpf_n1_device_pointers: null, or n is not GPF_N_N1_POINTERS");
-  if (!e->n1_on) return fail(GPF_E_INVALID, "gpf_n1_device_pointers: the N-1 screen is off (gpf_set_n1_screen)");
+  if (!e->fan.on(N1)) return fail(GPF_E_INVALID, "gpf_n1_device_pointers: the N-1 screen is off (gpf_set_n1_screen)");
   out[0] = e->n1_value.p; out[1] = e->n1_worst.p; out[2] = e->n1_info.p; out[3] = e->n1_lines.p;
   return GPF_OK;
 }

@@ -23,7 +23,7 @@ gpf::TopoDev topo_dev(const gpf_engine* e) {
 gpf::TopoLanes topo_lanes(const gpf_engine* e) {
   gpf::TopoLanes t{};
   t.act = e->ta_act.p; t.sub_cd = e->ta_sub_cd.p; t.last_bus = e->ta_last_bus.p; t.flags = e->ta_flags.p; t.aff = e->ta_aff.p;
-  t.ep_snap = e->ta_ep_snap.p; t.list = e->ta_list.p; t.list_rows = e->ta_list_rows.p; t.pos_sub = e->ta_pos_sub.p; t.pos_other = e->ta_pos_other.p;
+  t.ep_snap = e->ta_ep_snap.p; t.list = e->ta_moved_list.list.p; t.list_rows = e->ta_moved_list.rows.p; t.pos_sub = e->ta_pos_sub.p; t.pos_other = e->ta_pos_other.p;
   t.n_slot = e->ta_n_slot;
   return t;
 }
@@ -78,7 +78,7 @@ int topo_enable(gpf_engine* e) {
   HIP_TRY(e->ta_pos_other.upload(pos_other.data(), pos_other.size()));
   if (e->ta_n_area) HIP_TRY(e->ta_sub_area.upload(e->h_ta_sub_area.data(), e->h_ta_sub_area.size()));
   HIP_TRY(e->ta_act.alloc(cap * e->ta_n_slot)); HIP_TRY(e->ta_sub_cd.alloc(cap * g.n_sub)); HIP_TRY(e->ta_last_bus.alloc(cap * g.dim_topo));
-  HIP_TRY(e->ta_ep_snap.alloc(cap)); HIP_TRY(e->ta_list.alloc(cap + 1)); HIP_TRY(e->ta_list_rows.alloc(cap * ((size_t)g.dim_topo + g.n_shunt)));
+  HIP_TRY(e->ta_ep_snap.alloc(cap)); HIP_TRY(e->ta_moved_list.alloc(cap, (size_t)g.dim_topo + g.n_shunt));
   HIP_TRY(e->ta_flags.alloc(cap * 2)); HIP_TRY(e->ta_aff.alloc(cap * ((size_t)g.n_line + g.n_sub)));
   HIP_TRY(hipMemsetAsync(e->ta_aff.p, 0, cap * ((size_t)g.n_line + g.n_sub), e->stream));
   e->ta_moved.assign(cap, 0);
@@ -108,7 +108,7 @@ int topo_rows(gpf_engine* e, DevArr<T>& arr, size_t stride, int lane0, int n, T*
 int topo_prestep(gpf_engine* e, bool acts) {
   const gpf::GridDev& g = e->g;
   const bool readback = acts && g.n_busbar >= 2 && (e->ta_bus_items || e->ta_may_split);
-  if (acts) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
+  if (acts) HIP_TRY(hipMemsetAsync(e->ta_moved_list.list.p, 0, sizeof(int), e->stream));
   const gpf::TopoTab tab{e->ta_off.p, e->ta_items.p, e->ta_amb.p, e->ta_n_act};
   const bool gen = topo_general(e);          // composite actions or areas: the GEN instantiation; else the kernel of one entry per lane
   const gpf::TopoComp comp{e->ta_n_area ? e->ta_sub_area.p : nullptr, e->ta_n_area, e->ta_max_items};
@@ -122,48 +122,21 @@ int topo_prestep(gpf_engine* e, bool acts) {
 
 // Step 5 (topo_poststep_kernel).  list_resets: the lanes that auto-reset in this launch are listed for topo_readback
 int topo_poststep(gpf_engine* e, bool acts, int n_steps, bool list_resets) {
-  if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_list.p, 0, sizeof(int), e->stream));
+  if (list_resets) HIP_TRY(hipMemsetAsync(e->ta_moved_list.list.p, 0, sizeof(int), e->stream));
   hipLaunchKernelGGL(gpf::topo_poststep_kernel, dim3((unsigned)e->n_lanes), dim3(64), 0, e->stream, topo_dev(e), topo_lanes(e), e->ta_rules,
                      e->n_lanes, acts ? 1 : 0, n_steps, list_resets ? 1 : 0);
   HIP_TRY(hipGetLastError());
   return GPF_OK;
 }
 
-// The compact list the topology kernels left in ta_list / ta_list_rows (count, lane ids, rows) -> the host's per-lane planning bookkeeping
-// (note_lane_row: what gpf_set_topology does).  moved: the rows are action results (the lane's class may differ from its reset
-// topology's); else they are reset topologies (the lane is back on the class of the rows last sent).
+// The compact list the topology kernels left in ta_moved_list -> the host's per-lane planning bookkeeping (note_lane_row: what
+// gpf_set_topology does).  moved: the rows are action results (the lane's class may differ from its reset topology's); else they are
+// reset topologies (the lane is back on the class of the rows last sent).
 int topo_readback(gpf_engine* e, bool moved) {
-  const gpf::GridDev& g = e->g;
-  const size_t w = (size_t)g.dim_topo + g.n_shunt;
-  const size_t need = 1 + (size_t)e->n_lanes + (size_t)e->n_lanes * w;
-  if (e->ta_pin.n < need) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(e->ta_pin.reserve(need));
-  }
-  HIP_TRY(hipMemcpyAsync(e->ta_pin.p, e->ta_list.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const int cnt = e->ta_pin.p[0];
-  if (cnt <= 0) return GPF_OK;
-  if (cnt > e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back count)");
-  int* ids = e->ta_pin.p + 1;
-  int* rows = ids + e->n_lanes;
-  HIP_TRY(hipMemcpyAsync(ids, e->ta_list.p + 1, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(rows, e->ta_list_rows.p, (size_t)cnt * w * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  std::vector<int> order(cnt);                           // lane order: classes are created in the order gpf_set_topology would create them
-  for (int i = 0; i < cnt; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [ids](int a, int b) { return ids[a] < ids[b]; });
-  bool changed = false;
-  for (int i : order) {
-    const int lane = ids[i];
-    if (lane < 0 || lane >= e->n_lanes) return fail(GPF_E_DEVICE, "gpf_step_n: internal (topology read-back lane)");
-    const int* t = rows + (size_t)i * w;
-    changed |= note_lane_row(e, lane, t, g.n_shunt ? t + g.dim_topo : nullptr);
+  return moved_list_readback(e, e->ta_moved_list, 0, e->n_lanes, "gpf_step_n: internal (topology read-back", [e, moved](int lane) {
     if (moved && !e->ta_moved[lane]) { e->ta_moved[lane] = 1; ++e->ta_n_moved; }
     if (!moved && e->ta_moved[lane]) { e->ta_moved[lane] = 0; --e->ta_n_moved; }
-  }
-  if (changed) e->plan_valid = false;
-  return GPF_OK;
+  });
 }
 
 // acting-path state of lanes [lane0, lane0 + n) back to env.reset(): no cooldown, no pending action, last known busbar = the lanes'
@@ -222,15 +195,7 @@ int gpf_upload_topo_actions(gpf_handle e, int32_t n_act, const int32_t* act_off,
   if (n_act && (act_off[0] != 0 || (n_items_total > 0 && !act_items))) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action offsets");
   for (int k = 0; k < n_act; ++k) if (act_off[k + 1] < act_off[k]) return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action offsets");
   bool bus_items = false;
-  for (int q = 0; q < n_items_total; ++q) {                  // (the validation of gpf_simulate_batch)
-    const int kind = act_items[3 * q], id = act_items[3 * q + 1], v = act_items[3 * q + 2];
-    const bool pos_kind = kind == GPF_ACT_SET_BUS || kind == GPF_ACT_CHANGE_BUS, line_kind = kind == GPF_ACT_SET_LINE_STATUS || kind == GPF_ACT_CHANGE_LINE_STATUS;
-    if (!(pos_kind || line_kind || kind == GPF_ACT_SET_SHUNT_BUS) || id < 0 || (pos_kind && id >= g.dim_topo) || (line_kind && id >= g.n_line) ||
-        (kind == GPF_ACT_SET_SHUNT_BUS && id >= g.n_shunt) || ((kind == GPF_ACT_SET_BUS || kind == GPF_ACT_SET_SHUNT_BUS) && (v < -1 || v > g.n_busbar)) ||
-        (kind == GPF_ACT_CHANGE_BUS && g.n_busbar != 2))
-      return fail(GPF_E_INVALID, "gpf_upload_topo_actions: bad action item (kind, id or bus; change_bus needs exactly 2 busbars per substation)");
-    bus_items |= kind == GPF_ACT_CHANGE_BUS || kind == GPF_ACT_SET_SHUNT_BUS || (kind == GPF_ACT_SET_BUS && v != 0);
-  }
+  if (int rc_i = check_action_items(e, "gpf_upload_topo_actions", n_items_total, act_items, &bus_items)) return rc_i;
   const int max_items = topo_max_items(n_act, act_off, e->ta_n_slot);
   if (topo_prestep_lds_bytes(e, e->ta_n_slot, e->ta_n_area, max_items) > TOPO_LDS_LIMIT)
     return fail(GPF_E_INVALID, "gpf_upload_topo_actions: the gathered item list (gpf_set_topo_slots times the table's longest entry) does not fit "

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -15,6 +16,7 @@
 #include "../../include/gridpf.h"
 #include "gridpf_common.hpp"
 #include "gridpf_host.hpp"
+#include "gridpf_lane_fan.hpp"
 #include "gridpf_symbolic.hpp"
 #include "gridpf_topo.hpp"                  // (TopoRules; its kernels exist in gridpf_capi_topo.hip only)
 
@@ -128,6 +130,16 @@ struct Event {
   operator hipEvent_t() const { return h; }
 };
 
+// A moved-lane list: the lanes whose topology row a kernel moved off the one the host noted (device: count | lane ids, and their rows),
+// with the pinned block the host reads it back into (moved_list_readback)
+struct MovedList {
+  DevArr<int> list, rows;
+  HostPin<int> pin;
+  hipError_t alloc(size_t cap, size_t w) { hipError_t err = list.alloc(cap + 1); return err == hipSuccess ? rows.alloc(cap * w) : err; }
+  void release() { list.release(); rows.release(); }
+};
+using LaneFan = LaneFanT<LaunchPlan, DevArr<int>>;
+
 struct gpf_engine {
   ~gpf_engine();                        // (gridpf_capi.hip: waits for the stream; the members free themselves)
   int device = 0;
@@ -156,7 +168,7 @@ struct gpf_engine {
   // gpf_upload_topo_actions
   bool ta_on = false;
   gpf::TopoRules ta_rules{};            // (on = 0 until gpf_set_topo_rules)
-  DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_list, ta_list_rows, ta_off, ta_items, ta_pos_sub, ta_pos_other;
+  DevArr<int> ta_act, ta_sub_cd, ta_last_bus, ta_ep_snap, ta_off, ta_items, ta_pos_sub, ta_pos_other;
   DevArr<unsigned char> ta_flags, ta_aff, ta_amb;
   int ta_n_act = 0;
   // legality masks of the table (gridpf_topo_mask.hpp): its static summary, uploaded with it, and the engine-owned masks [cap_lanes][ta_n_act]
@@ -176,7 +188,7 @@ struct gpf_engine {
   bool ta_host = false, ta_dev = false; // the next launch carries indices set by the host / written on the device
   std::vector<char> ta_moved;           // per lane: an action moved it to another topology class than its reset topology's (auto-reset re-keys it)
   int ta_n_moved = 0;
-  HostPin<int> ta_pin;                  // pinned read-back block: count | lane ids | rows
+  MovedList ta_moved_list;              // the lanes the pre-step moved, the lanes that auto-reset or were truncated
   // topology-derived state of the reference topology shared by the lanes of one-step launches (gpf::KeepArgs): two blobs (Ybus in LDS /
   // in registers), allocated and keyed by the first gpf_step_n with n_steps = 1; GRIDPF_KEEP=0 at gpf_create turns it off
   DevArr<unsigned char> keep;
@@ -297,32 +309,20 @@ struct gpf_engine {
   DevArr<int> cb_ill_snap;
   DevArr<float> cb_max_prod, cb_max_absorb;
   DevArr<unsigned long long> ta_sto_word;
-  // the N-1 screen (gridpf_n1.hpp, gridpf_capi_n1.hip): lanes [0, n1_n_env) are environments, lane n1_n_env + i K + k is contingency k of
-  // environment i; the watched lines (host and device), the values [n_env][K] and the summary of the last one-step launch, the table index
-  // of every reward slot (-1: not a GPF_RW_N1 slot) and the launch plans of the two lane ranges with device lane lists of their own (valid
-  // while plan_valid and n1_plan_valid both hold: whatever invalidates the batch's plan invalidates them).  n1_host_on: a header-only handle
-  // was given a valid screen (gpf_step_n refuses multi-step launches there too)
-  bool n1_on = false, n1_host_on = false, n1_slots = false, n1_plan_valid = false;
-  int n1_n_env = 0, n1_K = 0;
-  std::vector<int> h_n1_lines;
+  LaneFan fan;                          // the lanes behind the environments: who owns them, the split, the cached plans of its two ranges
+  // the N-1 screen (gridpf_n1.hpp, gridpf_capi_n1.hip; the fan's secondary lanes are its contingency lanes): the watched lines, the values
+  // [n_env][K] and the summary of the last one-step launch and the table index of every reward slot (-1: not a GPF_RW_N1 slot)
+  bool n1_slots = false;
   DevArr<int> n1_lines, n1_info, n1_slot_idx;
   DevArr<float> n1_value, n1_worst;
-  LaunchPlan n1_env_p{}, n1_env_pb{}, n1_con_p{}, n1_con_pb{};
-  DevArr<int> n1_env_lists[3], n1_con_lists[3];
-  // the look-ahead screen (gridpf_lookahead.hpp, gridpf_capi_lookahead.hip): lanes [0, la_n_env) are environments, lane la_n_env + i K + k
-  // is scratch lane (i, k); the candidates, the outputs of the last call, the moved list of the play kernel (count | lane ids, rows) with the
-  // rows the host last noted for the scratch lanes, the scheduled maintenance alone (the device's outage table is its union with the
-  // hazards) and the launch plans of the two lane ranges, cached as the N-1 screen caches its own.  la_host_on: a header-only handle was
-  // given a valid look-ahead (gpf_step_n refuses multi-step launches there too)
-  bool la_on = false, la_host_on = false, la_plan_valid = false, la_noted_stale = true;
-  int la_n_env = 0, la_K = 0;
-  long long la_maint_gen = -1;          // generation of the outage tables la_maint was uploaded from
-  DevArr<int> la_cand, la_best, la_info, la_list, la_list_rows, la_noted, la_src;
+  // the look-ahead screen (gridpf_lookahead.hpp, gridpf_capi_lookahead.hip; the fan's secondary lanes are its scratch lanes): the
+  // candidates, the outputs of the last call, the play kernel's moved list, the rows the host last noted for the scratch lanes (la_noted:
+  // the host's mirrors while la_noted_gen is the fan's plans_gen) and the scheduled maintenance alone (the device holds its union with the hazards)
+  long long la_noted_gen = -1, la_maint_gen = -1;       // la_maint_gen: generation of the outage tables la_maint was uploaded from
+  DevArr<int> la_cand, la_best, la_info, la_noted, la_src;
   DevArr<float> la_value, la_best_value;
   DevArr<unsigned char> la_flags, la_maint;
-  LaunchPlan la_env_p{}, la_env_pb{}, la_sim_p{}, la_sim_pb{};
-  DevArr<int> la_env_lists[3], la_sim_lists[3];
-  HostPin<int> la_pin;                  // pinned read-back block: count | lane ids | rows
+  MovedList la_moved_list;
   // the look-ahead chain (gpf_set_lookahead_chain): the sticky record of every scratch lane over up to lc_max steps and the fall-back slot
   // of every environment.  lc_host_on: a header-only handle was given a valid chain
   bool lc_on = false, lc_host_on = false;
@@ -480,6 +480,13 @@ hipError_t rows_copy(const gpf_engine* e, const DevArr<T>& arr, size_t stride, i
 // "the lanes' rows were sent by the host" (their reset topology is their topology again)
 bool note_lane_row(gpf_engine* e, int lane, const int* t, const int* sb);
 void topo_unmoved(gpf_engine* e, int lane0, int n);
+// ... lane `dst` takes lane `src`'s planning entries, and its mirror of the sent rows (else the mirror is unknown: a kernel wrote the row);
+// the read-back of a moved-lane list of lanes in [lane_lo, lane_hi): count first, then ids and rows, note_lane_row and per_lane(lane) (may
+// be empty) in lane order -- a count or a lane out of range: nothing is noted, GPF_E_DEVICE "<who> count)" / "<who> lane)"; and what is
+// refused in a list of action items (kind, id, value) of `who` (*bus_items, may be null: an item sets or changes a bus)
+void lane_inherit(gpf_engine* e, int dst, int src, bool copy_mirror);
+int moved_list_readback(gpf_engine* e, MovedList& list, int lane_lo, int lane_hi, const char* who, const std::function<void(int)>& per_lane);
+int check_action_items(gpf_engine* e, const char* who, int n_items, const int32_t* items, bool* bus_items);
 
 // gridpf_capi_env.hip: the state pointers of the injection dynamics (no action pointers: upload_params_s adds its launch's), the
 // feature's share of gpf_reset_lanes / gpf_copy_lanes, and simulate_env_copy_kernel: lanes dst0 + q, q < n_dst, take the state of lane
@@ -521,7 +528,7 @@ int reward_poststep(gpf_engine* e, bool topo_flags, bool combined = false);
 int reward_reset_lanes(gpf_engine* e, int lane0, int n);
 
 // gridpf_capi_episode.hip: episode_kernel, queued last in a one-step launch with a limit set (list_resets: truncated lanes are appended to
-// ta_list / ta_list_rows for the host's re-keying), the feature's share of gpf_reset_lanes / gpf_copy_lanes, and what gpf_set_rewards
+// ta_moved_list for the host's re-keying), the feature's share of gpf_reset_lanes / gpf_copy_lanes, and what gpf_set_rewards
 // does to the returns (a new slot table starts them at 0)
 int episode_poststep(gpf_engine* e, bool auto_reset, bool track_cooldown, bool list_resets);
 int episode_reset_lanes(gpf_engine* e, int lane0, int n);
@@ -544,23 +551,25 @@ int combined_settle(gpf_engine* e, bool acts, bool screened);
 int combined_reset_lanes(gpf_engine* e, int lane0, int n);
 hipError_t combined_copy_lanes(gpf_engine* e, int src, int dst, int n);
 
-// gridpf_capi.hip, for the N-1 screen: the plan of a lane range with the caller's device lane lists (list_a / list_b / list_c of the engine
+// gridpf_capi.hip, for the fan: the plan of a lane range with the caller's device lane lists (list_a / list_b / list_c of the engine
 // and the batch's cached plan are left alone), and gpf_runpf's launch on a range with a plan made that way
 // (list_tail: a range that does not end on an instance group keeps the batch's group width, from a ghost-padded lane list)
 int plan_launch_own(gpf_engine* e, int lane0, int n, LaunchPlan& p, LaunchPlan& pb, DevArr<int>* lists, bool list_tail = false);
 int runpf_range(gpf_engine* e, int lane0, int n, int is_dc, int max_iter, double tol_mva, const LaunchPlan* pre_p, const LaunchPlan* pre_pb);
+// ... the fan's plans brought up to date (no work while nothing invalidated the batch's plan), and the secondary lanes marked (1) or
+// unmarked (0) in a host flag vector and, with the cursor on, in its skip bytes
+int fan_plans(gpf_engine* e);
+int fan_mark_lanes(gpf_engine* e, std::vector<char>& flags, int mark);
 
-// gridpf_capi_n1.hip: the screen's plans brought up to date (the contingency lanes take their environments' planning entries; no work
-// while nothing invalidated the batch's plan), the screen itself, queued behind the step and the topology post-step of a one-step launch
-// (fan-out, the power flows of the contingency lanes, values, summary), the GPF_RW_N1 slots of lanes [lane0, lane0 + n) from the table
-// into `reward`, what gpf_set_rewards does to the slot indices (refusals included), and the skip byte / contingency mark of the
-// contingency lanes (gpf_set_lane_chronics clears them for every lane)
+// gridpf_capi_n1.hip: fan_plans for the screen (in front of it the contingency lanes take their environments' planning entries), the
+// screen itself, queued behind the step and the topology post-step of a one-step launch (fan-out, the power flows of the contingency
+// lanes, values, summary), the GPF_RW_N1 slots of lanes [lane0, lane0 + n) from the table into `reward` and what gpf_set_rewards does to
+// the slot indices (refusals included)
 int n1_plans(gpf_engine* e);
 int n1_screen(gpf_engine* e, int max_iter, double tol_mva);
 int n1_fill_slots(gpf_engine* e, int lane0, int n, float* reward, long long row_stride);
 int n1_check_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots);
 int n1_set_slots(gpf_engine* e, int n_slot, const gpf_reward_slot* slots);
-int n1_mark_lanes(gpf_engine* e);
 
 // gridpf_capi.hip, for the look-ahead: simulate_prepare_kernel on scratch lanes dst0 + q, q < n_dst, of sources src_lanes_dev[q / n_act]
 // (everything of a source that is not topology, and the chronics or forecast row to step on), one step of a lane range as gpf_simulate_batch
@@ -568,9 +577,8 @@ int n1_mark_lanes(gpf_engine* e);
 // the caller's, and the multi-step refusal's test
 int simulate_prepare(gpf_engine* e, const int* src_lanes_dev, int n_act, int n_dst, int dst0, int t_obs, int time_step);
 int simulate_step(gpf_engine* e, int lane0, int n, int time_step, const gpf_step_opts* o, const char* who, const LaunchPlan* pre_p, const LaunchPlan* pre_pb);
-// gridpf_capi_lookahead.hip: the plans of the two lane ranges brought up to date, and the marks of the scratch lanes (their chronics
-// cursor is an absolute row, they start no scenario of their own; gpf_set_lane_chronics clears the marks of every lane)
-int la_plans(gpf_engine* e);
+// gridpf_capi_lookahead.hip: the marks of the scratch lanes (their chronics cursor is an absolute row, they start no scenario of their
+// own; gpf_set_lane_chronics clears the marks of every lane)
 int la_mark_lanes(gpf_engine* e);
 
 inline bool check_range(gpf_engine* e, int lane0, int n) { return e && lane0 >= 0 && n >= 0 && lane0 + n <= e->n_lanes; }

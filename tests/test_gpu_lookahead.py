@@ -354,3 +354,60 @@ def test_a_sharded_engine_over_one_device_agrees_with_the_plain_engine():
         assert a[key].tobytes() == b[key].tobytes(), key
     assert len(se.lookahead_views()) == 1 and np.array_equal(se.lookahead_views()[0]["cand"].cpu().numpy(), cand)
     eng.close(); se.close()
+
+
+def test_one_engine_passes_the_fan_from_screen_to_look_ahead_and_back():
+    """The N-1 screen and the look-ahead cut the batch with the same fan (its plans and lane lists).  One engine of 12 lanes, n_env = 3 (the
+    environment range does not end on an instance group): the screen on two watched lines for two launches, off; the look-ahead with three
+    candidates (another K; a bus split moves a scratch lane to another topology class), off; the screen again for one launch.  Twins that
+    never had the other feature on, stepped through the same environment steps: the look-ahead's outputs, the last screen's table and
+    summary and the environment lanes' rows are theirs, bit for bit."""
+    n, n_env, lines = 12, 3, [3, 7]
+    cand = np.array([[4, 0, -1], [2, 4, 3], [5, 8, 4]], np.int32)
+
+    def engine():
+        _, e = _engine("l2rpn_case14_sandbox", n)
+        e.set_topo_rules(max_sub_changed=1, max_line_status_changed=1)
+        e.upload_topo_actions(TABLE14)
+        return e
+
+    def screen_launch(e, t):
+        e.step(t, nb_ts_reco=10)
+        return e.n1_values().tobytes(), tuple(v.tobytes() for v in e.n1_summary().values())
+
+    def look_ahead(e):
+        e.set_lookahead(3, n_env)
+        e.lookahead(2, 1, cand)
+        got, _, _ = _check_outputs(e, n_env, 3)
+        assert (got["flags"][cand == 4] & 3 == 0).all()                   # the bus split was played
+        assert len({row.tobytes() for row in e.get_topology(n_env, n_env * 3)[0]}) >= 3
+        return {k: v.tobytes() for k, v in got.items()}
+
+    def env_rows(e):
+        r = e.results(0, n_env)
+        return r.out.tobytes(), r.status.tobytes(), r.topo_vect.tobytes()
+
+    eng = engine()
+    eng.set_n1_screen(lines, n_env)
+    for t in (0, 1):
+        screen_launch(eng, t)
+    eng.set_n1_screen(None)
+    la = look_ahead(eng)
+    eng.set_lookahead(0)
+    eng.set_n1_screen(lines, n_env)
+    table, rows = screen_launch(eng, 2), env_rows(eng)
+    eng.close()
+
+    twin = engine()                                                          # never had the screen on
+    for t in (0, 1):
+        twin.step(t, nb_ts_reco=10)
+    assert look_ahead(twin) == la
+    twin.close()
+
+    twin = engine()                                                          # never had the look-ahead on
+    for t in (0, 1):
+        twin.step(t, nb_ts_reco=10)
+    twin.set_n1_screen(lines, n_env)
+    assert screen_launch(twin, 2) == table and env_rows(twin) == rows
+    assert np.isfinite(np.frombuffer(table[0], np.float32)).all()
+    twin.close()
