@@ -139,7 +139,7 @@ int gpf_ptdf_build(gpf_handle e, int32_t lane) {
       const bool dangling = (n_lines_at[lf[k]] == 1 && n_other_at[lf[k]] == 0) || (n_lines_at[lt[k]] == 1 && n_other_at[lt[k]] == 0);
       for (int l = 0; l < g.n_line; ++l) {
         const double hlk = e->h_ptdf[(size_t)l * nbt + lf[k]] - e->h_ptdf[(size_t)l * nbt + lt[k]];
-        lo_[(size_t)l * line_pad + k] = std::fabs(den) < 1e-8 ? (dangling ? (l == k ? -1.0 : 0.0) : std::nan("")) : (l == k ? -1.0 : hlk / den);   // (diagonal -1 as in the batch builder)
+        lo_[(size_t)l * line_pad + k] = std::fabs(den) < 1e-8 ? (dangling ? 0.0 : std::nan("")) : (l == k ? -1.0 : hlk / den);   // (a dangling line: the whole column is zero, as in the batch builder)
       }
     }
     { std::vector<float> lof(lo_.begin(), lo_.end()); HIP_TRY(e->lodf.upload(lof.data(), lof.size())); }

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(PTDFB_THREADS) void ptdf_build_kernel(PtdfBuildDev 
   PTDFB_STAMP(4);
   if (!LO) return;
   __syncthreads();
-  // ---- 4. LODF[m][k] = H[m][k] / (1 - H[k][k]),  H[m][k] = PTDF[m][from_k] - PTDF[m][to_k];  LODF[k][k] = -1;  NaN column: the outage
+  // ---- 4. LODF[m][k] = H[m][k] / (1 - H[k][k]),  H[m][k] = PTDF[m][from_k] - PTDF[m][to_k];  LODF[k][k] = -1 (0 in an lflag column);  NaN column: the outage
   //         of k islands the grid (as gpf_ptdf_build); column of zeros: line k is out of service, or its outage only removes a bus that
   //         carries nothing else (lflag) ---------------------------------------------------------------------------------------------
   for (int k = tid; k < D.line_pad; k += PTDFB_THREADS) {
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(PTDFB_THREADS) void ptdf_build_kernel(PtdfBuildDev 
         if (f >= 0) {                                                  // (an open line: its outage changes nothing -> column of zeros)
           const double hd = hden[k];
           const double h = (f < nr ? wrow[u * n_pad + f] : 0.0) - (t < nr ? wrow[u * n_pad + t] : 0.0);
-          v = (hd != hd) ? hd : (m == k ? -1.0 : h * hd);
+          v = (hd != hd) ? hd : ((m == k && hd != 0.0) ? -1.0 : h * hd);     // (hd == 0: the lflag column, zero on the diagonal too)
         }
         LO[(size_t)m * D.line_pad + k] = (float)v;
       }
@@ -570,7 +570,7 @@ __global__ __launch_bounds__(PTDFB_LDS_THREADS) void ptdf_build_lds_kernel(PtdfB
   if (tid == 0) D.status[cls] = bad ? 1 : 0;
   PTDFB_STAMP(4);
   if (!LO) return;
-  // ---- 4. LODF[m][k] = (PTDF[m][from_k] - PTDF[m][to_k]) / (1 - H[k][k]); LODF[k][k] = -1.  With PTDF[m][b] = bdc_m (X[from_m][b] - X[to_m][b])
+  // ---- 4. LODF[m][k] = (PTDF[m][from_k] - PTDF[m][to_k]) / (1 - H[k][k]); LODF[k][k] = -1 (0 in an lflag column: all of it is zero).  With PTDF[m][b] = bdc_m (X[from_m][b] - X[to_m][b])
   //         and X symmetric, PTDF[m][from_k] - PTDF[m][to_k] = bdc_m (PT[from_m][k] - PT[to_m][k]) / bdc_k: two entries of the PTDF^T table phase 3
   //         just wrote, on ROW from_m / to_m (the same for every thread) and the thread's own column k -- coalesced reads through L1 / L2
   //         instead of gathers of X at random columns of LDS (4 per output: the lanes' from-buses collide in the 32 eight-byte banks, 47 k
@@ -588,6 +588,7 @@ __global__ __launch_bounds__(PTDFB_LDS_THREADS) void ptdf_build_lds_kernel(PtdfB
     const int m_lo = str * per, m_hi = (m_lo + per < D.n_line) ? m_lo + per : D.n_line;
     const double kbd = s_bdc[kk];
     const double ksc = (kf >= 0 && kbd != 0.0) ? khd / kbd : 0.0;      // 1 / (bdc_k (1 - H[k][k]))
+    const double kdg = khd != 0.0 ? -1.0 : 0.0;                        // LODF[k][k]; khd == 0: the lflag column, zero on the diagonal too
     const double* const PTk = PT + kk;
     constexpr int UN = 8;                                              // lines in flight per thread: every load of a trip is issued before the first is used
     for (int m0 = m_lo; m0 < m_hi; m0 += UN) {
@@ -606,7 +607,7 @@ __global__ __launch_bounds__(PTDFB_LDS_THREADS) void ptdf_build_lds_kernel(PtdfB
         const int m = m0 + u;
         if (m >= m_hi) break;
         double v = 0.0;
-        if (kf >= 0) v = (khd != khd) ? khd : (m == kk ? -1.0 : bm_[u] * (a_[u] - b_[u]) * ksc);
+        if (kf >= 0) v = (khd != khd) ? khd : (m == kk ? kdg : bm_[u] * (a_[u] - b_[u]) * ksc);
         LO[(size_t)m * D.line_pad + kk] = (float)v;
       }
     }

@@ -131,14 +131,15 @@ def test_tables_and_flows_of_every_class_match_the_oracle(name, n_lanes, n_topo,
         assert np.allclose(w[kk][fin], ref[fin], rtol=2e-5, atol=2e-4), (kk, np.abs(w[kk][fin] - ref[fin]).max())
     assert np.isnan(w[~ok]).all()
     # the single-topology tables come back with gpf_ptdf_build, and equal the class tables of that topology
+    # (the host's Gauss-Jordan pivots by rows, the device's does not: the two tables agree within 1e-12, not bit for bit)
     k0 = int(np.nonzero(ok)[0][0])
+    T_class = eng.ptdf_class(int(lc[k0]))                               # of the batch build above: gpf_ptdf_build replaces the batch tables
     eng.ptdf_build(lane=k0)
-    assert np.abs(eng.ptdf() - eng_class_table(eng, m, states[k0])).max() < 1e-9
+    T_single = eng.ptdf()
+    assert np.abs(T_single - ptdf(m, states[k0])).max() < 1e-9
+    print(f"[ptdf_batch] {name}: gpf_ptdf_build vs the class table of lane {k0}: max |d| = {np.abs(T_single - T_class).max():.3e}")
+    assert np.abs(T_single - T_class).max() < 1e-12
     eng.close()
-
-
-def eng_class_table(eng, m, st):
-    return ptdf(m, st)
 
 
 def test_bench_shape_2048_lanes_256_topologies_on_118_substations(load_model, load_npz):
